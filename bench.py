@@ -19,11 +19,17 @@ every rank owns its own shard (no data-path collective); the only exchange is
 the final gather of the per-chunk (size, status) verdicts to rank 0 over
 RCCL, inside the timed region.
 
+A plain run sets up, warms up, times the steps, writes the last step's
+outputs (--dump-outputs DIR) and prints the line.  Everything else, the
+decode of the timed streams by the real reference included, runs only with
+--full.
+
 The JSON line also carries
   roofline      for the dominant kernel (the LZ77+Huffman compress kernel):
                 algorithmic bytes (U read + C written) per launch / its
                 average duration, HIP events on the launch stream, vs 8 TB/s.
-  cpu_baseline  the real reference (oracle/_ref, built from /root/reference's
+With --full it also carries
+  cpu_baseline  the real reference (oracle/_ref, built from the reference's
                 sources) timed by a C pthread harness (oracle/cpu_bench.c) on
                 this box's host cores, T = 1 and T = all, on a bounded sample
                 of the same batch.
@@ -398,9 +404,10 @@ def device_batch(torch, dev, chunks, count, first=0):
 
 
 def roundtrip_config(torch, dist, world, rank, dev, stream, api, shard, chunks,
-                     count, first, fmt, level, steps, warmup):
+                     count, first, fmt, level, steps, warmup, ref_check=True):
     """compress then decompress `count` device-resident chunks; verifies the
-    round trip byte for byte after the timed region."""
+    round trip byte for byte after the timed region, and with `ref_check`
+    has the real reference decode every distinct stream."""
     size = len(chunks[0])
     data, in_off, in_n = device_batch(torch, dev, chunks, count, first)
     comp_c, dec = api.Compressor(level), api.Decompressor()
@@ -432,15 +439,48 @@ def roundtrip_config(torch, dist, world, rank, dev, stream, api, shard, chunks,
     assert bool((res == 0).all()), "a chunk failed to decompress"
     assert torch.equal(out, data), "round trip is not byte-exact"
     assert bool((c_n > 0).all()) and bool((c_n <= comp_c.bound(fmt, size)).all())
-    from tests import oracle_util
-    ref = oracle_util.load_ref()
-    nref = ref_verify(torch, ref, fmt, chunks, comp, c_off, c_n, first, len(chunks)) if ref else 0
+    nref = 0
+    if ref_check:
+        from tests import oracle_util
+        ref = oracle_util.load_ref()
+        nref = ref_verify(torch, ref, fmt, chunks, comp, c_off, c_n, first, len(chunks)) if ref else 0
     U = count * size
     C = int(c_n.sum().item())
     r = {"elapsed": elapsed, "t_comp": tm.span(0, 1), "t_dec": tm.span(1, 2),
          "U": U, "C": C, "verdict": verdict, "nref": nref,
          "tensors": (data, in_off, in_n, comp, c_off, c_av, c_n, out, res, comp_c, dec)}
     return r
+
+
+DUMP_SAMPLE = 64          # chunks whose bytes --dump-outputs writes
+DUMP_SEED = 0x0E1100D0
+
+
+def dump_outputs(torch, dump_dir, tensors):
+    """What the timed path handed its caller in its last step, as float64 /
+    float32 .npy files, so that two builds can be compared output for output:
+    every chunk's compressed size and decompress result, and for a fixed,
+    seeded sample of DUMP_SAMPLE chunks the compressed streams (concatenated
+    in sample order) and the decompressed bytes.  The whole batch would be
+    4096 x 64 KiB twice over; the sample keeps the files near 34 MB."""
+    import numpy as np
+    data, in_off, in_n, comp, c_off, c_av, c_n, out, res, comp_c, dec = tensors
+    n = c_n.numel()
+    size = out.numel() // n
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_SAMPLE),
+                                                         replace=False))
+    sizes = c_n.cpu().numpy()
+    offs = c_off.cpu().numpy()
+    streams = torch.cat([comp[int(offs[i]):int(offs[i]) + int(sizes[i])] for i in idx])
+    rows = out.view(n, size)[torch.from_numpy(idx).to(out.device)]
+    os.makedirs(dump_dir, exist_ok=True)
+    arrays = {"compressed_sizes": sizes.astype(np.float64),
+              "decompress_results": res.cpu().numpy().astype(np.float64),
+              "sample_chunks": idx.astype(np.float64),
+              "compressed_sample": streams.cpu().numpy().astype(np.float32),
+              "decompressed_sample": rows.cpu().numpy().astype(np.float32)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(dump_dir, name + ".npy"), arr)
 
 
 def end_to_end(torch, dev, stream, api, tensors, slices=8):
@@ -754,8 +794,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--chunks", type=int, default=CHUNKS_PER_GPU)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the "
+                         "reference's decode of the timed streams, the end-to-end "
+                         "leg, the other BASELINE configs, the single-stream calls "
+                         "and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--configs", default="all", choices=["all", "headline"],
-                    help="'headline' skips the other BASELINE configs")
+                    help="with --full: 'headline' skips the other BASELINE configs")
     ap.add_argument("--streams", type=int, default=65536,
                     help="configs[3] stream count (total over all ranks)")
     ap.add_argument("--blocks", type=int, default=1 << 20,
@@ -808,17 +855,20 @@ def main():
     chunks = gen_chunks(n, CHUNK, 0x0E110003 + rank * 100003)
 
     head = roundtrip_config(torch, dist, world, rank, dev, stream, api, shard,
-                            chunks, n, 0, FMT, LEVEL, a.steps, a.warmup)
+                            chunks, n, 0, FMT, LEVEL, a.steps, a.warmup, ref_check=a.full)
     elapsed, t_comp, t_dec = head["elapsed"], head["t_comp"], head["t_dec"]
     U, C = head["U"], head["C"]
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(torch, a.dump_outputs, head["tensors"])
+    extended = a.full and a.configs == "all"
     e2e = None
-    if rank == 0 and a.configs == "all":
+    if rank == 0 and extended:
         e2e = end_to_end(torch, dev, stream, api, head["tensors"])
     del head["tensors"]
     torch.cuda.empty_cache()
 
     extras = {}
-    if a.configs == "all":
+    if extended:
         extras["configs[1]"] = extra_roundtrip(
             "l1", "configs[1]: 4096 x 64 KiB raw DEFLATE buffers, level 1, "
             "compress then decompress, per GPU", torch, dist, world, rank, dev,
@@ -868,7 +918,8 @@ def main():
             "verified": "round trip byte-exact on every rank (torch.equal over the batch); " +
                         (f"all {head['nref']} compressed streams of rank 0 decoded by the real "
                          "reference (oracle/_ref) to the original bytes, outside the timed region"
-                         if head["nref"] else "oracle/_ref not on this box"),
+                         if head["nref"] else "oracle/_ref not on this box" if a.full
+                         else "the reference decodes the streams with --full"),
             "roofline": {
                 "bound": "valu-issue", "kernel": "lda_deflate_batch_kernel",
                 "bound_note": "frac (below) = algorithmic bytes / launch time / HBM peak, "
@@ -904,7 +955,7 @@ def main():
             line["end_to_end"] = e2e
         if extras:
             line["configs"] = extras
-        line["cpu_baseline"] = None if a.no_cpu else cpu_baseline(chunks, FMT, LEVEL)
+        line["cpu_baseline"] = None if a.no_cpu or not a.full else cpu_baseline(chunks, FMT, LEVEL)
         print(json.dumps(line))
     if dist:
         dist.destroy_process_group()

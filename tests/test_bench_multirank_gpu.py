@@ -32,7 +32,7 @@ def _run(args):
 
 def test_bench_two_ranks_one_device():
     streams, blocks, chunks = 4096, 65536, 512
-    line = _run(["--gpus", "2", "--backend", "gloo", "--one-device", "--configs", "all",
+    line = _run(["--gpus", "2", "--backend", "gloo", "--one-device", "--full", "--configs", "all",
                  "--streams", str(streams), "--blocks", str(blocks),
                  "--chunks", str(chunks), "--steps", "2", "--warmup", "1", "--no-cpu"])
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["warmup"] == 1
@@ -64,7 +64,7 @@ def test_bench_eight_ranks_one_device():
     so that it stays under a minute); n_gpus 8, eight partitions that add up,
     eight verdict vectors at rank 0"""
     streams, blocks, chunks = 1024, 16384, 64
-    line = _run(["--gpus", "8", "--backend", "gloo", "--one-device", "--configs", "all",
+    line = _run(["--gpus", "8", "--backend", "gloo", "--one-device", "--full", "--configs", "all",
                  "--streams", str(streams), "--blocks", str(blocks),
                  "--chunks", str(chunks), "--steps", "2", "--warmup", "1", "--no-cpu"])
     assert line["n_gpus"] == 8 and line["scaling"] == "weak"
@@ -81,11 +81,24 @@ def test_bench_eight_ranks_one_device():
     assert c4["verdicts"] == {"chunks": blocks, "failed": 0}
 
 
-def test_bench_single_rank_line_shape():
+def test_bench_single_rank_line_shape(tmp_path):
     line = _run(["--configs", "headline", "--chunks", "256", "--steps", "2",
-                 "--warmup", "1", "--no-cpu"])
+                 "--warmup", "1", "--no-cpu", "--dump-outputs", str(tmp_path)])
     assert line["n_gpus"] == 1 and line["verdicts"]["failed"] == 0
     for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in line
     assert line["config"]["workload"].startswith("configs[2]")
+    # the last timed step's outputs: sizes and results of every chunk, the
+    # bytes of a seeded sample, float32 / float64 only
+    import numpy as np
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(out) == ["compressed_sample", "compressed_sizes", "decompress_results",
+                           "decompressed_sample", "sample_chunks"]
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert out["compressed_sizes"].shape == out["decompress_results"].shape == (256,)
+    assert (out["decompress_results"] == 0).all() and (out["compressed_sizes"] > 0).all()
+    idx = out["sample_chunks"].astype(np.int64)
+    assert out["decompressed_sample"].shape == (len(idx), 65536)
+    assert out["compressed_sample"].size == out["compressed_sizes"][idx].sum()
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20

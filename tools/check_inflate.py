@@ -1,7 +1,7 @@
 """Decode N reference-compressed chunks on the GPU and compare every byte.
 Usage: python tools/check_inflate.py [N] [size]   (LDA_INFLATE_PAR=0 selects lane-per-stream)"""
 import os, sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
 from libdeflate_amd import api
 from tests import datagen, oracle_util

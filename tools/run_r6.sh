@@ -5,8 +5,8 @@ timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | grep -v amdgpu.ids | tai
 cat gpurun_out/r06_gpu_tests.txt
 bash tools/prof_all.sh r06 > gpurun_out/prof_all.log 2>&1
 for w in bench l1 l9 opt small inflate64k stream; do [ -f gpurun_out/pmc_$w.json ] && cp gpurun_out/pmc_$w.json profiles/r06_pmc_$w.json; done
-timeout 1200 python bench.py > gpurun_out/r06_bench_line.json 2> gpurun_out/r06_bench_err.txt
-tail -c 600 gpurun_out/r06_bench_line.json
+timeout 1200 python bench.py --full | grep "^{" | tail -1 > profiles/r06_bench_line.json
+tail -c 600 profiles/r06_bench_line.json
 PC=$PWD/libdeflate_amd/libdeflate_amd_profc.so
 {
 for k in "" "--kind 0" "--kind 5" "--kind 6"; do LIBDEFLATE_AMD_LIB=$PC timeout 120 python tools/microbench.py inflate --chunks 4096 $k 2>&1 | grep -v amdgpu.ids; done
