@@ -309,6 +309,86 @@ libdeflate_amd_decompress_batch(struct libdeflate_decompressor *decompressor,
 				void *stream);
 
 /*
+ * Preset dictionaries (zlib's deflateSetDictionary / inflateSetDictionary,
+ * the FDICT / DICTID fields of RFC 1950 2.2), for LIBDEFLATE_AMD_DEFLATE and
+ * LIBDEFLATE_AMD_ZLIB.  zlib refuses a dictionary on a gzip stream, and so do
+ * these calls: the batch forms return LIBDEFLATE_AMD_BAD_ARG, the
+ * single-buffer forms report it like their counterparts report a bad
+ * argument - compress returns 0, decompress LIBDEFLATE_BAD_DATA - with the
+ * reason in libdeflate_amd_last_error().
+ *
+ * One dictionary serves every chunk of a batch.  dict_nbytes == 0 gives
+ * exactly the result of the call without a dictionary (dict may then be
+ * NULL).  Semantics are zlib's:
+ *  - compress primes the window with the dictionary's last
+ *    min(dict_nbytes, LIBDEFLATE_AMD_DICT_WINDOW) bytes - what the compress
+ *    kernel's window holds ahead of a chunk; a longer dictionary is not an
+ *    error.  zlib streams get FDICT and DICTID = the Adler-32 of the WHOLE
+ *    dictionary, big-endian, after the 2-byte header; the footer stays the
+ *    Adler-32 of the chunk alone.  Such a stream takes 4 bytes more than
+ *    libdeflate_zlib_compress_bound().
+ *  - decompress accepts a dictionary of any length and uses its last 32 KiB.
+ *    Raw DEFLATE: a distance may reach min(dict_nbytes, 32768) bytes before
+ *    the output; further is BAD_DATA.  zlib: a stream with FDICT must name
+ *    the dictionary's Adler-32 in DICTID (else BAD_DATA, also when
+ *    dict_nbytes == 0); a stream without FDICT decodes as if no dictionary
+ *    were given.  actual_in counts the 4 DICTID bytes.
+ *  - the calls without a dictionary still reject FDICT.
+ *
+ * Device batches: the arguments of libdeflate_amd_compress_batch /
+ * libdeflate_amd_decompress_batch plus d_dict, a device pointer on the
+ * object's device that stays valid until the batch completes.  They only
+ * enqueue (the DICTID is computed on the device).  Every chunk, also one of a
+ * few bytes, runs on the ordinary compress kernel.
+ */
+#define LIBDEFLATE_AMD_DICT_WINDOW 20480
+
+LIBDEFLATEAPI int
+libdeflate_amd_compress_batch_dict(struct libdeflate_compressor *compressor,
+				   int format, size_t n_chunks,
+				   const void *d_dict, size_t dict_nbytes,
+				   const void *d_in, const uint64_t *d_in_offsets,
+				   const uint64_t *d_in_nbytes,
+				   void *d_out, const uint64_t *d_out_offsets,
+				   const uint64_t *d_out_avail,
+				   uint64_t *d_out_nbytes, void *stream);
+
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_batch_dict(struct libdeflate_decompressor *decompressor,
+				     int format, size_t n_chunks,
+				     const void *d_dict, size_t dict_nbytes,
+				     const void *d_in, const uint64_t *d_in_offsets,
+				     const uint64_t *d_in_nbytes,
+				     void *d_out, const uint64_t *d_out_offsets,
+				     const uint64_t *d_out_avail,
+				     int32_t *d_results,
+				     uint64_t *d_actual_in, uint64_t *d_actual_out,
+				     void *stream);
+
+/*
+ * Single buffer, host pointers, blocking - like libdeflate_*_compress and
+ * libdeflate_*_decompress_ex.  Compress returns the bytes written, 0 when
+ * they do not fit; inputs of 128 KiB and more are compressed in segments side
+ * by side like libdeflate_*_compress, the first primed with the dictionary.
+ * Decompress runs as a batch of one: the many-wave path that
+ * libdeflate_*_decompress takes for large streams does not take dictionary
+ * streams.
+ */
+LIBDEFLATEAPI size_t
+libdeflate_amd_compress_dict(struct libdeflate_compressor *compressor, int format,
+			     const void *dict, size_t dict_nbytes,
+			     const void *in, size_t in_nbytes,
+			     void *out, size_t out_nbytes_avail);
+
+LIBDEFLATEAPI enum libdeflate_result
+libdeflate_amd_decompress_dict_ex(struct libdeflate_decompressor *decompressor,
+				  int format, const void *dict, size_t dict_nbytes,
+				  const void *in, size_t in_nbytes,
+				  void *out, size_t out_nbytes_avail,
+				  size_t *actual_in_nbytes_ret,
+				  size_t *actual_out_nbytes_ret);
+
+/*
  * Checksums of N chunks.  d_init may be NULL (CRC: 0, Adler: 1), otherwise
  * d_init[i] is the running value to continue from (libdeflate.h:326-346).
  */

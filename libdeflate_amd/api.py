@@ -85,6 +85,33 @@ class Compressor:
                 out_nbytes.data_ptr(), int(max_chunk), _stream_ptr(stream)),
                 "compress_batch_bounded")
 
+    def compress_dict(self, fmt, dictionary, data, out_avail=None):
+        """libdeflate_amd_compress_dict: one host buffer with a preset
+        dictionary ("deflate" or "zlib").  Returns the compressed bytes, or
+        None when the call returns 0 (does not fit, or a bad argument)."""
+        p, n = _buf(data)
+        dp, dn = _buf(dictionary)
+        if out_avail is None:
+            out_avail = self.bound(fmt, n) + 4     # + DICTID
+        out = np.empty(max(out_avail, 1), dtype=np.uint8)
+        r = self._lib.libdeflate_amd_compress_dict(
+            self._h, FORMATS[fmt], dp, dn, p, n, out.ctypes.data_as(c_void_p), out_avail)
+        if r == 0:
+            return None
+        return out[:r].tobytes()
+
+    def compress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
+                            out_offsets, out_avail, out_nbytes, stream=None):
+        """Device batch with one preset dictionary for every chunk
+        (libdeflate_amd_compress_batch_dict): `dictionary` is a uint8 torch
+        CUDA tensor, the rest as in compress_batch."""
+        check(self._lib.libdeflate_amd_compress_batch_dict(
+            self._h, FORMATS[fmt], in_offsets.numel(),
+            dictionary.data_ptr() if dictionary.numel() else None, dictionary.numel(),
+            data.data_ptr(), in_offsets.data_ptr(), in_nbytes.data_ptr(), out.data_ptr(),
+            out_offsets.data_ptr(), out_avail.data_ptr(), out_nbytes.data_ptr(),
+            _stream_ptr(stream)), "compress_batch_dict")
+
     def compress_batch_host(self, fmt, chunks, out_avail=None):
         """List of bytes -> list of compressed bytes (None where it did not
         fit), through libdeflate_amd_compress_batch_host."""
@@ -135,6 +162,19 @@ class Decompressor:
         nout = ao.value if want_actual_out else out_avail
         return r, ai.value, ao.value, out[:nout].tobytes()
 
+    def decompress_dict_ex(self, fmt, dictionary, data, out_avail, want_actual_out=True):
+        """libdeflate_amd_decompress_dict_ex -> (result, actual_in,
+        actual_out, out_bytes), like decompress_ex."""
+        p, n = _buf(data)
+        dp, dn = _buf(dictionary)
+        out = np.zeros(max(out_avail, 1), dtype=np.uint8)
+        ai, ao = c_size_t(0), c_size_t(0)
+        r = self._lib.libdeflate_amd_decompress_dict_ex(
+            self._h, FORMATS[fmt], dp, dn, p, n, out.ctypes.data_as(c_void_p), out_avail,
+            ctypes.byref(ai), ctypes.byref(ao) if want_actual_out else None)
+        nout = ao.value if want_actual_out else out_avail
+        return r, ai.value, ao.value, out[:nout].tobytes()
+
     def decompress(self, fmt, data, out_avail, want_actual_out=True):
         p, n = _buf(data)
         out = np.zeros(max(out_avail, 1), dtype=np.uint8)
@@ -167,6 +207,21 @@ class Decompressor:
             actual_in.data_ptr() if actual_in is not None else None,
             actual_out.data_ptr() if actual_out is not None else None,
             _stream_ptr(stream)), "decompress_batch")
+
+    def decompress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
+                              out_offsets, out_avail, results, actual_in=None,
+                              actual_out=None, stream=None):
+        """Device batch with one preset dictionary for every stream
+        (libdeflate_amd_decompress_batch_dict); `dictionary` is a uint8
+        torch CUDA tensor, the rest as in decompress_batch."""
+        check(self._lib.libdeflate_amd_decompress_batch_dict(
+            self._h, FORMATS[fmt], in_offsets.numel(),
+            dictionary.data_ptr() if dictionary.numel() else None, dictionary.numel(),
+            data.data_ptr(), in_offsets.data_ptr(), in_nbytes.data_ptr(), out.data_ptr(),
+            out_offsets.data_ptr(), out_avail.data_ptr(), results.data_ptr(),
+            actual_in.data_ptr() if actual_in is not None else None,
+            actual_out.data_ptr() if actual_out is not None else None,
+            _stream_ptr(stream)), "decompress_batch_dict")
 
     def decompress_batch_host(self, fmt, chunks, out_avail,
                               want_actual_out=True):

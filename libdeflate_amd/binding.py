@@ -48,6 +48,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_gzip_decompress_members",
     "libdeflate_amd_stream_stats", "libdeflate_amd_last_fanout",
     "libdeflate_amd_selfcheck",
+    "libdeflate_amd_compress_batch_dict", "libdeflate_amd_decompress_batch_dict",
+    "libdeflate_amd_compress_dict", "libdeflate_amd_decompress_dict_ex",
 ]
 
 _lib = None
@@ -121,6 +123,15 @@ def load():
     sig("libdeflate_amd_selfcheck", c_int, POINTER(c_uint64))
     sig("libdeflate_amd_compact_offsets_len", SZ, SZ)
     sig("libdeflate_amd_compact_batch", c_int, SZ, P, P, P, P, P, P)
+    # preset dictionaries: the batch arguments with (dict, dict_nbytes) after
+    # n_chunks, the single-buffer ones with them after the format
+    sig("libdeflate_amd_compress_batch_dict", c_int, P, c_int, SZ, P, SZ, P, P, P, P,
+        P, P, P, P)
+    sig("libdeflate_amd_decompress_batch_dict", c_int, P, c_int, SZ, P, SZ, P, P, P, P,
+        P, P, P, P, P, P)
+    sig("libdeflate_amd_compress_dict", SZ, P, c_int, P, SZ, P, SZ, P, SZ)
+    sig("libdeflate_amd_decompress_dict_ex", c_int, P, c_int, P, SZ, P, SZ, P, SZ,
+        psz, psz)
     _lib = lib
     return lib
 

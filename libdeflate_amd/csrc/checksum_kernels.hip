@@ -244,3 +244,30 @@ lda_adler32_batch_kernel(u64 n_chunks, const u8 *__restrict__ base,
 			out[c] = (u32)((s2 << 16) | s1);
 	}
 }
+
+/*
+ * The per-batch block of a preset dictionary (host_compress.hip,
+ * host_decompress.hip), 64 bytes of header and the compressor's prefix:
+ *   [0] u32  the compress kernel's segment word: prefix bytes | unused bytes
+ *            in front of the dictionary tail << 16 | last segment
+ *   [4] u32  DICTID, written by lda_adler32_batch_kernel right after this
+ *   [16] u64 0, [24] u64 dict_nbytes: that kernel's descriptors (one chunk,
+ *            the whole dictionary)
+ *   [64]     pre_len bytes: pre_len - tail zeros, then the dictionary's last
+ *            `tail` bytes
+ * One workgroup; everything stays on the caller's stream.
+ */
+extern "C" __global__ void
+lda_dict_prep_kernel(const u8 *__restrict__ dict, u64 dict_nbytes, u32 tail,
+		     u32 pre_len, u32 sinfo, u8 *__restrict__ blk)
+{
+	if (threadIdx.x == 0) {
+		((u32 *)blk)[0] = sinfo;
+		((u64 *)blk)[2] = 0;
+		((u64 *)blk)[3] = dict_nbytes;
+	}
+	const u32 skip = pre_len - tail;
+	const u8 *src = dict + dict_nbytes - tail;
+	for (u32 i = threadIdx.x; i < pre_len; i += blockDim.x)
+		blk[64 + i] = i < skip ? 0 : src[i - skip];
+}

@@ -979,6 +979,14 @@ stage_input(lds_t *L, const u8 *__restrict__ inp, u32 loaded, u32 want,
 	}
 }
 
+/* a preset dictionary's tiles into the ring, once per buffer: out of line,
+ * so the body's own schedule stays what it is without a dictionary */
+static __device__ __attribute__((noinline)) void
+stage_prefix(lds_t *L, const u8 *__restrict__ pre, u32 n, u32 tid)
+{
+	stage_input(L, pre, 0, n, true, tid);
+}
+
 /* ---------------- progressive search ---------------- */
 
 /*
@@ -2153,7 +2161,8 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		   const u32 *__restrict__ sums,
 		   u64 *__restrict__ seq_scratch,
 		   const u32 *__restrict__ seg_info,
-		   u32 *__restrict__ next_chunk)
+		   u32 *__restrict__ next_chunk,
+		   const u8 *__restrict__ dict_pre)
 {
 	lds_t *L = (lds_t *)(uintptr_t)0;
 	const u32 tid = threadIdx.x;
@@ -2197,12 +2206,34 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		if (c >= n_chunks)
 			break;
 		const u8 *inp = in_base + in_offsets[c];
-		const u64 n64 = in_nbytes[c];
+		u64 n64 = in_nbytes[c];
+		/* Segment mode (one large buffer cut into sub-ranges that are
+		 * compressed side by side): the first dict_len bytes (whole tiles)
+		 * of this "chunk" are the tail of the previous sub-range; they only
+		 * prime the hash chains.  Every segment but the last ends with a
+		 * non-final block and an empty stored block, so the segments'
+		 * outputs are byte aligned and concatenate into one stream
+		 * (lib/deflate_compress.c:1839-1847 is the same alignment rule).
+		 * Matches reach no further back than lo_min: the unused bytes in
+		 * front of a dictionary shorter than its whole tiles.
+		 * A preset dictionary (dict_pre, NULL otherwise: see
+		 * lda_dict_prep_kernel()) is the same for every buffer of the
+		 * batch: its tiles [lo_min unused bytes | dictionary tail] sit in
+		 * dict_pre + 64 and are read from there, the buffer's own bytes
+		 * follow them at position dict_len.  An empty buffer takes none. */
+		const u32 sinfo = dict_pre ? (n64 ? ((const u32 *)dict_pre)[0] : 0x80000000u) :
+				  seg_info ? seg_info[c] : 0x80000000u;
+		const u32 dict_len = sinfo & 0xFFFFu;
+		const u32 lo_min = (sinfo >> 16) & 0x7FFFu;
+		const bool seg_last = sinfo >> 31;
+		const u32 pre_len = dict_pre ? dict_len : 0;
+		inp -= pre_len;		/* (never read below pre_len) */
+		n64 += pre_len;
 		struct outstate os;
 		os.out = out_base + out_offsets[c];
 		os.avail = out_avail_arr[c];
 		const u32 hdr_bytes = format == LDA_FMT_GZIP ? 10 :
-				      format == LDA_FMT_ZLIB ? 2 : 0;
+				      format == LDA_FMT_ZLIB ? (dict_pre ? 6 : 2) : 0;
 		const u32 ftr_bytes = format == LDA_FMT_GZIP ? 8 :
 				      format == LDA_FMT_ZLIB ? 4 : 0;
 		bool overflow = false;
@@ -2259,7 +2290,15 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 					u32 fl = level < 2 ? 0 : level < 6 ? 1 :
 						 level < 8 ? 2 : 3;
 					u32 h = (0x78u << 8) | (fl << 6);
-					h |= 31 - (h % 31);
+					if (dict_pre) {
+						/* FDICT, then DICTID: the Adler-32 of the
+						 * whole dictionary, big-endian (RFC 1950 2.2) */
+						h |= 0x20;
+						h += (31 - h % 31) % 31;
+						stg_put(L, &os, 16, __builtin_bswap32(((const u32 *)dict_pre)[1]), 32);
+					} else {
+						h |= 31 - (h % 31);
+					}
 					stg_put(L, &os, 0, ((h & 0xFF) << 8) | (h >> 8), 16);
 				}
 			}
@@ -2268,16 +2307,6 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		__syncthreads();
 		stg_save(L, &os);
 
-		/* Segment mode (one large buffer cut into sub-ranges that are
-		 * compressed side by side): the first dict_len bytes (whole tiles)
-		 * of this "chunk" are the tail of the previous sub-range; they only
-		 * prime the hash chains.  Every segment but the last ends with a
-		 * non-final block and an empty stored block, so the segments'
-		 * outputs are byte aligned and concatenate into one stream
-		 * (lib/deflate_compress.c:1839-1847 is the same alignment rule). */
-		const u32 sinfo = seg_info ? seg_info[c] : 0x80000000u;
-		const u32 dict_len = sinfo & 0x7FFFFFFFu;
-		const bool seg_last = sinfo >> 31;
 		u32 loaded = 0;		/* input bytes present in the ring */
 		u32 block_start = dict_len;
 		u32 walkpos = dict_len;	/* absolute position the parse has reached */
@@ -2290,6 +2319,11 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		u32 num_tiles = (n + TILE - 1) / TILE;
 		if (num_tiles == 0)
 			num_tiles = 1;
+		if (pre_len && !stored_only && !overflow) {
+			/* the dictionary's tiles into the ring up front */
+			stage_prefix(L, dict_pre + 64, pre_len, tid);
+			loaded = pre_len;
+		}
 
 		const bool ra_all = depth <= 4;	/* a search of a few steps is done in full by the first pass */
 		const bool optm = OPT && mode == 3;
@@ -2372,11 +2406,12 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 				AS3 u32 *const MX = (AS3 u32 *)L->nxtB;
 #ifdef LDA_SMALL
 				const u32 lo_cur = 0, lo_nxt = 0;	/* the whole buffer is resident */
+				(void)lo_min;	/* (no dictionary here) */
 #else
 				const s32 lo_s = (s32)(t + 2 * TILE + LOOKAHEAD) - (s32)RING;
-				const u32 lo_cur = lo_s > 0 ? (u32)lo_s : 0;
+				const u32 lo_cur = lo_s > (s32)lo_min ? (u32)lo_s : lo_min;
 				const s32 lo_n = (s32)(tn + 2 * TILE + LOOKAHEAD) - (s32)RING;
-				const u32 lo_nxt = lo_n > 0 ? (u32)lo_n : 0;
+				const u32 lo_nxt = lo_n > (s32)lo_min ? (u32)lo_n : lo_min;
 #endif
 				u16 *c3nxt = c3g + (it & 1) * (TILE + 8);
 				u16 *c3ins = c3g + ((it + 1) & 1) * (TILE + 8);
@@ -3339,11 +3374,12 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 	const u64 *__restrict__ out_offsets,                                   \
 	const u64 *__restrict__ out_avail_arr, u64 *__restrict__ out_nbytes,   \
 	const u32 *__restrict__ sums, u64 *__restrict__ seq_scratch,           \
-	const u32 *__restrict__ seg_info, u32 *__restrict__ next_chunk
+	const u32 *__restrict__ seg_info, u32 *__restrict__ next_chunk,       \
+	const u8 *__restrict__ dict_pre
 #define DEFLATE_KERNEL_ARGS                                                    \
 	lds_raw, n_chunks, format, level, depth, nice, mode, in_base,          \
 	in_offsets, in_nbytes, out_base, out_offsets, out_avail_arr,           \
-	out_nbytes, sums, seq_scratch, seg_info, next_chunk
+	out_nbytes, sums, seq_scratch, seg_info, next_chunk, dict_pre
 
 #ifdef LDA_SMALL
 /* buffers of at most RING bytes, 256 threads, SMALL_WGS workgroups per CU

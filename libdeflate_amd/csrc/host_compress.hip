@@ -137,13 +137,40 @@ libdeflate_gzip_compress_bound(struct libdeflate_compressor *c, size_t n)
 	return 18 + libdeflate_deflate_compress_bound(c, n);
 }
 
+/*
+ * Preset dictionaries: the compress kernel's ring holds W bytes ahead of a
+ * buffer - 32 KiB minus two tiles (the kernel inserts one tile ahead) and the
+ * lookahead, in whole tiles (20 KiB).  A dictionary of `tail` = min(dict, W)
+ * bytes takes tail rounded up to whole tiles; the unused bytes in front of it
+ * are never a match source.
+ */
+static size_t dict_window(void)
+{
+	const size_t tile = lda_deflate_tile();
+	return (32768 - 2 * tile - 272) / tile * tile;
+}
+
+struct dict_shape { uint32_t tail, pre_len, sinfo; };
+
+static dict_shape shape_dict(int level, size_t dict_nbytes)
+{
+	const size_t tile = lda_deflate_tile();
+	dict_shape d;
+	/* (level 0 stores: the dictionary only changes the zlib header) */
+	d.tail = level == 0 ? 0 : (uint32_t)std::min(dict_nbytes, dict_window());
+	d.pre_len = (uint32_t)((d.tail + tile - 1) / tile * tile);
+	d.sinfo = d.pre_len | ((d.pre_len - d.tail) << 16) | 0x80000000u;
+	return d;
+}
+
 static int
 compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		    const void *d_in, const uint64_t *d_in_offsets,
 		    const uint64_t *d_in_nbytes, void *d_out,
 		    const uint64_t *d_out_offsets, const uint64_t *d_out_avail,
 		    uint64_t *d_out_nbytes, void *stream,
-		    const uint32_t *d_seg_info, size_t max_in_nbytes = SIZE_MAX)
+		    const uint32_t *d_seg_info, size_t max_in_nbytes = SIZE_MAX,
+		    const void *d_dict = NULL, size_t dict_nbytes = 0)
 {
 	if (!c) {
 		set_error("compress_batch: bad argument");
@@ -168,17 +195,41 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 	/* buffers of at most 4 KiB (filesystem blocks): the 256-thread kernel,
 	 * several workgroups per CU (deflate_small.hip); levels 10-12 keep the
 	 * big one (their parse wants its LDS) */
+	/* (a dictionary needs the ring of the big kernel: it never takes the
+	 * small one) */
+	const bool dict = d_dict && dict_nbytes;
 	const bool small = max_in_nbytes <= lda_deflate_small_max() &&
-			   c->level <= 9 && !d_seg_info && !env_cfg().no_small;
-	/* scratch: [token lists: u64 x words x grid][chunk counter][sums u32 x n] */
+			   c->level <= 9 && !d_seg_info && !dict && !env_cfg().no_small;
+	/* scratch: [token lists: u64 x words x grid][chunk counter][sums u32 x n]
+	 * [dictionary block, see lda_dict_prep_kernel()] */
 	size_t grid_max = (size_t)ctx->num_cus * (small ? lda_deflate_small_wgs() : 1);
 	size_t grid = n < grid_max ? n : grid_max;
 	size_t seq_bytes = grid * lda_deflate_seq_words() * 8;
-	uint8_t *scr = (uint8_t *)c->scratch.reserve(seq_bytes + 16 + n * 4);
+	const size_t blk_at = align_up(seq_bytes + 16 + n * 4, 64);
+	uint8_t *scr = (uint8_t *)c->scratch.reserve(
+		dict ? blk_at + LDA_DICT_BLK_HDR + dict_window() : seq_bytes + 16 + n * 4);
 	if (!scr)
 		return LIBDEFLATE_AMD_OOM;
 	uint32_t *next_chunk = (uint32_t *)(scr + seq_bytes);
 	LDA_HIP_TRY(hipMemsetAsync(next_chunk, 0, 16, st), LIBDEFLATE_AMD_NO_DEVICE);
+	uint8_t *blk = NULL;
+	if (dict) {
+		/* the prefix every buffer starts from and, for zlib, the DICTID:
+		 * both on the device, nothing waits */
+		const dict_shape sh = shape_dict(c->level, dict_nbytes);
+		blk = scr + blk_at;
+		hipLaunchKernelGGL(lda_dict_prep_kernel, dim3(1), dim3(256), 0, st,
+				   (const uint8_t *)d_dict, (uint64_t)dict_nbytes, sh.tail,
+				   sh.pre_len, sh.sinfo, blk);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		if (format == LIBDEFLATE_AMD_ZLIB) {
+			int rc = libdeflate_amd_adler32_batch(1, d_dict, (const uint64_t *)(blk + 16),
+							      (const uint64_t *)(blk + 24), NULL,
+							      (uint32_t *)(blk + 4), stream);
+			if (rc != LIBDEFLATE_AMD_OK)
+				return rc;
+		}
+	}
 	uint32_t *sums = NULL;
 	if (format != LIBDEFLATE_AMD_DEFLATE) {
 		sums = (uint32_t *)(scr + seq_bytes + 16);
@@ -215,9 +266,32 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 			   lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
 			   d_in_offsets, d_in_nbytes, (uint8_t *)d_out,
 			   d_out_offsets, d_out_avail, d_out_nbytes, sums,
-			   (uint64_t *)scr, d_seg_info, next_chunk);
+			   (uint64_t *)scr, d_seg_info, next_chunk, (const uint8_t *)blk);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	return LIBDEFLATE_AMD_OK;
+}
+
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_compress_batch_dict(struct libdeflate_compressor *c, int format,
+				   size_t n, const void *d_dict, size_t dict_nbytes,
+				   const void *d_in, const uint64_t *d_in_offsets,
+				   const uint64_t *d_in_nbytes, void *d_out,
+				   const uint64_t *d_out_offsets,
+				   const uint64_t *d_out_avail,
+				   uint64_t *d_out_nbytes, void *stream)
+{
+	/* zlib refuses a dictionary on a gzip stream */
+	if (format != LIBDEFLATE_AMD_DEFLATE && format != LIBDEFLATE_AMD_ZLIB) {
+		set_error("compress_batch_dict: format %d takes no dictionary", format);
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	if (dict_nbytes && !d_dict) {
+		set_error("compress_batch_dict: bad argument");
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	return compress_batch_impl(c, format, n, d_in, d_in_offsets, d_in_nbytes,
+				   d_out, d_out_offsets, d_out_avail,
+				   d_out_nbytes, stream, NULL, SIZE_MAX, d_dict, dict_nbytes);
 }
 
 extern "C" LIBDEFLATEAPI int
@@ -533,12 +607,16 @@ static size_t large_fail(const char *what)
  */
 static size_t compress_large(struct libdeflate_compressor *c, int format,
 			     const uint8_t *in, size_t n, uint8_t *out,
-			     size_t out_avail)
+			     size_t out_avail, const uint8_t *dict = NULL,
+			     size_t dict_nbytes = 0)
 {
 	/* sub-ranges of 64 KiB; an input that would not fill the CUs with those
-	 * is cut finer (more blocks and sync markers: ~1 % larger at 16 KiB) */
+	 * is cut finer (more blocks and sync markers: ~1 % larger at 16 KiB).
+	 * A preset dictionary's call below LDA_LARGE_MIN is one segment. */
 	size_t S = LDA_SEG_BYTES;
-	if (env_cfg().seg_bytes)
+	if (dict && n < LDA_LARGE_MIN)
+		S = n ? n : 1;
+	else if (env_cfg().seg_bytes)
 		S = env_cfg().seg_bytes;
 	else if (n <= ((size_t)4 << 20))
 		S = 16384;
@@ -547,11 +625,15 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	const size_t tile = lda_deflate_tile();
 	/* usable window is 32 KiB minus two tiles (the kernel inserts one tile
 	 * ahead) and the lookahead; whole tiles */
-	const size_t D = (32768 - 2 * tile - 272) / tile * tile;
-	const size_t nseg = (n + S - 1) / S;
+	const size_t D = dict_window();
+	const size_t nseg = n ? (n + S - 1) / S : 1;
 	const size_t slot = align_up(libdeflate_deflate_compress_bound(c, S) + 32, 16);
+	/* the caller's dictionary primes the first segment: its prefix (see
+	 * shape_dict()) lies in front of the input in the staging area */
+	const dict_shape dsh = shape_dict(c->level, dict ? dict_nbytes : 0);
+	const size_t pre = dict && n ? dsh.pre_len : 0;
 	const uint32_t hdr = format == LIBDEFLATE_AMD_GZIP ? 10 :
-			     format == LIBDEFLATE_AMD_ZLIB ? 2 : 0;
+			     format == LIBDEFLATE_AMD_ZLIB ? (dict ? 6 : 2) : 0;
 	const uint32_t ftr = format == LIBDEFLATE_AMD_GZIP ? 8 :
 			     format == LIBDEFLATE_AMD_ZLIB ? 4 : 0;
 
@@ -573,7 +655,7 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 			std::min(per_slice, nseg - k * per_slice));
 	const size_t ncmp = cmp_pos[ns];
 	const size_t desc_bytes = align_up(nseg * (7 * 8 + 4 + 4) + 64, 64);
-	const size_t cmp_at = desc_bytes, in_at = align_up(cmp_at + ncmp * 8 + 64, 64);
+	const size_t cmp_at = desc_bytes, in_at = align_up(cmp_at + ncmp * 8 + 64, 64) + pre;
 	const size_t out_at = align_up(in_at + n + 64, 64);
 	const size_t pk_at = align_up(out_at + nseg * slot + 64, 64);
 	uint8_t *st = (uint8_t *)c->stage.reserve(pk_at + nseg * slot + 64);
@@ -593,15 +675,22 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	uint64_t *in_off = &d64[0], *in_n = &d64[nseg], *out_off = &d64[2 * nseg],
 		 *out_av = &d64[3 * nseg], *pc_off = &d64[5 * nseg], *pc_n = &d64[6 * nseg];
 	for (size_t i = 0; i < nseg; i++) {
-		const size_t dict = i ? std::min(D, i * S) / tile * tile : 0;
+		const size_t prime = i ? std::min(D, i * S) / tile * tile : 0;
 		const size_t len = i + 1 < nseg ? S : n - i * S;
-		in_off[i] = in_at + i * S - dict;
-		in_n[i] = dict + len;
+		in_off[i] = in_at + i * S - prime;
+		in_n[i] = prime + len;
 		out_off[i] = out_at + i * slot;
 		out_av[i] = slot;
 		pc_off[i] = in_at + i * S;
 		pc_n[i] = len;
-		d32[i] = (uint32_t)dict | (i + 1 == nseg ? 0x80000000u : 0);
+		d32[i] = (uint32_t)prime | (i + 1 == nseg ? 0x80000000u : 0);
+	}
+	std::vector<uint8_t> prefix(pre);
+	if (pre) {
+		in_off[0] -= pre;
+		in_n[0] += pre;
+		d32[0] |= dsh.sinfo & 0x7FFFFFFFu;
+		memcpy(&prefix[pre - dsh.tail], dict + dict_nbytes - dsh.tail, dsh.tail);
 	}
 	uint64_t *d_desc = (uint64_t *)st;
 	uint32_t *d_seg = (uint32_t *)(st + 7 * 8 * nseg);
@@ -614,7 +703,9 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	uint64_t *h_out_n = h_back, *h_tot = h_back + nseg;
 	uint32_t *h_sums = (uint32_t *)(h_back + nseg + ns);
 	if (hipMemcpyAsync(d_desc, d64.data(), 7 * 8 * nseg, hipMemcpyHostToDevice, s_copy) != hipSuccess ||
-	    hipMemcpyAsync(d_seg, d32.data(), 4 * nseg, hipMemcpyHostToDevice, s_copy) != hipSuccess)
+	    hipMemcpyAsync(d_seg, d32.data(), 4 * nseg, hipMemcpyHostToDevice, s_copy) != hipSuccess ||
+	    (pre && hipMemcpyAsync(st + in_at - pre, prefix.data(), pre, hipMemcpyHostToDevice,
+				   s_copy) != hipSuccess))
 		return large_fail("copy in");
 	std::vector<hipEvent_t> ev_done(ns, nullptr);
 	/* A call of one slice (up to 32 MiB) takes the copy helpers' own pieces:
@@ -656,7 +747,8 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 		const size_t a = lo * S, b = std::min(n, (lo + nk) * S);
 		/* (returns when the slice - and, the first time, the descriptors -
 		 * are on the device) */
-		if (span_in(&c->pinned, st, in_at + a, in + a, b - a, s_copy, piece) != LIBDEFLATE_AMD_OK) {
+		if (b > a ? span_in(&c->pinned, st, in_at + a, in + a, b - a, s_copy, piece) != LIBDEFLATE_AMD_OK :
+			    hipStreamSynchronize(s_copy) != hipSuccess) {
 			failed = true;
 			break;
 		}
@@ -721,7 +813,16 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 			ad = i ? adler32_concat(ad, h_sums[i], pc_n[i]) : h_sums[0];
 		uint32_t fl = c->level < 2 ? 0 : c->level < 6 ? 1 : c->level < 8 ? 2 : 3;
 		uint32_t hw = (0x78u << 8) | (fl << 6);
-		hw |= 31 - (hw % 31);
+		if (dict) {
+			/* FDICT and DICTID (RFC 1950 2.2) */
+			hw |= 0x20;
+			hw += (31 - hw % 31) % 31;
+			const uint32_t id = libdeflate_adler32(1, dict, dict_nbytes);
+			for (int k = 0; k < 4; k++)
+				out[2 + k] = (uint8_t)(id >> (8 * (3 - k)));
+		} else {
+			hw |= 31 - (hw % 31);
+		}
 		out[0] = (uint8_t)(hw >> 8);
 		out[1] = (uint8_t)hw;
 		for (int k = 0; k < 4; k++)
@@ -785,4 +886,32 @@ libdeflate_gzip_compress(struct libdeflate_compressor *c, const void *in,
 			 size_t in_nbytes, void *out, size_t out_avail)
 {
 	return compress_one(c, LIBDEFLATE_AMD_GZIP, in, in_nbytes, out, out_avail);
+}
+
+/* include/libdeflate_amd.h: one host buffer with a preset dictionary - the
+ * segmented path, its first segment primed with the dictionary */
+extern "C" LIBDEFLATEAPI size_t
+libdeflate_amd_compress_dict(struct libdeflate_compressor *c, int format,
+			     const void *dict, size_t dict_nbytes, const void *in,
+			     size_t in_nbytes, void *out, size_t out_avail)
+{
+	if (format != LIBDEFLATE_AMD_DEFLATE && format != LIBDEFLATE_AMD_ZLIB) {
+		set_error("libdeflate_amd_compress_dict: format %d takes no dictionary", format);
+		return 0;
+	}
+	if (!dict_nbytes)
+		return compress_one(c, format, in, in_nbytes, out, out_avail);
+	if (!c || !dict || (!in && in_nbytes) || !out) {
+		set_error("libdeflate_amd_compress_dict: bad argument");
+		return 0;
+	}
+	DeviceGuard on(c->device);
+	if (!on.ok()) {
+		complain("libdeflate_amd_compress_dict", LIBDEFLATE_AMD_NO_DEVICE);
+		return 0;
+	}
+	return no_unwind("libdeflate_amd_compress_dict", (size_t)0, [&]() {
+		return compress_large(c, format, (const uint8_t *)in, in_nbytes, (uint8_t *)out,
+				      out_avail, (const uint8_t *)dict, dict_nbytes);
+	});
 }

@@ -165,15 +165,15 @@ libdeflate_free_decompressor(struct libdeflate_decompressor *d)
 
 /* ------------------------------------------------------------------ */
 
-extern "C" LIBDEFLATEAPI int
-libdeflate_amd_decompress_batch(struct libdeflate_decompressor *d, int format,
-				size_t n, const void *d_in,
-				const uint64_t *d_in_offsets,
-				const uint64_t *d_in_nbytes, void *d_out,
-				const uint64_t *d_out_offsets,
-				const uint64_t *d_out_avail, int32_t *d_results,
-				uint64_t *d_actual_in, uint64_t *d_actual_out,
-				void *stream)
+static int
+decompress_batch_impl(struct libdeflate_decompressor *d, int format,
+		      size_t n, const void *d_in,
+		      const uint64_t *d_in_offsets,
+		      const uint64_t *d_in_nbytes, void *d_out,
+		      const uint64_t *d_out_offsets,
+		      const uint64_t *d_out_avail, int32_t *d_results,
+		      uint64_t *d_actual_in, uint64_t *d_actual_out,
+		      void *stream, const void *d_dict = NULL, size_t dict_nbytes = 0)
 {
 	if (!d) {
 		set_error("decompress_batch: bad argument");
@@ -195,11 +195,37 @@ libdeflate_amd_decompress_batch(struct libdeflate_decompressor *d, int format,
 		set_error("decompress_batch: bad argument");
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
-	/* scratch: [sums u32 x n][actual_in u64 x n][actual_out u64 x n][order u32 x n] */
+	/* scratch: [sums u32 x n][actual_in u64 x n][actual_out u64 x n][order u32 x n]
+	 * [dictionary block: its header, see lda_dict_prep_kernel()] */
 	size_t sums_bytes = align_up(n * 4, 16);
-	uint8_t *s = (uint8_t *)d->scratch.reserve(sums_bytes + 16 * n + 4 * n + 16);
+	const bool dict = d_dict && dict_nbytes;
+	const size_t blk_at = align_up(sums_bytes + 16 * n + 4 * n + 16, 64);
+	uint8_t *s = (uint8_t *)d->scratch.reserve(dict ? blk_at + LDA_DICT_BLK_HDR :
+							  sums_bytes + 16 * n + 4 * n + 16);
 	if (!s)
 		return LIBDEFLATE_AMD_OOM;
+	/* a preset dictionary: its last 32 KiB are what a distance can reach,
+	 * its Adler-32 (the DICTID a zlib stream names) is computed here, on
+	 * the device */
+	const uint8_t *dtail = NULL;
+	uint32_t dlen = 0;
+	uint32_t *dict_id = NULL;
+	if (dict) {
+		dlen = (uint32_t)(dict_nbytes < 32768 ? dict_nbytes : 32768);
+		dtail = (const uint8_t *)d_dict + dict_nbytes - dlen;
+		uint8_t *blk = s + blk_at;
+		hipLaunchKernelGGL(lda_dict_prep_kernel, dim3(1), dim3(64), 0, st,
+				   (const uint8_t *)d_dict, (uint64_t)dict_nbytes, 0u, 0u, 0u, blk);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		if (format == LIBDEFLATE_AMD_ZLIB) {
+			dict_id = (uint32_t *)(blk + 4);
+			int rc = libdeflate_amd_adler32_batch(1, d_dict, (const uint64_t *)(blk + 16),
+							      (const uint64_t *)(blk + 24), NULL, dict_id,
+							      stream);
+			if (rc != LIBDEFLATE_AMD_OK)
+				return rc;
+		}
+	}
 	uint32_t *sums = (uint32_t *)s;
 	uint64_t *ain = d_actual_in ? d_actual_in : (uint64_t *)(s + sums_bytes);
 	uint64_t *aout = d_actual_out ? d_actual_out :
@@ -262,7 +288,7 @@ libdeflate_amd_decompress_batch(struct libdeflate_decompressor *d, int format,
 				   (const uint32_t *)order,
 				   (const uint8_t *)d_in, d_in_offsets, d_in_nbytes,
 				   (uint8_t *)d_out, d_out_offsets, d_out_avail,
-				   d_results, ain, aout);
+				   d_results, ain, aout, dtail, dlen, (const uint32_t *)dict_id);
 	} else {
 		size_t lds = lda_inflate_lds_per_stream() * lpw +
 			     lda_inflate_lds_shared();
@@ -271,7 +297,7 @@ libdeflate_amd_decompress_batch(struct libdeflate_decompressor *d, int format,
 				   lds, st, (uint64_t)n, format, lpw,
 				   (const uint8_t *)d_in, d_in_offsets, d_in_nbytes,
 				   (uint8_t *)d_out, d_out_offsets, d_out_avail,
-				   d_results, ain, aout);
+				   d_results, ain, aout, dtail, dlen, (const uint32_t *)dict_id);
 	}
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	if (format != LIBDEFLATE_AMD_DEFLATE) {
@@ -292,6 +318,45 @@ libdeflate_amd_decompress_batch(struct libdeflate_decompressor *d, int format,
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
 	return LIBDEFLATE_AMD_OK;
+}
+
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_decompress_batch(struct libdeflate_decompressor *d, int format,
+				size_t n, const void *d_in,
+				const uint64_t *d_in_offsets,
+				const uint64_t *d_in_nbytes, void *d_out,
+				const uint64_t *d_out_offsets,
+				const uint64_t *d_out_avail, int32_t *d_results,
+				uint64_t *d_actual_in, uint64_t *d_actual_out,
+				void *stream)
+{
+	return decompress_batch_impl(d, format, n, d_in, d_in_offsets, d_in_nbytes, d_out,
+				     d_out_offsets, d_out_avail, d_results, d_actual_in,
+				     d_actual_out, stream);
+}
+
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_decompress_batch_dict(struct libdeflate_decompressor *d, int format,
+				     size_t n, const void *d_dict, size_t dict_nbytes,
+				     const void *d_in, const uint64_t *d_in_offsets,
+				     const uint64_t *d_in_nbytes, void *d_out,
+				     const uint64_t *d_out_offsets,
+				     const uint64_t *d_out_avail, int32_t *d_results,
+				     uint64_t *d_actual_in, uint64_t *d_actual_out,
+				     void *stream)
+{
+	/* zlib refuses a dictionary on a gzip stream */
+	if (format != LIBDEFLATE_AMD_DEFLATE && format != LIBDEFLATE_AMD_ZLIB) {
+		set_error("decompress_batch_dict: format %d takes no dictionary", format);
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	if (dict_nbytes && !d_dict) {
+		set_error("decompress_batch_dict: bad argument");
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	return decompress_batch_impl(d, format, n, d_in, d_in_offsets, d_in_nbytes, d_out,
+				     d_out_offsets, d_out_avail, d_results, d_actual_in,
+				     d_actual_out, stream, d_dict, dict_nbytes);
 }
 
 static int decompress_batch_host_body(struct libdeflate_decompressor *d,
@@ -705,4 +770,91 @@ decompress_members_body(struct libdeflate_decompressor *d,
 	if (members_ret)
 		*members_ret = members;
 	return LIBDEFLATE_SUCCESS;
+}
+
+/*
+ * One host buffer with a preset dictionary: a batch of one on the object's
+ * compute stream (the many-wave path of host_stream.hip takes no
+ * dictionary).  Staging: [in_off in_n out_off out_av ain aout][result]
+ * [dictionary][input][output].
+ */
+static enum libdeflate_result
+decompress_dict_body(struct libdeflate_decompressor *d, int format, const void *dict,
+		     size_t dict_nbytes, const void *in, size_t in_nbytes, void *out,
+		     size_t out_avail, size_t *actual_in_ret, size_t *actual_out_ret)
+{
+	DeviceGuard on(d->device);
+	if (!on.ok() || !device_ctx()) {
+		complain("libdeflate_amd_decompress_dict_ex", LIBDEFLATE_AMD_NO_DEVICE);
+		return LIBDEFLATE_BAD_DATA;	/* see decompress_one() */
+	}
+	const size_t dict_at = 64, in_at = align_up(dict_at + dict_nbytes, 64);
+	const size_t out_at = align_up(in_at + in_nbytes + 16, 64);
+	uint8_t *st = (uint8_t *)d->stage.reserve(out_at + out_avail + 64);
+	if (!st || !d->streams.ensure()) {
+		complain("libdeflate_amd_decompress_dict_ex", st ? LIBDEFLATE_AMD_NO_DEVICE :
+									   LIBDEFLATE_AMD_OOM);
+		return LIBDEFLATE_BAD_DATA;
+	}
+	hipStream_t sc = d->streams.comp;
+	uint64_t desc[6] = { in_at, in_nbytes, out_at, out_avail, 0, 0 };
+	uint64_t *dd = (uint64_t *)st;
+	int32_t res = LIBDEFLATE_BAD_DATA;
+	int rc = LIBDEFLATE_AMD_OK;
+	if (hipMemcpyAsync(st, desc, sizeof(desc), hipMemcpyHostToDevice, sc) != hipSuccess ||
+	    hipMemcpyAsync(st + dict_at, dict, dict_nbytes, hipMemcpyHostToDevice, sc) != hipSuccess ||
+	    (in_nbytes && hipMemcpyAsync(st + in_at, in, in_nbytes, hipMemcpyHostToDevice,
+					 sc) != hipSuccess))
+		rc = LIBDEFLATE_AMD_NO_DEVICE;
+	if (rc == LIBDEFLATE_AMD_OK)
+		rc = decompress_batch_impl(d, format, 1, st, dd, dd + 1, st, dd + 2, dd + 3,
+					   (int32_t *)(st + 48), dd + 4,
+					   actual_out_ret ? dd + 5 : NULL, sc, st + dict_at,
+					   dict_nbytes);
+	if (rc == LIBDEFLATE_AMD_OK &&
+	    (hipMemcpyAsync(desc, st, sizeof(desc), hipMemcpyDeviceToHost, sc) != hipSuccess ||
+	     hipMemcpyAsync(&res, st + 48, 4, hipMemcpyDeviceToHost, sc) != hipSuccess ||
+	     hipStreamSynchronize(sc) != hipSuccess))
+		rc = LIBDEFLATE_AMD_NO_DEVICE;
+	if (rc == LIBDEFLATE_AMD_OK && res == LIBDEFLATE_SUCCESS) {
+		const size_t nout = actual_out_ret ? desc[5] : out_avail;
+		if (nout && hipMemcpy(out, st + out_at, nout, hipMemcpyDeviceToHost) != hipSuccess)
+			rc = LIBDEFLATE_AMD_NO_DEVICE;
+	}
+	if (rc != LIBDEFLATE_AMD_OK) {
+		(void)hipStreamSynchronize(sc);
+		complain("libdeflate_amd_decompress_dict_ex", rc);
+		return LIBDEFLATE_BAD_DATA;
+	}
+	if (res == LIBDEFLATE_SUCCESS) {
+		if (actual_in_ret)
+			*actual_in_ret = desc[4];
+		if (actual_out_ret)
+			*actual_out_ret = desc[5];
+	}
+	return (enum libdeflate_result)res;
+}
+
+extern "C" LIBDEFLATEAPI enum libdeflate_result
+libdeflate_amd_decompress_dict_ex(struct libdeflate_decompressor *d, int format,
+				  const void *dict, size_t dict_nbytes, const void *in,
+				  size_t in_nbytes, void *out, size_t out_avail,
+				  size_t *actual_in_ret, size_t *actual_out_ret)
+{
+	if (format != LIBDEFLATE_AMD_DEFLATE && format != LIBDEFLATE_AMD_ZLIB) {
+		set_error("libdeflate_amd_decompress_dict_ex: format %d takes no dictionary",
+			  format);
+		return LIBDEFLATE_BAD_DATA;
+	}
+	if (!dict_nbytes)
+		return decompress_one(d, format, in, in_nbytes, out, out_avail, actual_in_ret,
+				      actual_out_ret);
+	if (!d || !dict || (!in && in_nbytes) || (!out && out_avail)) {
+		set_error("libdeflate_amd_decompress_dict_ex: bad argument");
+		return LIBDEFLATE_BAD_DATA;
+	}
+	return no_unwind("libdeflate_amd_decompress_dict_ex", LIBDEFLATE_BAD_DATA, [&]() {
+		return decompress_dict_body(d, format, dict, dict_nbytes, in, in_nbytes, out,
+					    out_avail, actual_in_ret, actual_out_ret);
+	});
 }

@@ -1046,7 +1046,8 @@ static __device__ u32
 par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	  const slds_t *S, const shlds_t *SH,
 	  u32 *__restrict__ tok, lu8 *win, lu8 *stage, u64 ring_lo, u32 lane,
-	  u64 bpos_abs, u64 out0, u64 *bpos_ret, u64 *out_ret, u32 ltb, u32 otb)
+	  u64 bpos_abs, u64 out0, u64 *bpos_ret, u64 *out_ret, u32 ltb, u32 otb,
+	  const u8 *__restrict__ dict, u32 dlen)
 {
 	const u32 lmask = (1u << ltb) - 1, omask = (1u << otb) - 1;	/* wave-uniform */
 	/* lanes in this round: one PAR_CB-bit chunk each, up to the end of the
@@ -1388,7 +1389,7 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 				 * ballot of a compound predicate goes through a 0 / 1 detour
 				 * in a vector register), and the four slots share ONE
 				 * section: nothing of it runs when the batch has no such byte */
-				u64 mfar[SB], anyfar = 0, anyneed = 0;
+				u64 mfar[SB], anyfar = 0, anyneed = 0, tfar = 0;
 #pragma unroll
 				for (u32 k = 0; k < SB; k++) {
 					const u32 bi = s0 + 64 * k + lane, tw = own[k];
@@ -1397,7 +1398,7 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 					const u64 before = __ballot((s32)tw < 0) & __ballot(dist > bi);
 					const u64 toofar = before & __ballot(back > back_max);
 					mfar[k] = before & ~toofar & __ballot(back > ring_rel);
-					badm |= toofar;
+					tfar |= toofar;
 					anyfar |= mfar[k];
 					/* a source at or above safe_hi was stored by this wave
 					 * after its last wait: see below */
@@ -1424,6 +1425,25 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 							vfar[k] = gfar[bi + 32768u - dist];
 					}
 				}
+				if (tfar && dlen) {
+					/* a preset dictionary: sources up to dlen bytes in
+					 * front of the stream are its last bytes */
+					u64 still = 0;
+#pragma unroll
+					for (u32 k = 0; k < SB; k++) {
+						const u32 bi = s0 + 64 * k + lane, tw = own[k];
+						const u32 dist = (tw >> 9) & 0xFFFF;
+						const u32 back = dist - bi;
+						const u64 tf = __ballot((s32)tw < 0) & __ballot(dist > bi) &
+							       __ballot(back > back_max);
+						const u64 ind = tf & __ballot(back - gb <= dlen);
+						if (lane_bit(ind))
+							vfar[k] = dict[dlen - (back - gb)];
+						still |= tf & ~ind;
+					}
+					tfar = still;
+				}
+				badm |= tfar;
 				/* copies inside a slot: where each lane's byte finally comes
 				 * from.  That depends on the tokens alone, so the SB slots'
 				 * pointer chains are jumped together (their latencies
@@ -1530,7 +1550,11 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	      const u64 *__restrict__ out_avail_arr,
 	      s32 *__restrict__ results,
 	      u64 *__restrict__ actual_in,	/* incl. container header */
-	      u64 *__restrict__ actual_out)
+	      u64 *__restrict__ actual_out,
+	      /* a preset dictionary (NULL: none): its last dict_len (<= 32 KiB)
+	       * bytes, and the Adler-32 of all of it */
+	      const u8 *__restrict__ dict, u32 dict_len,
+	      const u32 *__restrict__ dict_id)
 {
 	slds_t *SL = (slds_t *)lds_raw;
 	const u32 lane = threadIdx.x;
@@ -1562,6 +1586,7 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	u64 in_n = 0, out_avail = 0;
 	u8 *outp = out_base;
 	u32 hdr = 0;
+	u32 dlen = dict ? dict_len : 0;	/* bytes of dictionary in front of the output */
 	s32 result = LDA_SUCCESS;
 	u32 state = ST_DONE;
 
@@ -1578,11 +1603,26 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 				result = LDA_BAD_DATA;
 			} else {
 				u32 h = ((u32)inp[0] << 8) | inp[1];
+				const bool fdict = (h >> 5) & 1;
 				if (h % 31 || ((h >> 8) & 0xF) != 8 || (h >> 12) > 7 ||
-				    ((h >> 5) & 1))
+				    (fdict && !dict_id))
 					result = LDA_BAD_DATA;
 				hdr = 2;
 				in_n -= 6;
+				/* FDICT: DICTID names the dictionary (RFC 1950 2.2);
+				 * a stream without it has none, as with zlib */
+				if (result == LDA_SUCCESS && fdict) {
+					if (in_n < 4 ||
+					    (((u32)inp[2] << 24) | ((u32)inp[3] << 16) |
+					     ((u32)inp[4] << 8) | inp[5]) != *dict_id) {
+						result = LDA_BAD_DATA;
+					} else {
+						hdr = 6;
+						in_n -= 4;
+					}
+				}
+				if (!fdict)
+					dlen = 0;
 			}
 		} else if (format == LDA_FMT_GZIP) {
 			/* lib/gzip_decompress.c:45-107 */
@@ -1960,7 +2000,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 						   bcast64(out_avail), &SL[0], SH, tok,
 						   (lu8 *)(SH + 1), (lu8 *)(SH + 1) + PAR_RW,
 						   ring_lo, lane, bpos0, o0,
-						   &nb, &no, bcast_first(ltb), bcast_first(otb));
+						   &nb, &no, bcast_first(ltb), bcast_first(otb),
+						   dict, bcast_first(dlen));
 
 				PROF_COUNT(12 + pr, 1);
 				if (pr == PAR_STOP)
@@ -2188,8 +2229,19 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			u32 dist = base + ((u32)bitbuf & ((1u << xb) - 1));
 			CONSUME(xb);
 			if (dist > out_pos) {
-				result = LDA_BAD_DATA;
-				state = ST_DONE;
+				if (dist - out_pos > dlen) {
+					result = LDA_BAD_DATA;
+					state = ST_DONE;
+					continue;
+				}
+				/* the source begins in the preset dictionary: byte by
+				 * byte, the first dist - out_pos of them from there */
+				const u32 nd = (u32)(dist - out_pos);
+				for (u32 j = 0; j < length; j++)
+					outp[out_pos + j] = j < nd ? dict[dlen - nd + j] :
+								     outp[out_pos + j - dist];
+				hist_n = 0;
+				out_pos += length;
 				continue;
 			}
 			/* the lane copies from its own earlier output; short
@@ -2293,13 +2345,15 @@ lda_inflate_batch_kernel(u64 n_chunks, int format, u32 lpw,
 			 const u64 *__restrict__ out_avail_arr,
 			 s32 *__restrict__ results,
 			 u64 *__restrict__ actual_in,
-			 u64 *__restrict__ actual_out)
+			 u64 *__restrict__ actual_out,
+			 const u8 *__restrict__ dict, u32 dict_len,
+			 const u32 *__restrict__ dict_id)
 {
 	lu8 *lds_raw = (lu8 *)(uintptr_t)0;
 
 	inflate_block(blockIdx.x, lds_raw, 0, NULL, n_chunks, format, lpw, in_base,
 		      in_offsets, in_nbytes, out_base, out_offsets, out_avail_arr,
-		      results, actual_in, actual_out);
+		      results, actual_in, actual_out, dict, dict_len, dict_id);
 }
 
 /*
@@ -2377,7 +2431,9 @@ lda_inflate_wave_kernel(u64 n_chunks, int format, u32 *__restrict__ tokscratch,
 			const u64 *__restrict__ out_avail_arr,
 			s32 *__restrict__ results,
 			u64 *__restrict__ actual_in,
-			u64 *__restrict__ actual_out)
+			u64 *__restrict__ actual_out,
+			const u8 *__restrict__ dict, u32 dict_len,
+			const u32 *__restrict__ dict_id)
 {
 	lu8 *lds_raw = (lu8 *)(uintptr_t)0;
 	u32 *tok = tokscratch + (size_t)blockIdx.x * PAR_SCRATCH;
@@ -2403,7 +2459,8 @@ lda_inflate_wave_kernel(u64 n_chunks, int format, u32 *__restrict__ tokscratch,
 		/* (order: see lda_inflate_order_kernel(); NULL = index order) */
 		inflate_block(order ? order[blk] : blk, lds_raw, 1, tok, n_chunks, format, 1, in_base,
 			      in_offsets, in_nbytes, out_base, out_offsets,
-			      out_avail_arr, results, actual_in, actual_out);
+			      out_avail_arr, results, actual_in, actual_out, dict, dict_len,
+			      dict_id);
 		wave_sync();
 		u32 nx = 0;
 		if (lane_id() == 0)

@@ -18,6 +18,11 @@ extern "C" __global__ void
 lda_adler32_batch_kernel(uint64_t n_chunks, const uint8_t *base,
 			 const uint64_t *offsets, const uint64_t *nbytes,
 			 const uint32_t *init, uint32_t *out);
+/* a preset dictionary's per-batch block (layout in checksum_kernels.hip) */
+#define LDA_DICT_BLK_HDR 64
+extern "C" __global__ void
+lda_dict_prep_kernel(const uint8_t *dict, uint64_t dict_nbytes, uint32_t tail,
+		     uint32_t pre_len, uint32_t sinfo, uint8_t *blk);
 
 /* inflate_kernel.hip */
 extern "C" __global__ void
@@ -26,7 +31,9 @@ lda_inflate_batch_kernel(uint64_t n_chunks, int format, uint32_t lpw,
 			 const uint64_t *in_offsets, const uint64_t *in_nbytes,
 			 uint8_t *out_base, const uint64_t *out_offsets,
 			 const uint64_t *out_avail, int32_t *results,
-			 uint64_t *actual_in, uint64_t *actual_out);
+			 uint64_t *actual_in, uint64_t *actual_out,
+			 const uint8_t *dict, uint32_t dict_len,
+			 const uint32_t *dict_id);
 extern "C" __global__ void
 lda_inflate_wave_kernel(uint64_t n_chunks, int format, uint32_t *tokscratch,
 			uint32_t *next_stream, const uint32_t *order,
@@ -34,7 +41,9 @@ lda_inflate_wave_kernel(uint64_t n_chunks, int format, uint32_t *tokscratch,
 			const uint64_t *in_offsets, const uint64_t *in_nbytes,
 			uint8_t *out_base, const uint64_t *out_offsets,
 			const uint64_t *out_avail, int32_t *results,
-			uint64_t *actual_in, uint64_t *actual_out);
+			uint64_t *actual_in, uint64_t *actual_out,
+			const uint8_t *dict, uint32_t dict_len,
+			const uint32_t *dict_id);
 extern "C" __global__ void
 lda_inflate_order_kernel(uint64_t n, const uint64_t *in_nbytes, const uint64_t *out_avail,
 			 uint32_t *order);
@@ -57,7 +66,7 @@ lda_deflate_batch_kernel(uint64_t n_chunks, int format, int level,
 			 const uint64_t *out_offsets, const uint64_t *out_avail,
 			 uint64_t *out_nbytes, const uint32_t *sums,
 			 uint64_t *seq_scratch, const uint32_t *seg_info,
-			 uint32_t *next_chunk);
+			 uint32_t *next_chunk, const uint8_t *dict_pre);
 /* same body with the min-cost parse compiled in: levels 10-12 */
 extern "C" __global__ void
 lda_deflate_opt_kernel(uint64_t n_chunks, int format, int level,
@@ -67,7 +76,7 @@ lda_deflate_opt_kernel(uint64_t n_chunks, int format, int level,
 		       const uint64_t *out_offsets, const uint64_t *out_avail,
 		       uint64_t *out_nbytes, const uint32_t *sums,
 		       uint64_t *seq_scratch, const uint32_t *seg_info,
-		       uint32_t *next_chunk);
+		       uint32_t *next_chunk, const uint8_t *dict_pre);
 /* deflate_small.hip: buffers of at most lda_deflate_small_max() bytes */
 #define LDA_DEFLATE_SMALL_THREADS 256
 extern "C" __global__ void
@@ -78,7 +87,7 @@ lda_deflate_small_kernel(uint64_t n_chunks, int format, int level,
 			 const uint64_t *out_offsets, const uint64_t *out_avail,
 			 uint64_t *out_nbytes, const uint32_t *sums,
 			 uint64_t *seq_scratch, const uint32_t *seg_info,
-			 uint32_t *next_chunk);
+			 uint32_t *next_chunk, const uint8_t *dict_pre);
 extern "C" size_t lda_deflate_small_lds_bytes(void);
 extern "C" size_t lda_deflate_small_max(void);
 extern "C" size_t lda_deflate_small_wgs(void);	/* workgroups per CU it is built for */
