@@ -275,8 +275,11 @@ libdeflate_amd_compress_batch(struct libdeflate_compressor *compressor,
  * kernel that keeps three chunks per CU in flight instead of one.  The bound
  * is a promise, and it is only CHECKED where it selects that kernel (bound <=
  * 4096, levels 0-9): there a chunk larger than the bound reports 0, like one
- * that does not fit its slot.  With any other bound, or at levels 10-12, the
- * ordinary kernel runs and takes chunks of any size.
+ * that does not fit its slot.  With any other bound, or at levels 10-12,
+ * chunks of any size are compressed.  (At levels 0-9 a batch of at least four
+ * chunks per CU runs in two kernels whose scratch is sized by the bound; a
+ * chunk larger than the bound is compressed by the one-kernel path behind
+ * them, into the same bytes.)
  */
 LIBDEFLATEAPI int
 libdeflate_amd_compress_batch_bounded(struct libdeflate_compressor *compressor,

@@ -70,7 +70,9 @@ class Compressor:
         int64 descriptors).  Enqueues on `stream` (torch stream or None).
         max_chunk: an upper bound of the chunk sizes, if the caller knows one
         (libdeflate_amd_compress_batch_bounded: small chunks get their own
-        kernel)."""
+        kernel, and at levels 0-9 large batches split the block end off into
+        a kernel of its own).  Only a bound <= 4096 is enforced: a chunk above
+        it reports 0; above any larger bound a chunk is still compressed."""
         if max_chunk is None:
             check(self._lib.libdeflate_amd_compress_batch(
                 self._h, FORMATS[fmt], in_offsets.numel(), data.data_ptr(),

@@ -4,6 +4,13 @@
  * lib/deflate_compress.c:759-1396 (deflate_make_huffman_code and its helpers)
  * do, by one wave.
  */
+/* number of set bits of a wave-uniform mask below this lane */
+static __device__ __forceinline__ u32 rank_below(u64 uniform_mask)
+{
+	return __builtin_amdgcn_mbcnt_hi((u32)(uniform_mask >> 32),
+					 __builtin_amdgcn_mbcnt_lo((u32)uniform_mask, 0));
+}
+
 /* ---------------- Huffman code construction (wave 0) ---------------- */
 
 /*

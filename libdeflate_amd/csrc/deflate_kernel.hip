@@ -54,6 +54,15 @@
  *       bit lengths gives the bit offset, ds_or packs the bits into an LDS
  *       staging buffer that is written to HBM with coalesced stores.
  *
+ * S5 and S6 are block_emit() of deflate_blockend.h.  Levels 0-9 of a batch
+ * with a size bound do not run them here: lda_deflate_batch_kernel writes a
+ * descriptor per block (histogram, token range, byte range) and goes on with
+ * the next tile, and lda_deflate_entropy_kernel (deflate_entropy.hip) writes
+ * the streams from the descriptors with small workgroups, several per CU.
+ * lda_deflate_fused_kernel (no bound: the token lists cannot be sized),
+ * lda_deflate_opt_kernel and the small-buffer kernel keep them in the tile
+ * loop.
+ *
  * HBM traffic beyond input-once / output-once: the token list (4 B per token,
  * written in S4, read in S6) and the 3-byte-table candidates (2 B per
  * position, from the inserting wave to the next tile's round A).  The
@@ -116,7 +125,6 @@
 #define S3_TAIL 256u		/* positions at the end of a tile searched with reduced depth */
 #define S3_CLAIM 24u		/* finished lanes that trigger a claim pass */
 #define S3_RA_DEPTH 2u		/* chain members the shallow pass measures at every position */
-#define S6_ALWAYS_FLUSH 0
 #define S3_HALF_SHIFT 1		/* the look-ahead positions are searched to depth >> this (the reference: 1) */
 #define S3_HALF 1		/* 0: the lazy rule's look-ahead positions are not searched deeper */
 #define P1_PASSES 0xFFFFFFFFu	/* passes of the first (worklist) parse */
@@ -297,85 +305,6 @@ static __device__ __forceinline__ bool lane_bit(u64 uniform_mask)
 	return __builtin_amdgcn_inverse_ballot_w64(uniform_mask);
 }
 
-/* number of set bits of a wave-uniform mask below this lane */
-static __device__ __forceinline__ u32 rank_below(u64 uniform_mask)
-{
-	return __builtin_amdgcn_mbcnt_hi((u32)(uniform_mask >> 32),
-					 __builtin_amdgcn_mbcnt_lo((u32)uniform_mask, 0));
-}
-
-/* workgroup exclusive scan of one value per thread; returns the exclusive
- * prefix and writes the total to *total.  Two barriers. */
-static __device__ u32 block_scan(lds_t *L, u32 v, u32 *total)
-{
-	const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	u32 incl = wave_scan_incl(v);
-
-	if (lane == 63)
-		L->scan[0][wave] = incl;
-	__syncthreads();
-	/* the waves' sums one per lane, a wave scan over them (a loop over the
-	 * sixteen words is six times the instructions, on every wave's path) */
-	const u32 sw = lane < NWAVES ? L->scan[0][lane] : 0;
-	const u32 iw = wave_scan_incl(sw);
-	const u32 base = bcast_lane(iw - sw, wave);
-	__syncthreads();
-	*total = bcast_lane(iw, NWAVES - 1);
-	return base + incl - v;
-}
-
-/* the same with ONE barrier: the partial sums alternate between two arrays
- * (*tog flips per call, uniformly), so a fast thread's next call cannot
- * overwrite what a slow thread still reads.  Every second call reuses an
- * array, and the barrier of the call in between orders that. */
-static __device__ u32 block_scan1(lds_t *L, u32 v, u32 *total,
-				  u32 *tog)
-{
-	const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	u32 incl = wave_scan_incl(v);
-	u32 *sc = L->scan[*tog];
-
-	*tog ^= 1;
-	if (lane == 63)
-		sc[wave] = incl;
-	__syncthreads();
-	const u32 sw = lane < NWAVES ? sc[lane] : 0;
-	const u32 iw = wave_scan_incl(sw);
-	*total = bcast_lane(iw, NWAVES - 1);
-	return bcast_lane(iw - sw, wave) + incl - v;
-}
-
-/* length slot / extra bits (lib/deflate_compress.c:237-308 tables, computed) */
-static __device__ __forceinline__ void
-length_code(u32 len, u32 *slot, u32 *xbits, u32 *xval)
-{
-	u32 l = len - 3;
-	if (l < 8) {
-		*slot = l; *xbits = 0; *xval = 0;
-	} else if (len == 258) {
-		*slot = 28; *xbits = 0; *xval = 0;
-	} else {
-		u32 hb = 31 - __builtin_clz(l);
-		*xbits = hb - 2;
-		*slot = 4 * (hb - 1) + ((l >> (hb - 2)) & 3);
-		*xval = l & ((1u << (hb - 2)) - 1);
-	}
-}
-
-static __device__ __forceinline__ void
-dist_code(u32 dist, u32 *slot, u32 *xbits, u32 *xval)
-{
-	u32 d = dist - 1;
-	if (d < 4) {
-		*slot = d; *xbits = 0; *xval = 0;
-	} else {
-		u32 hb = 31 - __builtin_clz(d);
-		*xbits = hb - 1;
-		*slot = 2 * hb + ((d >> (hb - 1)) & 1);
-		*xval = d & ((1u << (hb - 1)) - 1);
-	}
-}
-
 /*
  * Minimum useful match length from the number of distinct literals in use:
  * with few distinct literals a literal is so cheap that short matches lose.
@@ -475,107 +404,9 @@ token_step(u32 m0, u32 m1, u32 m2, u32 mode, u32 nice)
 	return l0 == 0 ? 1 : st;
 }
 
-#include "deflate_opt.h"
 #include "deflate_huffman.h"
-
-/* ---------------- bit output through the LDS staging area ---------------- */
-
-struct outstate {
-	u8 *out;		/* output slot of this buffer */
-	u64 avail;
-	u64 sg;			/* global byte offset (relative to out, may be
-				 * negative via wrap) of staging word 0; 16-aligned
-				 * as an absolute address */
-	u64 bits;		/* bits produced so far, relative to out[0] */
-};
-
-static __device__ __forceinline__ u32 *stg_of(lds_t *L)
-{
-	return (u32 *)L->nxtA;
-}
-
-/* OR 'nbits' (<= 57) bits of 'code' at absolute bit position 'bitpos' */
-static __device__ __forceinline__ void
-stg_put(lds_t *L, const struct outstate *os, u64 bitpos, u64 code,
-	u32 nbits)
-{
-	if (!nbits)
-		return;
-	u64 rel = bitpos - 8 * os->sg;	/* sg <= bitpos/8 by construction */
-	u32 w = (u32)(rel >> 5), s = (u32)rel & 31;
-	u32 *stg = stg_of(L);
-	u64 lo = code << s;
-	atomicOr((u32 *)&stg[w], (u32)lo);
-	if (s + nbits > 32)
-		atomicOr((u32 *)&stg[w + 1], (u32)(lo >> 32));
-	if (s + nbits > 64)
-		atomicOr((u32 *)&stg[w + 2], (u32)(code >> (64 - s)));
-}
-
-/*
- * Write the completed bytes of the staging area to HBM and slide the rest to
- * the front.  Whole workgroup; 'final' also writes the last partial unit.
- */
-static __device__ __forceinline__ void
-stg_flush(lds_t *L, struct outstate *os, bool final)
-{
-	u32 *stg = stg_of(L);
-	u8 *stgb = (u8 *)stg;
-	const u32 tid = threadIdx.x;
-	u64 done_bytes = final ? (os->bits + 7) / 8 : os->bits / 8;
-	u64 rel_end = done_bytes - os->sg;	/* staging bytes that are final */
-	s64 first = -(s64)os->sg;		/* staging index of out[0] if sg<0 */
-	u32 start = first > 0 ? (u32)first : 0;
-	u32 units = final ? (u32)((rel_end + 15) / 16) : (u32)(rel_end / 16);
-
-	__syncthreads();
-	/* 16-byte units: unit u covers staging bytes [16u, 16u+16) */
-	for (u32 u = tid; u < units; u += NT) {
-		u32 b0 = u * 16, b1 = b0 + 16;
-		u8 *g = os->out + (s64)(os->sg + b0);
-		if (b0 >= start && b1 <= rel_end) {
-			*(uint4 *)g = *(const uint4 *)(stgb + b0);
-		} else {
-			for (u32 b = b0 < start ? start : b0; b < b1 && b < rel_end; b++)
-				g[b - b0] = stgb[b];
-		}
-	}
-	/* slide the unfinished tail to the front; thread i both clears word i
-	 * and (for the few tail words) rewrites it, so no barrier in between */
-	u32 keep_from = units * 16;
-	u32 total_words = (u32)((os->bits - 8 * os->sg + 31) / 32) + 1;
-	u32 keep_words = final ? 0 : total_words - keep_from / 4;
-	u32 v = 0;
-	if (tid < keep_words && keep_from / 4 + tid < STG_WORDS + 8)
-		v = stg[keep_from / 4 + tid];
-	__syncthreads();
-	for (u32 i = tid; i < STG_WORDS + 8; i += NT)
-		stg[i] = 0;
-	if (tid < keep_words)
-		stg[tid] = v;
-	os->sg += keep_from;
-	/* callers put a barrier before the next stg_put by another thread */
-}
-
-/* bring back the few unfinished bytes saved in carry[] (the staging area
- * shares LDS with the tile scratch and is clobbered between blocks) */
-static __device__ __forceinline__ void stg_restore(lds_t *L)
-{
-	u32 *stg = stg_of(L);
-
-	__syncthreads();
-	for (u32 i = threadIdx.x; i < STG_WORDS + 8; i += NT)
-		stg[i] = i < 6 ? L->carry[i] : 0;
-	__syncthreads();
-}
-
-static __device__ __forceinline__ void stg_save(lds_t *L, struct outstate *os)
-{
-	stg_flush(L, os, false);
-	if (threadIdx.x < 6)
-		L->carry[threadIdx.x] = stg_of(L)[threadIdx.x];
-	__syncthreads();
-}
+#include "deflate_blockend.h"
+#include "deflate_opt.h"
 
 /* ---------------- chain construction without a sort ---------------- */
 
@@ -2144,11 +1975,19 @@ extern "C" __attribute__((visibility("default"))) void libdeflate_amd_debug_read
 /* ---------------- the kernel ---------------- */
 
 /*
- * The body is compiled twice: OPT = false for levels 0-9 (the min-cost parse
- * and its re-parse loop compile away, so the lazy levels keep their register
- * allocation), OPT = true for levels 10-12.
+ * The body is compiled three times: OPT = false for levels 0-9 (the min-cost
+ * parse and its re-parse loop compile away, so the lazy levels keep their
+ * register allocation), OPT = true for levels 10-12.  SPLIT = true is the LZ77
+ * stage of levels 0-9 for callers that state a size bound: at a block end it
+ * writes the block's descriptor (tok_buf / blk_buf, see LDA_BLK_*) instead of
+ * writing the block, and lda_deflate_entropy_kernel (deflate_entropy.hip)
+ * writes the streams afterwards.  tok_stride is that bound: the token entries
+ * of a buffer's list and the most bytes a buffer may have (a larger one is
+ * marked LDA_BLK_FUSED and listed for the fused kernel, *fused_cnt of them);
+ * blk_stride the descriptors per buffer (one per tile at most).  Fused with
+ * blk_buf set: only the *fused_cnt buffers so listed.
  */
-template <bool OPT> static __device__ __forceinline__ void
+template <bool OPT, bool SPLIT = false> static __device__ __forceinline__ void
 deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		   u32 nice, u32 mode,
 		   const u8 *__restrict__ in_base,
@@ -2162,14 +2001,16 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		   u64 *__restrict__ seq_scratch,
 		   const u32 *__restrict__ seg_info,
 		   u32 *__restrict__ next_chunk,
-		   const u8 *__restrict__ dict_pre)
+		   const u8 *__restrict__ dict_pre,
+		   u32 *__restrict__ tok_buf = NULL, u32 *__restrict__ blk_buf = NULL,
+		   u32 tok_stride = 0, u32 blk_stride = 0, u32 *__restrict__ fused_cnt = NULL)
 {
+	static_assert(!(OPT && SPLIT), "levels 10-12 keep the fused block end");
 	lds_t *L = (lds_t *)(uintptr_t)0;
 	const u32 tid = threadIdx.x;
 	if ((u32)(uintptr_t)(__attribute__((address_space(3))) u8 *)lds_raw != 0)
 		__builtin_trap();	/* see LDS32(): the dynamic LDS block must start at 0 */
 	u64 *__restrict__ seqg = seq_scratch + (size_t)blockIdx.x * SEQ_STRIDE;
-	u32 *__restrict__ tokg = (u32 *)seqg;	/* the block's tokens, see TOK_MATCH */
 	/* levels 10-12: the search results of a block's first tile, kept while
 	 * that tile is parsed more than once */
 	u32 *__restrict__ msave = (u32 *)(seqg + SEQ_GCAP);
@@ -2194,6 +2035,10 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 	/* Buffers are handed out dynamically (one global counter): their cost
 	 * depends on their content, and a fixed stride gives every workgroup
 	 * the same kind of buffer whenever the batch is periodic. */
+	/* the fused kernel behind a split launch: only the buffers its LZ77 stage
+	 * listed (larger than the bound, LDA_BLK_FUSED) - usually none */
+	const u32 *__restrict__ only = !SPLIT && blk_buf ? blk_buf + LDA_BLK_LIST(n_chunks) : NULL;
+	const u64 n_todo = only ? bcast_first(*fused_cnt) : n_chunks;
 	for (;;) {
 		__syncthreads();
 		if (tid == 0)
@@ -2202,11 +2047,19 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		/* (workgroup-uniform values read back from LDS are made scalar: what
 		 * derives from them - descriptors, addresses, loop bounds - then lives
 		 * in SGPRs instead of vector registers) */
-		const u64 c = bcast_first(L->vars[V_TMP0]);
-		if (c >= n_chunks)
+		const u64 i_todo = bcast_first(L->vars[V_TMP0]);
+		if (i_todo >= n_todo)
 			break;
+		const u64 c = only ? bcast_first(only[i_todo]) : i_todo;
 		const u8 *inp = in_base + in_offsets[c];
 		u64 n64 = in_nbytes[c];
+		/* the block's tokens (see TOK_MATCH): fused, a list per workgroup
+		 * that restarts with every block; SPLIT, one list per buffer that
+		 * the blocks are consecutive ranges of */
+		u32 *__restrict__ const tokg = SPLIT ? tok_buf + c * tok_stride : (u32 *)seqg;
+		u32 *__restrict__ const blk_desc = SPLIT ?
+			blk_buf + LDA_BLK_HDR_WORDS(n_chunks) + c * blk_stride * LDA_BLK_WORDS : NULL;
+		u32 nblocks = 0, blk_tok0 = 0;
 		/* Segment mode (one large buffer cut into sub-ranges that are
 		 * compressed side by side): the first dict_len bytes (whole tiles)
 		 * of this "chunk" are the tail of the previous sub-range; they only
@@ -2248,6 +2101,11 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		if (n64 > RING)		/* the caller's size bound was wrong */
 			overflow = true;
 #endif
+		/* a buffer above the bound does not fit its token list: the fused
+		 * kernel launched behind the entropy kernel compresses it */
+		const bool over_bound = SPLIT && n64 > tok_stride;
+		if (over_bound)
+			overflow = true;
 		const u32 n = (u32)n64;
 
 		/* ---- per-buffer init ---- */
@@ -2277,35 +2135,12 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		__syncthreads();
 
 		/* container header through the staging area */
-		if (!overflow && hdr_bytes) {
-			if (tid == 0) {
-				if (format == LDA_FMT_GZIP) {
-					/* gzip_compress.c:44-64: XFL 4 fastest, 2 best */
-					u32 xfl = level < 2 ? 4 : level >= 8 ? 2 : 0;
-					stg_put(L, &os, 0, 0x00088B1Full, 32);
-					stg_put(L, &os, 32, 0, 32);	/* MTIME */
-					stg_put(L, &os, 64, xfl | (0xFFu << 8), 16);
-				} else {
-					/* zlib_compress.c:45-60 */
-					u32 fl = level < 2 ? 0 : level < 6 ? 1 :
-						 level < 8 ? 2 : 3;
-					u32 h = (0x78u << 8) | (fl << 6);
-					if (dict_pre) {
-						/* FDICT, then DICTID: the Adler-32 of the
-						 * whole dictionary, big-endian (RFC 1950 2.2) */
-						h |= 0x20;
-						h += (31 - h % 31) % 31;
-						stg_put(L, &os, 16, __builtin_bswap32(((const u32 *)dict_pre)[1]), 32);
-					} else {
-						h |= 31 - (h % 31);
-					}
-					stg_put(L, &os, 0, ((h & 0xFF) << 8) | (h >> 8), 16);
-				}
-			}
-			os.bits = 8 * hdr_bytes;
+		if (!SPLIT) {
+			if (!overflow && hdr_bytes)
+				put_container_header(L, &os, format, level, dict_pre, hdr_bytes, tid);
+			__syncthreads();
+			stg_save(L, &os);
 		}
-		__syncthreads();
-		stg_save(L, &os);
 
 		u32 loaded = 0;		/* input bytes present in the ring */
 		u32 block_start = dict_len;
@@ -2848,7 +2683,7 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 				nseq_now = stored_only ? 0 : bcast_first(pv.x);
 			}
 			bool end_block = last_tile || splitv ||
-				(!stored_only && nseq_now + 2 * TOK_TILE_MAX > TOK_CAP) ||
+				(!stored_only && nseq_now - blk_tok0 + 2 * TOK_TILE_MAX > TOK_CAP) ||
 				walkpos - block_start > MAX_BLOCK_LEN;
 			if (!end_block)
 				continue;
@@ -2862,6 +2697,31 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 			const u32 nseq_all = nseq_now;
 			const u32 nseq = retro ? bcast_first(L->vars[V_NSEQ_PRE]) : nseq_all;
 			const u32 is_final = last_tile && seg_last ? 1 : 0;
+			if (SPLIT) {
+				/* the block's descriptor (LDA_BLK_*) for the entropy
+				 * kernel; the tokens stay where they are, the next block's
+				 * start behind this one's in the buffer's list */
+				u32 *d = blk_desc + (size_t)nblocks * LDA_BLK_WORDS;
+				for (u32 i = tid; i < 320; i += NT) {
+					const u32 f = L->freq[i], fp = retro ? fsave[i] : f;
+					d[LDA_BLK_FREQ + i] = fp;
+					L->freq[i] = f - fp;
+				}
+				if (tid == 0) {
+					d[LDA_BLK_TOK0] = blk_tok0;
+					d[LDA_BLK_NTOK] = nseq - blk_tok0;
+					d[LDA_BLK_START] = bstart;
+					d[LDA_BLK_END] = bend;
+					d[LDA_BLK_FLAGS] = is_final | (stored_only ? LDA_BLK_STORED : 0);
+				}
+				nblocks++;
+				blk_tok0 = nseq;
+				/* (as after a written block: see below) */
+				carryv = 0;
+				block_start = bend;
+				__syncthreads();
+				continue;
+			}
 			if (retro) {
 				for (u32 i = tid; i < 320; i += NT) {
 					u32 f = L->freq[i], fp = fsave[i];
@@ -2871,422 +2731,21 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 				__syncthreads();
 			}
 
-			/* ---- S5: codes, costs, block type ---- */
-			u32 btype = 0;	/* 0 stored, 1 static, 2 dynamic */
-			if (!stored_only) {
-				/* the block-end tables and the bit staging area are MX's
-				 * LDS: the next tile's search results wait in HBM meanwhile */
-				if (mx_pending) {
-					const AS3 u32 *MXs = (const AS3 u32 *)L->nxtB;
-					for (u32 i = tid; i < TILE; i += NT)
-						msave[4 + i] = MXs[4 + i];
-				}
-				if (tid == 0)
-					L->freq[256]++;
-				__syncthreads();
-				/* rank sort of both alphabets by the whole workgroup: the
-				 * used symbols are collected first (their keys, freq << 9 |
-				 * symbol, in any order), then every key counts the keys
-				 * below it - a block uses a third of the litlen alphabet,
-				 * a small one a fifth; M[] is free scratch here */
-				{
-					u32 *keys = L->M;		/* [288] litlen, [288, 320) offset keys */
-					u32 *usedv = L->M + 320;	/* [2] used counts */
-					u16 *sortedO = (u16 *)(L->M + 324);	/* [32] */
-					if (tid < 2)
-						usedv[tid] = 0;
-					__syncthreads();
-					for (u32 vt = tid; vt < 320; vt += NT) {
-						const u32 f = L->freq[vt];
-						if (f) {
-							if (vt < 288)
-								keys[atomicAdd(&usedv[0], 1u)] = (f << 9) | vt;
-							else
-								keys[288 + atomicAdd(&usedv[1], 1u)] =
-									(f << 9) | (vt - 288);
-						}
-					}
-					__syncthreads();
-					{
-						const u32 m1 = usedv[0], m2 = usedv[1];
-						for (u32 i = tid; i < m1 + m2; i += NT) {
-							const bool lit = i < m1;
-							const u32 lo = lit ? 0 : 288, m = lit ? m1 : m2;
-							const u32 key = keys[lit ? i : 288 + i - m1];
-							u32 r = 0;
-							for (u32 q = 0; q < m; q++)
-								r += keys[lo + q] < key;
-							if (lit)
-								L->sorted[r] = (u16)(key & 511);
-							else
-								sortedO[r] = (u16)(key & 511);
-						}
-					}
-					__syncthreads();
-					PROF_MARK(10);
-					/* the two trees are built side by side on two waves */
-					if (wave == 0)
-						make_code(L->freq, 288, 15, L->lens, L->codes,
-							  L->sorted, HUFF_LITLEN(L),
-							  usedv[0], true, lane);
-					else if (wave == 1)
-						make_code(L->freq + 288, 32, 15, L->lens + 288,
-							  L->codes + 288, sortedO,
-							  (huff_scratch<32> *)L->hw,
-							  usedv[1], true, lane);
-				}
-				__syncthreads();
-				PROF_MARK(11);
-				/* precode items: run-length coding of the code lengths
-				 * (deflate_compress.c:1482-1557 semantics), one thread per
-				 * length, then one thread per run */
-				{
-					u32 *starts = L->M;		/* [<= 321] run start indices */
-					if (tid == 0) {
-						L->vars[V_TMP1] = 257;
-						L->vars[V_TMP2] = 1;
-					}
-					if (tid < 19)
-						L->pre_freq[tid] = 0;
-					__syncthreads();
-					for (u32 vt = tid; vt < 320; vt += NT) {
-						if (vt < 288 && vt >= 257 && L->lens[vt])
-							atomicMax((u32 *)&L->vars[V_TMP1], vt + 1);
-						if (vt >= 288 && L->lens[vt])
-							atomicMax((u32 *)&L->vars[V_TMP2], vt - 288 + 1);
-					}
-					__syncthreads();
-					const u32 nlit = L->vars[V_TMP1], noff = L->vars[V_TMP2];
-					const u32 total = nlit + noff;
-					/* element e of the concatenated lengths: thread tid owns
-					 * the VPT consecutive elements from tid * VPT */
-					u32 isst[VPT], nst = 0;
-#pragma unroll
-					for (u32 j = 0; j < VPT; j++) {
-						const u32 e = tid * VPT + j;
-						isst[j] = 0;
-						if (e < total) {
-							u32 v = L->lens[e < nlit ? e : 288 + (e - nlit)];
-							u32 pv = 0xFF;
-							if (e)
-								pv = L->lens[e - 1 < nlit ? e - 1 :
-									     288 + (e - 1 - nlit)];
-							isst[j] = pv != v;
-						}
-						nst += isst[j];
-					}
-					u32 nruns;
-					u32 ridx = block_scan(L, nst, &nruns);
-#pragma unroll
-					for (u32 j = 0; j < VPT; j++) {
-						if (isst[j])
-							starts[ridx] = tid * VPT + j;
-						ridx += isst[j];
-					}
-					if (tid == 0)
-						starts[nruns] = total;
-					__syncthreads();
-					/* run r: thread tid owns the runs from tid * VPT */
-					u32 rv[VPT], rlen[VPT], nitems[VPT], nit = 0;
-#pragma unroll
-					for (u32 j = 0; j < VPT; j++) {
-						const u32 r = tid * VPT + j;
-						rv[j] = rlen[j] = nitems[j] = 0;
-						if (r < nruns) {
-							u32 st = starts[r];
-							rlen[j] = starts[r + 1] - st;
-							rv[j] = L->lens[st < nlit ? st : 288 + (st - nlit)];
-							if (rv[j] == 0) {
-								u32 full = rlen[j] / 138, rem = rlen[j] % 138;
-								nitems[j] = full + (rem >= 3 ? 1 : rem);
-							} else if (rlen[j] >= 4) {
-								u32 l1 = rlen[j] - 1;
-								nitems[j] = 1 + l1 / 6 + (l1 % 6 >= 3 ? 1 : l1 % 6);
-							} else {
-								nitems[j] = rlen[j];
-							}
-						}
-						nit += nitems[j];
-					}
-					u32 ni;
-					u32 at = block_scan(L, nit, &ni);
-#pragma unroll
-					for (u32 j = 0; j < VPT; j++) {
-						if (tid * VPT + j < nruns) {
-							u32 left = rlen[j];
-							const u32 rvj = rv[j];
-							if (rvj == 0) {
-								while (left >= 11) {
-									u32 r = left > 138 ? 138 : left;
-									L->pre_items[at++] = 18 | ((r - 11) << 5);
-									atomicAdd((u32 *)&L->pre_freq[18], 1u);
-									left -= r;
-								}
-								if (left >= 3) {
-									L->pre_items[at++] = 17 | ((left - 3) << 5);
-									atomicAdd((u32 *)&L->pre_freq[17], 1u);
-									left = 0;
-								}
-							} else if (left >= 4) {
-								L->pre_items[at++] = (u16)rvj;
-								left--;
-								u32 n16 = 0;
-								while (left >= 3) {
-									u32 r = left > 6 ? 6 : left;
-									L->pre_items[at++] = 16 | ((r - 3) << 5);
-									n16++;
-									left -= r;
-								}
-								atomicAdd((u32 *)&L->pre_freq[16], n16);
-								atomicAdd((u32 *)&L->pre_freq[rvj], 1u);
-							}
-							if (left)
-								atomicAdd((u32 *)&L->pre_freq[rvj], left);
-							while (left) {
-								L->pre_items[at++] = (u16)rvj;
-								left--;
-							}
-						}
-					}
-					if (tid == 0)
-						L->vars[V_NPRE] = ni;
-				}
-				__syncthreads();
-				PROF_MARK(23);
-				if (wave == 0)
-					make_code(L->pre_freq, 19, 7, L->pre_lens, L->pre_codes,
-						  L->sorted, (huff_scratch<32> *)L->hw,
-						  0, false, lane);
-				__syncthreads();
-				PROF_MARK(22);
-				/* exact costs (deflate_compress.c:1747-1808) */
-				u32 dyn = 0, stat = 0;
-				for (u32 vt = tid; vt < 320; vt += NT) {
-					u32 f = L->freq[vt];
-					u32 xb = 0, sl = 8;
-					if (vt < 288) {
-						sl = vt < 144 ? 8 : vt < 256 ? 9 : vt < 280 ? 7 : 8;
-						if (vt >= 265 && vt < 285)
-							xb = (vt - 261) >> 2;
-					} else {
-						u32 ds = vt - 288;
-						sl = 5;
-						if (ds >= 4)
-							xb = (ds >> 1) - 1;
-					}
-					dyn += f * (L->lens[vt] + xb);
-					stat += f * (sl + xb);
-				}
-				if (tid < 19) {
-					u32 xb = tid == 16 ? 2 : tid == 17 ? 3 : tid == 18 ? 7 : 0;
-					dyn += L->pre_freq[tid] * (L->pre_lens[tid] + xb);
-				}
-				u32 dyn_tot, stat_tot;
-				(void)block_scan(L, dyn, &dyn_tot);
-				(void)block_scan(L, stat, &stat_tot);
-				static const u8 perm[19] = { 16, 17, 18, 0, 8, 7, 9, 6, 10,
-							     5, 11, 4, 12, 3, 13, 2, 14,
-							     1, 15 };
-				u32 nexp = 19;
-				while (nexp > 4 && L->pre_lens[perm[nexp - 1]] == 0)
-					nexp--;
-				u32 cost_dyn = 3 + 5 + 5 + 4 + 3 * nexp + dyn_tot;
-				u32 cost_stat = 3 + stat_tot;
-				/* stored: align + (LEN,NLEN) per <= 65535 piece */
-				u32 pieces = blen ? (blen + 65534) / 65535 : 1;
-				u32 pad = (u32)((0 - (os.bits + 3)) & 7);
-				u64 cost_stored = 3 + pad + 32 + 8ull * blen +
-						  (u64)(pieces - 1) * 40;
-				u64 best = cost_stored;
-				btype = 0;
-				if (cost_stat < best) {
-					best = cost_stat;
-					btype = 1;
-				}
-				if (cost_dyn < best) {
-					best = cost_dyn;
-					btype = 2;
-				}
-				if ((os.bits + best + 7) / 8 + ftr_bytes > os.avail)
-					overflow = true;
-				L->vars[V_TMP3] = nexp;
-			} else {
-				u32 pieces = blen ? (blen + 65534) / 65535 : 1;
-				u64 cost = (u64)pieces * 40 + 8ull * blen;
-				if ((os.bits + cost + 7) / 8 + ftr_bytes > os.avail)
-					overflow = true;
+			/* ---- S5, S6: the block is written (block_emit()) ---- */
+			/* the block-end tables and the bit staging area are MX's LDS:
+			 * the next tile's search results wait in HBM meanwhile */
+			if (!stored_only && mx_pending) {
+				const AS3 u32 *MXs = (const AS3 u32 *)L->nxtB;
+				for (u32 i = tid; i < TILE; i += NT)
+					msave[4 + i] = MXs[4 + i];
 			}
-			if (overflow)
+			PROF_MARK(10);
+			if (!block_emit(L, &os, tokg, nseq, inp, bstart, blen, is_final, stored_only,
+					ftr_bytes, &tog, tid, lane, wave)) {
+				overflow = true;
 				break;
-
-			PROF_MARK(7);
-			/* ---- S6: emit ---- */
-			stg_restore(L);
-			if (btype == 0) {
-				/* stored pieces: header by thread 0, bytes as 8-bit
-				 * "codes" through the same staging path */
-				u32 done = 0;
-				do {
-					u32 piece = blen - done > 65535 ? 65535 : blen - done;
-					u32 fin = (is_final && done + piece == blen) ? 1 : 0;
-					u32 pad = (u32)((0 - (os.bits + 3)) & 7);
-					if (tid == 0) {
-						stg_put(L, &os, os.bits, fin, 3);
-						u64 b = os.bits + 3 + pad;
-						stg_put(L, &os, b, piece | ((u64)(piece ^ 0xFFFF) << 16), 32);
-					}
-					os.bits += 3 + pad + 32;
-					__syncthreads();
-					for (u32 w0 = 0; w0 < piece; w0 += 2048) {
-						u32 cnt = piece - w0 < 2048 ? piece - w0 : 2048;
-						stg_flush(L, &os, false);
-						__syncthreads();
-						for (u32 j = tid; j < cnt; j += NT) {
-							u32 pos = bstart + done + w0 + j;
-							stg_put(L, &os, os.bits + 8ull * j, inp[pos], 8);
-						}
-						os.bits += 8ull * cnt;
-						__syncthreads();
-					}
-					done += piece;
-				} while (done < blen);
-				stg_flush(L, &os, false);
-			} else {
-				if (btype == 1) {
-					/* static codes: lens fixed, canonical codewords */
-					__syncthreads();
-					for (u32 s = tid; s < 320; s += NT)
-						L->lens[s] = s < 144 ? 8 : s < 256 ? 9 :
-							     s < 280 ? 7 : s < 288 ? 8 : 5;
-					__syncthreads();
-					if (tid == 0) {
-						u32 nc[16] = { 0 }, bl[16] = { 0 };
-						for (u32 s = 0; s < 288; s++)
-							bl[L->lens[s]]++;
-						u32 code = 0;
-						for (u32 d = 1; d < 16; d++) {
-							code = (code + bl[d - 1]) << 1;
-							nc[d] = code;
-						}
-						for (u32 s = 0; s < 288; s++) {
-							u32 l = L->lens[s];
-							L->codes[s] = (u16)(__brev(nc[l]++) >> (32 - l));
-						}
-						for (u32 s = 0; s < 32; s++)
-							L->codes[288 + s] = (u16)(__brev(s) >> 27);
-					}
-					__syncthreads();
-				}
-				/* block header: thread 0 the fixed fields, threads
-				 * 1..nexp the precode lengths, then one thread per
-				 * precode item; bit offsets by a workgroup scan */
-				{
-					u64 hcode[VPT];
-					u32 hbits[VPT], hsum = 0;
-					const u32 nexp = btype == 2 ? L->vars[V_TMP3] : 0;
-					const u32 ni = btype == 2 ? L->vars[V_NPRE] : 0;
-#pragma unroll
-					for (u32 j = 0; j < VPT; j++) {
-						const u32 vt = tid * VPT + j;	/* header item */
-						hcode[j] = 0;
-						hbits[j] = 0;
-						if (vt == 0) {
-							hcode[j] = is_final | (btype << 1);
-							hbits[j] = 3;
-							if (btype == 2) {
-								u32 nlit = L->vars[V_TMP1], noff = L->vars[V_TMP2];
-								hcode[j] |= (u64)((nlit - 257) | ((noff - 1) << 5) |
-										  ((nexp - 4) << 10)) << 3;
-								hbits[j] = 17;
-							}
-						} else if (vt <= nexp) {
-							static const u8 perm2[19] = { 16, 17, 18, 0, 8, 7,
-								9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15 };
-							hcode[j] = L->pre_lens[perm2[vt - 1]];
-							hbits[j] = 3;
-						} else if (vt <= nexp + ni) {
-							u32 it = L->pre_items[vt - nexp - 1];
-							u32 sym = it & 31, ex = it >> 5;
-							u32 l = L->pre_lens[sym];
-							u32 xb = sym == 16 ? 2 : sym == 17 ? 3 :
-								 sym == 18 ? 7 : 0;
-							hcode[j] = L->pre_codes[sym] | ((u64)ex << l);
-							hbits[j] = l + xb;
-						}
-						hsum += hbits[j];
-					}
-					u32 htot;
-					u32 hoff = block_scan(L, hsum, &htot);
-#pragma unroll
-					for (u32 j = 0; j < VPT; j++) {
-						stg_put(L, &os, os.bits + hoff, hcode[j], hbits[j]);
-						hoff += hbits[j];
-					}
-					os.bits += htot;
-				}
-				stg_flush(L, &os, false);
-
-				PROF_MARK(9);
-				/* tokens, NT at a time: one token per thread, a workgroup
-				 * prefix sum of the bit lengths (single-barrier scan),
-				 * ds_or into the staging area.  The staging area is only
-				 * written out when another window might not fit (a token is
-				 * at most 48 bits: 6 KiB per window in the worst case, a
-				 * fifth of that on text). */
-				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-				/* (the next window's token is requested before this one is
-				 * encoded: the list is in HBM) */
-				u32 tok_nxt = tid < nseq ? tokg[tid] : 0;
-				for (u32 b0 = 0; b0 < nseq; b0 += NT) {
-					u64 code = 0;
-					u32 nb = 0;
-					const u32 tok = tok_nxt;
-					if (b0 + NT + tid < nseq)
-						tok_nxt = tokg[b0 + NT + tid];
-					if (b0 + tid < nseq) {
-						if (tok & TOK_MATCH) {
-							const u32 len = (tok & 0xFF) + 3, dist = ((tok >> 8) & 0x7FFF) + 1;
-							u32 sl, xb, xv, ds, dxb, dxv;
-							length_code(len, &sl, &xb, &xv);
-							dist_code(dist, &ds, &dxb, &dxv);
-							u32 ll = L->lens[257 + sl];
-							u32 dl = L->lens[288 + ds];
-							u64 v = L->codes[257 + sl];
-							u32 sh = ll;
-							v |= (u64)xv << sh;
-							sh += xb;
-							v |= (u64)L->codes[288 + ds] << sh;
-							sh += dl;
-							v |= (u64)dxv << sh;
-							sh += dxb;
-							code = v;
-							nb = sh;
-						} else {
-							code = L->codes[tok];
-							nb = L->lens[tok];
-						}
-					}
-					u32 tot;
-					u32 off = block_scan1(L, nb, &tot, &tog);
-					stg_put(L, &os, os.bits + off, code, nb);
-					os.bits += tot;
-					/* room for one more window of 48-bit tokens? */
-					if (S6_ALWAYS_FLUSH || os.bits - 8 * os.sg + 48 * NT + 64 > 32 * STG_WORDS)
-						stg_flush(L, &os, false);
-				}
-				stg_flush(L, &os, false);
-				__syncthreads();
-				/* end of block */
-				if (tid == 0)
-					stg_put(L, &os, os.bits, L->codes[256], L->lens[256]);
-				os.bits += L->lens[256];
-				__syncthreads();
 			}
-
-			/* keep the unfinished staging bytes across the next tiles
-			 * (M is reused as tile scratch) */
-			stg_save(L, &os);
-			PROF_MARK(8);
+			PROF_START();
 			if (OPT && mode == 3 && tid < 256)
 				bsave[tid] = 0;	/* the previous tile's bytes are added by the next one */
 			if (retro) {
@@ -3327,42 +2786,19 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		}
 
 		/* ---- finish the stream ---- */
-		__syncthreads();
-		if (!overflow && !seg_last &&
-		    (os.bits + 3 + 7) / 8 + 4 > os.avail)
-			overflow = true;
-		if (!overflow) {
-			stg_restore(L);
-			if (!seg_last) {
-				/* empty stored block: BFINAL 0, BTYPE 00, pad, LEN 0, NLEN ~0 */
-				u64 fb = 8 * ((os.bits + 3 + 7) / 8);
-				if (tid == 0)
-					stg_put(L, &os, fb, 0xFFFF0000ull, 32);
-				os.bits = fb + 32;
-				__syncthreads();
+		if (SPLIT) {
+			/* the block count, or that the stream does not fit */
+			__syncthreads();
+			if (tid == 0) {
+				blk_buf[c] = over_bound ? LDA_BLK_FUSED :
+					     overflow ? LDA_BLK_OVERFLOW : nblocks;
+				if (over_bound)
+					blk_buf[LDA_BLK_LIST(n_chunks) + atomicAdd(fused_cnt, 1u)] = (u32)c;
 			}
-			if (ftr_bytes) {
-				/* gzip_compress.c:73-79 / zlib_compress.c:66-72 */
-				u32 sum = sums ? sums[c] : 0;
-				u64 fb = 8 * ((os.bits + 7) / 8);
-				if (tid == 0) {
-					if (format == LDA_FMT_GZIP) {
-						stg_put(L, &os, fb, sum, 32);
-						stg_put(L, &os, fb + 32, n, 32);
-					} else {
-						stg_put(L, &os, fb, __builtin_bswap32(sum), 32);
-					}
-				}
-				os.bits = fb + 8 * ftr_bytes;
-				__syncthreads();
-			}
-			stg_flush(L, &os, true);
-			if (tid == 0)
-				out_nbytes[c] = (os.bits + 7) / 8;
-		} else if (tid == 0) {
-			out_nbytes[c] = 0;
+		} else {
+			finish_stream(L, &os, overflow, seg_last, format, ftr_bytes, sums, c, n,
+				      out_nbytes, tid);
 		}
-		__syncthreads();
 	}
 }
 
@@ -3408,11 +2844,27 @@ extern "C" size_t lda_deflate_small_wgs(void)
 
 LDA_PROF_DEFINE_READER(libdeflate_amd_profile_read_deflate_small)
 #else
+/* levels 0-9, the LZ77 stage: block descriptors for lda_deflate_entropy_kernel */
 extern "C" __global__ void __launch_bounds__(NT)
-lda_deflate_batch_kernel(DEFLATE_KERNEL_PARAMS)
+lda_deflate_batch_kernel(DEFLATE_KERNEL_PARAMS, u32 *__restrict__ tok_buf,
+			 u32 *__restrict__ blk_buf, u32 tok_stride, u32 blk_stride,
+			 u32 *__restrict__ fused_cnt)
 {
 	extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
-	deflate_batch_body<false>(DEFLATE_KERNEL_ARGS);
+	deflate_batch_body<false, true>(DEFLATE_KERNEL_ARGS, tok_buf, blk_buf, tok_stride,
+					blk_stride, fused_cnt);
+}
+
+/* levels 0-9 with the block end in the tile loop: callers without a size
+ * bound; behind a split launch (blk_buf and fused_cnt of that launch, else
+ * NULL) the buffers its LZ77 stage listed as LDA_BLK_FUSED */
+extern "C" __global__ void __launch_bounds__(NT)
+lda_deflate_fused_kernel(DEFLATE_KERNEL_PARAMS, const u32 *__restrict__ blk_buf,
+			 const u32 *__restrict__ fused_cnt)
+{
+	extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+	deflate_batch_body<false>(DEFLATE_KERNEL_ARGS, NULL, (u32 *)blk_buf, 0, 0,
+				  (u32 *)fused_cnt);
 }
 
 /* levels 10-12 */

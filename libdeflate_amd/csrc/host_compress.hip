@@ -163,6 +163,80 @@ static dict_shape shape_dict(int level, size_t dict_nbytes)
 	return d;
 }
 
+/*
+ * The split path's scratch (kernels.h, LDA_BLK_*) is at most this much per
+ * launch: 4 B of token list per byte of the size bound plus the block
+ * descriptors, so 4096 buffers of 64 KiB (1.08 GiB) are one launch.  A batch
+ * that needs more runs as consecutive slices of buffers on the same stream; a
+ * bound whose single buffer needs more keeps the fused kernel.
+ */
+#define LDA_SPLIT_SCRATCH ((size_t)1280 << 20)
+/* buffers per CU from which a call takes the split path (see plan_batch()) */
+#define LDA_SPLIT_MIN_PER_CU 4
+
+/*
+ * The kernels' scratch of one compress_batch_impl() call: [per-workgroup
+ * state: u64 x lda_deflate_seq_words() x grid][chunk counters: three u32 per
+ * slice (the LZ77 stage's, the fused kernel's behind it, the count of buffers
+ * left to that one), 16-byte padded][sums: u32 x n], then the dictionary block (see
+ * lda_dict_prep_kernel()) or, on the split path, one slice's token lists and
+ * block descriptors.  The same sum sizes the reservations the host-pointer
+ * entry points make up front.
+ */
+struct batch_plan {
+	bool small, split;
+	size_t grid, per_slice, nslices;
+	uint32_t tok_stride, blk_stride;	/* u32 entries / descriptors per buffer */
+	size_t cnt_at, sums_at, tok_at, blk_at, dict_at, total;
+};
+
+static batch_plan plan_batch(const struct libdeflate_compressor *c, size_t n,
+			     size_t max_in, bool seg, bool dict)
+{
+	batch_plan p = {};
+	/* buffers of at most 4 KiB (filesystem blocks): the 256-thread kernel,
+	 * several workgroups per CU (deflate_small.hip); levels 10-12 keep the
+	 * big one (their parse wants its LDS); a dictionary needs the ring of
+	 * the big kernel */
+	p.small = max_in <= lda_deflate_small_max() && c->level <= 9 && !seg && !dict &&
+		  !env_cfg().no_small;
+	/* levels 0-9 of the big kernel split the block end off into the entropy
+	 * kernel (deflate_entropy.hip) wherever the host knows a size bound to
+	 * size the token lists by, and the call has buffers enough to fill the
+	 * CUs several times over: the entropy kernel's work per buffer (0.19 ms
+	 * for 64 KiB at level 6) is what the split saves only where other
+	 * buffers' block ends run beside it - with one buffer per CU it is a tail
+	 * the fused kernel does not have (a 16 MiB single-buffer call, 256
+	 * segments: 1.24 -> 1.49 ms; 4096 x 64 KiB: 7.16 -> 6.57 ms) */
+	const size_t tile = lda_deflate_tile();
+	const size_t tok_stride = align_up(max_in, 16);
+	const size_t blk_stride = std::max<size_t>(1, (tok_stride + tile - 1) / tile);
+	const size_t per_buf = tok_stride * 4 + blk_stride * LDA_BLK_WORDS * 4 + 4;
+	const size_t num_cus = (size_t)device_ctx()->num_cus;
+	p.split = !p.small && c->level <= 9 && !dict && max_in != SIZE_MAX &&
+		  n >= LDA_SPLIT_MIN_PER_CU * num_cus &&
+		  per_buf <= LDA_SPLIT_SCRATCH && tok_stride <= 0xFFFFFFF0u;
+	p.per_slice = p.split ? std::min(n, LDA_SPLIT_SCRATCH / per_buf) : n;
+	p.per_slice = std::max<size_t>(p.per_slice, 1);
+	p.nslices = (n + p.per_slice - 1) / p.per_slice;
+	const size_t grid_max = num_cus * (p.small ? lda_deflate_small_wgs() : 1);
+	p.grid = std::min(p.per_slice, grid_max);
+	p.cnt_at = p.grid * lda_deflate_seq_words() * 8;
+	p.sums_at = p.cnt_at + align_up(12 * p.nslices, 16);
+	p.dict_at = p.tok_at = align_up(p.sums_at + n * 4, 64);
+	p.total = p.sums_at + n * 4;
+	if (dict)
+		p.total = p.dict_at + LDA_DICT_BLK_HDR + dict_window();
+	if (p.split) {
+		p.tok_stride = (uint32_t)tok_stride;
+		p.blk_stride = (uint32_t)blk_stride;
+		p.blk_at = align_up(p.tok_at + p.per_slice * tok_stride * 4, 64);
+		p.total = p.blk_at + (LDA_BLK_HDR_WORDS(p.per_slice) +
+				      p.per_slice * blk_stride * LDA_BLK_WORDS) * 4;
+	}
+	return p;
+}
+
 static int
 compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		    const void *d_in, const uint64_t *d_in_offsets,
@@ -192,32 +266,21 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		set_error("compress_batch: bad argument");
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
-	/* buffers of at most 4 KiB (filesystem blocks): the 256-thread kernel,
-	 * several workgroups per CU (deflate_small.hip); levels 10-12 keep the
-	 * big one (their parse wants its LDS) */
-	/* (a dictionary needs the ring of the big kernel: it never takes the
-	 * small one) */
 	const bool dict = d_dict && dict_nbytes;
-	const bool small = max_in_nbytes <= lda_deflate_small_max() &&
-			   c->level <= 9 && !d_seg_info && !dict && !env_cfg().no_small;
-	/* scratch: [token lists: u64 x words x grid][chunk counter][sums u32 x n]
-	 * [dictionary block, see lda_dict_prep_kernel()] */
-	size_t grid_max = (size_t)ctx->num_cus * (small ? lda_deflate_small_wgs() : 1);
-	size_t grid = n < grid_max ? n : grid_max;
-	size_t seq_bytes = grid * lda_deflate_seq_words() * 8;
-	const size_t blk_at = align_up(seq_bytes + 16 + n * 4, 64);
-	uint8_t *scr = (uint8_t *)c->scratch.reserve(
-		dict ? blk_at + LDA_DICT_BLK_HDR + dict_window() : seq_bytes + 16 + n * 4);
+	const batch_plan pl = plan_batch(c, n, max_in_nbytes, d_seg_info != NULL, dict);
+	const bool small = pl.small;
+	uint8_t *scr = (uint8_t *)c->scratch.reserve(pl.total);
 	if (!scr)
 		return LIBDEFLATE_AMD_OOM;
-	uint32_t *next_chunk = (uint32_t *)(scr + seq_bytes);
-	LDA_HIP_TRY(hipMemsetAsync(next_chunk, 0, 16, st), LIBDEFLATE_AMD_NO_DEVICE);
+	uint32_t *next_chunk = (uint32_t *)(scr + pl.cnt_at);
+	LDA_HIP_TRY(hipMemsetAsync(next_chunk, 0, align_up(12 * pl.nslices, 16), st),
+		    LIBDEFLATE_AMD_NO_DEVICE);
 	uint8_t *blk = NULL;
 	if (dict) {
 		/* the prefix every buffer starts from and, for zlib, the DICTID:
 		 * both on the device, nothing waits */
 		const dict_shape sh = shape_dict(c->level, dict_nbytes);
-		blk = scr + blk_at;
+		blk = scr + pl.dict_at;
 		hipLaunchKernelGGL(lda_dict_prep_kernel, dim3(1), dim3(256), 0, st,
 				   (const uint8_t *)d_dict, (uint64_t)dict_nbytes, sh.tail,
 				   sh.pre_len, sh.sinfo, blk);
@@ -232,7 +295,7 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 	}
 	uint32_t *sums = NULL;
 	if (format != LIBDEFLATE_AMD_DEFLATE) {
-		sums = (uint32_t *)(scr + seq_bytes + 16);
+		sums = (uint32_t *)(scr + pl.sums_at);
 		int rc = format == LIBDEFLATE_AMD_GZIP ?
 			libdeflate_amd_crc32_batch(n, d_in, d_in_offsets,
 						   d_in_nbytes, NULL, sums, stream) :
@@ -255,19 +318,72 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 				(const void *)lda_deflate_opt_kernel,
 				hipFuncAttributeMaxDynamicSharedMemorySize,
 				(int)lda_deflate_lds_bytes()), LIBDEFLATE_AMD_NO_DEVICE);
+		LDA_HIP_TRY(hipFuncSetAttribute(
+				(const void *)lda_deflate_fused_kernel,
+				hipFuncAttributeMaxDynamicSharedMemorySize,
+				(int)lda_deflate_lds_bytes()), LIBDEFLATE_AMD_NO_DEVICE);
 		ctx->deflate_attr_set.store(true, std::memory_order_release);
 	}
 	const level_cfg &lv = k_levels[c->level];
-	hipLaunchKernelGGL(small ? lda_deflate_small_kernel :
-			   lv.mode == 3 ? lda_deflate_opt_kernel :
-					  lda_deflate_batch_kernel, dim3((unsigned)grid),
-			   dim3(small ? LDA_DEFLATE_SMALL_THREADS : LDA_DEFLATE_THREADS),
-			   lds, st, (uint64_t)n, format, c->level,
-			   lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
-			   d_in_offsets, d_in_nbytes, (uint8_t *)d_out,
-			   d_out_offsets, d_out_avail, d_out_nbytes, sums,
-			   (uint64_t *)scr, d_seg_info, next_chunk, (const uint8_t *)blk);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+	if (!pl.split && (small || lv.mode == 3)) {
+		hipLaunchKernelGGL(small ? lda_deflate_small_kernel : lda_deflate_opt_kernel,
+				   dim3((unsigned)pl.grid),
+				   dim3(small ? LDA_DEFLATE_SMALL_THREADS : LDA_DEFLATE_THREADS),
+				   lds, st, (uint64_t)n, format, c->level,
+				   lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
+				   d_in_offsets, d_in_nbytes, (uint8_t *)d_out,
+				   d_out_offsets, d_out_avail, d_out_nbytes, sums,
+				   (uint64_t *)scr, d_seg_info, next_chunk, (const uint8_t *)blk);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		return LIBDEFLATE_AMD_OK;
+	}
+	if (!pl.split) {
+		hipLaunchKernelGGL(lda_deflate_fused_kernel, dim3((unsigned)pl.grid),
+				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)n, format,
+				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
+				   d_in_offsets, d_in_nbytes, (uint8_t *)d_out,
+				   d_out_offsets, d_out_avail, d_out_nbytes, sums,
+				   (uint64_t *)scr, d_seg_info, next_chunk, (const uint8_t *)blk,
+				   (const uint32_t *)NULL, (const uint32_t *)NULL);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		return LIBDEFLATE_AMD_OK;
+	}
+	/* the split path, slice by slice: the LZ77 stage leaves tokens and block
+	 * descriptors, the entropy kernel writes the streams, and the fused
+	 * kernel compresses the buffers larger than the bound (the bound is a
+	 * promise the host cannot check; what such a buffer gets does not depend
+	 * on which path its batch took).  Stream order is the only hand-over. */
+	uint32_t *tok = (uint32_t *)(scr + pl.tok_at), *bd = (uint32_t *)(scr + pl.blk_at);
+	for (size_t k = 0; k < pl.nslices; k++) {
+		const size_t lo = k * pl.per_slice, nk = std::min(pl.per_slice, n - lo);
+		const uint32_t *sk = sums ? sums + lo : NULL;
+		const uint32_t *gk = d_seg_info ? d_seg_info + lo : NULL;
+		hipLaunchKernelGGL(lda_deflate_batch_kernel, dim3((unsigned)std::min(nk, pl.grid)),
+				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)nk, format,
+				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
+				   d_in_offsets + lo, d_in_nbytes + lo, (uint8_t *)d_out,
+				   d_out_offsets + lo, d_out_avail + lo, d_out_nbytes + lo, sk,
+				   (uint64_t *)scr, gk, next_chunk + k, (const uint8_t *)NULL,
+				   tok, bd, pl.tok_stride, pl.blk_stride, next_chunk + 2 * pl.nslices + k);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		hipLaunchKernelGGL(lda_deflate_entropy_kernel, dim3((unsigned)nk),
+				   dim3(LDA_DEFLATE_ENTROPY_THREADS), lda_deflate_entropy_lds_bytes(),
+				   st, (uint64_t)nk, format, c->level, (const uint8_t *)d_in,
+				   d_in_offsets + lo, d_in_nbytes + lo, (uint8_t *)d_out,
+				   d_out_offsets + lo, d_out_avail + lo, d_out_nbytes + lo, sk, gk,
+				   (const uint32_t *)tok, (const uint32_t *)bd, pl.tok_stride,
+				   pl.blk_stride);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		hipLaunchKernelGGL(lda_deflate_fused_kernel, dim3((unsigned)std::min(nk, pl.grid)),
+				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)nk, format,
+				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
+				   d_in_offsets + lo, d_in_nbytes + lo, (uint8_t *)d_out,
+				   d_out_offsets + lo, d_out_avail + lo, d_out_nbytes + lo, sk,
+				   (uint64_t *)scr, gk, next_chunk + pl.nslices + k,
+				   (const uint8_t *)NULL, (const uint32_t *)bd,
+				   (const uint32_t *)(next_chunk + 2 * pl.nslices + k));
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+	}
 	return LIBDEFLATE_AMD_OK;
 }
 
@@ -450,11 +566,7 @@ static int compress_batch_host_body(struct libdeflate_compressor *c, int format,
 		size_t max_nk = 0;
 		for (size_t k = 0; k < ns; k++)
 			max_nk = bounds[k + 1] - bounds[k] > max_nk ? bounds[k + 1] - bounds[k] : max_nk;
-		const bool small = max_in <= lda_deflate_small_max() && c->level <= 9 &&
-				   !env_cfg().no_small;
-		const size_t grid_max = (size_t)device_ctx()->num_cus * (small ? lda_deflate_small_wgs() : 1);
-		const size_t grid = max_nk < grid_max ? max_nk : grid_max;
-		if (!c->scratch.reserve(grid * lda_deflate_seq_words() * 8 + 16 + max_nk * 4))
+		if (!c->scratch.reserve(plan_batch(c, max_nk, max_in, false, false).total))
 			return LIBDEFLATE_AMD_OOM;
 	}
 	/* what comes back per slice (sizes, compaction offsets) lands in pinned
@@ -627,6 +739,9 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	 * ahead) and the lookahead; whole tiles */
 	const size_t D = dict_window();
 	const size_t nseg = n ? (n + S - 1) / S : 1;
+	/* a segment's bytes: its own and at most D (whole tiles) in front, of the
+	 * previous segment or of the dictionary */
+	const size_t seg_bound = S + (D + tile - 1) / tile * tile;
 	const size_t slot = align_up(libdeflate_deflate_compress_bound(c, S) + 32, 16);
 	/* the caller's dictionary primes the first segment: its prefix (see
 	 * shape_dict()) lies in front of the input in the staging area */
@@ -664,8 +779,8 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 		return 0;
 	}
 	{	/* the kernels' scratch for the largest launch, before any is queued */
-		const size_t g = std::min<size_t>(std::min(per_slice, nseg), (size_t)ctx->num_cus);
-		if (!c->scratch.reserve(g * lda_deflate_seq_words() * 8 + 16 + std::min(per_slice, nseg) * 4)) {
+		if (!c->scratch.reserve(plan_batch(c, std::min(per_slice, nseg), seg_bound, true,
+						   false).total)) {
 			complain("libdeflate_*_compress (device memory)", LIBDEFLATE_AMD_OOM);
 			return 0;
 		}
@@ -755,7 +870,7 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 		int rc = compress_batch_impl(c, LIBDEFLATE_AMD_DEFLATE, nk, st, d_desc + lo,
 					     d_desc + nseg + lo, st, d_desc + 2 * nseg + lo,
 					     d_desc + 3 * nseg + lo, d_desc + 4 * nseg + lo, s_comp,
-					     d_seg + lo);
+					     d_seg + lo, seg_bound);
 		if (rc == LIBDEFLATE_AMD_OK && ftr)
 			rc = format == LIBDEFLATE_AMD_GZIP ?
 				libdeflate_amd_crc32_batch(nk, st, d_desc + 5 * nseg + lo,

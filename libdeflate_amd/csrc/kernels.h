@@ -58,6 +58,32 @@ lda_inflate_finalize_kernel(uint64_t n_chunks, int format, int exact_fill,
 
 /* deflate_kernel.hip */
 #define LDA_DEFLATE_THREADS 1024	/* one workgroup (16 waves) per buffer */
+/*
+ * Levels 0-9 of a batch with a size bound run in two kernels: the LZ77 stage
+ * (lda_deflate_batch_kernel) leaves every buffer's tokens in a list of its own
+ * (tok_buf + c * tok_stride, u32 each, TOK_MATCH of deflate_kernel.hip) and
+ * one descriptor per block; lda_deflate_entropy_kernel (deflate_entropy.hip)
+ * writes the streams from them.  blk_buf: [count of buffer c: u32 x n, padded
+ * to 16 words][list of the LDA_BLK_FUSED buffers: u32 x n, padded][blk_stride
+ * descriptors of LDA_BLK_WORDS u32 per buffer]; the count is LDA_BLK_OVERFLOW
+ * where the stream cannot fit (its size becomes 0), LDA_BLK_FUSED where the
+ * buffer is larger than the bound: the LZ77 stage lists it (*fused_cnt, zero
+ * before the launch, counts the list), the entropy kernel skips it and
+ * lda_deflate_fused_kernel, launched behind it with the same blk_buf and
+ * fused_cnt, compresses it.
+ */
+#define LDA_BLK_TOK0 0		/* first token: index in the buffer's list */
+#define LDA_BLK_NTOK 1		/* tokens */
+#define LDA_BLK_START 2		/* bytes [start, end) of the buffer */
+#define LDA_BLK_END 3
+#define LDA_BLK_FLAGS 4		/* BFINAL | LDA_BLK_STORED */
+#define LDA_BLK_STORED 2u	/* level 0 and tiny inputs: stored only */
+#define LDA_BLK_FREQ 8		/* [320] litlen 0..287, offset 288..319 (no end-of-block) */
+#define LDA_BLK_WORDS (LDA_BLK_FREQ + 320)
+#define LDA_BLK_OVERFLOW 0xFFFFFFFFu
+#define LDA_BLK_FUSED 0xFFFFFFFEu
+#define LDA_BLK_LIST(n) (((n) + 15) / 16 * 16)
+#define LDA_BLK_HDR_WORDS(n) (2 * LDA_BLK_LIST(n))
 extern "C" __global__ void
 lda_deflate_batch_kernel(uint64_t n_chunks, int format, int level,
 			 uint32_t depth, uint32_t nice, uint32_t mode,
@@ -66,7 +92,34 @@ lda_deflate_batch_kernel(uint64_t n_chunks, int format, int level,
 			 const uint64_t *out_offsets, const uint64_t *out_avail,
 			 uint64_t *out_nbytes, const uint32_t *sums,
 			 uint64_t *seq_scratch, const uint32_t *seg_info,
-			 uint32_t *next_chunk, const uint8_t *dict_pre);
+			 uint32_t *next_chunk, const uint8_t *dict_pre,
+			 uint32_t *tok_buf, uint32_t *blk_buf, uint32_t tok_stride,
+			 uint32_t blk_stride, uint32_t *fused_cnt);
+/* the same body with the block end inside the tile loop (no bound: unbounded
+ * batches, a preset dictionary; blk_buf NULL), or behind a split launch for
+ * the buffers it marked LDA_BLK_FUSED (blk_buf of that launch) */
+extern "C" __global__ void
+lda_deflate_fused_kernel(uint64_t n_chunks, int format, int level,
+			 uint32_t depth, uint32_t nice, uint32_t mode,
+			 const uint8_t *in_base, const uint64_t *in_offsets,
+			 const uint64_t *in_nbytes, uint8_t *out_base,
+			 const uint64_t *out_offsets, const uint64_t *out_avail,
+			 uint64_t *out_nbytes, const uint32_t *sums,
+			 uint64_t *seq_scratch, const uint32_t *seg_info,
+			 uint32_t *next_chunk, const uint8_t *dict_pre,
+			 const uint32_t *blk_buf, const uint32_t *fused_cnt);
+/* deflate_entropy.hip: one workgroup per buffer of the launch before it */
+#define LDA_DEFLATE_ENTROPY_THREADS 256
+extern "C" __global__ void
+lda_deflate_entropy_kernel(uint64_t n_chunks, int format, int level,
+			   const uint8_t *in_base, const uint64_t *in_offsets,
+			   const uint64_t *in_nbytes, uint8_t *out_base,
+			   const uint64_t *out_offsets, const uint64_t *out_avail,
+			   uint64_t *out_nbytes, const uint32_t *sums,
+			   const uint32_t *seg_info, const uint32_t *tok_buf,
+			   const uint32_t *blk_buf, uint32_t tok_stride,
+			   uint32_t blk_stride);
+extern "C" size_t lda_deflate_entropy_lds_bytes(void);
 /* same body with the min-cost parse compiled in: levels 10-12 */
 extern "C" __global__ void
 lda_deflate_opt_kernel(uint64_t n_chunks, int format, int level,

@@ -75,7 +75,7 @@ PHASES_DEFLATE = ["init/other", "S0 load", "S2 insert", "S3 round B + worklist",
                   "RB: generation 0", "RB: generation 1", "RB: generation 2", "RB: generations 3+", "worklist"]
 
 
-def read_profile(name, labels):
+def read_profile(name, labels, title="thread 0 of each workgroup, summed"):
     import ctypes
     from libdeflate_amd import binding
     lib = binding.load()
@@ -88,7 +88,7 @@ def read_profile(name, labels):
     tot = sum(buf)
     if not tot:
         return
-    print("  phase cycles (thread 0 of each workgroup, summed):")
+    print(f"  phase cycles ({title}):")
     for i, v in enumerate(buf):
         if v:
             lab = labels[i] if i < len(labels) else f"slot{i}"
@@ -170,12 +170,16 @@ def bench_deflate(a, fmt="gzip", level=6):
               if a.size <= 4096 and level <= 9 and not os.environ.get("LDA_NO_SMALL")
               else "libdeflate_amd_profile_read_deflate")
     read_profile(reader, PHASES_DEFLATE)  # reset
+    # the block ends of levels 0-9 run in lda_deflate_entropy_kernel (deflate_entropy.hip)
+    read_profile("libdeflate_amd_profile_read_deflate_entropy", PHASES_DEFLATE)
     t = timeit(f, iters=a.iters, warmup=0)
     U = n * a.size
     C = int(c_n.sum())
     print(f"deflate[{fmt} L{level}]: {U/t/1e9:.2f} GB/s uncompressed, algorithmic "
           f"{(U+C)/t/1e9:.2f} GB/s, {t*1e3:.2f} ms, ratio {C/U:.4f}")
     read_profile(reader, PHASES_DEFLATE)
+    read_profile("libdeflate_amd_profile_read_deflate_entropy", PHASES_DEFLATE,
+                 "entropy kernel: thread 0 of each workgroup, summed")
 
 
 if __name__ == "__main__":
