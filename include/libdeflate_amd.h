@@ -189,6 +189,7 @@ enum libdeflate_amd_format {
 	LIBDEFLATE_AMD_DEFLATE = 0,	/* raw DEFLATE     */
 	LIBDEFLATE_AMD_ZLIB = 1,	/* + 2 B header, Adler-32 footer (BE) */
 	LIBDEFLATE_AMD_GZIP = 2,	/* + 10 B header, CRC-32 + ISIZE (LE) */
+	LIBDEFLATE_AMD_BGZF = 3,	/* gzip member with BGZF's 18 B header (below) */
 };
 
 /* status of the library itself (not of a stream) */
@@ -499,6 +500,84 @@ libdeflate_amd_gzip_decompress_members(struct libdeflate_decompressor *d,
 				       size_t *actual_in_nbytes_ret,
 				       size_t *actual_out_nbytes_ret,
 				       size_t *members_ret);
+
+/*
+ * BGZF (blocked gzip, SAM/BAM spec 4.1: BAM, tabix, bgzip, .vcf.gz): a file
+ * is a run of gzip members of at most LIBDEFLATE_AMD_BGZF_BLOCK input bytes
+ * each, ended by a fixed 28-byte empty member (the EOF marker).  Every member
+ * starts with htslib's 16 bytes
+ *     1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00
+ * (FEXTRA, MTIME 0, XFL 0, OS 0xff, XLEN 6, subfield "BC" of length 2)
+ * followed by BSIZE = member size - 1 as u16 LE, so a member is at most
+ * LIBDEFLATE_AMD_BGZF_MEMBER_MAX bytes.  Its deflate body is byte for byte
+ * what LIBDEFLATE_AMD_GZIP gives the same block at the same level; the
+ * blocks are independent (no window crosses a member boundary), so a reader
+ * may start at any member.
+ *
+ * LIBDEFLATE_AMD_BGZF is also a format of libdeflate_amd_compress_batch,
+ * _bounded and _batch_host, for callers who cut their own blocks (htslib cuts
+ * them at record boundaries): chunk i becomes one member in slot i; a chunk
+ * of more than LIBDEFLATE_AMD_BGZF_BLOCK bytes, or one whose member does not
+ * fit min(out_avail[i], LIBDEFLATE_AMD_BGZF_MEMBER_MAX), reports 0.  The
+ * dictionary calls and the decompress batch refuse the format: members
+ * decode as LIBDEFLATE_AMD_GZIP, whole files with
+ * libdeflate_amd_gzip_decompress_members.
+ */
+#define LIBDEFLATE_AMD_BGZF_BLOCK	65280	/* input bytes per member (htslib BGZF_BLOCK_SIZE) */
+#define LIBDEFLATE_AMD_BGZF_MEMBER_MAX	65536	/* BSIZE + 1 is 16 bits */
+#define LIBDEFLATE_AMD_BGZF_EOF_BYTES	28	/* the EOF member */
+#define LIBDEFLATE_AMD_BGZF_NO_EOF	1	/* flag: omit the EOF member (appending writers) */
+
+/*
+ * Bytes a BGZF file of in_nbytes input needs at most: m members of at most
+ * LIBDEFLATE_AMD_BGZF_MEMBER_MAX bytes, m = ceil(in_nbytes / 65280), and the
+ * EOF member.  compressor may be NULL.
+ */
+LIBDEFLATEAPI size_t
+libdeflate_amd_bgzf_compress_bound(struct libdeflate_compressor *compressor,
+				   size_t in_nbytes);
+
+/*
+ * A whole BGZF file from ONE device buffer d_in of in_nbytes bytes: block k
+ * is bytes [65280 k, 65280 (k + 1)), the last one shorter; in_nbytes == 0
+ * gives m = 0 members, the EOF member alone.  Enqueues on `stream` and
+ * returns; d_out_nbytes[0] (device memory) receives the file's size, or 0
+ * when a member did not fit (cannot happen) or the file does not fit
+ * out_avail - then nothing is written past out_avail, and d_index is
+ * undefined.  (With LIBDEFLATE_AMD_BGZF_NO_EOF and in_nbytes == 0 the size is
+ * 0 too: there is nothing to write.)
+ *
+ * d_index: NULL, or device room for 2 (m + 1) u64: the pairs (compressed
+ * offset, uncompressed offset) of the start of every member, and as pair m
+ * (offset of the EOF member - or where it would be under NO_EOF -,
+ * in_nbytes).  flags: 0 or LIBDEFLATE_AMD_BGZF_NO_EOF.
+ *
+ * The arguments are checked before any device work: LIBDEFLATE_AMD_BAD_ARG
+ * for a NULL object or pointer, unknown flags, or an out_avail below 27 bytes
+ * per member plus the EOF member (no file can fit that).  d_out must not
+ * overlap d_in.  The object's scratch holds the m members before they are
+ * packed (64 KiB per member).
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_bgzf_compress_batch(struct libdeflate_compressor *compressor,
+				   const void *d_in, size_t in_nbytes,
+				   void *d_out, size_t out_avail,
+				   uint64_t *d_out_nbytes, uint64_t *d_index,
+				   unsigned flags, void *stream);
+
+/*
+ * The same from and to HOST memory, blocking: returns the file's size, 0 when
+ * it does not fit out_avail or an argument is bad (reason in
+ * libdeflate_amd_last_error()).  index: NULL, or index_avail u64 entries of
+ * which 2 (m + 1) are written as above.  The bytes are those of
+ * libdeflate_amd_bgzf_compress_batch; large inputs go through in slices whose
+ * transfers overlap the kernels.
+ */
+LIBDEFLATEAPI size_t
+libdeflate_amd_bgzf_compress(struct libdeflate_compressor *compressor,
+			     const void *in, size_t in_nbytes,
+			     void *out, size_t out_avail,
+			     uint64_t *index, size_t index_avail, unsigned flags);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,50 @@ class Compressor:
     __del__ = close
 
     def bound(self, fmt, n):
+        if fmt == "bgzf":   # one member: gzip's bound with 8 more header bytes
+            return self._lib.libdeflate_gzip_compress_bound(self._h, n) + 8
         return getattr(self._lib, f"libdeflate_{fmt}_compress_bound")(self._h, n)
+
+    def bgzf_bound(self, n):
+        """libdeflate_amd_bgzf_compress_bound: the most bytes a BGZF file of n
+        input bytes takes (64 KiB per member and the EOF member)."""
+        return self._lib.libdeflate_amd_bgzf_compress_bound(self._h, n)
+
+    def compress_bgzf(self, data, index=False, eof=True, out_avail=None):
+        """libdeflate_amd_bgzf_compress: host bytes -> a BGZF file (one member
+        per 65280 bytes, then the EOF member unless eof=False).  Returns the
+        bytes, or (bytes, index) with index=True: a numpy uint64 array of
+        m + 1 rows (compressed offset, uncompressed offset), the last row the
+        EOF member's (or the end's).  None when the call returns 0."""
+        p, n = _buf(data)
+        m = -(-n // binding.BGZF_BLOCK)
+        if out_avail is None:
+            out_avail = self.bgzf_bound(n)
+        out = np.empty(max(out_avail, 1), dtype=np.uint8)
+        idx = np.zeros(2 * (m + 1), dtype=np.uint64) if index else None
+        r = self._lib.libdeflate_amd_bgzf_compress(
+            self._h, p, n, out.ctypes.data_as(c_void_p), out_avail,
+            idx.ctypes.data_as(c_void_p) if index else None, idx.size if index else 0,
+            0 if eof else binding.BGZF_NO_EOF)
+        if r == 0 and (eof or n):
+            return None
+        if index:
+            return out[:r].tobytes(), idx.reshape(m + 1, 2)
+        return out[:r].tobytes()
+
+    def compress_bgzf_batch(self, data, out, out_nbytes, index=None, eof=True,
+                            stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_bgzf_compress_batch: a BGZF file of the uint8 torch
+        CUDA tensor `data` (its first in_nbytes bytes) into `out` (out_avail
+        bytes of it, default all); out_nbytes: int64 CUDA tensor, [0] gets the
+        file's size (0: does not fit).  index: None or an int64 CUDA tensor of
+        2 (m + 1) entries.  Only enqueues on `stream`."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_bgzf_compress_batch(
+            self._h, data.data_ptr(), n, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), out_nbytes.data_ptr(),
+            index.data_ptr() if index is not None else None,
+            0 if eof else binding.BGZF_NO_EOF, _stream_ptr(stream)), "bgzf_compress_batch")
 
     def compress(self, fmt, data, out_avail=None):
         """Returns the compressed bytes, or None when the reference API would
@@ -247,6 +290,25 @@ class Decompressor:
             r.append((res[i], ain[i], aout[i],
                       outs[i][:nout].tobytes() if res[i] == 0 else b""))
         return r
+
+
+def bgzf_gzi(index):
+    """The index of a BGZF file (rows of compressed / uncompressed offsets of
+    every member start, as compress_bgzf(index=True) returns them, the EOF row
+    last) as the bytes of bgzip's .gzi: u64 LE count, then the pairs of the
+    member starts after the first.  Follows htslib's description of the
+    format; not compared with bgzip -i itself."""
+    rows = np.asarray(index, dtype=np.uint64).reshape(-1, 2)[1:-1]
+    return (np.array([len(rows)], dtype="<u8").tobytes() +
+            rows.astype("<u8").tobytes())
+
+
+def bgzf_gzi_parse(blob):
+    """bgzf_gzi()'s bytes back to rows (compressed, uncompressed) of the member
+    starts after the first."""
+    count = int(np.frombuffer(blob[:8], dtype="<u8")[0])
+    assert len(blob) == 8 + 16 * count, "truncated .gzi"
+    return np.frombuffer(blob[8:], dtype="<u8").reshape(count, 2)
 
 
 def _stream_ptr(stream):

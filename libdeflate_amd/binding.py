@@ -18,8 +18,11 @@ LIB_PATH = os.environ.get("LIBDEFLATE_AMD_LIB",
                           os.path.join(_HERE, "libdeflate_amd.so"))
 
 SUCCESS, BAD_DATA, SHORT_OUTPUT, INSUFFICIENT_SPACE = 0, 1, 2, 3
-FMT_DEFLATE, FMT_ZLIB, FMT_GZIP = 0, 1, 2
-FORMATS = {"deflate": FMT_DEFLATE, "zlib": FMT_ZLIB, "gzip": FMT_GZIP}
+FMT_DEFLATE, FMT_ZLIB, FMT_GZIP, FMT_BGZF = 0, 1, 2, 3
+FORMATS = {"deflate": FMT_DEFLATE, "zlib": FMT_ZLIB, "gzip": FMT_GZIP, "bgzf": FMT_BGZF}
+# BGZF (include/libdeflate_amd.h): input bytes per member, largest member, the
+# EOF member's size, the flag that leaves it out
+BGZF_BLOCK, BGZF_MEMBER_MAX, BGZF_EOF_BYTES, BGZF_NO_EOF = 65280, 65536, 28, 1
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -50,6 +53,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_selfcheck",
     "libdeflate_amd_compress_batch_dict", "libdeflate_amd_decompress_batch_dict",
     "libdeflate_amd_compress_dict", "libdeflate_amd_decompress_dict_ex",
+    "libdeflate_amd_bgzf_compress_bound", "libdeflate_amd_bgzf_compress_batch",
+    "libdeflate_amd_bgzf_compress",
 ]
 
 _lib = None
@@ -132,6 +137,10 @@ def load():
     sig("libdeflate_amd_compress_dict", SZ, P, c_int, P, SZ, P, SZ, P, SZ)
     sig("libdeflate_amd_decompress_dict_ex", c_int, P, c_int, P, SZ, P, SZ, P, SZ,
         psz, psz)
+    # BGZF files from one buffer: bound, device (enqueue only), host (blocking)
+    sig("libdeflate_amd_bgzf_compress_bound", SZ, P, SZ)
+    sig("libdeflate_amd_bgzf_compress_batch", c_int, P, P, SZ, P, SZ, P, P, c_uint32, P)
+    sig("libdeflate_amd_bgzf_compress", SZ, P, P, SZ, P, SZ, P, SZ, c_uint32)
     _lib = lib
     return lib
 

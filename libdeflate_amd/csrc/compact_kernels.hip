@@ -17,6 +17,8 @@
  *                            = local prefix + block prefix, then a copy with
  *                            16-byte stores to the aligned part of the
  *                            destination
+ *
+ * and the BGZF file assembly behind a compress batch (lda_bgzf_*).
  */
 #include "device_common.h"
 #include "kernels.h"
@@ -111,6 +113,27 @@ lda_scan_blocks_kernel(u64 nblocks, u64 *__restrict__ block_sums)
 		block_sums[nblocks] = carry_s;
 }
 
+/* len bytes src -> dst by a 256-thread workgroup: bytes up to the first 16-byte
+ * boundary of dst, 16-byte stores, the tail */
+static __device__ __forceinline__ void
+copy_span(const u8 *__restrict__ src, u8 *__restrict__ dst, u64 len, u32 tid)
+{
+	u64 head = (0 - (uintptr_t)dst) & 15;
+	if (head > len)
+		head = len;
+	if (tid < head)
+		dst[tid] = src[tid];
+	const u64 body = (len - head) & ~(u64)15;
+	for (u64 k = head + 16 * (u64)tid; k < head + body; k += 16 * 256) {
+		uint4 v;
+		__builtin_memcpy(&v, src + k, 16);	/* source may be unaligned */
+		*(uint4 *)(dst + k) = v;
+	}
+	const u64 tail = head + body;
+	if (tail + tid < len)
+		dst[tail + tid] = src[tail + tid];
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 lda_compact_copy_kernel(u64 n, const u8 *__restrict__ in_base,
 			const u64 *__restrict__ in_offsets,
@@ -132,20 +155,88 @@ lda_compact_copy_kernel(u64 n, const u8 *__restrict__ in_base,
 			if (c == n - 1)
 				offsets[n] = block_sums[(n + SCAN_BLOCK - 1) / SCAN_BLOCK];
 		}
-		/* head: up to the first 16-byte boundary of the destination */
-		u64 head = (0 - (uintptr_t)dst) & 15;
-		if (head > len)
-			head = len;
-		if (tid < head)
-			dst[tid] = src[tid];
-		const u64 body = (len - head) & ~(u64)15;
-		for (u64 k = head + 16 * (u64)tid; k < head + body; k += 16 * 256) {
-			uint4 v;
-			__builtin_memcpy(&v, src + k, 16);	/* source may be unaligned */
-			*(uint4 *)(dst + k) = v;
+		copy_span(src, dst, len, tid);
+	}
+}
+
+/*
+ * A BGZF file (SAM/BAM spec 4.1) from one device buffer of n bytes: block k
+ * is bytes [LDA_BGZF_BLOCK k, +LDA_BGZF_BLOCK) - the last one shorter - and
+ * becomes member k, compressed into slot k (LDA_BGZF_MEMBER_MAX bytes) of a
+ * scratch area by the compress kernels (format LDA_FMT_BGZF).  The scan
+ * kernels above turn the member sizes into offsets; these three do the rest.
+ */
+
+/* the batch descriptors of the m blocks: input offset and size, slot offset
+ * and size; nothing is uploaded from the host */
+extern "C" __global__ void __launch_bounds__(256)
+lda_bgzf_desc_kernel(u64 m, u64 n, u64 *__restrict__ in_off, u64 *__restrict__ in_n,
+		     u64 *__restrict__ slot_off, u64 *__restrict__ slot_avail)
+{
+	const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (k >= m)
+		return;
+	const u64 a = k * LDA_BGZF_BLOCK;
+	in_off[k] = a;
+	in_n[k] = n - a < LDA_BGZF_BLOCK ? n - a : LDA_BGZF_BLOCK;
+	slot_off[k] = k * LDA_BGZF_MEMBER_MAX;
+	slot_avail[k] = LDA_BGZF_MEMBER_MAX;
+}
+
+/* the members back to back at out, when all of them and eof_bytes more fit
+ * out_avail (otherwise nothing is written: the finalize kernel reports 0);
+ * index[2k], index[2k + 1] = the compressed and uncompressed offsets of
+ * member k.  offsets / block_sums: the scan kernels' output */
+extern "C" __global__ void __launch_bounds__(256)
+lda_bgzf_copy_kernel(u64 m, const u8 *__restrict__ slots, const u64 *__restrict__ sizes,
+		     const u64 *__restrict__ offsets, const u64 *__restrict__ block_sums,
+		     u8 *__restrict__ out, u64 out_avail, u32 eof_bytes, u64 *__restrict__ index)
+{
+	const u32 tid = threadIdx.x;
+	const u64 total = block_sums[(m + SCAN_BLOCK - 1) / SCAN_BLOCK];
+
+	if (total > out_avail || out_avail - total < eof_bytes)
+		return;
+	for (u64 c = blockIdx.x; c < m; c += gridDim.x) {
+		const u64 start = offsets[c] + block_sums[c / SCAN_BLOCK];
+		if (tid == 0 && index) {
+			index[2 * c] = start;
+			index[2 * c + 1] = c * LDA_BGZF_BLOCK;
 		}
-		const u64 tail = head + body;
-		if (tail + tid < len)
-			dst[tail + tid] = src[tail + tid];
+		copy_span(slots + c * LDA_BGZF_MEMBER_MAX, out + start, sizes[c], tid);
+	}
+}
+
+/* the empty member that ends a BGZF file (SAM/BAM spec 4.1.2) */
+static __device__ const u8 k_bgzf_eof[28] = {
+	0x1f, 0x8b, 0x08, 0x04, 0x00, 0x00, 0x00, 0x00, 0x00, 0xff, 0x06, 0x00, 0x42, 0x43,
+	0x02, 0x00, 0x1b, 0x00, 0x03, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00,
+};
+
+/* one workgroup behind the copy: the EOF member (eof_bytes 28 or 0), the
+ * file's size into *out_nbytes - 0 when a member did not fit its slot or the
+ * file does not fit out_avail - and the index's last pair (EOF member, n).
+ * total_at: the scan's grand total, NULL for m == 0 */
+extern "C" __global__ void __launch_bounds__(256)
+lda_bgzf_finalize_kernel(u64 m, u64 n, const u64 *__restrict__ sizes,
+			 const u64 *__restrict__ total_at, u8 *__restrict__ out, u64 out_avail,
+			 u32 eof_bytes, u64 *__restrict__ out_nbytes, u64 *__restrict__ index)
+{
+	const u32 tid = threadIdx.x;
+	int missing = 0;
+
+	for (u64 k = tid; k < m; k += 256)
+		missing |= sizes[k] == 0;
+	missing = __syncthreads_or(missing);
+	const u64 total = total_at ? *total_at : 0;
+	const bool ok = !missing && total <= out_avail && out_avail - total >= eof_bytes;
+	if (ok && tid < eof_bytes)
+		out[total + tid] = k_bgzf_eof[tid];
+	if (tid == 0) {
+		*out_nbytes = ok ? total + eof_bytes : 0;
+		if (ok && index) {
+			index[2 * m] = total;
+			index[2 * m + 1] = n;
+		}
 	}
 }

@@ -184,13 +184,20 @@ static __device__ __forceinline__ void stg_save(lds_t *L, struct outstate *os)
 }
 
 /* the container header (gzip_compress.c:44-64, zlib_compress.c:45-60) at bit
- * 0: thread 0 writes it, every thread advances os */
+ * 0: thread 0 writes it, every thread advances os.  BGZF: htslib's fixed
+ * 16 bytes - FEXTRA, XFL 0 and OS 0xff at every level, XLEN 6, the "BC"
+ * subfield of length 2 - and BSIZE as 0 until finish_stream() knows it */
 static __device__ __forceinline__ void
 put_container_header(lds_t *L, struct outstate *os, int format, int level,
 		     const u8 *__restrict__ dict_pre, u32 hdr_bytes, u32 tid)
 {
 	if (tid == 0) {
-		if (format == LDA_FMT_GZIP) {
+		if (format == LDA_FMT_BGZF) {
+			stg_put(L, os, 0, 0x04088B1Full, 32);
+			stg_put(L, os, 32, 0, 32);	/* MTIME */
+			stg_put(L, os, 64, 0xFFu << 8, 16);
+			stg_put(L, os, 80, 0x0243420006ull, 48);	/* 06 00 'B' 'C' 02 00 */
+		} else if (format == LDA_FMT_GZIP) {
 			/* XFL 4 fastest, 2 best */
 			u32 xfl = level < 2 ? 4 : level >= 8 ? 2 : 0;
 			stg_put(L, os, 0, 0x00088B1Full, 32);
@@ -645,8 +652,9 @@ block_emit(lds_t *L, struct outstate *os, const u32 *__restrict__ tokg, u32 nseq
 /*
  * After the last block: the empty stored block that byte-aligns a segment
  * other than the last (lib/deflate_compress.c:1839-1847), the trailer
- * (gzip_compress.c:73-79 / zlib_compress.c:66-72: sum, and n for gzip), the
- * last bytes, and the stream's size - 0 when it does not fit.  Whole workgroup.
+ * (gzip_compress.c:73-79 / zlib_compress.c:66-72: sum, and n for gzip and
+ * BGZF), the last bytes, the stream's size - 0 when it does not fit - and a
+ * BGZF member's BSIZE.  Whole workgroup.
  */
 static __device__ __forceinline__ void
 finish_stream(lds_t *L, struct outstate *os, bool overflow, bool seg_last,
@@ -671,7 +679,7 @@ finish_stream(lds_t *L, struct outstate *os, bool overflow, bool seg_last,
 			u32 sum = sums ? sums[c] : 0;
 			u64 fb = 8 * ((os->bits + 7) / 8);
 			if (tid == 0) {
-				if (format == LDA_FMT_GZIP) {
+				if (format != LDA_FMT_ZLIB) {	/* gzip, BGZF */
 					stg_put(L, os, fb, sum, 32);
 					stg_put(L, os, fb + 32, n, 32);
 				} else {
@@ -682,8 +690,23 @@ finish_stream(lds_t *L, struct outstate *os, bool overflow, bool seg_last,
 			__syncthreads();
 		}
 		stg_flush(L, os, true);
+		const u32 size = (u32)((os->bits + 7) / 8);
 		if (tid == 0)
-			out_nbytes[c] = (os->bits + 7) / 8;
+			out_nbytes[c] = size;
+		if (format == LDA_FMT_BGZF) {
+			/* BSIZE = size - 1 (<= 65535: os->avail is at most
+			 * LDA_BGZF_MEMBER_MAX).  Bytes 16..17 went out as zeros in
+			 * some thread's 16-byte unit, maybe in the flush above: every
+			 * thread waits for its stores (acknowledged by the L2 that
+			 * thread 0's store goes to as well), then thread 0 overwrites
+			 * the two bytes with one vector store */
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			__syncthreads();
+			if (tid == 0) {
+				const u16 bsize = (u16)(size - 1);
+				__builtin_memcpy(os->out + 16, &bsize, 2);
+			}
+		}
 	} else if (tid == 0) {
 		out_nbytes[c] = 0;
 	}

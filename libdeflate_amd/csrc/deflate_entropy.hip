@@ -97,12 +97,16 @@ lda_deflate_entropy_kernel(u64 n_chunks, int format, int level,
 	const u8 *__restrict__ inp = in_base + in_offsets[c];
 	const u32 n = (u32)in_nbytes[c];	/* (checked by the LZ77 stage) */
 	const bool seg_last = seg_info ? seg_info[c] >> 31 : true;
-	const u32 hdr_bytes = format == LDA_FMT_GZIP ? 10 : format == LDA_FMT_ZLIB ? 2 : 0;
-	const u32 ftr_bytes = format == LDA_FMT_GZIP ? 8 : format == LDA_FMT_ZLIB ? 4 : 0;
+	const u32 hdr_bytes = format == LDA_FMT_GZIP ? 10 : format == LDA_FMT_BGZF ? 18 :
+			      format == LDA_FMT_ZLIB ? 2 : 0;
+	const u32 ftr_bytes = format == LDA_FMT_GZIP || format == LDA_FMT_BGZF ? 8 :
+			      format == LDA_FMT_ZLIB ? 4 : 0;
 	bool overflow = nb == LDA_BLK_OVERFLOW;
 	struct outstate os;
 	os.out = out_base + out_offsets[c];
 	os.avail = out_avail_arr[c];
+	if (format == LDA_FMT_BGZF && os.avail > LDA_BGZF_MEMBER_MAX)
+		os.avail = LDA_BGZF_MEMBER_MAX;	/* (the LZ77 stage refused a larger block) */
 	os.sg = (u64)(0 - ((uintptr_t)os.out & 15));
 	os.bits = 0;
 	u32 tog = 0;

@@ -2085,11 +2085,18 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		struct outstate os;
 		os.out = out_base + out_offsets[c];
 		os.avail = out_avail_arr[c];
-		const u32 hdr_bytes = format == LDA_FMT_GZIP ? 10 :
+		const u32 hdr_bytes = format == LDA_FMT_GZIP ? 10 : format == LDA_FMT_BGZF ? 18 :
 				      format == LDA_FMT_ZLIB ? (dict_pre ? 6 : 2) : 0;
-		const u32 ftr_bytes = format == LDA_FMT_GZIP ? 8 :
+		const u32 ftr_bytes = format == LDA_FMT_GZIP || format == LDA_FMT_BGZF ? 8 :
 				      format == LDA_FMT_ZLIB ? 4 : 0;
 		bool overflow = false;
+		/* a BGZF member holds at most LDA_BGZF_BLOCK bytes and states its
+		 * size in 16 bits: it fits LDA_BGZF_MEMBER_MAX or reports 0 */
+		if (format == LDA_FMT_BGZF) {
+			os.avail = os.avail < LDA_BGZF_MEMBER_MAX ? os.avail : LDA_BGZF_MEMBER_MAX;
+			if (n64 > LDA_BGZF_BLOCK)
+				overflow = true;
+		}
 
 		/* the reference refuses outright when the container cannot fit
 		 * (gzip_compress.c:41-42, zlib_compress.c:42-43) */

@@ -41,6 +41,11 @@ typedef int64_t s64;
 #define LDA_FMT_DEFLATE 0
 #define LDA_FMT_ZLIB 1
 #define LDA_FMT_GZIP 2
+/* a BGZF member (SAM/BAM spec 4.1): gzip with the 18-byte header of htslib,
+ * whose BSIZE the kernel writes once the member's size is known */
+#define LDA_FMT_BGZF 3
+#define LDA_BGZF_BLOCK 65280u		/* input bytes per member (htslib BGZF_BLOCK_SIZE) */
+#define LDA_BGZF_MEMBER_MAX 65536u	/* BSIZE is 16 bits: BSIZE + 1 bytes per member */
 
 static __device__ __forceinline__ u32 lane_id(void)
 {

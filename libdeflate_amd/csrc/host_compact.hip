@@ -7,8 +7,6 @@
 
 using namespace lda;
 
-#define LDA_SCAN_BLOCK 2048	/* compact_kernels.hip: SCAN_BLOCK */
-
 extern "C" LIBDEFLATEAPI size_t
 libdeflate_amd_compact_offsets_len(size_t n_chunks)
 {

@@ -106,6 +106,7 @@ libdeflate_free_compressor(struct libdeflate_compressor *c)
 	c->stage.release();
 	c->pinned.release();
 	c->meta.release();
+	c->bgzf.release();
 	c->streams.release();
 	free_func_t f = c->free_func;
 	c->~libdeflate_compressor();
@@ -262,7 +263,7 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		return LIBDEFLATE_AMD_OK;
 	if (!c || !d_in || !d_in_offsets || !d_in_nbytes || !d_out ||
 	    !d_out_offsets || !d_out_avail || !d_out_nbytes ||
-	    format < LIBDEFLATE_AMD_DEFLATE || format > LIBDEFLATE_AMD_GZIP) {
+	    format < LIBDEFLATE_AMD_DEFLATE || format > LIBDEFLATE_AMD_BGZF) {
 		set_error("compress_batch: bad argument");
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
@@ -296,7 +297,7 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 	uint32_t *sums = NULL;
 	if (format != LIBDEFLATE_AMD_DEFLATE) {
 		sums = (uint32_t *)(scr + pl.sums_at);
-		int rc = format == LIBDEFLATE_AMD_GZIP ?
+		int rc = format == LIBDEFLATE_AMD_GZIP || format == LIBDEFLATE_AMD_BGZF ?
 			libdeflate_amd_crc32_batch(n, d_in, d_in_offsets,
 						   d_in_nbytes, NULL, sums, stream) :
 			libdeflate_amd_adler32_batch(n, d_in, d_in_offsets,

@@ -58,6 +58,7 @@ struct libdeflate_compressor {
 	int level;
 	lda::DevBuf scratch;	/* parse/encode workspace + per-chunk sums */
 	lda::DevBuf stage;
+	lda::DevBuf bgzf;	/* BGZF files: block descriptors, member slots (host_bgzf.hip) */
 	lda::PinnedPair pinned;	/* host-pointer entry points */
 	lda::PinnedBuf meta;	/* host-pointer entry points: per-chunk read-backs */
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */

@@ -152,6 +152,7 @@ extern "C" size_t lda_inflate_lds_per_stream(void);
 extern "C" size_t lda_inflate_lds_shared(void);
 
 /* compact_kernels.hip */
+#define LDA_SCAN_BLOCK 2048	/* compact_kernels.hip: SCAN_BLOCK, sizes per lda_scan_local_kernel workgroup */
 extern "C" __global__ void
 lda_scan_local_kernel(uint64_t n, const uint64_t *sizes, uint64_t *offsets,
 		      uint64_t *block_sums);
@@ -162,6 +163,18 @@ lda_compact_copy_kernel(uint64_t n, const uint8_t *in_base,
 			const uint64_t *in_offsets, const uint64_t *sizes,
 			uint8_t *out_base, uint64_t *offsets,
 			const uint64_t *block_sums);
+/* compact_kernels.hip: a BGZF file from one device buffer (host_bgzf.hip) */
+extern "C" __global__ void
+lda_bgzf_desc_kernel(uint64_t m, uint64_t n, uint64_t *in_off, uint64_t *in_n,
+		     uint64_t *slot_off, uint64_t *slot_avail);
+extern "C" __global__ void
+lda_bgzf_copy_kernel(uint64_t m, const uint8_t *slots, const uint64_t *sizes,
+		     const uint64_t *offsets, const uint64_t *block_sums, uint8_t *out,
+		     uint64_t out_avail, uint32_t eof_bytes, uint64_t *index);
+extern "C" __global__ void
+lda_bgzf_finalize_kernel(uint64_t m, uint64_t n, const uint64_t *sizes,
+			 const uint64_t *total_at, uint8_t *out, uint64_t out_avail,
+			 uint32_t eof_bytes, uint64_t *out_nbytes, uint64_t *index);
 
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
