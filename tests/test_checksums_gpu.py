@@ -69,3 +69,70 @@ def test_single_buffer_api(oracle):
     assert api.crc32(b, api.crc32(a)) == api.crc32(data)
     assert api.adler32(b, api.adler32(a)) == api.adler32(data)
     assert api.crc32(b"") == 0 and api.adler32(b"") == 1
+
+
+SEG = 1 << 24    # ADLER_SEG: the Adler-32 kernel's segment of one chunk
+
+
+def test_batch_above_one_segment():
+    """chunks of 2^24 - 1, 2^24, 2^24 + 1 and 2^25 + 17 bytes (the Adler-32
+    kernel's multi-segment update s2 += n*s1 + W): all 0xFF and random bytes,
+    the default and the largest initial value, offsets 0 and 13"""
+    import torch
+    from libdeflate_amd import api
+    rng = np.random.default_rng(0x0E110A32)
+    rnd = rng.integers(0, 256, size=2 * SEG + 17, dtype=np.uint8).tobytes()
+    sizes = [SEG - 1, SEG, SEG + 1, 2 * SEG + 17]
+    for pad in (0, 13):
+        for fill in ("ff", "random"):
+            chunks = [b"\xff" * n if fill == "ff" else rnd[:n] for n in sizes]
+            data, offs, nb = _device_batch(chunks, pad)
+            out = torch.zeros(len(chunks), dtype=torch.int32, device="cuda")
+            for kind, inits in (("adler32", (1, (65520 << 16) | 65520)),
+                                ("crc32", (0, 0xFFFFFFFF))):
+                for iv in inits:
+                    init = torch.from_numpy(
+                        np.full(len(chunks), iv, dtype=np.uint32).view(np.int32)).cuda()
+                    api.checksum_batch(kind, data, offs, nb, out, init=init)
+                    torch.cuda.synchronize()
+                    got = out.cpu().numpy().view(np.uint32)
+                    for i, c in enumerate(chunks):
+                        z = zlib.adler32(c, iv) if kind == "adler32" else zlib.crc32(c, iv)
+                        assert got[i] == z, (kind, fill, pad, len(c), hex(iv))
+            del data
+
+
+def test_single_buffer_above_one_segment():
+    """libdeflate_adler32 / libdeflate_crc32 on 40 MiB, and chained over a
+    split that leaves both sides longer than one segment"""
+    from libdeflate_amd import api
+    rng = np.random.default_rng(0x0E110A33)
+    data = rng.integers(0, 256, size=40 << 20, dtype=np.uint8).tobytes()
+    assert api.adler32(data) == zlib.adler32(data)
+    assert api.crc32(data) == zlib.crc32(data)
+    cut = SEG + 4097
+    a, b = data[:cut], data[cut:]
+    assert api.adler32(b, api.adler32(a)) == zlib.adler32(data)
+    assert api.crc32(b, api.crc32(a)) == zlib.crc32(data)
+    ff = b"\xff" * (2 * SEG + 17)
+    assert api.adler32(ff, (65520 << 16) | 65520) == zlib.adler32(ff, (65520 << 16) | 65520)
+
+
+def test_zlib_footer_above_one_segment():
+    """a zlib stream of 2^24 + 4097 bytes of output as a batch of one: its
+    footer is checked with the whole output's Adler-32 in one chunk; a
+    wrong footer is refused"""
+    from libdeflate_amd import api
+    n = SEG + 4097
+    raw = datagen.text_chunk(n, 0x0E110A34)
+    z = zlib.compress(raw, 1)
+    d = api.Decompressor()
+    try:
+        r = d.decompress_batch_host("zlib", [z], [n])[0]
+        assert r[0] == 0 and r[1] == len(z) and r[2] == n and r[3] == raw
+        for at in (-1, -3):
+            b = bytearray(z)
+            b[at] ^= 0x01
+            assert d.decompress_batch_host("zlib", [bytes(b)], [n])[0][0] == 1
+    finally:
+        d.close()
