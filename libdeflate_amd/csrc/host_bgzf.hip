@@ -10,7 +10,6 @@
  */
 #include <string.h>
 #include <algorithm>
-#include <vector>
 
 #include "host_objects.h"
 #include "kernels.h"
@@ -147,10 +146,10 @@ libdeflate_amd_bgzf_compress_batch(struct libdeflate_compressor *c, const void *
  * split path asks for (LDA_SPLIT_MIN_PER_CU in host_compress.hip), so every
  * slice but a short last one takes it; each slice is a file of its own
  * without the EOF member (bgzf_enqueue() with NO_EOF), since the members are
- * independent the slices' files concatenate into the whole one.  While the
- * kernels of slice k run on the compute stream, the host sends slice k + 1
- * and brings back slice k - 1 (two input and two output areas alternate, as
- * in compress_large()).  Nothing is primed and no checksum is stitched.
+ * independent the slices' files concatenate into the whole one.  On
+ * run_slices(): while the kernels of slice k run on the compute stream, the
+ * host sends slice k + 1 and brings back slice k - 1 (two input and two
+ * output areas alternate).  Nothing is primed and no checksum is stitched.
  */
 static size_t bgzf_host(struct libdeflate_compressor *c, const uint8_t *in, size_t n,
 			uint8_t *out, size_t out_avail, uint64_t *index, unsigned flags)
@@ -180,32 +179,9 @@ static size_t bgzf_host(struct libdeflate_compressor *c, const uint8_t *in, size
 		}
 		hipStream_t s_copy = c->streams.copy, s_comp = c->streams.comp;
 		const size_t piece = ns > 1 ? (size_t)1 << 20 : 0;
-		std::vector<hipEvent_t> ev_done(ns, nullptr);
-		bool fits = true, failed = false;
-		auto drain = [&](size_t k) -> bool {
-			const size_t lo = k * per, mk = std::min(per, m - lo);
-			if (hipEventSynchronize(ev_done[k]) != hipSuccess)
-				return false;
-			const uint64_t *h = h_meta + (k & 1) * meta_words;
-			const size_t tk = (size_t)h[0];
-			if (!tk || total + tk > out_avail - eof) {
-				if (!tk)
-					set_error("libdeflate_amd_bgzf_compress: a member did not fit");
-				fits = false;
-				return true;
-			}
-			if (span_out(&c->pinned, st, out_at + (k & 1) * out_cap, out + total, tk, s_copy,
-				     piece) != LIBDEFLATE_AMD_OK)
-				return false;
-			if (index)
-				for (size_t j = 0; j < mk; j++) {
-					index[2 * (lo + j)] = total + h[1 + 2 * j];
-					index[2 * (lo + j) + 1] = lo * BGZF_BLOCK + h[2 + 2 * j];
-				}
-			total += tk;
-			return true;
-		};
-		for (size_t k = 0; k < ns && fits && !failed; k++) {
+		/* slice k uses the areas k & 1: run_slices() has drained slice
+		 * k - 2 before it sends slice k */
+		auto enqueue = [&](size_t k) -> int {
 			const size_t lo = k * per, mk = std::min(per, m - lo);
 			const size_t a = lo * BGZF_BLOCK, b = std::min(n, (lo + mk) * BGZF_BLOCK);
 			uint64_t *d_meta = (uint64_t *)st + (k & 1) * meta_words;
@@ -218,31 +194,40 @@ static size_t bgzf_host(struct libdeflate_compressor *c, const uint8_t *in, size
 					 s_comp) != LIBDEFLATE_AMD_OK ||
 			    hipMemcpyAsync(h_meta + (k & 1) * meta_words, d_meta,
 					   (index ? 1 + 2 * mk : 1) * 8, hipMemcpyDeviceToHost,
-					   s_comp) != hipSuccess ||
-			    hipEventCreateWithFlags(&ev_done[k], hipEventDisableTiming) != hipSuccess ||
-			    hipEventRecord(ev_done[k], s_comp) != hipSuccess) {
-				failed = true;
-				break;
+					   s_comp) != hipSuccess)
+				return LIBDEFLATE_AMD_NO_DEVICE;
+			return LIBDEFLATE_AMD_OK;
+		};
+		auto drain = [&](size_t k) -> int {
+			const size_t lo = k * per, mk = std::min(per, m - lo);
+			const uint64_t *h = h_meta + (k & 1) * meta_words;
+			const size_t tk = (size_t)h[0];
+			if (!tk || total + tk > out_avail - eof) {
+				if (!tk)
+					set_error("libdeflate_amd_bgzf_compress: a member did not fit");
+				return SLICES_STOP;
 			}
-			if (k && !drain(k - 1))
-				failed = true;
-		}
-		if (!failed && fits && !drain(ns - 1))
-			failed = true;
-		(void)hipStreamSynchronize(s_comp);
-		(void)hipStreamSynchronize(s_copy);
-		for (size_t k = 0; k < ns; k++)
-			if (ev_done[k])
-				(void)hipEventDestroy(ev_done[k]);
-		if (failed) {
+			if (span_out(&c->pinned, st, out_at + (k & 1) * out_cap, out + total, tk, s_copy,
+				     piece) != LIBDEFLATE_AMD_OK)
+				return LIBDEFLATE_AMD_NO_DEVICE;
+			if (index)
+				for (size_t j = 0; j < mk; j++) {
+					index[2 * (lo + j)] = total + h[1 + 2 * j];
+					index[2 * (lo + j) + 1] = lo * BGZF_BLOCK + h[2 + 2 * j];
+				}
+			total += tk;
+			return LIBDEFLATE_AMD_OK;
+		};
+		const int rc = run_slices("libdeflate_amd_bgzf_compress", c->streams, ns, enqueue, drain);
+		if (rc == SLICES_STOP)
+			return 0;
+		if (rc != LIBDEFLATE_AMD_OK) {
 			hipError_t e = hipGetLastError();
 			if (e != hipSuccess)
 				set_error("libdeflate_amd_bgzf_compress: %s", hipGetErrorString(e));
 			complain("libdeflate_amd_bgzf_compress", LIBDEFLATE_AMD_NO_DEVICE);
 			return 0;
 		}
-		if (!fits)
-			return 0;
 	}
 	memcpy(out + total, k_bgzf_eof, eof);
 	if (index) {

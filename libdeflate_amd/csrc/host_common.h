@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include <atomic>
 #include <exception>
+#include <functional>
 #include <mutex>
 
 #include "../../include/libdeflate_amd.h"
@@ -141,6 +142,29 @@ struct StreamPair {
 	bool ensure();
 	void release();
 };
+
+/*
+ * The slice pipeline of the host-pointer calls, on an object's StreamPair.
+ * For k = 0 .. ns - 1, enqueue(k) sends slice k on `copy` and returns once
+ * its bytes are on the device, then queues the slice's kernels and its
+ * read-backs into pinned memory on `comp`.  The runner records slice k's
+ * event on `comp`; for k > 0 it waits for slice k - 1's event and calls
+ * drain(k - 1), which hands the read-backs to the caller and brings the
+ * slice's output back on `copy`, returning once it is on the host.  The last
+ * slice is drained after the loop.  So drain(k - 1) has returned before
+ * enqueue(k + 1) starts: a staging area that slices k - 1 and k + 1 share is
+ * free again when slice k + 1 is sent into it.
+ *
+ * The run stops at the first status of either callback that is not
+ * LIBDEFLATE_AMD_OK and returns it; a drain returns SLICES_STOP to end the
+ * run without an error (the output does not fit).  A failed event call sets
+ * the error "<what>: <HIP error>" and returns LIBDEFLATE_AMD_NO_DEVICE.
+ * However it returns (an exception included), both streams are synchronised
+ * and the events destroyed.
+ */
+enum { SLICES_STOP = 1 };
+int run_slices(const char *what, const StreamPair &sp, size_t ns,
+	       const std::function<int(size_t)> &enqueue, const std::function<int(size_t)> &drain);
 
 /* cut n chunks into at most `max_slices` consecutive slices of about equal
  * byte counts (each at least `min_bytes`, as far as the total allows);

@@ -17,10 +17,6 @@
 #include "host_objects.h"
 #include "kernels.h"
 
-namespace lda {
-bool pick_allocator(const struct libdeflate_options *options,
-		    malloc_func_t *m, free_func_t *f);
-}
 using namespace lda;
 
 /*
@@ -443,63 +439,6 @@ libdeflate_amd_compress_batch_bounded(struct libdeflate_compressor *c, int forma
 static int compress_batch_host_body(struct libdeflate_compressor *c, int format,
 				   size_t n, const void *const *in,
 				   const size_t *in_nbytes, void *const *out,
-				   const size_t *out_avail, size_t *out_nbytes);
-
-extern "C" LIBDEFLATEAPI int
-libdeflate_amd_compress_batch_host(struct libdeflate_compressor *c, int format,
-				   size_t n, const void *const *in,
-				   const size_t *in_nbytes, void *const *out,
-				   const size_t *out_avail, size_t *out_nbytes)
-{
-	return no_unwind("compress_batch_host", (int)LIBDEFLATE_AMD_OOM, [&]() {
-		if (!c || !in_nbytes || n == 0)
-			return compress_batch_host_body(c, format, n, in, in_nbytes, out, out_avail,
-							out_nbytes);
-		/* several GPUs (LDA_DEVICES, host_fanout.hip): contiguous shards,
-		 * an object and a host thread per device, results in place */
-		size_t bounds[LDA_MAX_SHARDS + 1];
-		int devs[LDA_MAX_SHARDS];
-		const size_t shards = fanout_plan(c->device, n, in_nbytes, bounds, devs);
-		fanout_note(shards);
-		if (shards < 2)
-			return compress_batch_host_body(c, format, n, in, in_nbytes, out, out_avail,
-							out_nbytes);
-		if (!in || !out || !out_avail || !out_nbytes) {
-			set_error("compress_batch_host: NULL argument");
-			return (int)LIBDEFLATE_AMD_BAD_ARG;
-		}
-		for (size_t k = 1; k < shards; k++) {
-			if (c->shard[k])
-				continue;
-			DeviceGuard on(devs[k]);
-			struct libdeflate_options o = {};
-			o.sizeof_options = sizeof(o);
-			o.malloc_func = c->malloc_func;
-			o.free_func = c->free_func;
-			if (on.ok())
-				c->shard[k] = libdeflate_alloc_compressor_ex(c->level, &o);
-			if (!c->shard[k]) {
-				/* a device that cannot take its shard (out of memory,
-				 * refused by the self-check, busy): the batch stays on
-				 * the object's own device rather than fail - the reason
-				 * stays in libdeflate_amd_last_error() */
-				fanout_note(1);
-				return compress_batch_host_body(c, format, n, in, in_nbytes, out, out_avail,
-							out_nbytes);
-			}
-		}
-		return fanout_run(shards, [&](size_t k) {
-			const size_t lo = bounds[k], cnt = bounds[k + 1] - lo;
-			return compress_batch_host_body(k ? c->shard[k] : c, format, cnt, in + lo,
-							in_nbytes + lo, out + lo, out_avail + lo,
-							out_nbytes + lo);
-		});
-	});
-}
-
-static int compress_batch_host_body(struct libdeflate_compressor *c, int format,
-				   size_t n, const void *const *in,
-				   const size_t *in_nbytes, void *const *out,
 				   const size_t *out_avail, size_t *out_nbytes)
 {
 	if (n == 0)
@@ -514,9 +453,9 @@ static int compress_batch_host_body(struct libdeflate_compressor *c, int format,
 	/* The batch goes through in SLICES (up to 8, >= 64 MiB of input each - a
 	 * slice has to fill the GPU several times over, or its kernel's tail
 	 * costs more than the overlap gives: 8 MiB slices measured slower than
-	 * no slices): the
-	 * kernels of slice k run on the object's compute stream while the host
-	 * packs and sends slice k + 1 and unpacks slice k - 1 on its copy stream.
+	 * no slices) on run_slices(): the kernels of slice k run on the object's
+	 * compute stream while the host packs and sends slice k + 1 and unpacks
+	 * slice k - 1 on its copy stream.
 	 * device layout: [in_off in_n out_off out_av out_n][cmp_off of every
 	 * slice] [inputs] [output slots] [compacted outputs, slice after slice];
 	 * everything 16-byte aligned */
@@ -582,58 +521,60 @@ static int compress_batch_host_body(struct libdeflate_compressor *c, int format,
 	LDA_HIP_TRY(hipMemcpyAsync(st, desc.data(), 4 * n * 8, hipMemcpyHostToDevice,
 				   s_copy), LIBDEFLATE_AMD_NO_DEVICE);
 	uint64_t *d_desc = (uint64_t *)st;
-	hipEvent_t ev_done[MAX_SLICES] = {};
-	int rc = LIBDEFLATE_AMD_OK;
-	auto cleanup = [&]() {
-		(void)hipStreamSynchronize(s_comp);
-		(void)hipStreamSynchronize(s_copy);
-		for (size_t k = 0; k < ns; k++)
-			if (ev_done[k])
-				(void)hipEventDestroy(ev_done[k]);
+	auto enqueue = [&](size_t k) -> int {
+		const size_t lo = bounds[k], nk = bounds[k + 1] - lo;
+		/* (returns when the slice is on the device) */
+		int rc = copy_in_packed(&c->pinned, st, nk, in + lo, in_nbytes + lo, in_off + lo, s_copy);
+		if (rc == LIBDEFLATE_AMD_OK)
+			rc = libdeflate_amd_compress_batch_bounded(
+				c, format, nk, st, d_desc + lo, d_desc + n + lo, st, d_desc + 2 * n + lo,
+				d_desc + 3 * n + lo, d_desc + 4 * n + lo, max_in, s_comp);
+		if (rc == LIBDEFLATE_AMD_OK)
+			rc = libdeflate_amd_compact_batch(nk, st, d_desc + 2 * n + lo, d_desc + 4 * n + lo,
+							  st + cmp_at + avail_before[k] + 64 * k,
+							  d_desc + 5 * n + cmp_pos[k], s_comp);
+		if (rc != LIBDEFLATE_AMD_OK)
+			return rc;
+		if (hipMemcpyAsync(out_n + lo, d_desc + 4 * n + lo, nk * 8, hipMemcpyDeviceToHost,
+				   s_comp) != hipSuccess ||
+		    hipMemcpyAsync(cmp_off + cmp_pos[k], d_desc + 5 * n + cmp_pos[k], (nk + 1) * 8,
+				   hipMemcpyDeviceToHost, s_comp) != hipSuccess) {
+			set_error("compress_batch_host: %s", hipGetErrorString(hipGetLastError()));
+			return LIBDEFLATE_AMD_NO_DEVICE;
+		}
+		return LIBDEFLATE_AMD_OK;
 	};
 	/* slice k's streams are complete on the device: sizes to the caller,
 	 * bytes through the pinned pair */
 	auto drain = [&](size_t k) -> int {
 		const size_t lo = bounds[k], nk = bounds[k + 1] - lo;
-		LDA_HIP_TRY(hipEventSynchronize(ev_done[k]), LIBDEFLATE_AMD_NO_DEVICE);
 		for (size_t i = lo; i < lo + nk; i++)
 			out_nbytes[i] = out_n[i];
 		return copy_out_packed(&c->pinned, st + cmp_at + avail_before[k] + 64 * k, nk,
 				       out + lo, out_n + lo, cmp_off + cmp_pos[k], s_copy);
 	};
-	for (size_t k = 0; k < ns && rc == LIBDEFLATE_AMD_OK; k++) {
-		const size_t lo = bounds[k], nk = bounds[k + 1] - lo;
-		/* (returns when the slice is on the device) */
-		rc = copy_in_packed(&c->pinned, st, nk, in + lo, in_nbytes + lo, in_off + lo, s_copy);
-		if (rc != LIBDEFLATE_AMD_OK)
-			break;
-		rc = libdeflate_amd_compress_batch_bounded(
-			c, format, nk, st, d_desc + lo, d_desc + n + lo, st, d_desc + 2 * n + lo,
-			d_desc + 3 * n + lo, d_desc + 4 * n + lo, max_in, s_comp);
-		if (rc != LIBDEFLATE_AMD_OK)
-			break;
-		rc = libdeflate_amd_compact_batch(nk, st, d_desc + 2 * n + lo, d_desc + 4 * n + lo,
-						  st + cmp_at + avail_before[k] + 64 * k,
-						  d_desc + 5 * n + cmp_pos[k], s_comp);
-		if (rc != LIBDEFLATE_AMD_OK)
-			break;
-		if (hipMemcpyAsync(out_n + lo, d_desc + 4 * n + lo, nk * 8, hipMemcpyDeviceToHost,
-				   s_comp) != hipSuccess ||
-		    hipMemcpyAsync(cmp_off + cmp_pos[k], d_desc + 5 * n + cmp_pos[k], (nk + 1) * 8,
-				   hipMemcpyDeviceToHost, s_comp) != hipSuccess ||
-		    hipEventCreateWithFlags(&ev_done[k], hipEventDisableTiming) != hipSuccess ||
-		    hipEventRecord(ev_done[k], s_comp) != hipSuccess) {
-			set_error("compress_batch_host: %s", hipGetErrorString(hipGetLastError()));
-			rc = LIBDEFLATE_AMD_NO_DEVICE;
-			break;
-		}
-		if (k)
-			rc = drain(k - 1);
-	}
-	if (rc == LIBDEFLATE_AMD_OK)
-		rc = drain(ns - 1);
-	cleanup();
-	return rc;
+	return run_slices("compress_batch_host", c->streams, ns, enqueue, drain);
+}
+
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_compress_batch_host(struct libdeflate_compressor *c, int format,
+				   size_t n, const void *const *in,
+				   const size_t *in_nbytes, void *const *out,
+				   const size_t *out_avail, size_t *out_nbytes)
+{
+	return no_unwind("compress_batch_host", (int)LIBDEFLATE_AMD_OOM, [&]() {
+		auto body = [&](struct libdeflate_compressor *o, size_t lo, size_t cnt) {
+			return compress_batch_host_body(o, format, cnt, in + lo, in_nbytes + lo,
+							out + lo, out_avail + lo, out_nbytes + lo);
+		};
+		/* (a bad argument is reported by the one-device path) */
+		if (!c || n == 0 || !in || !in_nbytes || !out || !out_avail || !out_nbytes)
+			return body(c, 0, n);
+		/* several GPUs (LDA_DEVICES): shards of about equal input */
+		return fanout<libdeflate_compressor>(c, n, in_nbytes, [&](const libdeflate_options *o) {
+			return libdeflate_alloc_compressor_ex(c->level, o);
+		}, body);
+	});
 }
 
 /*
@@ -711,8 +652,8 @@ static size_t large_fail(const char *what)
 }
 
 /*
- * The segments go through in SLICES of up to 32 MiB of input on the object's
- * two streams, like the host-pointer batches: while the kernels of slice k
+ * The segments go through in SLICES of up to 32 MiB of input on run_slices(),
+ * like the host-pointer batches: while the kernels of slice k
  * (deflate of its segments, their checksums, the compaction of their streams)
  * run on the compute stream, the host packs slice k + 1 into the pinned
  * staging and sends it, and brings the compacted streams of slice k - 1 back.
@@ -823,7 +764,6 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	    (pre && hipMemcpyAsync(st + in_at - pre, prefix.data(), pre, hipMemcpyHostToDevice,
 				   s_copy) != hipSuccess))
 		return large_fail("copy in");
-	std::vector<hipEvent_t> ev_done(ns, nullptr);
 	/* A call of one slice (up to 32 MiB) takes the copy helpers' own pieces:
 	 * all copy threads on its input AND on its output (16 MiB: 10.9 -> 12.2
 	 * GB/s, round 6).  A call of several slices keeps pieces of 1 MiB, with
@@ -833,41 +773,14 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	 * the calling thread is what queues the next slice's kernels). */
 	const size_t piece = ns > 1 ? (size_t)1 << 20 : 0;
 	size_t total = hdr;	/* bytes of the output so far */
-	bool fits = true, failed = false;
-	auto cleanup = [&]() {
-		(void)hipStreamSynchronize(s_comp);
-		(void)hipStreamSynchronize(s_copy);
-		for (size_t k = 0; k < ns; k++)
-			if (ev_done[k])
-				(void)hipEventDestroy(ev_done[k]);
-	};
-	auto drain = [&](size_t k) -> bool {
-		const size_t lo = k * per_slice, nk = std::min(per_slice, nseg - lo);
-		if (hipEventSynchronize(ev_done[k]) != hipSuccess)
-			return false;
-		for (size_t i = lo; i < lo + nk; i++)
-			if (h_out_n[i] == 0)
-				fits = false;	/* a segment did not fit its slot: cannot happen within the bound */
-		const size_t tk = (size_t)h_tot[k];
-		if (!fits || total + tk + ftr > out_avail) {
-			fits = false;
-			return true;
-		}
-		if (tk && span_out(&c->pinned, st, pk_at + lo * slot, out + total, tk, s_copy, piece) != LIBDEFLATE_AMD_OK)
-			return false;
-		total += tk;
-		return true;
-	};
-	for (size_t k = 0; k < ns && fits && !failed; k++) {
+	auto enqueue = [&](size_t k) -> int {
 		const size_t lo = k * per_slice, nk = std::min(per_slice, nseg - lo);
 		const size_t a = lo * S, b = std::min(n, (lo + nk) * S);
 		/* (returns when the slice - and, the first time, the descriptors -
 		 * are on the device) */
 		if (b > a ? span_in(&c->pinned, st, in_at + a, in + a, b - a, s_copy, piece) != LIBDEFLATE_AMD_OK :
-			    hipStreamSynchronize(s_copy) != hipSuccess) {
-			failed = true;
-			break;
-		}
+			    hipStreamSynchronize(s_copy) != hipSuccess)
+			return LIBDEFLATE_AMD_NO_DEVICE;
 		int rc = compress_batch_impl(c, LIBDEFLATE_AMD_DEFLATE, nk, st, d_desc + lo,
 					     d_desc + nseg + lo, st, d_desc + 2 * nseg + lo,
 					     d_desc + 3 * nseg + lo, d_desc + 4 * nseg + lo, s_comp,
@@ -888,21 +801,27 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 		    hipMemcpyAsync(h_tot + k, d_cmp + cmp_pos[k] + nk, 8, hipMemcpyDeviceToHost,
 				   s_comp) != hipSuccess ||
 		    (ftr && hipMemcpyAsync(h_sums + lo, d_sums + lo, nk * 4, hipMemcpyDeviceToHost,
-					   s_comp) != hipSuccess) ||
-		    hipEventCreateWithFlags(&ev_done[k], hipEventDisableTiming) != hipSuccess ||
-		    hipEventRecord(ev_done[k], s_comp) != hipSuccess) {
-			failed = true;
-			break;
-		}
-		if (k && !drain(k - 1))
-			failed = true;
-	}
-	if (!failed && fits && !drain(ns - 1))
-		failed = true;
-	cleanup();
-	if (failed)
+					   s_comp) != hipSuccess))
+			return LIBDEFLATE_AMD_NO_DEVICE;
+		return LIBDEFLATE_AMD_OK;
+	};
+	auto drain = [&](size_t k) -> int {
+		const size_t lo = k * per_slice, nk = std::min(per_slice, nseg - lo);
+		for (size_t i = lo; i < lo + nk; i++)
+			if (h_out_n[i] == 0)
+				return SLICES_STOP;	/* a segment did not fit its slot: cannot happen within the bound */
+		const size_t tk = (size_t)h_tot[k];
+		if (total + tk + ftr > out_avail)
+			return SLICES_STOP;
+		if (tk && span_out(&c->pinned, st, pk_at + lo * slot, out + total, tk, s_copy, piece) != LIBDEFLATE_AMD_OK)
+			return LIBDEFLATE_AMD_NO_DEVICE;
+		total += tk;
+		return LIBDEFLATE_AMD_OK;
+	};
+	const int rc = run_slices("segmented compress", c->streams, ns, enqueue, drain);
+	if (rc != LIBDEFLATE_AMD_OK && rc != SLICES_STOP)
 		return large_fail("segmented compress");
-	if (!fits || total + ftr > out_avail)
+	if (rc == SLICES_STOP || total + ftr > out_avail)
 		return 0;
 	const size_t at = total;
 	total += ftr;

@@ -191,6 +191,48 @@ void StreamPair::release()
 	mark = mark2 = nullptr;
 }
 
+int run_slices(const char *what, const StreamPair &sp, size_t ns,
+	       const std::function<int(size_t)> &enqueue, const std::function<int(size_t)> &drain)
+{
+	/* whatever way this returns, nothing of the run is left in flight when
+	 * the caller's staging and pinned memory go on to other work */
+	struct Events {
+		const StreamPair &sp;
+		std::vector<hipEvent_t> done;
+		~Events()
+		{
+			(void)hipStreamSynchronize(sp.comp);
+			(void)hipStreamSynchronize(sp.copy);
+			for (hipEvent_t e : done)
+				if (e)
+					(void)hipEventDestroy(e);
+		}
+	} ev{ sp, {} };
+	ev.done.assign(ns, nullptr);
+	int rc = LIBDEFLATE_AMD_OK;
+	/* step k queues slice k (if any) and then drains slice k - 1 (if any) */
+	for (size_t k = 0; k <= ns && rc == LIBDEFLATE_AMD_OK; k++) {
+		hipError_t e = hipSuccess;
+		if (k < ns) {
+			rc = enqueue(k);
+			if (rc != LIBDEFLATE_AMD_OK)
+				break;
+			e = hipEventCreateWithFlags(&ev.done[k], hipEventDisableTiming);
+			if (e == hipSuccess)
+				e = hipEventRecord(ev.done[k], sp.comp);
+		}
+		if (e == hipSuccess && k)
+			e = hipEventSynchronize(ev.done[k - 1]);
+		if (e != hipSuccess) {
+			set_error("%s: %s", what, hipGetErrorString(e));
+			return LIBDEFLATE_AMD_NO_DEVICE;
+		}
+		if (k)
+			rc = drain(k - 1);
+	}
+	return rc;
+}
+
 size_t slice_by_bytes(size_t n, const size_t *nbytes, size_t max_slices,
 		      size_t min_bytes, size_t *bounds)
 {

@@ -45,7 +45,6 @@ void DevBuf::release()
 	cap = 0;
 }
 
-/* resolve the allocator the way lib/deflate_compress.c:3910-3917 does */
 bool pick_allocator(const struct libdeflate_options *options,
 		    malloc_func_t *m, free_func_t *f)
 {
@@ -364,69 +363,6 @@ static int decompress_batch_host_body(struct libdeflate_decompressor *d,
 				     const void *const *in,
 				     const size_t *in_nbytes, void *const *out,
 				     const size_t *out_avail, int32_t *results,
-				     size_t *actual_in, size_t *actual_out);
-
-extern "C" LIBDEFLATEAPI int
-libdeflate_amd_decompress_batch_host(struct libdeflate_decompressor *d,
-				     int format, size_t n,
-				     const void *const *in,
-				     const size_t *in_nbytes, void *const *out,
-				     const size_t *out_avail, int32_t *results,
-				     size_t *actual_in, size_t *actual_out)
-{
-	return no_unwind("decompress_batch_host", (int)LIBDEFLATE_AMD_OOM, [&]() {
-		if (!d || !out_avail || n == 0)
-			return decompress_batch_host_body(d, format, n, in, in_nbytes, out, out_avail,
-							  results, actual_in, actual_out);
-		/* several GPUs (LDA_DEVICES, host_fanout.hip): shards of about equal
-		 * OUTPUT (what a stream costs to decode), an object and a host thread
-		 * per device, results in place */
-		size_t bounds[LDA_MAX_SHARDS + 1];
-		int devs[LDA_MAX_SHARDS];
-		const size_t shards = fanout_plan(d->device, n, out_avail, bounds, devs);
-		fanout_note(shards);
-		if (shards < 2)
-			return decompress_batch_host_body(d, format, n, in, in_nbytes, out, out_avail,
-							  results, actual_in, actual_out);
-		if (!in || !in_nbytes || !out || !results) {
-			set_error("decompress_batch_host: NULL argument");
-			return (int)LIBDEFLATE_AMD_BAD_ARG;
-		}
-		for (size_t k = 1; k < shards; k++) {
-			if (d->shard[k])
-				continue;
-			DeviceGuard on(devs[k]);
-			struct libdeflate_options o = {};
-			o.sizeof_options = sizeof(o);
-			o.malloc_func = d->malloc_func;
-			o.free_func = d->free_func;
-			if (on.ok())
-				d->shard[k] = libdeflate_alloc_decompressor_ex(&o);
-			if (!d->shard[k]) {
-				/* a device that cannot take its shard (out of memory,
-				 * refused by the self-check, busy): the batch stays on
-				 * the object's own device rather than fail - the reason
-				 * stays in libdeflate_amd_last_error() */
-				fanout_note(1);
-				return decompress_batch_host_body(d, format, n, in, in_nbytes, out, out_avail,
-							  results, actual_in, actual_out);
-			}
-		}
-		return fanout_run(shards, [&](size_t k) {
-			const size_t lo = bounds[k], cnt = bounds[k + 1] - lo;
-			return decompress_batch_host_body(k ? d->shard[k] : d, format, cnt, in + lo,
-							  in_nbytes + lo, out + lo, out_avail + lo,
-							  results + lo, actual_in ? actual_in + lo : NULL,
-							  actual_out ? actual_out + lo : NULL);
-		});
-	});
-}
-
-static int decompress_batch_host_body(struct libdeflate_decompressor *d,
-				     int format, size_t n,
-				     const void *const *in,
-				     const size_t *in_nbytes, void *const *out,
-				     const size_t *out_avail, int32_t *results,
 				     size_t *actual_in, size_t *actual_out)
 {
 	if (n == 0)
@@ -438,11 +374,11 @@ static int decompress_batch_host_body(struct libdeflate_decompressor *d,
 	DeviceGuard on(d->device);
 	if (!on.ok() || !device_ctx())
 		return LIBDEFLATE_AMD_NO_DEVICE;
-	/* In slices like libdeflate_amd_compress_batch_host(): the kernels of
-	 * slice k (compute stream) run while the host packs and sends slice k + 1
-	 * and unpacks slice k - 1 (copy stream).  Slices of at least 256 MiB of
-	 * output: a launch of few streams is latency bound (one wave per stream),
-	 * so small slices cost more kernel time than their overlap saves.
+	/* In slices on run_slices(): the kernels of slice k (compute stream) run
+	 * while the host packs and sends slice k + 1 and unpacks slice k - 1
+	 * (copy stream).  Slices of at least 256 MiB of output: a launch of few
+	 * streams is latency bound (one wave per stream), so small slices cost
+	 * more kernel time than their overlap saves.
 	 * staging layout: 6 u64 arrays + results, then inputs, then outputs */
 	enum { MAX_SLICES = 8 };
 	size_t bounds[MAX_SLICES + 1];
@@ -488,18 +424,30 @@ static int decompress_batch_host_body(struct libdeflate_decompressor *d,
 	uint64_t *d_desc = (uint64_t *)st;
 	int32_t *d_res = (int32_t *)(st + 6 * n * 8);
 	std::vector<uint64_t> nout(n);
-	hipEvent_t ev_done[MAX_SLICES] = {};
-	int rc = LIBDEFLATE_AMD_OK;
-	auto cleanup = [&]() {
-		(void)hipStreamSynchronize(s_comp);
-		(void)hipStreamSynchronize(s_copy);
-		for (size_t k = 0; k < ns; k++)
-			if (ev_done[k])
-				(void)hipEventDestroy(ev_done[k]);
+	auto enqueue = [&](size_t k) -> int {
+		const size_t lo = bounds[k], nk = bounds[k + 1] - lo;
+		int rc = copy_in_packed(&d->pinned, st, nk, in + lo, in_nbytes + lo, in_off + lo, s_copy);
+		if (rc == LIBDEFLATE_AMD_OK)
+			rc = libdeflate_amd_decompress_batch(
+				d, format, nk, st, d_desc + lo, d_desc + n + lo, st, d_desc + 2 * n + lo,
+				d_desc + 3 * n + lo, d_res + lo, d_desc + 4 * n + lo,
+				actual_out ? d_desc + 5 * n + lo : NULL, s_comp);
+		if (rc != LIBDEFLATE_AMD_OK)
+			return rc;
+		if (hipMemcpyAsync(h_ain + lo, d_desc + 4 * n + lo, nk * 8,
+				   hipMemcpyDeviceToHost, s_comp) != hipSuccess ||
+		    (actual_out &&
+		     hipMemcpyAsync(h_aout + lo, d_desc + 5 * n + lo, nk * 8,
+				    hipMemcpyDeviceToHost, s_comp) != hipSuccess) ||
+		    hipMemcpyAsync(h_res + lo, d_res + lo, nk * 4, hipMemcpyDeviceToHost,
+				   s_comp) != hipSuccess) {
+			set_error("decompress_batch_host: %s", hipGetErrorString(hipGetLastError()));
+			return LIBDEFLATE_AMD_NO_DEVICE;
+		}
+		return LIBDEFLATE_AMD_OK;
 	};
 	auto drain = [&](size_t k) -> int {
 		const size_t lo = bounds[k], nk = bounds[k + 1] - lo;
-		LDA_HIP_TRY(hipEventSynchronize(ev_done[k]), LIBDEFLATE_AMD_NO_DEVICE);
 		/* bytes to bring back per chunk: the produced ones of successful
 		 * chunks (output is undefined on failure, libdeflate.h:216-217) */
 		for (size_t i = lo; i < lo + nk; i++) {
@@ -514,37 +462,32 @@ static int decompress_batch_host_body(struct libdeflate_decompressor *d,
 		return copy_out_packed(&d->pinned, st, nk, out + lo, nout.data() + lo,
 				       out_off + lo, s_copy);
 	};
-	for (size_t k = 0; k < ns && rc == LIBDEFLATE_AMD_OK; k++) {
-		const size_t lo = bounds[k], nk = bounds[k + 1] - lo;
-		rc = copy_in_packed(&d->pinned, st, nk, in + lo, in_nbytes + lo, in_off + lo, s_copy);
-		if (rc != LIBDEFLATE_AMD_OK)
-			break;
-		rc = libdeflate_amd_decompress_batch(
-			d, format, nk, st, d_desc + lo, d_desc + n + lo, st, d_desc + 2 * n + lo,
-			d_desc + 3 * n + lo, d_res + lo, d_desc + 4 * n + lo,
-			actual_out ? d_desc + 5 * n + lo : NULL, s_comp);
-		if (rc != LIBDEFLATE_AMD_OK)
-			break;
-		if (hipMemcpyAsync(h_ain + lo, d_desc + 4 * n + lo, nk * 8,
-				   hipMemcpyDeviceToHost, s_comp) != hipSuccess ||
-		    (actual_out &&
-		     hipMemcpyAsync(h_aout + lo, d_desc + 5 * n + lo, nk * 8,
-				    hipMemcpyDeviceToHost, s_comp) != hipSuccess) ||
-		    hipMemcpyAsync(h_res + lo, d_res + lo, nk * 4, hipMemcpyDeviceToHost,
-				   s_comp) != hipSuccess ||
-		    hipEventCreateWithFlags(&ev_done[k], hipEventDisableTiming) != hipSuccess ||
-		    hipEventRecord(ev_done[k], s_comp) != hipSuccess) {
-			set_error("decompress_batch_host: %s", hipGetErrorString(hipGetLastError()));
-			rc = LIBDEFLATE_AMD_NO_DEVICE;
-			break;
-		}
-		if (k)
-			rc = drain(k - 1);
-	}
-	if (rc == LIBDEFLATE_AMD_OK)
-		rc = drain(ns - 1);
-	cleanup();
-	return rc;
+	return run_slices("decompress_batch_host", d->streams, ns, enqueue, drain);
+}
+
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_decompress_batch_host(struct libdeflate_decompressor *d,
+				     int format, size_t n,
+				     const void *const *in,
+				     const size_t *in_nbytes, void *const *out,
+				     const size_t *out_avail, int32_t *results,
+				     size_t *actual_in, size_t *actual_out)
+{
+	return no_unwind("decompress_batch_host", (int)LIBDEFLATE_AMD_OOM, [&]() {
+		auto body = [&](struct libdeflate_decompressor *o, size_t lo, size_t cnt) {
+			return decompress_batch_host_body(o, format, cnt, in + lo, in_nbytes + lo,
+							  out + lo, out_avail + lo, results + lo,
+							  actual_in ? actual_in + lo : NULL,
+							  actual_out ? actual_out + lo : NULL);
+		};
+		/* (a bad argument is reported by the one-device path) */
+		if (!d || n == 0 || !in || !in_nbytes || !out || !out_avail || !results)
+			return body(d, 0, n);
+		/* several GPUs (LDA_DEVICES): shards of about equal OUTPUT (what a
+		 * stream costs to decode) */
+		return fanout<libdeflate_decompressor>(d, n, out_avail,
+						       libdeflate_alloc_decompressor_ex, body);
+	});
 }
 
 /* ---- the single-buffer calls: batches of one ---- */

@@ -30,12 +30,10 @@ namespace lda {
 
 static thread_local size_t t_last_fanout = 1;
 
-void fanout_note(size_t shards)
-{
-	t_last_fanout = shards;
-}
-
-size_t fanout_plan(int own_device, size_t n, const size_t *nbytes, size_t *bounds, int *devs)
+/* the devices a batch of n chunks is spread over (1 = the object's own device
+ * only), and the plan: shard k takes the chunks [bounds[k], bounds[k+1]) on
+ * device devs[k] */
+static size_t fanout_plan(int own_device, size_t n, const size_t *nbytes, size_t *bounds, int *devs)
 {
 	const EnvCfg &env = env_cfg();
 	int want = env.devices, count = 0;
@@ -63,7 +61,9 @@ size_t fanout_plan(int own_device, size_t n, const size_t *nbytes, size_t *bound
 	return k;
 }
 
-int fanout_run(size_t shards, const std::function<int(size_t)> &fn)
+/* fn(k) for k = 1 .. shards-1 on threads of their own and fn(0) on the
+ * calling one; returns the first non-OK status */
+static int fanout_run(size_t shards, const std::function<int(size_t)> &fn)
 {
 	/* Nothing may unwind past a joinable std::thread (that is std::terminate),
 	 * and the error text is per thread: every shard - the calling thread's
@@ -116,6 +116,48 @@ int fanout_run(size_t shards, const std::function<int(size_t)> &fn)
 	delete[] slot;
 	return rc;
 }
+
+template <typename Obj>
+int fanout(Obj *o, size_t n, const size_t *weight,
+	   const std::function<Obj *(const struct libdeflate_options *)> &alloc,
+	   const std::function<int(Obj *, size_t, size_t)> &body)
+{
+	size_t bounds[LDA_MAX_SHARDS + 1];
+	int devs[LDA_MAX_SHARDS];
+	const size_t shards = fanout_plan(o->device, n, weight, bounds, devs);
+	t_last_fanout = shards;
+	if (shards < 2)
+		return body(o, 0, n);
+	for (size_t k = 1; k < shards; k++) {
+		if (o->shard[k])
+			continue;
+		DeviceGuard on(devs[k]);
+		struct libdeflate_options opt = {};
+		opt.sizeof_options = sizeof(opt);
+		opt.malloc_func = o->malloc_func;
+		opt.free_func = o->free_func;
+		if (on.ok())
+			o->shard[k] = alloc(&opt);
+		if (!o->shard[k]) {
+			/* a device that cannot take its shard (out of memory, refused
+			 * by the self-check, busy): the batch stays on the object's
+			 * own device rather than fail - the reason stays in
+			 * libdeflate_amd_last_error() */
+			t_last_fanout = 1;
+			return body(o, 0, n);
+		}
+	}
+	return fanout_run(shards, [&](size_t k) {
+		return body(k ? o->shard[k] : o, bounds[k], bounds[k + 1] - bounds[k]);
+	});
+}
+
+template int fanout(struct libdeflate_compressor *, size_t, const size_t *,
+		    const std::function<libdeflate_compressor *(const libdeflate_options *)> &,
+		    const std::function<int(libdeflate_compressor *, size_t, size_t)> &);
+template int fanout(struct libdeflate_decompressor *, size_t, const size_t *,
+		    const std::function<libdeflate_decompressor *(const libdeflate_options *)> &,
+		    const std::function<int(libdeflate_decompressor *, size_t, size_t)> &);
 
 } /* namespace lda */
 

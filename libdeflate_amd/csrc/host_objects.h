@@ -65,14 +65,24 @@ struct libdeflate_compressor {
 };
 
 namespace lda {
-/* host_fanout.hip: the devices a host-pointer batch of n chunks is spread over
- * (1 = the object's own device only), and the plan: shard k takes the chunks
- * [bounds[k], bounds[k+1]) on device devs[k] */
-size_t fanout_plan(int own_device, size_t n, const size_t *nbytes, size_t *bounds, int *devs);
-void fanout_note(size_t shards);	/* what libdeflate_amd_last_fanout() reports */
-/* run fn(k) for k = 1 .. shards-1 on threads of their own and fn(0) on the
- * calling one; returns the first non-OK status */
-int fanout_run(size_t shards, const std::function<int(size_t)> &fn);
+/* host_decompress.hip: the allocator of an object, the way
+ * lib/deflate_compress.c:3910-3917 resolves it; false = options of another size */
+bool pick_allocator(const struct libdeflate_options *options,
+		    malloc_func_t *m, free_func_t *f);
+
+/*
+ * host_fanout.hip: one host-pointer batch of n chunks over the GPUs of a node
+ * (LDA_DEVICES).  The chunks are cut into contiguous shards of about equal
+ * weight[] (what a chunk costs); shard k > 0 runs through o->shard[k], built
+ * on first use by alloc() with its device current and o's allocator.
+ * body(object, lo, count) runs every shard on a host thread of its own and the
+ * first non-OK status is returned.  One shard, or a shard object that cannot
+ * be built, is body(o, 0, n) on the calling thread.
+ */
+template <typename Obj>
+int fanout(Obj *o, size_t n, const size_t *weight,
+	   const std::function<Obj *(const struct libdeflate_options *)> &alloc,
+	   const std::function<int(Obj *, size_t, size_t)> &body);
 
 /* host_stream.hip: true = answered (result, sizes, output); false = the
  * caller takes the sequential path */

@@ -240,6 +240,8 @@ def test_bgzf_host_call_matches_the_device_call(torch):
         assert fh == fd and np.array_equal(rh, rd), n
         if n > 10 * B:
             _check_file(fh, data)
+            # no room for the EOF member: found by the last slice's drain
+            assert c.compress_bgzf(data, out_avail=len(fh) - 1) is None
 
 
 def test_bgzf_format_is_refused_where_it_has_no_meaning(torch):

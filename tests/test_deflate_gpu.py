@@ -328,6 +328,30 @@ def test_large_single_buffer_is_segmented(level, oracle):
     _check_roundtrip(oracle, "gzip", d, z, ("zeros", level))
 
 
+def test_large_single_buffer_over_several_slices():
+    """80 MiB through the single-buffer calls: 1280 segments of 64 KiB in three
+    slices of at most 512.  The stream round-trips through zlib with its footer;
+    one byte too little output space returns 0, and so does half of it, which
+    runs out in the drain of a slice before the last."""
+    from libdeflate_amd import api
+    n = 80 << 20
+    part = [datagen.chunk(k, 1 << 20, 0x0E110420) for k in range(20)]
+    d = b"".join(part[k % 20] for k in range(n >> 20))
+    c = api.Compressor(6)
+    for fmt in ("gzip", "zlib"):
+        z = c.compress(fmt, d)
+        assert z is not None and len(z) <= c.bound(fmt, n)
+        assert zlib.decompress(z, WBITS[fmt]) == d, fmt
+        if fmt == "gzip":
+            assert int.from_bytes(z[-8:-4], "little") == zlib.crc32(d)
+            assert int.from_bytes(z[-4:], "little") == n
+        else:
+            assert int.from_bytes(z[-4:], "big") == zlib.adler32(d)
+        assert c.compress(fmt, d, out_avail=len(z) - 1) is None, fmt
+        assert c.compress(fmt, d, out_avail=len(z) // 2) is None, fmt
+    c.close()
+
+
 def test_block_split_follows_content():
     """lib/deflate_compress.c:2092-2218 (a10): a buffer whose content changes
     is cut into blocks near the changes (the block ends in front of the first
@@ -502,6 +526,33 @@ def test_batch_host_many_small_chunks():
     back = d.decompress_batch_host("zlib", comp, [size] * n)
     assert all(r[0] == 0 for r in back)
     assert all(back[i][3] == chunks[i] for i in range(0, n, 61))
+
+
+def test_batch_host_over_several_slices():
+    """2176 x 64 KiB (136 MiB: two slices of at least 64 MiB of input) through
+    the host-pointer batch: every stream is the one calls of at most 512 chunks
+    (one slice each) give, and decodes with zlib.  A chunk of the second slice
+    with one byte too little output space comes back None; its neighbours do
+    not change."""
+    from libdeflate_amd import api
+    n, size = 2176, 65536
+    chunks = datagen.batch(n, size, 0x0E110400, distinct=137)
+    c = api.Compressor(6)
+    want = []
+    for lo in range(0, n, 512):
+        want += c.compress_batch_host("zlib", chunks[lo:lo + 512])
+    got = c.compress_batch_host("zlib", chunks)
+    assert all(z is not None for z in got)
+    assert got == want
+    for x, z in zip(chunks, got):
+        assert zlib.decompress(z) == x
+    k = n - 100
+    avail = [c.bound("zlib", size)] * n
+    avail[k] = len(want[k]) - 1
+    short = c.compress_batch_host("zlib", chunks, out_avail=avail)
+    assert short[k] is None
+    assert short[:k] == want[:k] and short[k + 1:] == want[k + 1:]
+    c.close()
 
 
 @pytest.mark.parametrize("level", [0, 1, 3, 6, 9])

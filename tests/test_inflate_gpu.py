@@ -285,6 +285,28 @@ def test_many_streams_all_formats(dec):
         del d_in, d_out
 
 
+def test_batch_host_over_several_slices(dec, oracle):
+    """2176 gzip streams of 64 KiB with 256 KiB of output space each (544 MiB:
+    two slices of at least 256 MiB) through the host-pointer batch: result,
+    actual_in, actual_out and bytes of every stream.  One damaged stream in
+    each slice returns its own error; every other stream still succeeds."""
+    n, size, distinct, avail = 2176, 65536, 137, 4 * 65536
+    chunks = datagen.batch(distinct, size, 0x0E110410)
+    comp = [streams._zcompress("gzip", 6, x) for x in chunks]
+    data = [comp[i % distinct] for i in range(n)]
+    bad = {300: data[300][:len(data[300]) // 2],                  # truncated
+           n - 300: data[n - 300][:-8] + bytes(8)}                # wrong CRC-32 and ISIZE
+    for i, z in bad.items():
+        data[i] = z
+    got = dec.decompress_batch_host("gzip", data, [avail] * n)
+    for i, g in enumerate(got):
+        if i in bad:
+            want = oracle.decompress_ex("gzip", data[i], avail)[0]
+            assert want != 0 and g[0] == want, (i, g[:3], want)
+        else:
+            assert g == (0, len(data[i]), size, chunks[i % distinct]), (i, g[:3])
+
+
 def _big_stream_cases(ref, seed):
     """Streams long enough for the sub-block parallel rounds, in the shapes
     that exercise their hand-overs to the sequential decoder."""
