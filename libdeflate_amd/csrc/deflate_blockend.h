@@ -155,7 +155,15 @@ stg_flush(lds_t *L, struct outstate *os, bool final)
 	if (tid < keep_words && keep_from / 4 + tid < STG_WORDS + 8)
 		v = stg[keep_from / 4 + tid];
 	__syncthreads();
-	for (u32 i = tid; i < STG_WORDS + 8; i += NT)
+#if LDA_ENTROPY
+	/* nothing is ever put at or behind os->bits, and nothing but this
+	 * function and stg_restore() clears: the words from total_words on are
+	 * still zero */
+	const u32 clear_words = total_words < STG_WORDS + 8 ? total_words : STG_WORDS + 8;
+#else
+	const u32 clear_words = STG_WORDS + 8;
+#endif
+	for (u32 i = tid; i < clear_words; i += NT)
 		stg[i] = 0;
 	if (tid < keep_words)
 		stg[tid] = v;
@@ -221,6 +229,167 @@ put_container_header(lds_t *L, struct outstate *os, int format, int level,
 	}
 	os->bits = 8 * hdr_bytes;
 }
+
+#if LDA_ENTROPY
+/*
+ * The entropy kernel's token encode: packed code tables and ENC_K consecutive
+ * tokens per thread.  (The fused kernels keep the one-token-per-thread loop in
+ * block_emit(): their LDS has no room for the wider staging area, and their
+ * bytes are what tests/test_entropy_encode_gpu.py compares these with.)
+ *
+ * What lives in M[] when:
+ *   S5 rank sort      keys [0, 320), used counts [320, 322), sortedO [324, 340)
+ *   S5 two trees      the litlen tree's scratch from M + 512 (HUFF_LITLEN)
+ *   S5 precode items  run starts [0, 321]
+ *   S6                the tables below, [0, ENC_TAB_WORDS): written once per
+ *                     dynamic or static block after its codes exist and before
+ *                     its header (whose scan and flush are the barriers between
+ *                     the build and the first lookup), read by the token loop
+ */
+#define ENC_K 4			/* tokens per thread per window: one 16-byte load */
+#define ENC_LIT 0		/* [256] by byte:        codeword | bits << 24 */
+#define ENC_LEN 256		/* [256] by length - 3:  codeword | extra value << code bits | (code + extra bits) << 24 */
+#define ENC_OFF 512		/* [30] by offset slot:  codeword | code bits << 16 | extra bits << 20 */
+#define ENC_TAB_WORDS 544
+static_assert(ENC_TAB_WORDS <= sizeof(((struct deflate_lds *)0)->M) / sizeof(u32), "the tables live in M[]");
+/* a window of ENC_K * NT tokens of at most 48 bits behind what a flush leaves
+ * (under 16 bytes and a partial byte) must fit the staging area, with the 64
+ * bits of slack the flush rule in encode_tokens() keeps */
+static_assert(32 * STG_WORDS >= 48 * ENC_K * NT + 64 + 8 * 16 + 8, "a worst-case window fits the staging area");
+
+/* 542 entries per block against its thousands of tokens: three LDS stores per
+ * thread and no barrier of its own, less than one round of the token loop, so
+ * there is no block too small for it */
+static __device__ __forceinline__ void enc_tables_build(lds_t *L, u32 tid)
+{
+	u32 *tab = L->M;
+
+	for (u32 i = tid; i < 256; i += NT) {
+		u32 sl, xb, xv;
+		tab[ENC_LIT + i] = L->codes[i] | ((u32)L->lens[i] << 24);
+		length_code(i + 3, &sl, &xb, &xv);
+		const u32 ll = L->lens[257 + sl];
+		tab[ENC_LEN + i] = L->codes[257 + sl] | (xv << ll) | ((ll + xb) << 24);
+	}
+	if (tid < 30) {
+		const u32 xb = tid < 4 ? 0 : (tid >> 1) - 1;
+		tab[ENC_OFF + tid] = L->codes[288 + tid] | ((u32)L->lens[288 + tid] << 16) | (xb << 20);
+	}
+}
+
+/* one token's bits (at most 48) and their count; 0 bits when !valid.  No
+ * branch between literal and match: the first word is the literal's or the
+ * length's entry, the offset part is masked away for a literal */
+static __device__ __forceinline__ u64 enc_token(const u32 *tab, u32 tok, bool valid, u32 *nbits)
+{
+	const bool match = (tok & TOK_MATCH) != 0;
+	const u32 e = tab[(match ? ENC_LEN : ENC_LIT) + (tok & 0xFF)];
+	const u32 d = (tok >> 8) & 0x7FFF;	/* offset - 1 */
+	const u32 hb = 31 - __builtin_clz(d | 2);	/* >= 1: the shift below stays defined for d < 4 */
+	const u32 slot = d < 4 ? d : 2 * hb + ((d >> (hb - 1)) & 1);
+	const u32 o = tab[ENC_OFF + slot];
+	const u32 n1 = e >> 24, ol = (o >> 16) & 15, oxb = o >> 20;
+	const u32 ov = (o & 0xFFFF) | ((d & ((1u << oxb) - 1)) << ol);	/* <= 15 + 13 bits */
+	u64 v = (e & 0xFFFFFF) | (match ? (u64)ov << n1 : 0);
+	u32 n = n1 + (match ? ol + oxb : 0);
+
+	*nbits = valid ? n : 0;
+	return valid ? v : 0;
+}
+
+/* OR v (< 2^48) at bit 'pos' of the 224 bits a[0..3]; pos <= 31 + 48 * J for
+ * the J-th token of a thread, which says which of a[] it can reach */
+template <int J>
+static __device__ __forceinline__ void enc_acc(u64 (&a)[4], u64 v, u32 pos)
+{
+	const u32 q = pos >> 6, sh = pos & 63;
+	const u64 lo = v << sh, hi = (v >> 1) >> (63 - sh);
+
+	if (J == 0) {
+		a[0] = lo;
+		a[1] = hi;
+		a[2] = a[3] = 0;
+	} else {
+		a[0] |= q == 0 ? lo : 0;
+		a[1] |= q == 0 ? hi : q == 1 ? lo : 0;
+		if (J < 3) {
+			a[2] |= q == 1 ? hi : 0;
+		} else {
+			a[2] |= q == 1 ? hi : q == 2 ? lo : 0;
+			a[3] |= q == 2 ? hi : 0;
+		}
+	}
+}
+
+/*
+ * The tokens tokg[0, nseq) of a block at os->bits, ENC_K * NT at a time: every
+ * thread takes ENC_K consecutive tokens (one 16-byte load; the list of a later
+ * block starts anywhere, so the windows start at the 16-byte boundary at or
+ * before tokg and the tokens in front of tokg[0] count as absent), joins their
+ * bits in registers at the bit phase its first staging word will have, and
+ * after ONE workgroup scan per window writes a run of consecutive staging
+ * words: the first and the last are shared with the neighbours (ds_or), the
+ * words between are this thread's alone (plain stores over zeros).  Ends with
+ * the staging area flushed.  Whole workgroup.
+ */
+static __device__ __forceinline__ void
+encode_tokens(lds_t *L, struct outstate *os, const u32 *__restrict__ tokg, u32 nseq,
+	      u32 *tog, u32 tid)
+{
+	const u32 *tab = L->M;
+	u32 *stg = stg_of(L);
+	const u32 mis = ((u32)(uintptr_t)tokg >> 2) & (ENC_K - 1);
+	const uint4 *__restrict__ tok4 = (const uint4 *)(tokg - mis);
+	const u32 end = nseq + mis;	/* window positions [mis, end) are tokens */
+
+	/* (the next window's tokens are requested before this one is encoded:
+	 * the list is in HBM.  A 16-byte unit with a token in it lies inside
+	 * the buffer's list: its base and its stride are multiples of 16 bytes) */
+	uint4 nxt = make_uint4(0, 0, 0, 0);
+	if (ENC_K * tid < end)
+		nxt = tok4[tid];
+	for (u32 b0 = 0; b0 < end; b0 += ENC_K * NT) {
+		const u32 i0 = b0 + ENC_K * tid;
+		const uint4 t = nxt;
+		if (i0 + ENC_K * NT < end)
+			nxt = tok4[(i0 + ENC_K * NT) / ENC_K];
+		u32 n0, n1, n2, n3;
+		const u64 v0 = enc_token(tab, t.x, i0 >= mis && i0 < end, &n0);
+		const u64 v1 = enc_token(tab, t.y, i0 + 1 >= mis && i0 + 1 < end, &n1);
+		const u64 v2 = enc_token(tab, t.z, i0 + 2 >= mis && i0 + 2 < end, &n2);
+		const u64 v3 = enc_token(tab, t.w, i0 + 3 >= mis && i0 + 3 < end, &n3);
+		const u32 nb = n0 + n1 + n2 + n3;	/* <= 192 */
+		u32 tot;
+		const u32 off = block_scan1(L, nb, &tot, tog);
+		/* bit position relative to staging word 0 (sg <= bits / 8) */
+		const u32 p = (u32)(os->bits - 8 * os->sg) + off;
+		const u32 w = p >> 5, s = p & 31;
+		u64 a[4];
+		enc_acc<0>(a, v0, s);
+		enc_acc<1>(a, v1, s + n0);
+		enc_acc<2>(a, v2, s + n0 + n1);
+		enc_acc<3>(a, v3, s + n0 + n1 + n2);
+		if (nb) {
+			const u32 last = (s + nb - 1) >> 5;	/* <= 6 */
+			const u32 wd[7] = { (u32)a[0], (u32)(a[0] >> 32), (u32)a[1], (u32)(a[1] >> 32),
+					    (u32)a[2], (u32)(a[2] >> 32), (u32)a[3] };
+			atomicOr(&stg[w], wd[0]);
+#pragma unroll
+			for (u32 i = 1; i < 7; i++) {
+				if (i < last)
+					stg[w + i] = wd[i];
+				else if (i == last)
+					atomicOr(&stg[w + i], wd[i]);
+			}
+		}
+		os->bits += tot;
+		/* room for one more window of 48-bit tokens? */
+		if (os->bits - 8 * os->sg + 48 * ENC_K * NT + 64 > 32 * STG_WORDS)
+			stg_flush(L, os, false);
+	}
+	stg_flush(L, os, false);
+}
+#endif /* LDA_ENTROPY */
 
 /*
  * One block at os->bits: the codes from the histogram in L->freq (without the
@@ -496,6 +665,41 @@ block_emit(lds_t *L, struct outstate *os, const u32 *__restrict__ tokg, u32 nseq
 			}
 			os->bits += 3 + pad + 32;
 			__syncthreads();
+#if LDA_ENTROPY
+			/* the piece's bytes start at a byte boundary of the
+			 * output: the few up to the next 16-byte boundary go
+			 * through the staging area and complete its last unit,
+			 * which leaves it empty, the 16-byte units after them
+			 * are copied from the input straight to the output
+			 * (the staging words stay zero, its base moves on),
+			 * and the rest of under 16 bytes is staged again */
+			{
+				const u8 *__restrict__ src = inp + bstart + done;
+				u8 *dst = os->out + (s64)(os->bits / 8);
+				u32 head = (0 - (u32)(uintptr_t)dst) & 15;
+				head = head < piece ? head : piece;
+				const u32 mid = (piece - head) & ~15u;
+				const u32 tail = piece - head - mid;
+				if (tid < head)
+					stg_put(L, os, os->bits + 8 * tid, src[tid], 8);
+				os->bits += 8 * head;
+				stg_flush(L, os, false);
+				for (u32 u = tid; u < mid / 16; u += NT) {
+					uint4 v;
+					__builtin_memcpy(&v, src + head + 16 * u, 16);
+					*(uint4 *)(dst + head + 16 * u) = v;
+				}
+				if (mid) {	/* (the staging area is empty) */
+					os->bits += 8ull * mid;
+					os->sg += mid;
+				}
+				__syncthreads();
+				if (tid < tail)
+					stg_put(L, os, os->bits + 8 * tid, src[head + mid + tid], 8);
+				os->bits += 8 * tail;
+				__syncthreads();
+			}
+#else
 			for (u32 w0 = 0; w0 < piece; w0 += 2048) {
 				u32 cnt = piece - w0 < 2048 ? piece - w0 : 2048;
 				stg_flush(L, os, false);
@@ -507,6 +711,7 @@ block_emit(lds_t *L, struct outstate *os, const u32 *__restrict__ tokg, u32 nseq
 				os->bits += 8ull * cnt;
 				__syncthreads();
 			}
+#endif
 			done += piece;
 		} while (done < blen);
 		stg_flush(L, os, false);
@@ -536,6 +741,10 @@ block_emit(lds_t *L, struct outstate *os, const u32 *__restrict__ tokg, u32 nseq
 			}
 			__syncthreads();
 		}
+#if LDA_ENTROPY
+		enc_tables_build(L, tid);
+		PROF_MARK(40);
+#endif
 		/* block header: thread 0 the fixed fields, threads
 		 * 1..nexp the precode lengths, then one thread per
 		 * precode item; bit offsets by a workgroup scan */
@@ -586,6 +795,10 @@ block_emit(lds_t *L, struct outstate *os, const u32 *__restrict__ tokg, u32 nseq
 		stg_flush(L, os, false);
 
 		PROF_MARK(9);
+#if LDA_ENTROPY
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+		encode_tokens(L, os, tokg, nseq, tog, tid);
+#else
 		/* tokens, NT at a time: one token per thread, a workgroup
 		 * prefix sum of the bit lengths (single-barrier scan),
 		 * ds_or into the staging area.  The staging area is only
@@ -634,6 +847,7 @@ block_emit(lds_t *L, struct outstate *os, const u32 *__restrict__ tokg, u32 nseq
 				stg_flush(L, os, false);
 		}
 		stg_flush(L, os, false);
+#endif
 		__syncthreads();
 		/* end of block */
 		if (tid == 0)

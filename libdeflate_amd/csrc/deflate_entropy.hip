@@ -2,7 +2,8 @@
  * deflate_entropy.hip - the entropy stage of the 64 KiB compress kernel: the
  * streams of a batch whose LZ77 stage (lda_deflate_batch_kernel) has left the
  * tokens of every buffer and one descriptor per block in HBM (kernels.h,
- * LDA_BLK_*).  One workgroup of 256 threads per buffer writes its container
+ * LDA_BLK_*).  One workgroup of 256 threads per buffer (claimed from a counter
+ * as the workgroup starts) writes its container
  * header, its blocks in order (a block's bit offset - so its stored padding
  * and its cost - depends on the block before it), the empty stored block of a
  * segment other than the last, and the trailer.  Each block goes through
@@ -14,7 +15,7 @@
  * that fills a CU's LDS (the input ring, the chains) and most of it is
  * latency-bound work on one or two waves (the tree merges are one lane) while
  * the others wait at barriers.  Inside the tile loop it held a 1024-thread
- * workgroup that owned the whole CU.  Here it needs 16 KiB of LDS and few
+ * workgroup that owned the whole CU.  Here it needs 20 KiB of LDS and few
  * registers, so several buffers' block ends share a CU and one buffer's
  * serial tree build runs beside another's token encode - the arrangement of
  * deflate_small.hip, for the same reason.
@@ -35,12 +36,13 @@
 #endif
 static_assert(NT == 256, "ENTROPY_WGS waves per EU are ENTROPY_WGS workgroups per CU");
 #define TOK_MATCH 0x80000000u
-/* bit staging: a window of NT tokens is at most 48 * NT bits (1.5 KiB); a
+/* bit staging: a window of 4 * NT tokens is at most 48 * 4 * NT bits (6 KiB,
+ * held by a static_assert next to the encode loop in deflate_blockend.h); a
  * stored piece goes through in 2 KiB steps */
-#define STG_WORDS 1020
+#define STG_WORDS 2044
 
 struct deflate_lds {
-	u32 M[1776];		/* keys, run starts; the litlen tree's scratch from M + 512 */
+	u32 M[1776];		/* keys, run starts; the litlen tree's scratch from M + 512; S6: the encode tables (deflate_blockend.h) */
 	u32 freq[320];		/* litlen 0..287, offset 288..319 */
 	u8 lens[320];
 	u16 codes[320];		/* bit-reversed codewords */
@@ -78,14 +80,24 @@ lda_deflate_entropy_kernel(u64 n_chunks, int format, int level,
 			   const u64 *__restrict__ out_avail_arr, u64 *__restrict__ out_nbytes,
 			   const u32 *__restrict__ sums, const u32 *__restrict__ seg_info,
 			   const u32 *__restrict__ tok_buf, const u32 *__restrict__ blk_buf,
-			   u32 tok_stride, u32 blk_stride)
+			   u32 tok_stride, u32 blk_stride, u32 *__restrict__ next_chunk)
 {
 	extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
 	lds_t *L = (lds_t *)(uintptr_t)0;
 	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	if ((u32)(uintptr_t)(__attribute__((address_space(3))) u8 *)lds_raw != 0)
 		__builtin_trap();	/* the LDS block is addressed from 0, as in the fused kernels */
-	const u64 c = blockIdx.x;
+	/* Buffers are claimed in the order the workgroups start, not by
+	 * blockIdx: consecutive workgroup ids go round the XCDs, so with
+	 * c = blockIdx.x every eighth buffer of the batch runs on the same
+	 * XCD, and a batch whose buffers differ with that period (one stored
+	 * 64 KiB buffer in eight takes twice a text buffer's time) leaves one
+	 * XCD working when seven are done.  *next_chunk is zero before the
+	 * launch; nobody waits for anybody. */
+	if (tid == 0)
+		L->vars[V_TMP1] = atomicAdd(next_chunk, 1u);
+	__syncthreads();
+	const u64 c = (u32)__builtin_amdgcn_readfirstlane((int)L->vars[V_TMP1]);
 	if (c >= n_chunks)
 		return;
 	const u32 nb = blk_buf[c];

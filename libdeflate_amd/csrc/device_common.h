@@ -169,7 +169,7 @@ static __device__ __forceinline__ void wave_sync(void)
  * thread 0 of each workgroup accumulates s_memtime deltas per phase.
  */
 #ifdef LDA_PROFILE
-#define LDA_PROF_SLOTS 40
+#define LDA_PROF_SLOTS 48
 static __device__ unsigned long long lda_prof[LDA_PROF_SLOTS];	/* per TU */
 /* exported reader for this translation unit's counters (reads and resets) */
 #define LDA_PROF_DEFINE_READER(name)                                          \

@@ -168,14 +168,17 @@ static dict_shape shape_dict(int level, size_t dict_nbytes)
  * bound whose single buffer needs more keeps the fused kernel.
  */
 #define LDA_SPLIT_SCRATCH ((size_t)1280 << 20)
-/* buffers per CU from which a call takes the split path (see plan_batch()) */
+/* buffers per CU from which a call takes the split path (see plan_batch());
+ * a tuning build may set another (make VARIANT=... EXTRA=-DLDA_SPLIT_MIN_PER_CU=1) */
+#ifndef LDA_SPLIT_MIN_PER_CU
 #define LDA_SPLIT_MIN_PER_CU 4
+#endif
 
 /*
  * The kernels' scratch of one compress_batch_impl() call: [per-workgroup
- * state: u64 x lda_deflate_seq_words() x grid][chunk counters: three u32 per
+ * state: u64 x lda_deflate_seq_words() x grid][chunk counters: four u32 per
  * slice (the LZ77 stage's, the fused kernel's behind it, the count of buffers
- * left to that one), 16-byte padded][sums: u32 x n], then the dictionary block (see
+ * left to that one, the entropy kernel's)][sums: u32 x n], then the dictionary block (see
  * lda_dict_prep_kernel()) or, on the split path, one slice's token lists and
  * block descriptors.  The same sum sizes the reservations the host-pointer
  * entry points make up front.
@@ -200,11 +203,15 @@ static batch_plan plan_batch(const struct libdeflate_compressor *c, size_t n,
 	/* levels 0-9 of the big kernel split the block end off into the entropy
 	 * kernel (deflate_entropy.hip) wherever the host knows a size bound to
 	 * size the token lists by, and the call has buffers enough to fill the
-	 * CUs several times over: the entropy kernel's work per buffer (0.19 ms
-	 * for 64 KiB at level 6) is what the split saves only where other
+	 * CUs several times over: the entropy kernel's work per buffer (0.11 ms
+	 * for 64 KiB at level 6: 0.42 ms per 4096 of the bench mix, four to a
+	 * CU; 0.19 before round 9) is what the split saves only where other
 	 * buffers' block ends run beside it - with one buffer per CU it is a tail
-	 * the fused kernel does not have (a 16 MiB single-buffer call, 256
-	 * segments: 1.24 -> 1.49 ms; 4096 x 64 KiB: 7.16 -> 6.57 ms) */
+	 * the fused kernel does not have (4096 x 64 KiB: 7.16 -> 6.57 ms in
+	 * round 7, 6.23 in round 9).  A 16 MiB single-buffer call (256
+	 * segments) forced onto the split path measured 1.24 -> 1.49 ms in round
+	 * 7; in round 9 fused and split are 1.26 - 1.39 and 1.29 - 1.40 ms, inside
+	 * each other's spread, so the threshold stays */
 	const size_t tile = lda_deflate_tile();
 	const size_t tok_stride = align_up(max_in, 16);
 	const size_t blk_stride = std::max<size_t>(1, (tok_stride + tile - 1) / tile);
@@ -219,7 +226,7 @@ static batch_plan plan_batch(const struct libdeflate_compressor *c, size_t n,
 	const size_t grid_max = num_cus * (p.small ? lda_deflate_small_wgs() : 1);
 	p.grid = std::min(p.per_slice, grid_max);
 	p.cnt_at = p.grid * lda_deflate_seq_words() * 8;
-	p.sums_at = p.cnt_at + align_up(12 * p.nslices, 16);
+	p.sums_at = p.cnt_at + 16 * p.nslices;
 	p.dict_at = p.tok_at = align_up(p.sums_at + n * 4, 64);
 	p.total = p.sums_at + n * 4;
 	if (dict)
@@ -270,7 +277,7 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 	if (!scr)
 		return LIBDEFLATE_AMD_OOM;
 	uint32_t *next_chunk = (uint32_t *)(scr + pl.cnt_at);
-	LDA_HIP_TRY(hipMemsetAsync(next_chunk, 0, align_up(12 * pl.nslices, 16), st),
+	LDA_HIP_TRY(hipMemsetAsync(next_chunk, 0, 16 * pl.nslices, st),
 		    LIBDEFLATE_AMD_NO_DEVICE);
 	uint8_t *blk = NULL;
 	if (dict) {
@@ -369,7 +376,7 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 				   d_in_offsets + lo, d_in_nbytes + lo, (uint8_t *)d_out,
 				   d_out_offsets + lo, d_out_avail + lo, d_out_nbytes + lo, sk, gk,
 				   (const uint32_t *)tok, (const uint32_t *)bd, pl.tok_stride,
-				   pl.blk_stride);
+				   pl.blk_stride, next_chunk + 3 * pl.nslices + k);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 		hipLaunchKernelGGL(lda_deflate_fused_kernel, dim3((unsigned)std::min(nk, pl.grid)),
 				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)nk, format,

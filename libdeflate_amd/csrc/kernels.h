@@ -108,7 +108,8 @@ lda_deflate_fused_kernel(uint64_t n_chunks, int format, int level,
 			 uint64_t *seq_scratch, const uint32_t *seg_info,
 			 uint32_t *next_chunk, const uint8_t *dict_pre,
 			 const uint32_t *blk_buf, const uint32_t *fused_cnt);
-/* deflate_entropy.hip: one workgroup per buffer of the launch before it */
+/* deflate_entropy.hip: one workgroup per buffer of the launch before it;
+ * *next_chunk (zero before the launch) hands the buffers out */
 #define LDA_DEFLATE_ENTROPY_THREADS 256
 extern "C" __global__ void
 lda_deflate_entropy_kernel(uint64_t n_chunks, int format, int level,
@@ -118,7 +119,7 @@ lda_deflate_entropy_kernel(uint64_t n_chunks, int format, int level,
 			   uint64_t *out_nbytes, const uint32_t *sums,
 			   const uint32_t *seg_info, const uint32_t *tok_buf,
 			   const uint32_t *blk_buf, uint32_t tok_stride,
-			   uint32_t blk_stride);
+			   uint32_t blk_stride, uint32_t *next_chunk);
 extern "C" size_t lda_deflate_entropy_lds_bytes(void);
 /* same body with the min-cost parse compiled in: levels 10-12 */
 extern "C" __global__ void

@@ -72,7 +72,8 @@ PHASES_DEFLATE = ["init/other", "S0 load", "S2 insert", "S3 round B + worklist",
                   "X: round A (wave 1)", "X: wait parse (wave 1)", "X: emit (wave 1)",
                   "X: barrier (wave 1)", "X: wave 0 after parse", "split stats",
                   "X: steps of first parse (wave 1)", "X: wave 0 until first parse done",
-                  "RB: generation 0", "RB: generation 1", "RB: generation 2", "RB: generations 3+", "worklist"]
+                  "RB: generation 0", "RB: generation 1", "RB: generation 2", "RB: generations 3+", "worklist",
+                  "S6 code tables"]
 
 
 def read_profile(name, labels, title="thread 0 of each workgroup, summed"):
@@ -83,7 +84,7 @@ def read_profile(name, labels, title="thread 0 of each workgroup, summed"):
         fn = getattr(lib, name)
     except AttributeError:
         return
-    buf = (ctypes.c_ulonglong * 40)()
+    buf = (ctypes.c_ulonglong * 48)()   # LDA_PROF_SLOTS
     fn(buf)
     tot = sum(buf)
     if not tot:
