@@ -520,8 +520,9 @@ libdeflate_amd_gzip_decompress_members(struct libdeflate_decompressor *d,
  * of more than LIBDEFLATE_AMD_BGZF_BLOCK bytes, or one whose member does not
  * fit min(out_avail[i], LIBDEFLATE_AMD_BGZF_MEMBER_MAX), reports 0.  The
  * dictionary calls and the decompress batch refuse the format: members
- * decode as LIBDEFLATE_AMD_GZIP, whole files with
- * libdeflate_amd_gzip_decompress_members.
+ * decode as LIBDEFLATE_AMD_GZIP, whole files with the BGZF reader below
+ * (libdeflate_amd_bgzf_decompress[_batch]) or, from host memory and for gzip
+ * files of any kind, with libdeflate_amd_gzip_decompress_members.
  */
 #define LIBDEFLATE_AMD_BGZF_BLOCK	65280	/* input bytes per member (htslib BGZF_BLOCK_SIZE) */
 #define LIBDEFLATE_AMD_BGZF_MEMBER_MAX	65536	/* BSIZE + 1 is 16 bits */
@@ -578,6 +579,121 @@ libdeflate_amd_bgzf_compress(struct libdeflate_compressor *compressor,
 			     const void *in, size_t in_nbytes,
 			     void *out, size_t out_avail,
 			     uint64_t *index, size_t index_avail, unsigned flags);
+
+/*
+ * Reading a BGZF file.  What a member is (htslib's check_header rule): the
+ * bytes 1f 8b 08 04, XLEN = 6 at bytes 10..11, the subfield 42 43 02 00 at
+ * bytes 12..15 and BSIZE at 16..17; MTIME, XFL and OS are free.  Its size is
+ * BSIZE + 1: at least 28 bytes, not past the end of the file.  ISIZE (its
+ * last 4 bytes) is at most 65536, the spec's limit - above the 65280 of our
+ * writer.  The chain of members starts at byte 0 and must end exactly at
+ * in_nbytes.  An empty member is an ordinary member of ISIZE 0 wherever it
+ * stands (`cat a.gz b.gz` leaves an EOF member in the middle of a valid
+ * file); LIBDEFLATE_AMD_BGZF_HAS_EOF only says whether the LAST member is the
+ * 28 fixed bytes.  An empty file is 0 members and SUCCESS.  gzip members with
+ * other extra fields, or plain concatenated gzip, are LIBDEFLATE_BAD_DATA
+ * here: libdeflate_amd_gzip_decompress_members stays the general loop.
+ */
+#define LIBDEFLATE_AMD_BGZF_MORE_MEMBERS 16	/* result[0]: the file has more members than max_members */
+#define LIBDEFLATE_AMD_BGZF_HAS_EOF 1		/* result[4] bit: the last member is the 28-byte EOF member */
+#define LIBDEFLATE_AMD_BGZF_RESULT_WORDS 5
+#define LIBDEFLATE_AMD_BGZF_VOFFSETS 2		/* read flag: ranges are virtual-offset pairs */
+
+/*
+ * A whole BGZF file in DEVICE memory -> its bytes in device memory.  Enqueues
+ * on `stream` and returns; the members are found on the device (in parallel:
+ * every offset is tested for the header rule, and only the candidates
+ * reachable from offset 0 count), a prefix sum of their ISIZEs gives every
+ * member its place, and one decompress batch decodes all of them there
+ * (exact fill: a member whose ISIZE lies fails, nothing lands elsewhere).
+ *
+ * max_members: the launches and the scratch are sized on the host, which
+ * does not know the member count; pass what is known (from a .gzi, from the
+ * compress call's index: blocks + 1), at worst in_nbytes / 28 + 1.  A
+ * generous bound costs empty chunks in the batch.
+ *
+ * d_result[0..4] (device memory):
+ *   [0] an enum libdeflate_result value or LIBDEFLATE_AMD_BGZF_MORE_MEMBERS,
+ *       in this order of precedence: LIBDEFLATE_BAD_DATA for a broken chain or
+ *       header, or an ISIZE above 65536 (checked on the first max_members
+ *       members); MORE_MEMBERS; LIBDEFLATE_INSUFFICIENT_SPACE when the sum of
+ *       the ISIZEs exceeds out_avail - all three decided BEFORE the decode,
+ *       and then nothing is decoded and d_out is not written; otherwise the
+ *       result of the first member in file order that failed (a lying ISIZE
+ *       is that member's SHORT_OUTPUT / INSUFFICIENT_SPACE, a bad CRC
+ *       BAD_DATA, a deflate stream that ends before BSIZE says BAD_DATA);
+ *   [1] members found (under MORE_MEMBERS: how many the file has; 0 under a
+ *       pre-decode BAD_DATA);
+ *   [2] compressed bytes consumed, [3] uncompressed bytes (both 0 under
+ *       BAD_DATA before the decode and under MORE_MEMBERS);
+ *   [4] flags: LIBDEFLATE_AMD_BGZF_HAS_EOF.
+ * No byte is written past out_avail, whatever the file says.
+ *
+ * d_index: NULL, or device room for 2 (max_members + 1) u64: the pairs
+ * (compressed offset, uncompressed offset) of every member, empty ones
+ * included, then the closing pair (result[2], result[3]).  For a file of m
+ * blocks from libdeflate_amd_bgzf_compress_batch the pairs 0..m are that
+ * call's.  Written unless [0] is a pre-decode BAD_DATA or MORE_MEMBERS.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work for a NULL object or pointer
+ * (d_out may be NULL only for an empty file), max_members == 0 with
+ * in_nbytes != 0 or above 2^28, in_nbytes above 2^36.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_bgzf_decompress_batch(struct libdeflate_decompressor *decompressor,
+				     const void *d_in, size_t in_nbytes, size_t max_members,
+				     void *d_out, size_t out_avail,
+				     uint64_t *d_result, uint64_t *d_index, void *stream);
+
+/* The index and the five words alone: nothing is decoded (out_avail counts
+ * as unlimited, and member results cannot show). */
+LIBDEFLATEAPI int
+libdeflate_amd_bgzf_index_batch(struct libdeflate_decompressor *decompressor,
+				const void *d_in, size_t in_nbytes, size_t max_members,
+				uint64_t *d_result, uint64_t *d_index, void *stream);
+
+/*
+ * n_ranges pieces of the uncompressed data, back to back into d_out; enqueues
+ * only.  `index` (members + 1 pairs as above, closing pair included) and
+ * `ranges` are HOST arrays.  Range r is the bytes [ranges[2r], ranges[2r] +
+ * ranges[2r + 1]), or with LIBDEFLATE_AMD_BGZF_VOFFSETS the BAM virtual
+ * offsets [ranges[2r], ranges[2r + 1]) (coffset << 16 | uoffset; the closing
+ * pair's coffset with uoffset 0 names the end).  Only the members a range
+ * touches are decoded, all ranges as ONE batch: members wholly inside a
+ * range straight into their place, the at most two edge members of a range
+ * through 64 KiB slots of the object's scratch.  d_results[r] (device) = the
+ * first non-success member result of range r, else 0; a failed range does
+ * not affect the others.  LIBDEFLATE_AMD_BAD_ARG before any device work: a
+ * NULL pointer, unknown flags, an index that does not describe BGZF members
+ * inside in_nbytes, a range past the end of the data, a virtual offset whose
+ * coffset is no member start of `index`, ranges that need more than
+ * out_avail.  d_out must not overlap d_in; the host arrays may be reused
+ * when the call returns.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_bgzf_read_batch(struct libdeflate_decompressor *decompressor,
+			       const void *d_in, size_t in_nbytes,
+			       const uint64_t *index, size_t members,
+			       size_t n_ranges, const uint64_t *ranges, unsigned flags,
+			       void *d_out, size_t out_avail, int32_t *d_results,
+			       void *stream);
+
+/*
+ * The whole file from and to HOST memory, blocking: a strict walk of the
+ * headers on the host, then the host-pointer decompress batch.  Same rule,
+ * same precedence of results as the device call; MORE_MEMBERS is returned
+ * (as a value of the enum's type) when `index` is given and index_avail is
+ * below 2 (members + 1) - *members_ret then says how many.  index: NULL or
+ * index_avail u64 entries.  A NULL object or buffer, or an index_avail below
+ * 2, is LIBDEFLATE_BAD_DATA with the reason in libdeflate_amd_last_error().
+ * The result pointers may be NULL.
+ */
+LIBDEFLATEAPI enum libdeflate_result
+libdeflate_amd_bgzf_decompress(struct libdeflate_decompressor *decompressor,
+			       const void *in, size_t in_nbytes,
+			       void *out, size_t out_avail,
+			       size_t *actual_out_ret, size_t *members_ret,
+			       uint64_t *index, size_t index_avail, unsigned *flags_ret);
 
 #ifdef __cplusplus
 }

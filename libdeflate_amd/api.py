@@ -242,6 +242,69 @@ class Decompressor:
             ctypes.byref(ai), ctypes.byref(ao), ctypes.byref(nm))
         return r, ai.value, ao.value, nm.value, out[:ao.value].tobytes()
 
+    def decompress_bgzf_batch(self, data, max_members, out, result, index=None, stream=None,
+                              in_nbytes=None, out_avail=None):
+        """libdeflate_amd_bgzf_decompress_batch: the BGZF file in the uint8
+        torch CUDA tensor `data` (its first in_nbytes bytes) into `out`
+        (out_avail bytes of it, default all).  result: int64 CUDA tensor of 5
+        (verdict, members, compressed bytes, uncompressed bytes, flags);
+        index: None or an int64 CUDA tensor of 2 (max_members + 1).  Only
+        enqueues on `stream`."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_bgzf_decompress_batch(
+            self._h, data.data_ptr(), n, int(max_members), out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
+            "bgzf_decompress_batch")
+
+    def index_bgzf_batch(self, data, max_members, result, index=None, stream=None,
+                         in_nbytes=None):
+        """libdeflate_amd_bgzf_index_batch: result and index as in
+        decompress_bgzf_batch; nothing is decoded."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_bgzf_index_batch(
+            self._h, data.data_ptr(), n, int(max_members), result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
+            "bgzf_index_batch")
+
+    def read_bgzf_batch(self, data, index, ranges, out, results, voffsets=False, stream=None,
+                        in_nbytes=None, out_avail=None):
+        """libdeflate_amd_bgzf_read_batch: `ranges` (host, rows of (begin,
+        nbytes), or of (v_begin, v_end) with voffsets=True) of the file in the
+        CUDA tensor `data`, back to back into `out`; index: host rows
+        (compressed, uncompressed offset) of every member and the closing
+        row; results: int32 CUDA tensor, one per range.  Only enqueues."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, 2)
+        rng = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_bgzf_read_batch(
+            self._h, data.data_ptr(), n, idx.ctypes.data_as(c_void_p), len(idx) - 1,
+            len(rng), rng.ctypes.data_as(c_void_p),
+            binding.BGZF_VOFFSETS if voffsets else 0, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), results.data_ptr(),
+            _stream_ptr(stream)), "bgzf_read_batch")
+
+    def decompress_bgzf(self, data, out_avail, index=False, index_avail=None):
+        """libdeflate_amd_bgzf_decompress: a BGZF file in host memory ->
+        (result, bytes, members, flags), or with index=True (result, bytes,
+        members, flags, rows): numpy uint64 rows (compressed, uncompressed
+        offset) of every member and the closing row."""
+        p, n = _buf(data)
+        out = np.zeros(max(out_avail, 1), dtype=np.uint8)
+        ao, nm, fl = c_size_t(0), c_size_t(0), ctypes.c_uint32(0)
+        if index and index_avail is None:
+            index_avail = 2 * (n // 28 + 2)
+        idx = np.zeros(max(index_avail, 1), dtype=np.uint64) if index else None
+        r = self._lib.libdeflate_amd_bgzf_decompress(
+            self._h, p, n, out.ctypes.data_as(c_void_p), out_avail, ctypes.byref(ao),
+            ctypes.byref(nm), idx.ctypes.data_as(c_void_p) if index else None,
+            index_avail if index else 0, ctypes.byref(fl))
+        got = out[:ao.value].tobytes() if r == 0 else b""
+        if index:
+            rows = idx[:2 * (nm.value + 1)].reshape(-1, 2) if r == 0 else None
+            return r, got, nm.value, fl.value, rows
+        return r, got, nm.value, fl.value
+
     def decompress_batch(self, fmt, data, in_offsets, in_nbytes, out,
                          out_offsets, out_avail, results, actual_in=None,
                          actual_out=None, stream=None):
@@ -301,6 +364,24 @@ def bgzf_gzi(index):
     rows = np.asarray(index, dtype=np.uint64).reshape(-1, 2)[1:-1]
     return (np.array([len(rows)], dtype="<u8").tobytes() +
             rows.astype("<u8").tobytes())
+
+
+def bgzf_index_gzi(index, members=None):
+    """.gzi bytes from what the BGZF reader returns: the index tensor or
+    array of decompress_bgzf_batch / index_bgzf_batch (`members` = result[1])
+    or the rows of decompress_bgzf.  bgzip's .gzi lists the starts of the
+    data members; a trailing EOF member's row closes the list as
+    bgzf_gzi() expects it."""
+    if hasattr(index, "cpu"):
+        index = index.cpu().numpy()
+    rows = np.asarray(index).astype(np.uint64).reshape(-1, 2)
+    if members is not None:
+        rows = rows[:int(members) + 1]
+    # an empty last member (the EOF member) stands where the closing row
+    # would: drop the closing row and let its row close the list
+    if len(rows) >= 2 and rows[-1][1] == rows[-2][1]:
+        rows = rows[:-1]
+    return bgzf_gzi(rows)
 
 
 def bgzf_gzi_parse(blob):

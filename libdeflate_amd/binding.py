@@ -23,6 +23,9 @@ FORMATS = {"deflate": FMT_DEFLATE, "zlib": FMT_ZLIB, "gzip": FMT_GZIP, "bgzf": F
 # BGZF (include/libdeflate_amd.h): input bytes per member, largest member, the
 # EOF member's size, the flag that leaves it out
 BGZF_BLOCK, BGZF_MEMBER_MAX, BGZF_EOF_BYTES, BGZF_NO_EOF = 65280, 65536, 28, 1
+# the BGZF reader: result[0] beyond enum libdeflate_result, the flag bit of
+# result[4], the words of a result, the read flag for virtual offsets
+BGZF_MORE_MEMBERS, BGZF_HAS_EOF, BGZF_RESULT_WORDS, BGZF_VOFFSETS = 16, 1, 5, 2
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -55,6 +58,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_compress_dict", "libdeflate_amd_decompress_dict_ex",
     "libdeflate_amd_bgzf_compress_bound", "libdeflate_amd_bgzf_compress_batch",
     "libdeflate_amd_bgzf_compress",
+    "libdeflate_amd_bgzf_decompress_batch", "libdeflate_amd_bgzf_index_batch",
+    "libdeflate_amd_bgzf_read_batch", "libdeflate_amd_bgzf_decompress",
 ]
 
 _lib = None
@@ -141,6 +146,13 @@ def load():
     sig("libdeflate_amd_bgzf_compress_bound", SZ, P, SZ)
     sig("libdeflate_amd_bgzf_compress_batch", c_int, P, P, SZ, P, SZ, P, P, c_uint32, P)
     sig("libdeflate_amd_bgzf_compress", SZ, P, P, SZ, P, SZ, P, SZ, c_uint32)
+    # BGZF files read: device file -> device bytes, the index alone, ranged
+    # reads (index and ranges on the host), host memory (blocking)
+    sig("libdeflate_amd_bgzf_decompress_batch", c_int, P, P, SZ, SZ, P, SZ, P, P, P)
+    sig("libdeflate_amd_bgzf_index_batch", c_int, P, P, SZ, SZ, P, P, P)
+    sig("libdeflate_amd_bgzf_read_batch", c_int, P, P, SZ, P, SZ, SZ, P, c_uint32, P, SZ, P, P)
+    sig("libdeflate_amd_bgzf_decompress", c_int, P, P, SZ, P, SZ, psz, psz, P, SZ,
+        POINTER(c_uint32))
     _lib = lib
     return lib
 

@@ -113,27 +113,6 @@ lda_scan_blocks_kernel(u64 nblocks, u64 *__restrict__ block_sums)
 		block_sums[nblocks] = carry_s;
 }
 
-/* len bytes src -> dst by a 256-thread workgroup: bytes up to the first 16-byte
- * boundary of dst, 16-byte stores, the tail */
-static __device__ __forceinline__ void
-copy_span(const u8 *__restrict__ src, u8 *__restrict__ dst, u64 len, u32 tid)
-{
-	u64 head = (0 - (uintptr_t)dst) & 15;
-	if (head > len)
-		head = len;
-	if (tid < head)
-		dst[tid] = src[tid];
-	const u64 body = (len - head) & ~(u64)15;
-	for (u64 k = head + 16 * (u64)tid; k < head + body; k += 16 * 256) {
-		uint4 v;
-		__builtin_memcpy(&v, src + k, 16);	/* source may be unaligned */
-		*(uint4 *)(dst + k) = v;
-	}
-	const u64 tail = head + body;
-	if (tail + tid < len)
-		dst[tail + tid] = src[tail + tid];
-}
-
 extern "C" __global__ void __launch_bounds__(256)
 lda_compact_copy_kernel(u64 n, const u8 *__restrict__ in_base,
 			const u64 *__restrict__ in_offsets,

@@ -164,6 +164,27 @@ static __device__ __forceinline__ void wave_sync(void)
 	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+/* len bytes src -> dst by a 256-thread workgroup: bytes up to the first 16-byte
+ * boundary of dst, 16-byte stores, the tail */
+static __device__ __forceinline__ void
+copy_span(const u8 *__restrict__ src, u8 *__restrict__ dst, u64 len, u32 tid)
+{
+	u64 head = (0 - (uintptr_t)dst) & 15;
+	if (head > len)
+		head = len;
+	if (tid < head)
+		dst[tid] = src[tid];
+	const u64 body = (len - head) & ~(u64)15;
+	for (u64 k = head + 16 * (u64)tid; k < head + body; k += 16 * 256) {
+		uint4 v;
+		__builtin_memcpy(&v, src + k, 16);	/* source may be unaligned */
+		*(uint4 *)(dst + k) = v;
+	}
+	const u64 tail = head + body;
+	if (tail + tid < len)
+		dst[tail + tid] = src[tail + tid];
+}
+
 /*
  * Optional phase profiling (make PROFILE=1 builds libdeflate_amd_prof.so):
  * thread 0 of each workgroup accumulates s_memtime deltas per phase.

@@ -157,6 +157,10 @@ libdeflate_free_decompressor(struct libdeflate_decompressor *d)
 	d->pinned.release();
 	d->meta.release();
 	d->streams.release();
+	d->bgzf.release();
+	d->bgzf_desc.release();
+	if (d->bgzf_up)
+		(void)hipEventDestroy(d->bgzf_up);
 	free_func_t f = d->free_func;
 	d->~libdeflate_decompressor();
 	f(d);

@@ -48,6 +48,12 @@ struct libdeflate_decompressor {
 	lda::PinnedPair pinned;	/* host-pointer entry points */
 	lda::PinnedBuf meta;	/* host-pointer entry points: per-chunk read-backs */
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */
+	/* BGZF files read on the device (host_bgzf_read.hip): candidates, chain,
+	 * descriptors, edge slots; the descriptors of a ranged read on their way
+	 * up, and the event behind that copy */
+	lda::DevBuf bgzf;
+	lda::PinnedBuf bgzf_desc;
+	hipEvent_t bgzf_up = nullptr;
 };
 
 struct libdeflate_compressor {

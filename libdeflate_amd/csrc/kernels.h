@@ -177,6 +177,62 @@ lda_bgzf_finalize_kernel(uint64_t m, uint64_t n, const uint64_t *sizes,
 			 const uint64_t *total_at, uint8_t *out, uint64_t out_avail,
 			 uint32_t eof_bytes, uint64_t *out_nbytes, uint64_t *index);
 
+/* bgzf_read_kernels.hip: a BGZF file read from device memory (host_bgzf_read.hip) */
+#define LDA_BR_TILE 4096	/* bytes per step of the candidate scan: 256 threads x 16 */
+#define LDA_BR_SCAN_WG 16384	/* bytes per workgroup of it */
+#define LDA_BR_JUMP 1024	/* candidates per block of the chain validation */
+#define LDA_BR_LOG 10
+#define LDA_BR_END 0xFFFFFFFFu	/* a candidate's successor: the end of the file */
+#define LDA_BR_NONE 0xFFFFFFFEu	/* no candidate starts where it ends */
+/* the finder's state (u32 words, zero before the first launch) */
+#define LDA_BR_CHAIN 0		/* 1: the chain from offset 0 ends exactly at n */
+#define LDA_BR_MEMBERS 1	/* its length */
+#define LDA_BR_BADISIZE 2	/* a member's ISIZE is above 64 KiB */
+#define LDA_BR_STATE_WORDS 4
+#define LDA_BR_MORE 16		/* LIBDEFLATE_AMD_BGZF_MORE_MEMBERS */
+#define LDA_BR_HAS_EOF 1	/* LIBDEFLATE_AMD_BGZF_HAS_EOF */
+#define LDA_BR_RESULT_WORDS 5
+extern "C" __global__ void
+lda_bgzf_scan_kernel(const uint8_t *in, uint64_t n, uint64_t *counts, const uint64_t *offsets,
+		     const uint64_t *block_sums, uint64_t cap, uint64_t *cand_pos,
+		     uint32_t *cand_size);
+extern "C" __global__ void
+lda_bgzf_jump_kernel(uint64_t n, const uint64_t *k_at, uint64_t cap, const uint64_t *cand_pos,
+		     const uint32_t *cand_size, uint32_t *next, uint32_t *exit_at, uint32_t *hops,
+		     uint32_t *entry);
+extern "C" __global__ void
+lda_bgzf_top_kernel(const uint64_t *k_at, uint64_t cap, const uint64_t *cand_pos,
+		    const uint32_t *exit_at, const uint32_t *hops, uint32_t *entry,
+		    uint32_t *base, uint32_t *state);
+extern "C" __global__ void
+lda_bgzf_members_kernel(const uint64_t *k_at, uint64_t cap, uint64_t max_members,
+			const uint64_t *cand_pos, const uint32_t *cand_size,
+			const uint32_t *next, const uint32_t *hops, const uint32_t *entry,
+			const uint32_t *base, const uint32_t *state, uint64_t *in_off,
+			uint64_t *in_n);
+extern "C" __global__ void
+lda_bgzf_walk_kernel(const uint8_t *in, uint64_t n, uint64_t max_members, const uint64_t *k_at,
+		     uint64_t cap, int force, uint64_t *in_off, uint64_t *in_n, uint32_t *state);
+extern "C" __global__ void
+lda_bgzf_isize_kernel(const uint8_t *in, uint64_t n, uint64_t max_members,
+		      const uint64_t *in_off, const uint64_t *in_n, uint32_t *state,
+		      uint64_t *isize);
+extern "C" __global__ void
+lda_bgzf_rdesc_kernel(uint64_t max_members, uint64_t out_avail, const uint32_t *state,
+		      const uint64_t *isize, const uint64_t *block_sums, uint64_t *in_off,
+		      uint64_t *in_n, uint64_t *out_off, uint64_t *out_av, uint64_t *index);
+extern "C" __global__ void
+lda_bgzf_rfinal_kernel(const uint8_t *in, uint64_t n, uint64_t max_members, uint64_t out_avail,
+		       const uint32_t *state, const uint64_t *total_at, const uint64_t *in_off,
+		       const uint64_t *in_n, const int32_t *results, const uint64_t *actual_in,
+		       uint64_t *result, uint64_t *index);
+extern "C" __global__ void
+lda_bgzf_trim_kernel(uint64_t n_trims, const uint64_t *trims, const uint8_t *slots,
+		     uint8_t *out);
+extern "C" __global__ void
+lda_bgzf_range_kernel(uint64_t n_ranges, const uint64_t *first, const uint64_t *in_n,
+		      const int32_t *results, const uint64_t *actual_in, int32_t *range_results);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
