@@ -370,6 +370,105 @@ libdeflate_amd_decompress_batch_dict(struct libdeflate_decompressor *decompresso
 				     void *stream);
 
 /*
+ * Uncompressed sizes of a batch, without decoding it.  Every decompress call
+ * wants the output size in advance, and a raw DEFLATE or zlib stream does not
+ * state it (a gzip footer states it modulo 2^32, and nothing vouches for it);
+ * the reference's callers guess, decode, and double on INSUFFICIENT_SPACE.
+ * Here the decoder itself counts: the same parser as the decompress calls,
+ * with no output buffer, no scratch and nothing written but the results.
+ *
+ * For stream i with limit L[i] = d_out_limit[i] (d_out_limit NULL, or a limit
+ * above it: LIBDEFLATE_AMD_SIZE_LIMIT_MAX), the call reports what
+ * libdeflate_{deflate,zlib,gzip}_decompress_ex reports for the same bytes
+ * with out_nbytes_avail = L[i] and a non-NULL actual_out_nbytes_ret - with ONE
+ * exception: the CRC-32 / Adler-32 of the produced bytes is not checked,
+ * because there are no bytes.  Everything else is: the container header's
+ * rules, FDICT, reserved flags, every code and distance rule, the overread
+ * rule, the footer's presence, and for gzip ISIZE == the count modulo 2^32.
+ *  - SUCCESS: d_out_nbytes[i] = the reference's actual_out, d_actual_in[i] =
+ *    its actual_in (header and footer included);
+ *  - a failed stream (BAD_DATA, or INSUFFICIENT_SPACE when it produces more
+ *    than L[i]) reports size 0 and actual_in 0, and never affects its
+ *    neighbours;
+ *  - a stream with a wrong checksum is SUCCESS here and BAD_DATA when decoded;
+ *  - streams of 4 GiB and more are not supported: they report
+ *    INSUFFICIENT_SPACE.
+ * d_actual_in may be NULL.  The device forms only enqueue on `stream`;
+ * LIBDEFLATE_AMD_BAD_ARG for NULL pointers and formats other than DEFLATE /
+ * ZLIB / GZIP (BGZF members state their size: the BGZF reader takes it from
+ * there), before any device is touched; n_chunks == 0 is OK.
+ *
+ * _dict: the dictionary semantics of libdeflate_amd_decompress_batch_dict (a
+ * count needs the dictionary's length and, for zlib, its Adler-32, computed
+ * on the device); a gzip format is BAD_ARG.
+ *
+ * _host: host pointers, blocking; only the inputs go to the device and three
+ * small arrays come back.  out_limit and actual_in may be NULL.  Spread over
+ * the GPUs of a node by LDA_DEVICES like the other host-pointer batches.
+ */
+#define LIBDEFLATE_AMD_SIZE_LIMIT_MAX 0xFFFFFFFFull	/* limit used for a NULL d_out_limit */
+
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_sizes_batch(struct libdeflate_decompressor *decompressor,
+				      int format, size_t n_chunks,
+				      const void *d_in, const uint64_t *d_in_offsets,
+				      const uint64_t *d_in_nbytes,
+				      const uint64_t *d_out_limit,
+				      int32_t *d_results,
+				      uint64_t *d_actual_in, uint64_t *d_out_nbytes,
+				      void *stream);
+
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_sizes_batch_dict(struct libdeflate_decompressor *decompressor,
+					   int format, size_t n_chunks,
+					   const void *d_dict, size_t dict_nbytes,
+					   const void *d_in, const uint64_t *d_in_offsets,
+					   const uint64_t *d_in_nbytes,
+					   const uint64_t *d_out_limit,
+					   int32_t *d_results,
+					   uint64_t *d_actual_in, uint64_t *d_out_nbytes,
+					   void *stream);
+
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_sizes_batch_host(struct libdeflate_decompressor *decompressor,
+					   int format, size_t n_chunks,
+					   const void *const *in, const size_t *in_nbytes,
+					   const size_t *out_limit, int32_t *results,
+					   size_t *actual_in, size_t *out_nbytes);
+
+/*
+ * Decompress a batch whose sizes nobody knows into ONE buffer, back to back:
+ * sizes, places, decode - one call, nothing but enqueues on `stream`.
+ *  1. the size query above with the maximum limit;
+ *  2. d_out_offsets[i] = exclusive prefix sum of the sizes, each rounded up to
+ *     out_align (a power of two, 1 .. 256, else BAD_ARG; 16 keeps the decode
+ *     kernel's 16-byte stores aligned).  A failed stream counts 0.
+ *     d_out_offsets has n_chunks + 1 entries: the last is the total the batch
+ *     needs, whatever out_capacity is;
+ *  3. every stream is decoded into d_out + d_out_offsets[i] with exactly its
+ *     size as room, all checks including the checksums.
+ * d_results[i]: a stream that failed the size query keeps that verdict and is
+ * not decoded; one with d_out_offsets[i] + size > out_capacity is
+ * INSUFFICIENT_SPACE, is not decoded and nothing of it is written; every
+ * other stream has the verdict of libdeflate_amd_decompress_batch - so a
+ * stream with a wrong checksum is BAD_DATA here, with its slot still reserved.
+ * d_actual_out[i] (required) and d_actual_in[i] (may be NULL) are 0 for a
+ * stream that did not succeed.  A caller whose buffer was too small reads
+ * d_out_offsets[n_chunks], allocates and calls again; a caller whose buffer
+ * was large enough never synchronises.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_batch_packed(struct libdeflate_decompressor *decompressor,
+				       int format, size_t n_chunks,
+				       const void *d_in, const uint64_t *d_in_offsets,
+				       const uint64_t *d_in_nbytes,
+				       void *d_out, size_t out_capacity, size_t out_align,
+				       uint64_t *d_out_offsets,
+				       int32_t *d_results,
+				       uint64_t *d_actual_in, uint64_t *d_actual_out,
+				       void *stream);
+
+/*
  * Single buffer, host pointers, blocking - like libdeflate_*_compress and
  * libdeflate_*_decompress_ex.  Compress returns the bytes written, 0 when
  * they do not fit; inputs of 128 KiB and more are compressed in segments side

@@ -331,6 +331,62 @@ class Decompressor:
             actual_out.data_ptr() if actual_out is not None else None,
             _stream_ptr(stream)), "decompress_batch_dict")
 
+    def decompress_sizes_batch(self, fmt, data, in_offsets, in_nbytes, results, out_nbytes,
+                               limits=None, actual_in=None, stream=None):
+        """libdeflate_amd_decompress_sizes_batch: the uncompressed size of
+        every stream, nothing decoded.  results: int32 CUDA tensor, out_nbytes
+        (and limits, actual_in when given): int64.  Only enqueues."""
+        check(self._lib.libdeflate_amd_decompress_sizes_batch(
+            self._h, FORMATS[fmt], in_offsets.numel(), data.data_ptr(),
+            in_offsets.data_ptr(), in_nbytes.data_ptr(),
+            limits.data_ptr() if limits is not None else None, results.data_ptr(),
+            actual_in.data_ptr() if actual_in is not None else None,
+            out_nbytes.data_ptr(), _stream_ptr(stream)), "decompress_sizes_batch")
+
+    def decompress_sizes_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes,
+                                    results, out_nbytes, limits=None, actual_in=None,
+                                    stream=None):
+        """libdeflate_amd_decompress_sizes_batch_dict: the same with the
+        preset dictionary (a uint8 torch CUDA tensor) of decompress_batch_dict."""
+        check(self._lib.libdeflate_amd_decompress_sizes_batch_dict(
+            self._h, FORMATS[fmt], in_offsets.numel(),
+            dictionary.data_ptr() if dictionary.numel() else None, dictionary.numel(),
+            data.data_ptr(), in_offsets.data_ptr(), in_nbytes.data_ptr(),
+            limits.data_ptr() if limits is not None else None, results.data_ptr(),
+            actual_in.data_ptr() if actual_in is not None else None,
+            out_nbytes.data_ptr(), _stream_ptr(stream)), "decompress_sizes_batch_dict")
+
+    def decompress_sizes_batch_host(self, fmt, chunks, limits=None):
+        """libdeflate_amd_decompress_sizes_batch_host: list of bytes -> list
+        of (result, actual_in, size)."""
+        n = len(chunks)
+        arrs = [np.frombuffer(c, dtype=np.uint8) for c in chunks]
+        inp = (c_void_p * n)(*[a.ctypes.data for a in arrs])
+        inn = (c_size_t * n)(*[a.size for a in arrs])
+        lim = (c_size_t * n)(*limits) if limits is not None else None
+        res = (ctypes.c_int32 * n)()
+        ain = (c_size_t * n)()
+        size = (c_size_t * n)()
+        check(self._lib.libdeflate_amd_decompress_sizes_batch_host(
+            self._h, FORMATS[fmt], n, inp, inn, lim, res, ain, size),
+            "decompress_sizes_batch_host")
+        return [(res[i], ain[i], size[i]) for i in range(n)]
+
+    def decompress_batch_packed(self, fmt, data, in_offsets, in_nbytes, out, out_offsets,
+                                results, actual_out, actual_in=None, out_align=16,
+                                out_capacity=None, stream=None):
+        """libdeflate_amd_decompress_batch_packed: streams of unknown size
+        into `out` back to back (slots aligned to out_align).  out_offsets:
+        int64 CUDA tensor of n + 1 entries, written; the last one is the total
+        the batch needs.  Only enqueues."""
+        check(self._lib.libdeflate_amd_decompress_batch_packed(
+            self._h, FORMATS[fmt], in_offsets.numel(), data.data_ptr(),
+            in_offsets.data_ptr(), in_nbytes.data_ptr(), out.data_ptr(),
+            out.numel() if out_capacity is None else int(out_capacity), int(out_align),
+            out_offsets.data_ptr(), results.data_ptr(),
+            actual_in.data_ptr() if actual_in is not None else None,
+            actual_out.data_ptr(), _stream_ptr(stream)), "decompress_batch_packed")
+
     def decompress_batch_host(self, fmt, chunks, out_avail,
                               want_actual_out=True):
         """-> list of (result, actual_in, actual_out, bytes)."""

@@ -26,6 +26,8 @@ BGZF_BLOCK, BGZF_MEMBER_MAX, BGZF_EOF_BYTES, BGZF_NO_EOF = 65280, 65536, 28, 1
 # the BGZF reader: result[0] beyond enum libdeflate_result, the flag bit of
 # result[4], the words of a result, the read flag for virtual offsets
 BGZF_MORE_MEMBERS, BGZF_HAS_EOF, BGZF_RESULT_WORDS, BGZF_VOFFSETS = 16, 1, 5, 2
+# the size query: the limit a NULL d_out_limit stands for
+SIZE_LIMIT_MAX = 0xFFFFFFFF
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -60,6 +62,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_bgzf_compress",
     "libdeflate_amd_bgzf_decompress_batch", "libdeflate_amd_bgzf_index_batch",
     "libdeflate_amd_bgzf_read_batch", "libdeflate_amd_bgzf_decompress",
+    "libdeflate_amd_decompress_sizes_batch", "libdeflate_amd_decompress_sizes_batch_dict",
+    "libdeflate_amd_decompress_sizes_batch_host", "libdeflate_amd_decompress_batch_packed",
 ]
 
 _lib = None
@@ -153,6 +157,14 @@ def load():
     sig("libdeflate_amd_bgzf_read_batch", c_int, P, P, SZ, P, SZ, SZ, P, c_uint32, P, SZ, P, P)
     sig("libdeflate_amd_bgzf_decompress", c_int, P, P, SZ, P, SZ, psz, psz, P, SZ,
         POINTER(c_uint32))
+    # sizes without decoding (device, with a dictionary, host pointers), and
+    # the packed decompress on top: sizes -> offsets -> decode, enqueue only
+    sig("libdeflate_amd_decompress_sizes_batch", c_int, P, c_int, SZ, P, P, P, P, P, P, P, P)
+    sig("libdeflate_amd_decompress_sizes_batch_dict", c_int, P, c_int, SZ, P, SZ, P, P, P, P,
+        P, P, P, P)
+    sig("libdeflate_amd_decompress_sizes_batch_host", c_int, P, c_int, SZ, P, P, P, P, P, P)
+    sig("libdeflate_amd_decompress_batch_packed", c_int, P, c_int, SZ, P, P, P, P, SZ, SZ, P,
+        P, P, P, P)
     _lib = lib
     return lib
 

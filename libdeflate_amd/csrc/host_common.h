@@ -41,6 +41,8 @@ struct DeviceCtx {
 	 * them again is harmless, so a race between two first calls only repeats
 	 * it); part of the context so that no table is indexed by a device id */
 	std::atomic<bool> deflate_attr_set{false}, inflate_attr_set{false}, stream_attr_set{false};
+	/* waves per CU the size query's kernel fits (host_sizes.hip; 0: not asked yet) */
+	std::atomic<int> sizes_waves_fit{0};
 };
 
 /* context of the calling thread's current device; nullptr (+error) if none */
@@ -78,6 +80,7 @@ struct EnvCfg {
 	int inflate_lpw = 0;		/* LDA_INFLATE_LPW (0 = automatic) */
 	bool inflate_par = true;	/* LDA_INFLATE_PAR */
 	int inflate_waves_per_cu = 16;	/* LDA_INFLATE_WAVES_PER_CU */
+	int sizes_waves_per_cu = 0;	/* LDA_SIZES_WAVES_PER_CU: the size query's (0 = what its registers and LDS allow) */
 	int host_threads = 4;		/* LDA_HOST_THREADS: packing threads of the host-pointer batches */
 	size_t seg_bytes = 0;		/* LDA_SEG_BYTES: sub-range of the segmented single-buffer compress (0 = by size) */
 	bool no_stream_par = false;	/* LDA_NO_STREAM_PAR: single streams stay on one wave */

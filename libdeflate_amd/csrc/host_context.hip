@@ -65,6 +65,11 @@ static EnvCfg read_env()
 		if (v >= 1 && v <= 16)
 			c.inflate_waves_per_cu = v;
 	}
+	if (const char *e = getenv("LDA_SIZES_WAVES_PER_CU")) {
+		int v = atoi(e);
+		if (v >= 1 && v <= 32)
+			c.sizes_waves_per_cu = v;
+	}
 	if (const char *e = getenv("LDA_SEG_BYTES")) {
 		size_t v = (size_t)strtoull(e, nullptr, 0);
 		if (v >= 8192 && v <= 65536 && v % 4096 == 0)

@@ -1041,8 +1041,15 @@ tok_fetch(const u32 *__restrict__ rows, lu8 *mk, const lu16 *tb, u32 tbase,
  * output by then is a match distance that reaches back before the stream,
  * found while its group is executed - the bytes written before it are the
  * ones the sequential decoder writes again before it reports the error.
+ *
+ * COUNT (lda_inflate_sizes_kernel, inflate_sizes.hip): the same passes with
+ * nothing behind them.  No token is recorded and no byte produced: outp, tok
+ * and win are unused, `stage` holds the input span alone, and the distance
+ * rule is applied to the passes' own figures - per lane the largest
+ * `dist - bytes the lane produced before that token`, which must not pass
+ * out0 + the bytes of the lanes before it + the dictionary's length.
  */
-static __device__ u32
+template <bool COUNT = false> static __device__ u32
 par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	  const slds_t *S, const shlds_t *SH,
 	  u32 *__restrict__ tok, lu8 *win, lu8 *stage, u64 ring_lo, u32 lane,
@@ -1080,7 +1087,10 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 		 * wave issued before this round (the rounds before, the sequential
 		 * decoder, a stored block): what this round reads back from the
 		 * output below `out0` is in memory */
-		global_stores_visible();
+		if constexpr (COUNT)
+			wave_sync();	/* nothing was stored: the span in LDS is all the parse reads */
+		else
+			global_stores_visible();
 	}
 	const lu8 *span = stage;	/* the parse reads the staged copy */
 	const u32 bpos0 = (u32)bpos_abs & 7;	/* positions relative to the span */
@@ -1090,6 +1100,7 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	const u32 cend = bpos0 + (lane + 1) * cb;
 	u32 start = bpos0 + lane * cb, end = 0;
 	u32 nbytes = 0, ntok = 0;
+	[[maybe_unused]] s32 reach = 0;	/* COUNT: how far before the lane's first byte its matches reach */
 	bool eob = false, dirty = lane < NL;
 	u32 K = NL - 1;		/* last lane of the round */
 	bool has_eob = false;
@@ -1102,6 +1113,8 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 		if (dirty) {
 			nbytes = 0;
 			ntok = 0;
+			if constexpr (COUNT)
+				reach = 0;
 			eob = false;
 		}
 		/* (a lane runs while its position is inside its piece: tested
@@ -1147,16 +1160,23 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 					eob = true;
 					run = false;
 				} else {
-					/* row ntok of the lane-interleaved list: the 64
-					 * lanes of an iteration write one 256-byte row */
-					if (ntok < PAR_LANECAP)
-						tokS[TOK_AT(ntok, lane)] = t.kind == K_LEN ?
-							0x80000000u | t.length | (t.dist << 9) : t.lit;
+					if constexpr (COUNT) {
+						const s32 back = (s32)t.dist - (s32)nbytes;
+						reach = t.kind == K_LEN && back > reach ? back : reach;
+					} else {
+						/* row ntok of the lane-interleaved list: the 64
+						 * lanes of an iteration write one 256-byte row */
+						if (ntok < PAR_LANECAP)
+							tokS[TOK_AT(ntok, lane)] = t.kind == K_LEN ?
+								0x80000000u | t.length | (t.dist << 9) : t.lit;
+					}
 					nbytes += t.kind == K_LEN ? t.length : 1;
 					ntok++;
 					if (two) {
-						if (ntok < PAR_LANECAP)
-							tokS[TOK_AT(ntok, lane)] = (e1 >> 4) & 0xFF;
+						if constexpr (!COUNT) {
+							if (ntok < PAR_LANECAP)
+								tokS[TOK_AT(ntok, lane)] = (e1 >> 4) & 0xFF;
+						}
 						nbytes++;
 						ntok++;
 						used += e1 & 15;
@@ -1205,7 +1225,7 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	bool valid = lane <= K;
 	u32 tcnt = valid ? ntok : 0;
 	u32 tbase = wave_scan_incl(tcnt) - tcnt;
-	{
+	if constexpr (!COUNT) {
 		u64 vm = __ballot(valid);
 		const u64 over = __ballot(lane <= K && ntok > PAR_LANECAP);
 		if (over)	/* a lane whose row list overflowed, and all after it */
@@ -1228,6 +1248,15 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	const u64 end_bits = bcast_lane(end, K) - bpos0 + bpos_abs;
 	if (end_bits > 8 * in_n)
 		return PAR_STOP;
+	if constexpr (COUNT) {
+		/* a distance that reaches before the stream (and its dictionary):
+		 * the sequential decoder reports it at its token */
+		if (__ballot(valid && reach > 0 && (u64)reach > out0 + obase + dlen))
+			return PAR_STOP;
+		*bpos_ret = end_bits;
+		*out_ret = out0 + total_bytes;
+		return has_eob ? PAR_EOB : PAR_OK;
+	} else {
 
 	/* Every lane's last parse started at its exact position, so the rows it
 	 * wrote then are its tokens: no further parse.  Token i of the round
@@ -1529,6 +1558,7 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	*bpos_ret = end_bits;
 	*out_ret = out0 + total_bytes;
 	return has_eob ? PAR_EOB : PAR_OK;
+	}	/* !COUNT */
 }
 
 /*
@@ -1538,7 +1568,16 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
  * the stream is far enough from both buffer ends; everything else - headers,
  * stored blocks, the last bytes of a stream, every error path - is the
  * sequential decoder below, so result codes do not depend on the mode.
+ *
+ * COUNT (a constant of the calling kernel; lda_inflate_sizes_kernel): the
+ * same decoder producing no bytes.
+ * out_base and out_offsets are unused, out_avail_arr holds the streams' limits
+ * (NULL: LDA_SIZE_LIMIT_MAX each), `dict` is unused and dict_len is the
+ * dictionary's length.  Every store to the output, every read from it and the
+ * copy phase of a round do not exist; every check stays, `distance > bytes
+ * produced` against the count.
  */
+#define LDA_SIZE_LIMIT_MAX 0xFFFFFFFFull
 static __device__ __forceinline__ void
 inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	      u64 n_chunks, int format, u32 lpw,
@@ -1554,7 +1593,10 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	      /* a preset dictionary (NULL: none): its last dict_len (<= 32 KiB)
 	       * bytes, and the Adler-32 of all of it */
 	      const u8 *__restrict__ dict, u32 dict_len,
-	      const u32 *__restrict__ dict_id)
+	      const u32 *__restrict__ dict_id,
+	      /* (a constant at every call: the function is inlined and the
+	       * mode's branches fold) */
+	      const bool COUNT = false)
 {
 	slds_t *SL = (slds_t *)lds_raw;
 	const u32 lane = threadIdx.x;
@@ -1586,15 +1628,23 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	u64 in_n = 0, out_avail = 0;
 	u8 *outp = out_base;
 	u32 hdr = 0;
-	u32 dlen = dict ? dict_len : 0;	/* bytes of dictionary in front of the output */
+	u32 dlen = COUNT || dict ? dict_len : 0;	/* bytes of dictionary in front of the output */
 	s32 result = LDA_SUCCESS;
 	u32 state = ST_DONE;
 
 	if (owner) {
 		inp = in_base + in_offsets[c];
 		in_n = in_nbytes[c];
-		outp = out_base + out_offsets[c];
-		out_avail = out_avail_arr[c];
+		if (COUNT) {
+			/* (positions are 32 bits wide in the rounds: a stream that
+			 * reaches the limit is INSUFFICIENT_SPACE) */
+			out_avail = out_avail_arr ? out_avail_arr[c] : LDA_SIZE_LIMIT_MAX;
+			if (out_avail > LDA_SIZE_LIMIT_MAX)
+				out_avail = LDA_SIZE_LIMIT_MAX;
+		} else {
+			outp = out_base + out_offsets[c];
+			out_avail = out_avail_arr[c];
+		}
 		state = ST_HDR;
 		/* ---- container header ---- */
 		if (format == LDA_FMT_ZLIB) {
@@ -1913,14 +1963,16 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 				const u8 *src = (const u8 *)bcast64((u64)(uintptr_t)(inp + rpos));
 				u8 *dst = (u8 *)bcast64((u64)(uintptr_t)(outp + out_pos));
 				const u64 len = bcast64(stored_left);
-				for (u64 k = 8 * (u64)lane; k + 8 <= len; k += 512) {
-					u64 v;
-					__builtin_memcpy(&v, src + k, 8);
-					__builtin_memcpy(dst + k, &v, 8);
+				if (!COUNT) {
+					for (u64 k = 8 * (u64)lane; k + 8 <= len; k += 512) {
+						u64 v;
+						__builtin_memcpy(&v, src + k, 8);
+						__builtin_memcpy(dst + k, &v, 8);
+					}
+					if ((len & ~7ull) + lane < len)
+						dst[(len & ~7ull) + lane] = src[(len & ~7ull) + lane];
+					global_stores_visible();	/* later matches read these bytes */
 				}
-				if ((len & ~7ull) + lane < len)
-					dst[(len & ~7ull) + lane] = src[(len & ~7ull) + lane];
-				global_stores_visible();	/* later matches read these bytes */
 				if (state == ST_STORED) {
 					/* the register history describes the bytes before
 					 * the stored block: a short-distance match of the
@@ -1939,13 +1991,15 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			const u8 *src = inp + rpos;
 			u8 *dst = outp + out_pos;
 			u64 k = 0;
-			for (; k + 8 <= stored_left; k += 8) {
-				u64 v;
-				__builtin_memcpy(&v, src + k, 8);
-				__builtin_memcpy(dst + k, &v, 8);
+			if (!COUNT) {
+				for (; k + 8 <= stored_left; k += 8) {
+					u64 v;
+					__builtin_memcpy(&v, src + k, 8);
+					__builtin_memcpy(dst + k, &v, 8);
+				}
+				for (; k < stored_left; k++)
+					dst[k] = src[k];
 			}
-			for (; k < stored_left; k++)
-				dst[k] = src[k];
 			if (stored_left)
 				hist_n = 0;	/* see the wave mode above */
 			out_pos += stored_left;
@@ -1964,8 +2018,10 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			for (;;) {
 				if (!bcast_first(state == ST_TOK ? 1u : 0u))
 					break;
-				if (lane == 0)
-					FLUSH_PENDING();
+				if (!COUNT) {
+					if (lane == 0)
+						FLUSH_PENDING();
+				}
 				const u64 bpos0 = bcast64(CONSUMED());
 				const u64 o0 = bcast64(out_pos);
 				const u8 *inp0 = (const u8 *)bcast64((u64)(uintptr_t)inp);
@@ -1996,7 +2052,15 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 						__builtin_amdgcn_s_setprio(0);
 				}
 #endif
-				u32 pr = par_round(inp0, bcast64(in_n), outp0,
+				/* (COUNT: no output mirror in front of the staged span) */
+				u32 pr = COUNT ?
+					 par_round<true>(inp0, bcast64(in_n), NULL,
+							 bcast64(out_avail), &SL[0], SH, NULL,
+							 NULL, (lu8 *)(SH + 1),
+							 ring_lo, lane, bpos0, o0,
+							 &nb, &no, bcast_first(ltb), bcast_first(otb),
+							 NULL, bcast_first(dlen)) :
+					 par_round(inp0, bcast64(in_n), outp0,
 						   bcast64(out_avail), &SL[0], SH, tok,
 						   (lu8 *)(SH + 1), (lu8 *)(SH + 1) + PAR_RW,
 						   ring_lo, lane, bpos0, o0,
@@ -2026,7 +2090,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			/* lane 0's sequential decoder may copy from what all lanes
 			 * stored in the rounds above (once per block; the staged
 			 * input of a following round waits the same way) */
-			global_stores_visible();
+			if (!COUNT)
+				global_stores_visible();
 		}
 
 		/* ------------ fast token loop ------------
@@ -2050,7 +2115,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 					ENSURE_INPUT();
 				REFILL();
 				u32 e = S->lit_tab[(u32)bitbuf & ((1u << ltb) - 1)];
-				FLUSH_PENDING();
+				if (!COUNT)
+					FLUSH_PENDING();
 				u32 cl = e & 15;
 				if (cl == 0) {
 					punt = true;
@@ -2060,13 +2126,16 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 					u32 e1 = S->lit_tab[(u32)bitbuf & ((1u << ltb) - 1)];
 					if ((e1 & 15) && (e1 & 0xC000) == K_LIT) {
 						u16 two = (u16)(pay | (((e1 >> 4) & 0xFF) << 8));
-						__builtin_memcpy(outp + out_pos, &two, 2);
+						if (!COUNT)
+							__builtin_memcpy(outp + out_pos, &two, 2);
 						out_pos += 2;
 						CONSUME(e1 & 15);
 						hist = (hist >> 16) | ((u64)two << 48);
 						hist_n = hist_n + 2 > 8 ? 8 : hist_n + 2;
 					} else {
-						outp[out_pos++] = (u8)pay;
+						if (!COUNT)
+							outp[out_pos] = (u8)pay;
+						out_pos++;
 						hist = (hist >> 8) | ((u64)pay << 56);
 						hist_n = hist_n + 1 > 8 ? 8 : hist_n + 1;
 					}
@@ -2095,6 +2164,9 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 					} else {
 						bitbuf = bb;
 						bitcnt -= used;
+						if (COUNT) {
+							/* counted below */
+						} else
 						if (dist <= hist_n && length <= 8) {
 							u64 pat = hist >> (8 * (8 - dist));
 							u32 sh = 8 * dist;
@@ -2170,7 +2242,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 				continue;
 			}
 			u32 e = S->lit_tab[(u32)bitbuf & ((1u << ltb) - 1)];
-			FLUSH_PENDING();
+			if (!COUNT)
+				FLUSH_PENDING();
 			u32 cl = e & 15, kind = e & 0xC000, pay = (e >> 4) & 0x3FF;
 			if (cl == 0) {
 				u32 sym = decode_long(&S->lit, S->lit_sorted, bitbuf, &cl);
@@ -2195,13 +2268,16 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 				if ((e1 & 0xC00F) > K_LIT && (e1 & 0xC000) == K_LIT &&
 				    rpos + 16 < in_n && out_pos + 1 < out_avail) {
 					u16 two = (u16)(pay | (((e1 >> 4) & 0xFF) << 8));
-					__builtin_memcpy(outp + out_pos, &two, 2);
+					if (!COUNT)
+						__builtin_memcpy(outp + out_pos, &two, 2);
 					out_pos += 2;
 					CONSUME(e1 & 15);
 					hist = (hist >> 16) | ((u64)two << 48);
 					hist_n = hist_n + 2 > 8 ? 8 : hist_n + 2;
 				} else {
-					outp[out_pos++] = (u8)pay;
+					if (!COUNT)
+						outp[out_pos] = (u8)pay;
+					out_pos++;
 					hist = (hist >> 8) | ((u64)pay << 56);
 					hist_n = hist_n + 1 > 8 ? 8 : hist_n + 1;
 				}
@@ -2237,9 +2313,11 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 				/* the source begins in the preset dictionary: byte by
 				 * byte, the first dist - out_pos of them from there */
 				const u32 nd = (u32)(dist - out_pos);
-				for (u32 j = 0; j < length; j++)
-					outp[out_pos + j] = j < nd ? dict[dlen - nd + j] :
-								     outp[out_pos + j - dist];
+				if (!COUNT) {
+					for (u32 j = 0; j < length; j++)
+						outp[out_pos + j] = j < nd ? dict[dlen - nd + j] :
+									     outp[out_pos + j - dist];
+				}
 				hist_n = 0;
 				out_pos += length;
 				continue;
@@ -2247,6 +2325,9 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			/* the lane copies from its own earlier output; short
 			 * non-overlapping copies are split: loads now, stores at the
 			 * next token, so the HBM/L2 round trip overlaps the decode */
+			if (COUNT) {
+				/* counted below */
+			} else
 			if (dist <= hist_n && length <= 8 && out_pos + 8 <= out_avail) {
 				/* source entirely in the register history: expand the
 				 * period in registers, one 8-byte store (the bytes past
@@ -2300,7 +2381,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 		PROF_MARK(2);
 	}
 
-	FLUSH_PENDING();
+	if (!COUNT)
+		FLUSH_PENDING();
 #ifdef LDA_PROFILE
 	if (lane == 0) {
 		atomicAdd(&lda_prof[4], pa_dec);
@@ -2321,8 +2403,28 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			u64 ain = (CONSUMED() + 7) / 8;
 			if (ain > in_n)
 				result = LDA_BAD_DATA;
-			else
+			else if (!COUNT || actual_in)
 				actual_in[c] = hdr + ain;
+		}
+		if (COUNT) {
+			/* the footer: present, and for gzip its ISIZE the count's low
+			 * 32 bits (the checksum of bytes nobody produced is all that
+			 * is not checked; actual_in[] gets hdr + ain + the footer).
+			 * Its bytes lie inside the buffer: the header rules kept them. */
+			if (result == LDA_SUCCESS && format == LDA_FMT_GZIP) {
+				const u8 *p = inp + (CONSUMED() + 7) / 8;
+				const u32 isize = p[4] | ((u32)p[5] << 8) | ((u32)p[6] << 16) |
+						  ((u32)p[7] << 24);
+				if (isize != (u32)out_pos)
+					result = LDA_BAD_DATA;
+			}
+			if (result == LDA_SUCCESS && actual_in && format != LDA_FMT_DEFLATE)
+				actual_in[c] += format == LDA_FMT_GZIP ? 8 : 4;
+			if (result != LDA_SUCCESS && actual_in)
+				actual_in[c] = 0;
+			results[c] = result;
+			actual_out[c] = result == LDA_SUCCESS ? out_pos : 0;
+			return;
 		}
 		results[c] = result;
 		actual_out[c] = result == LDA_SUCCESS ? out_pos : 0;

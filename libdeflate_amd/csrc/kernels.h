@@ -47,6 +47,24 @@ lda_inflate_wave_kernel(uint64_t n_chunks, int format, uint32_t *tokscratch,
 extern "C" __global__ void
 lda_inflate_order_kernel(uint64_t n, const uint64_t *in_nbytes, const uint64_t *out_avail,
 			 uint32_t *order);
+/* inflate_sizes.hip: the size query and the descriptors of the packed decode */
+extern "C" __global__ void
+lda_inflate_sizes_kernel(uint64_t n_chunks, int format, uint32_t par, uint32_t *next_stream,
+			 const uint32_t *order, const uint8_t *in_base,
+			 const uint64_t *in_offsets, const uint64_t *in_nbytes,
+			 const uint64_t *limits, int32_t *results, uint64_t *actual_in,
+			 uint64_t *out_nbytes, uint32_t dict_len, const uint32_t *dict_id);
+extern "C" size_t lda_inflate_sizes_lds_bytes(void);
+extern "C" __global__ void
+lda_packed_round_kernel(uint64_t n, uint64_t align_mask, const uint64_t *sizes,
+			uint64_t *rounded);
+extern "C" __global__ void
+lda_packed_desc_kernel(uint64_t n, uint64_t capacity, const uint64_t *in_nbytes,
+		       const uint64_t *sizes, const uint64_t *block_sums, uint64_t *offsets,
+		       int32_t *verdict, uint64_t *dec_in_nbytes, uint64_t *dec_avail);
+extern "C" __global__ void
+lda_packed_merge_kernel(uint64_t n, const int32_t *verdict, int32_t *results,
+			uint64_t *actual_in, uint64_t *actual_out);
 extern "C" size_t lda_inflate_tokcap(void);
 extern "C" size_t lda_inflate_window_bytes(void);
 extern "C" __global__ void
