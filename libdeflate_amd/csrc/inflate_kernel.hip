@@ -826,6 +826,8 @@ par_decode(const slds_t *S, const shlds_t *SH,
 #define PAR_GBYTES 1088u	/* output bytes resolved per group (>= 4 x 258; the mirror holds the group and 256 more) */
 #endif
 
+enum { PAR_SB = 4 };	/* slots of 64 bytes the copy phase resolves together */
+
 static __device__ __forceinline__ u64 shfl_up64(u64 v)
 {
 	/* DPP wave_shr:1 (lane 0 keeps its own value) */
@@ -867,6 +869,192 @@ static __device__ __forceinline__ void global_stores_visible(void)
 }
 
 /*
+ * `nbytes` (a multiple of 8) of input from byte0 on as 8-byte words, unaligned
+ * in HBM, aligned in LDS; zeros past the end of the input, exactly the implicit
+ * padding of the sequential decoder.
+ */
+static __device__ __forceinline__ void
+stage_span(lu8 *stage, const u8 *inp, u64 in_n, u64 byte0, u32 nbytes, u32 lane)
+{
+	for (u32 w = lane; w < nbytes / 8; w += 64) {
+		const u64 pos = byte0 + 8 * w;
+		*(lu64 *)(stage + 8 * w) = pos + 8 <= in_n ? ld8(inp + pos) :
+					  load_in(inp, in_n, pos);
+	}
+}
+
+/*
+ * ... and the wait: the staged words have arrived, and with them every store
+ * the wave issued before (the rounds before, the sequential decoder, a stored
+ * block): what the caller reads back from the output it has produced so far
+ * is in memory.
+ */
+static __device__ __forceinline__ void
+stage_input(lu8 *stage, const u8 *inp, u64 in_n, u64 byte0, u32 nbytes, u32 lane)
+{
+	stage_span(stage, inp, in_n, byte0, nbytes, lane);
+	global_stores_visible();
+}
+
+/*
+ * The section counters of a round, handed to its stages by address (NULL: a
+ * caller that is not profiled).  Nothing of it exists unless the build
+ * counts (LDA_PROFILE_COUNTS).
+ */
+#if defined(LDA_PROFILE) && defined(LDA_PROFILE_COUNTS)
+struct par_prof {
+	unsigned long long sec[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+	unsigned long long t = __builtin_readcyclecounter();
+};
+#define PAR_SEC(pf, i) do { if (pf) { unsigned long long n_ = __builtin_readcyclecounter(); \
+		(pf)->sec[i] += n_ - (pf)->t; (pf)->t = n_; } } while (0)
+#define PAR_SEC_ADD(pf, i, v) do { if (pf) (pf)->sec[i] += (v); } while (0)
+#define PAR_SEC_FLUSH8(pf, base) do { if (threadIdx.x == 0) for (int i_ = 0; i_ < 8; i_++) \
+		atomicAdd(&lda_prof[(base) + i_], (pf)->sec[i_]); } while (0)
+#else
+struct par_prof { };
+#define PAR_SEC(pf, i) do { } while (0)
+#define PAR_SEC_ADD(pf, i, v) do { } while (0)
+#define PAR_SEC_FLUSH8(pf, base) do { } while (0)
+#endif
+
+/*
+ * What a parse keeps of its tokens (parse_piece() below).  Nothing: only where
+ * the parse ends and whether at an end of block, which parse_piece() itself
+ * reports - the compiler drops what computes lengths and distances.
+ */
+struct tok_none {
+	enum { KEEPS = 0 };
+	__device__ __forceinline__ void token(const struct par_token &) { }
+	__device__ __forceinline__ void second(u32) { }
+};
+
+/* the bytes the tokens make */
+struct tok_bytes {
+	enum { KEEPS = 1 };
+	u32 &nbytes;
+	__device__ __forceinline__ void token(const struct par_token &t)
+	{
+		nbytes += t.kind == K_LEN ? t.length : 1;
+	}
+	__device__ __forceinline__ void second(u32) { nbytes++; }
+};
+
+/*
+ * Bytes and tokens of a round's lane (the caller's counters) and, where
+ * `keep`, the token words: row ntok of the lane-interleaved list (the 64
+ * lanes of an iteration write one 256-byte row).
+ */
+struct tok_rows {
+	enum { KEEPS = 1 };
+	u32 &nbytes, &ntok;
+	u32 *rows;	/* [PAR_LANECAP][64]: row k holds every lane's k-th token */
+	u32 lane;
+	bool keep;
+	__device__ __forceinline__ void token(const struct par_token &t)
+	{
+		if (keep && ntok < PAR_LANECAP)
+			rows[TOK_AT(ntok, lane)] = t.kind == K_LEN ?
+				0x80000000u | t.length | (t.dist << 9) : t.lit;
+		nbytes += t.kind == K_LEN ? t.length : 1;
+		ntok++;
+	}
+	__device__ __forceinline__ void second(u32 lit)
+	{
+		if (keep && ntok < PAR_LANECAP)
+			rows[TOK_AT(ntok, lane)] = lit;
+		nbytes++;
+		ntok++;
+	}
+};
+
+/* ... and `reach` instead: how far before the lane's first byte its matches reach */
+struct tok_reach {
+	enum { KEEPS = 1 };
+	u32 &nbytes, &ntok;
+	s32 &reach;
+	__device__ __forceinline__ void token(const struct par_token &t)
+	{
+		const s32 back = (s32)t.dist - (s32)nbytes;
+		reach = t.kind == K_LEN && back > reach ? back : reach;
+		nbytes += t.kind == K_LEN ? t.length : 1;
+		ntok++;
+	}
+	__device__ __forceinline__ void second(u32)
+	{
+		nbytes++;
+		ntok++;
+	}
+};
+
+/*
+ * The parse of one piece: from where `b` stands to `cend`, on the lanes that
+ * `run` (they stand in front of `cend`); every token goes to `sink`.  Stops
+ * behind an end-of-block symbol - unless `warm`: a parse that only looks for a
+ * token boundary runs over them.  Returns where the parse stands.
+ */
+struct piece_end {
+	u32 pos;	/* where the parse stands */
+	bool eob;	/* behind an end-of-block symbol */
+};
+template <class SINK> static __device__ __forceinline__ struct piece_end
+parse_piece(const slds_t *S, const shlds_t *SH, const struct par_long *pll,
+	    const struct par_long *plo, const lu8 *span, struct par_bits b, u32 cend,
+	    bool run, bool warm, SINK sink,
+	    u32 lmask = (1u << LIT_TB) - 1, u32 omask = (1u << OFF_TB) - 1,
+	    struct par_prof *pf = NULL)
+{
+	bool eob = false;
+	/* (a lane runs while its position is inside its piece: tested where the
+	 * position moves, at the end of the body, not at its top - that form
+	 * went round once more, a whole step, only to find every lane at its
+	 * end) */
+	while (__ballot(run)) {
+		PAR_SEC_ADD(pf, 1, 1);
+		pb_refill(&b, span);
+		const struct par_token t = par_decode(S, SH, pll, plo, b.buf, run, lmask, omask);
+		/* A literal takes a second one with it when that one starts inside
+		 * the piece and its codeword is in the table: a pass lasts as long
+		 * as its lane with the most tokens, and those are the lanes full of
+		 * literals. */
+		const u32 e1 = t.e1;
+		const bool two = t.kind == K_LIT && PB_POS(b) + t.used < cend &&
+				 (e1 & 0xC000) == K_LIT && (e1 & 15) != 0;
+		if constexpr (!SINK::KEEPS) {
+			/* (nothing to record: the position moves without a branch.
+			 * Under `if (run)` as below the first pass of the batch
+			 * rounds took 1.5 % more of a 4096-stream launch) */
+			const bool stop = t.kind == K_EOB && !warm;
+			const u32 used = run ? t.used + (two ? e1 & 15 : 0) : 0;
+			b.buf >>= used;
+			b.cnt -= used;
+			eob = eob || (run && stop);
+			run = run && !stop && PB_POS(b) < cend;
+		} else {
+			if (run) {
+				u32 used = t.used;
+				if (t.kind == K_EOB) {
+					if (!warm) {
+						eob = true;
+						run = false;
+					}
+				} else {
+					sink.token(t);
+					if (two) {
+						sink.second((e1 >> 4) & 0xFF);
+						used += e1 & 15;
+					}
+				}
+				b.buf >>= used;
+				b.cnt -= used;
+			}
+			run = run && PB_POS(b) < cend;
+		}
+	}
+	return { PB_POS(b), eob };
+}
+
+/*
  * A round whose passes do not converge.  The passes rest on a parse started
  * at a wrong bit falling in step with the true one within a few tokens; a
  * code whose codewords all have (nearly) one length never does - a dynamic
@@ -904,28 +1092,12 @@ par_phase_starts(const slds_t *S, const shlds_t *SH, const struct par_long *pll,
 	const bool mine = lane >= f && lane < NL && cend == pe;
 	for (u32 ph = 0; ph < PAR_PHASES; ph++) {
 		struct par_bits b;
-		bool stop = false;
 		pb_init(&b, span, ps + ph);
-		bool run = mine && PB_POS(b) < pe;	/* (tested at the end of the body: see par_round()) */
-		while (__ballot(run)) {
-			pb_refill(&b, span);
-			const struct par_token t = par_decode(S, SH, pll, plo, b.buf, run, lmask, omask);
-			const u32 e1 = t.e1;
-			const bool two = t.kind == K_LIT && PB_POS(b) + t.used < pe &&
-					 (e1 & 0xC000) == K_LIT && (e1 & 15) != 0;
-			if (run) {
-				u32 used = t.used + (two ? e1 & 15 : 0);
-				if (t.kind == K_EOB) {
-					stop = true;
-					run = false;
-				}
-				b.buf >>= used;
-				b.cnt -= used;
-			}
-			run = run && PB_POS(b) < pe;
-		}
-		const u32 over = PB_POS(b) - pe;
-		const u64 code = mine && !stop && PB_POS(b) >= pe && over < PAR_PHASES ? over : 63;
+		const struct piece_end e = parse_piece(S, SH, pll, plo, span, b, pe,
+						       mine && PB_POS(b) < pe, false,
+						       tok_none(), lmask, omask);
+		const u32 over = e.pos - pe;
+		const u64 code = mine && !e.eob && e.pos >= pe && over < PAR_PHASES ? over : 63;
 		ends = (ends & ~(63ull << (6 * ph))) | (code << (6 * ph));
 	}
 	u32 res = cur;
@@ -1033,6 +1205,451 @@ tok_fetch(const u32 *__restrict__ rows, lu8 *mk, const lu16 *tb, u32 tbase,
 }
 
 /*
+ * The stages of a round behind a pass's parse.  Where every lane's next parse
+ * starts: at the end of the lane before it (DPP wave_shr:1, lane 0 keeps its
+ * own value), lane 0 at the round's first bit.
+ */
+static __device__ __forceinline__ u32 pass_starts(u32 end, u32 lane, u32 bpos0)
+{
+	u32 ns = __builtin_amdgcn_update_dpp(end, end, 0x138, 0xF, 0xF, false);
+	if (lane == 0)
+		ns = bpos0;
+	return ns;
+}
+
+/*
+ * `dirty`: the lanes that parse again.  The lanes in front of the first of
+ * them are exact; `eobs`: those of them that stand behind an end of block -
+ * the round ends at the first of these.
+ */
+struct pass_masks {
+	u64 dirty, eobs;
+};
+static __device__ __forceinline__ struct pass_masks pass_settle(bool dirty, bool eob)
+{
+	const u64 dm = __ballot(dirty), em = __ballot(eob);
+	const u64 exact = dm ? (1ull << __builtin_ctzll(dm)) - 1 : ~0ull;
+	return { dm, em & exact };
+}
+
+/*
+ * Counts -> offsets over lanes 0 .. *K.  CLIP: the round is clipped to the
+ * token scratch - a lane whose row list overflowed, and all after it, are
+ * left to the next round.  false: no lane is left.
+ */
+struct par_sums {
+	bool valid;		/* this lane belongs to the round */
+	u32 tcnt, tbase;	/* its tokens, and the tokens of the lanes before it */
+	u32 obase;		/* the bytes of the lanes before it */
+	u32 total_tok;
+	u64 total_bytes;
+	u32 K;			/* the round's last lane */
+	bool has_eob;
+};
+template <bool CLIP> static __device__ __forceinline__ bool
+round_offsets(struct par_sums &r, u32 lane, u32 ntok, u32 nbytes, u32 K, bool has_eob)
+{
+	bool valid = lane <= K;
+	const u32 tcnt = valid ? ntok : 0;
+	const u32 tbase = wave_scan_incl(tcnt) - tcnt;
+	if constexpr (CLIP) {
+		u64 vm = __ballot(valid);
+		const u64 over = __ballot(lane <= K && ntok > PAR_LANECAP);
+		if (over)	/* a lane whose row list overflowed, and all after it */
+			vm &= (1ull << __builtin_ctzll(over)) - 1;
+		const u32 nv = __builtin_popcountll(vm);	/* a prefix of lanes */
+		if (nv == 0)
+			return false;
+		if (nv - 1 < K) {
+			K = nv - 1;
+			has_eob = false;
+		}
+		valid = lane <= K;
+	}
+	const u32 bcnt = valid ? nbytes : 0;
+	const u32 obase = wave_scan_incl(bcnt) - bcnt;
+	r.valid = valid;
+	r.tcnt = tcnt;
+	r.tbase = tbase;
+	r.obase = obase;
+	r.total_tok = bcast_lane(tbase + tcnt, K);
+	r.total_bytes = bcast_lane(obase + bcnt, K);
+	r.K = K;
+	r.has_eob = has_eob;
+	return true;
+}
+
+/*
+ * The next group of the copy phase: four consecutive tokens per lane from
+ * token g on, as many lanes (a prefix, `cnt`) as fit PAR_GBYTES bytes.
+ */
+struct par_group {
+	uint4 tq;		/* the lane's four token words */
+	u32 len4[4], lsum;	/* their bytes (0 past the round's last token) */
+	u32 incl0;		/* ... summed over the lanes up to this one */
+	u32 cnt, gtot;		/* lanes and bytes of the group */
+};
+static __device__ __forceinline__ void
+group_form(struct par_group *G, uint4 tq, u32 g, u32 total_tok, u32 lane)
+{
+	const u32 ti0 = g + 4 * lane;
+	const u32 tw4[4] = { tq.x, tq.y, tq.z, tq.w };
+	G->tq = tq;
+	G->lsum = 0;
+#pragma unroll
+	for (u32 j = 0; j < 4; j++) {
+		G->len4[j] = ti0 + j >= total_tok ? 0 :
+			     (tw4[j] >> 31) ? (tw4[j] & 0x1FF) : 1;
+		G->lsum += G->len4[j];
+	}
+	G->incl0 = wave_scan_incl(G->lsum);
+	/* the lanes whose tokens fit: a prefix */
+	const bool fits = ti0 < total_tok && G->incl0 <= PAR_GBYTES;
+	G->cnt = __builtin_popcountll(__ballot(fits));
+	G->gtot = bcast_lane(G->incl0, G->cnt - 1);
+}
+
+/*
+ * What the copy phase leaves to its caller (copy_phase<X>() below): the batch
+ * rounds write bytes, the rounds of inflate_stream.hip 16-bit symbols.
+ *   elem, NONE   the mirror's element type; a value that is no element
+ *   STOPS        a source in front of the stream ends the round at once
+ *   front()      how many bytes in front of a group can be a match's source
+ *   far_base()   the output 32768 elements in front of a group, for sources
+ *                older than the mirror (base + a non-negative 32-bit lane
+ *                offset: distances are <= 32768)
+ *   fronts()     false: every source further back than front() is invalid
+ *   in_front()   what such a source (lanes `tf`, `back` bytes in front of the
+ *                group) is; adds the lanes whose distance is invalid to *bad.
+ *                `back_max` is what front() returned for this group
+ *   store(), flush()   the output itself
+ * Here: bytes.  A source in front of the stream is a byte of the preset
+ * dictionary - sources up to dlen bytes in front of the stream are its last
+ * bytes - or invalid.
+ */
+struct copy_bytes {
+	typedef u8 elem;
+	typedef const gu8 *far_t;
+	enum { NONE = 0x100, STOPS = 1 };
+	gu8 *gout;
+	const u8 *__restrict__ dict;
+	u32 dlen;
+	/* a distance that reaches back before the stream: possible only in the
+	 * first 32 KiB */
+	__device__ __forceinline__ u32 front(u64 gbase) const
+	{
+		return gbase < 32768 ? (u32)gbase : 32768u;
+	}
+	__device__ __forceinline__ far_t far_base(u64 gbase) const
+	{
+		return (const gu8 *)((uintptr_t)gout + gbase - 32768);
+	}
+	__device__ __forceinline__ bool fronts(void) const { return dlen != 0; }
+	__device__ __forceinline__ u32
+	in_front(u32 v, u64 tf, u32 back, u64 gbase, u32 back_max, u64 *bad) const
+	{
+		const u32 gb = (u32)gbase;
+		const u64 ind = tf & __ballot(back - gb <= dlen);
+		if (lane_bit(ind))
+			v = dict[dlen - (back - gb)];
+		*bad |= tf & ~ind;
+		return v;
+	}
+	__device__ __forceinline__ void store(u64 pos, u32 v) const { gout[pos] = (u8)v; }
+	__device__ __forceinline__ u64 flush(const lu8 *win, u64 flushed, u64 end, u32 lane) const
+	{
+		return flush_ring(gout, win, flushed, end, lane);
+	}
+};
+
+/*
+ * Execute the round's tokens: up to 256 tokens / PAR_GBYTES bytes a group.
+ * Every lane's last parse started at its exact position, so the rows it
+ * wrote then are its tokens: no further parse.  Token i of the round
+ * (stream order) is row i - tbase[l] of the lane l whose range holds i;
+ * the copy phase finds l per group (tok_fetch).
+ * The copies of a group are resolved per output BYTE, not per token, 64
+ * bytes (a slot) at a time and in output order: byte b is a literal, or
+ * a copy of the byte dist before it.  That byte is final - in the LDS
+ * mirror of the recent output, or in the output itself when it is further
+ * back than the mirror reaches - unless it lies in the same slot; copies
+ * inside a slot (runs, short periods) are settled by pointer jumping over
+ * the 64 lanes, whatever the shape of the dependencies.  The bytes meet
+ * in the mirror; the output is written from there in whole words once
+ * per group (X::flush).
+ * Returns the lanes that met a distance reaching back before the stream: at
+ * once where X::STOPS, else when all tokens are executed.
+ */
+template <class X> static __device__ __forceinline__ u64
+copy_phase(const X x, const u32 *rows, AS3 typename X::elem *win, lu8 *stage, u64 ring_lo,
+	   u32 lane, u64 out0, u32 tbase, u32 own_cnt, u32 total_tok,
+	   struct par_prof *pf = NULL)
+{
+	lu8 *mk = stage + PAR_STAGE_BYTES;		/* [256] group token -> lane + 1 */
+	lu16 *tb = (lu16 *)(mk + 256);			/* [64] tbase per lane */
+	tb[lane] = (u16)tbase;
+	wave_sync();
+	lu32 *tk = (lu32 *)stage;			/* [256] the group's tokens */
+	/* (a group's tokens are numbered 0 .. 255 and its first byte starts
+	 * token 0, so a cleared entry and "token 0" say the same) */
+	lu8 *R = (lu8 *)((lu32 *)stage + 256);		/* [PAR_GBYTES] byte -> token of the group */
+	u64 gbase = out0;
+	u64 flushed = out0;	/* output below this is in memory */
+	u64 safe_hi = out0;	/* ... and below this its stores have been waited for */
+	u32 g = 0;		/* a multiple of 4: 16-byte token loads */
+	u64 bad_all = 0;
+	/* four consecutive tokens per lane; the next group's are requested
+	 * as soon as this group's extent is known, so their trip to the
+	 * scratch runs beside the group's LDS work */
+	uint4 tq_next = tok_fetch(rows, mk, tb, tbase, own_cnt, 0, total_tok, lane);
+	while (g < total_tok) {
+		struct par_group G;
+		group_form(&G, tq_next, g, total_tok, lane);
+		const u32 cnt = G.cnt, gtot = G.gtot;
+		if (g + 4 * cnt < total_tok)
+			tq_next = tok_fetch(rows, mk, tb, tbase, own_cnt,
+					    g + 4 * cnt, total_tok, lane);
+		/* byte -> token: every token drops its number at its first
+		 * byte, a running maximum over the bytes spreads it */
+		/* (the whole map is cleared with three 16-byte stores per lane
+		 * - 2 x 1024 + 128 bytes - instead of a loop of 2-byte stores
+		 * over the group's bytes: 12 rounds of 8 instructions) */
+		{
+			static_assert(PAR_GBYTES <= PAR_MAP_CLEAR && PAR_MAP_CLEAR == 2176 &&
+				      PAR_GBYTES + 256 <= PAR_RW && PAR_GBYTES >= 4 * 258,
+				      "two full wave stores and one of eight lanes");
+			const uint4 z = make_uint4(0, 0, 0, 0);
+			AS3 uint4 *R16 = (AS3 uint4 *)R;
+			R16[lane] = z;
+			R16[64 + lane] = z;
+			if (lane < 8)
+				R16[128 + lane] = z;
+		}
+		wave_sync();
+		if (lane < cnt) {
+			u32 o = G.incl0 - G.lsum;
+			*(AS3 uint4 *)&tk[4 * lane] = G.tq;	/* the lane's four token words */
+#pragma unroll
+			for (u32 j = 0; j < 4; j++) {
+				if (G.len4[j])
+					R[o] = (u8)(4 * lane + j);
+				o += G.len4[j];
+			}
+		}
+		wave_sync();
+		/* a source `rel` bytes before the group is still in the mirror
+		 * when the group's own bytes have not overwritten it and the
+		 * mirror has been kept that far back */
+		const u32 gb = (u32)gbase;
+		u32 ring_rel = PAR_RW - gtot;
+		if (gbase - ring_lo < ring_rel)
+			ring_rel = (u32)(gbase - ring_lo);
+		/* sources further back come from the output itself */
+		const typename X::far_t gfar = x.far_base(gbase);
+		const u32 back_max = x.front(gbase);
+		u64 badm = 0;	/* lanes whose distance reaches back before the stream */
+		/* The slots (64 bytes each) are resolved in order, so the
+		 * source of a byte is final in the mirror when its slot is
+		 * reached, unless it lies in the same slot.  The token lookup
+		 * of PAR_SB slots is done together (its LDS reads and the reads
+		 * from the output are independent of the mirror); then every
+		 * slot reads its sources, settles the copies inside itself
+		 * (pointer jumping over the 64 lanes, only when there are
+		 * any) and writes its bytes. */
+		u32 carry = 0;
+		PAR_SEC(pf, 2);
+		PAR_SEC_ADD(pf, 6, 1);
+		for (u32 s0 = 0; s0 < gtot; s0 += 64 * PAR_SB) {
+			u32 own[PAR_SB], vfar[PAR_SB];
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++) {
+				/* (an index past the group reads its last entry and is
+				 * masked: as `bi < gtot ? R[bi] : 0` each of the four
+				 * reads sat in an EXEC section of its own with its own
+				 * wait) */
+				const u32 bi = s0 + 64 * k + lane;
+				const u32 r = R[bi < gtot ? bi : gtot - 1];
+				own[k] = bi < gtot ? r : 0;
+			}
+#define DPP_MAX(k, ctrl, rm, bc)                                               \
+	do {                                                                   \
+		u32 t_ = __builtin_amdgcn_update_dpp(0, own[k], ctrl, rm, 0xF, bc); \
+		own[k] = own[k] > t_ ? own[k] : t_;                            \
+	} while (0)
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++)
+				DPP_MAX(k, 0x111, 0xF, true);
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++)
+				DPP_MAX(k, 0x112, 0xF, true);
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++)
+				DPP_MAX(k, 0x114, 0xF, true);
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++)
+				DPP_MAX(k, 0x118, 0xF, true);
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++)
+				DPP_MAX(k, 0x142, 0xA, false);
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++)
+				DPP_MAX(k, 0x143, 0xC, false);
+#undef DPP_MAX
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++) {
+				own[k] = own[k] > carry ? own[k] : carry;
+				carry = bcast_lane(own[k], 63);
+			}
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++) {
+				/* (the group's first byte starts token 0 and the running
+				 * maximum carries on) */
+				const u32 bi = s0 + 64 * k + lane;
+				const u32 w = tk[own[k]];	/* token word */
+				own[k] = bi < gtot ? w : 0;
+			}
+			/* bytes whose source is older than the mirror.  The tests are
+			 * one ballot per compare, combined on the scalar unit (a
+			 * ballot of a compound predicate goes through a 0 / 1 detour
+			 * in a vector register), and the four slots share ONE
+			 * section: nothing of it runs when the batch has no such byte */
+			u64 mfar[PAR_SB], anyfar = 0, anyneed = 0, tfar = 0;
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++) {
+				const u32 bi = s0 + 64 * k + lane, tw = own[k];
+				const u32 dist = (tw >> 9) & 0xFFFF;
+				const u32 back = dist - bi;	/* bytes in front of the group (when dist > bi) */
+				const u64 before = __ballot((s32)tw < 0) & __ballot(dist > bi);
+				const u64 toofar = before & __ballot(back > back_max);
+				mfar[k] = before & ~toofar & __ballot(back > ring_rel);
+				tfar |= toofar;
+				anyfar |= mfar[k];
+				/* a source at or above safe_hi was stored by this wave
+				 * after its last wait: see below */
+				anyneed |= mfar[k] & __ballot(back <= (u32)(gbase - safe_hi));
+				vfar[k] = X::NONE;	/* no far source */
+				/* (a value of its own per slot: with one constant copied
+				 * into the four, the first far load was followed by a wait
+				 * for it - and for the token rows requested ahead - before
+				 * the copies could be redone: 7 % of a batch of match-heavy
+				 * streams) */
+				asm volatile("" : "+v"(vfar[k]));
+			}
+			if (anyfar) {
+				/* The source may be an element another lane of this wave
+				 * stored earlier in THIS round (X::flush); everything
+				 * below safe_hi was stored before a wait.  Only a source
+				 * at or above it - rare: it must be older than the mirror
+				 * and younger than the last wait - makes the wave wait for
+				 * its stores (and for the token rows requested ahead)
+				 * before it loads. */
+				if (anyneed) {
+					global_stores_visible();
+					safe_hi = flushed;
+				}
+#pragma unroll
+				for (u32 k = 0; k < PAR_SB; k++) {
+					const u32 bi = s0 + 64 * k + lane;
+					const u32 dist = (own[k] >> 9) & 0xFFFF;
+					if (lane_bit(mfar[k]))
+						vfar[k] = gfar[bi + 32768u - dist];
+				}
+			}
+			if (tfar && x.fronts()) {
+				u64 still = 0;
+#pragma unroll
+				for (u32 k = 0; k < PAR_SB; k++) {
+					const u32 bi = s0 + 64 * k + lane, tw = own[k];
+					const u32 dist = (tw >> 9) & 0xFFFF;
+					const u32 back = dist - bi;
+					const u64 tf = __ballot((s32)tw < 0) & __ballot(dist > bi) &
+						       __ballot(back > back_max);
+					vfar[k] = x.in_front(vfar[k], tf, back, gbase, back_max, &still);
+				}
+				tfar = still;
+			}
+			badm |= tfar;
+			/* copies inside a slot: where each lane's byte finally comes
+			 * from.  That depends on the tokens alone, so the PAR_SB slots'
+			 * pointer chains are jumped together (their latencies
+			 * overlap) before the slots' bytes are settled in order. */
+			u32 root[PAR_SB];
+			bool any_intra = false;
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++) {
+				const u32 tw = own[k], dist = (tw >> 9) & 0xFFFF;
+				const bool intra = (tw >> 31) && dist <= lane;
+				root[k] = intra ? lane - dist : lane;
+				any_intra |= intra;
+			}
+			if (__ballot(any_intra)) {
+				for (;;) {
+					/* the four permutes go out together, one wait (as
+					 * `pp = permute; ch |= pp != root` per slot each
+					 * compare waited for its own permute) */
+					u32 pp[PAR_SB];
+#pragma unroll
+					for (u32 k = 0; k < PAR_SB; k++)
+						pp[k] = (u32)__builtin_amdgcn_ds_bpermute(
+								(int)(root[k] << 2), (int)root[k]);
+					asm volatile("" :: "v"(pp[0]), "v"(pp[1]), "v"(pp[2]), "v"(pp[3]));
+					u64 chm = 0;
+#pragma unroll
+					for (u32 k = 0; k < PAR_SB; k++) {
+						chm |= __ballot(pp[k] != root[k]);
+						root[k] = pp[k];
+					}
+					if (!chm)
+						break;
+				}
+			}
+#if defined(LDA_PROFILE) && defined(LDA_PROFILE_COUNTS)
+			/* the wait for the far sources on its own (the profile build
+			 * only: it also waits for the token rows requested ahead) */
+			PAR_SEC(pf, 3);
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			PAR_SEC(pf, 4);
+			PAR_SEC_ADD(pf, 7, 1);
+#endif
+#pragma unroll
+			for (u32 k = 0; k < PAR_SB; k++) {
+				const u32 bi = s0 + 64 * k + lane, tw = own[k];
+				const u32 dist = (tw >> 9) & 0xFFFF;
+				const bool match = (tw >> 31) != 0;	/* false past gtot */
+				/* every lane reads the mirror (the index is always
+				 * inside it); matches from outside the slot use it */
+				u32 wv = win[(gb + bi - dist) & (PAR_RW - 1)];
+				/* (kept out of the branches below: as part of one the
+				 * read, and its wait, sat inside an EXEC section) */
+				asm volatile("" : "+v"(wv));
+				u32 v = match ? wv : tw & 0xFF;
+				v = vfar[k] < X::NONE ? vfar[k] : v;
+				if (__ballot(root[k] != lane))
+					v = (u32)__builtin_amdgcn_ds_bpermute((int)(root[k] << 2), (int)v);
+				if (bi < gtot)
+					win[(gb + bi) & (PAR_RW - 1)] = (typename X::elem)v;
+			}
+		}
+		wave_sync();
+		PAR_SEC(pf, 3);
+		if constexpr (X::STOPS) {
+			if (badm)
+				return badm;
+		} else
+			bad_all |= badm;
+		gbase += gtot;
+		flushed = x.flush(win, flushed, gbase, lane);
+		PAR_SEC(pf, 5);
+		g += 4 * cnt;
+	}
+	/* the last elements (less than a unit of X::flush) */
+	if (flushed + lane < gbase)
+		x.store(flushed + lane, win[(u32)(flushed + lane) & (PAR_RW - 1)]);
+	wave_sync();
+	return bad_all;
+}
+
+/*
  * One round.  bpos0: bit position (in inp) of the next token; out0: bytes
  * produced so far.  Returns PAR_STOP with the decoder's position unchanged,
  * or PAR_OK / PAR_EOB with *bpos_ret / *out_ret advanced (PAR_EOB: the
@@ -1058,40 +1675,26 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 {
 	const u32 lmask = (1u << ltb) - 1, omask = (1u << otb) - 1;	/* wave-uniform */
 	/* lanes in this round: one PAR_CB-bit chunk each, up to the end of the
-	 * input.  Bytes past the end are staged as zeros, exactly the implicit
-	 * padding of the sequential decoder; a round whose exact parse ends
-	 * beyond the input is abandoned below and left to that decoder (it is
-	 * the one that knows the overread rules). */
+	 * input.  Bytes past the end are staged as zeros; a round whose exact
+	 * parse ends beyond the input is abandoned below and left to the
+	 * sequential decoder (it is the one that knows the overread rules). */
 	const u64 byte0 = bpos_abs >> 3;
 	/* (rounds run up to the last bytes of the input: what is left behind them
 	 * goes token by token through lane 0 - with a margin of 64 bytes that was
 	 * some fifty tokens per stream, 2 % of a 64 KiB stream's instructions) */
 	if (byte0 + PAR_TAIL > in_n)
 		return PAR_STOP;
-	u32 *__restrict__ tokS = tok;	/* [PAR_LANECAP][64]: row k holds every lane's k-th token */
 	/* long pieces need fewer rounds and fewer passes per round (a parse
 	 * falls in step within ~50 bits); when the input left would not fill
 	 * the 64 lanes with them, shorter pieces keep more lanes busy */
 	const u32 cb = in_n - byte0 >= 64 * (PAR_CB / 8) ? PAR_CB : 256u;
 	const u64 room = (in_n - byte0 + cb / 8 - 1) / (cb / 8);
 	const u32 NL = room < 64 ? (u32)room : 64;
-	/* stage the span: 8-byte words, unaligned in HBM, aligned in LDS */
-	{
-		const u32 nw = (NL * (cb / 8) + 80) / 8;
-		for (u32 w = lane; w < nw; w += 64) {
-			const u64 pos = byte0 + 8 * w;
-			*(lu64 *)(stage + 8 * w) = pos + 8 <= in_n ? ld8(inp + pos) :
-						  load_in(inp, in_n, pos);
-		}
-		/* the staged words have arrived, and with them every store the
-		 * wave issued before this round (the rounds before, the sequential
-		 * decoder, a stored block): what this round reads back from the
-		 * output below `out0` is in memory */
-		if constexpr (COUNT)
-			wave_sync();	/* nothing was stored: the span in LDS is all the parse reads */
-		else
-			global_stores_visible();
-	}
+	stage_span(stage, inp, in_n, byte0, (NL * (cb / 8) + 80) & ~7u, lane);
+	if constexpr (COUNT)
+		wave_sync();	/* nothing was stored: the span in LDS is all the parse reads */
+	else
+		global_stores_visible();	/* (see stage_input()) */
 	const lu8 *span = stage;	/* the parse reads the staged copy */
 	const u32 bpos0 = (u32)bpos_abs & 7;	/* positions relative to the span */
 	struct par_long pll, plo;
@@ -1100,12 +1703,12 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	const u32 cend = bpos0 + (lane + 1) * cb;
 	u32 start = bpos0 + lane * cb, end = 0;
 	u32 nbytes = 0, ntok = 0;
-	[[maybe_unused]] s32 reach = 0;	/* COUNT: how far before the lane's first byte its matches reach */
+	s32 reach = 0;	/* COUNT: how far before the lane's first byte its matches reach */
 	bool eob = false, dirty = lane < NL;
 	u32 K = NL - 1;		/* last lane of the round */
 	bool has_eob = false;
 
-	PROF_SEC_DECL;
+	[[maybe_unused]] struct par_prof prof, *pf = &prof;
 	/* ---- sync passes ---- */
 	for (u32 pass = 0; pass < 64; pass++) {
 		struct par_bits b;
@@ -1113,96 +1716,40 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 		if (dirty) {
 			nbytes = 0;
 			ntok = 0;
-			if constexpr (COUNT)
-				reach = 0;
+			reach = 0;
 			eob = false;
 		}
-		/* (a lane runs while its position is inside its piece: tested
-		 * where the position moves, at the end of the body, not at its
-		 * top - that form went round once more, a whole step, only to
-		 * find every lane at its end) */
-		bool run = dirty && PB_POS(b) < cend;
+		const bool run = dirty && PB_POS(b) < cend;
+		struct piece_end e;
 		if (pass == 0) {
 			/* The first pass is a guess for every lane but lane 0, and
 			 * every lane parses again in the second: all it has to find
-			 * is where each lane's parse ENDS.  Its loop keeps nothing
-			 * else - no token words, lengths, distances, counts (the
-			 * compiler drops what computes them) - and lane 0 records
-			 * its tokens in the second pass with everybody else. */
-			while (__ballot(run)) {
-				PROF_SEC_ADD(1, 1);
-				pb_refill(&b, span);
-				const struct par_token t = par_decode(S, SH, &pll, &plo, b.buf, run, lmask, omask);
-				const u32 e1 = t.e1;
-				const bool two = t.kind == K_LIT && PB_POS(b) + t.used < cend &&
-						 (e1 & 0xC000) == K_LIT && (e1 & 15) != 0;
-				const u32 used = run ? t.used + (two ? e1 & 15 : 0) : 0;
-				b.buf >>= used;
-				b.cnt -= used;
-				eob = eob || (run && t.kind == K_EOB);
-				run = run && t.kind != K_EOB && PB_POS(b) < cend;
-			}
-		} else
-		while (__ballot(run)) {
-			PROF_SEC_ADD(1, 1);
-			pb_refill(&b, span);
-			struct par_token t = par_decode(S, SH, &pll, &plo, b.buf, run, lmask, omask);
-			/* A literal takes a second one with it when that one starts
-			 * inside the piece and its codeword is in the table: a pass
-			 * lasts as long as its lane with the most tokens, and those
-			 * are the lanes full of literals. */
-			const u32 e1 = t.e1;
-			const bool two = t.kind == K_LIT && PB_POS(b) + t.used < cend &&
-					 (e1 & 0xC000) == K_LIT && (e1 & 15) != 0;
-			if (run) {
-				u32 used = t.used;
-				if (t.kind == K_EOB) {
-					eob = true;
-					run = false;
-				} else {
-					if constexpr (COUNT) {
-						const s32 back = (s32)t.dist - (s32)nbytes;
-						reach = t.kind == K_LEN && back > reach ? back : reach;
-					} else {
-						/* row ntok of the lane-interleaved list: the 64
-						 * lanes of an iteration write one 256-byte row */
-						if (ntok < PAR_LANECAP)
-							tokS[TOK_AT(ntok, lane)] = t.kind == K_LEN ?
-								0x80000000u | t.length | (t.dist << 9) : t.lit;
-					}
-					nbytes += t.kind == K_LEN ? t.length : 1;
-					ntok++;
-					if (two) {
-						if constexpr (!COUNT) {
-							if (ntok < PAR_LANECAP)
-								tokS[TOK_AT(ntok, lane)] = (e1 >> 4) & 0xFF;
-						}
-						nbytes++;
-						ntok++;
-						used += e1 & 15;
-					}
-				}
-				b.buf >>= used;
-				b.cnt -= used;
-			}
-			run = run && PB_POS(b) < cend;
+			 * is where each lane's parse ENDS.  It keeps nothing else,
+			 * and lane 0 records its tokens in the second pass with
+			 * everybody else. */
+			e = parse_piece(S, SH, &pll, &plo, span, b, cend, run, false,
+					tok_none(), lmask, omask, pf);
+		} else if constexpr (COUNT) {
+			e = parse_piece(S, SH, &pll, &plo, span, b, cend, run, false,
+					tok_reach{ nbytes, ntok, reach }, lmask, omask, pf);
+		} else {
+			e = parse_piece(S, SH, &pll, &plo, span, b, cend, run, false,
+					tok_rows{ nbytes, ntok, tok, lane, true }, lmask, omask, pf);
 		}
+		eob = eob || e.eob;
 		if (dirty)
-			end = PB_POS(b);
-		/* DPP wave_shr:1 (lane 0 keeps its own value) */
-		u32 ns = __builtin_amdgcn_update_dpp(end, end, 0x138, 0xF, 0xF, false);
-		if (lane == 0)
-			ns = bpos0;
+			end = e.pos;
+		u32 ns = pass_starts(end, lane, bpos0);
 		dirty = (ns != start || pass == 0) && lane < NL;
 		/* (the block ends in lane 0's piece - a stream of tiny blocks,
 		 * programs/test_slow_decompression.c: only lane 0 parses again, to
 		 * record its tokens; nothing behind it belongs to the round) */
 		if (pass == 0 && bcast_lane(eob ? 1u : 0u, 0))
 			dirty = lane == 0;
-		const u64 dm = __ballot(dirty), em = __ballot(eob);
-		const u64 exact = dm ? (1ull << __builtin_ctzll(dm)) - 1 : ~0ull;
-		if (em & exact) {	/* end of block on the exact prefix */
-			K = (u32)__builtin_ctzll(em & exact);
+		const struct pass_masks m = pass_settle(dirty, eob);
+		const u64 dm = m.dirty;
+		if (m.eobs) {	/* end of block on the exact prefix */
+			K = (u32)__builtin_ctzll(m.eobs);
 			has_eob = true;
 			break;
 		}
@@ -1220,345 +1767,34 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 		}
 		start = ns;
 	}
-	PROF_SEC(0);
-	/* ---- counts -> offsets; clip the round to the token scratch ---- */
-	bool valid = lane <= K;
-	u32 tcnt = valid ? ntok : 0;
-	u32 tbase = wave_scan_incl(tcnt) - tcnt;
-	if constexpr (!COUNT) {
-		u64 vm = __ballot(valid);
-		const u64 over = __ballot(lane <= K && ntok > PAR_LANECAP);
-		if (over)	/* a lane whose row list overflowed, and all after it */
-			vm &= (1ull << __builtin_ctzll(over)) - 1;
-		const u32 nv = __builtin_popcountll(vm);	/* a prefix of lanes */
-		if (nv == 0)
-			return PAR_STOP;
-		if (nv - 1 < K) {
-			K = nv - 1;
-			has_eob = false;
-		}
-		valid = lane <= K;
-	}
-	const u32 bcnt = valid ? nbytes : 0;
-	const u32 obase = wave_scan_incl(bcnt) - bcnt;
-	const u32 total_tok = bcast_lane(tbase + tcnt, K);
-	const u64 total_bytes = bcast_lane(obase + bcnt, K);
-	if (total_bytes > out_avail - out0)
+	PAR_SEC(pf, 0);
+	struct par_sums R;
+	if (!round_offsets<!COUNT>(R, lane, ntok, nbytes, K, has_eob))
 		return PAR_STOP;
-	const u64 end_bits = bcast_lane(end, K) - bpos0 + bpos_abs;
+	if (R.total_bytes > out_avail - out0)
+		return PAR_STOP;
+	const u64 end_bits = bcast_lane(end, R.K) - bpos0 + bpos_abs;
 	if (end_bits > 8 * in_n)
 		return PAR_STOP;
 	if constexpr (COUNT) {
 		/* a distance that reaches before the stream (and its dictionary):
 		 * the sequential decoder reports it at its token */
-		if (__ballot(valid && reach > 0 && (u64)reach > out0 + obase + dlen))
+		if (__ballot(R.valid && reach > 0 && (u64)reach > out0 + R.obase + dlen))
 			return PAR_STOP;
-		*bpos_ret = end_bits;
-		*out_ret = out0 + total_bytes;
-		return has_eob ? PAR_EOB : PAR_OK;
 	} else {
-
-	/* Every lane's last parse started at its exact position, so the rows it
-	 * wrote then are its tokens: no further parse.  Token i of the round
-	 * (stream order) is row i - tbase[l] of the lane l whose range holds i;
-	 * the copy phase finds l per group (tok_fetch). */
-	lu8 *mk = stage + PAR_STAGE_BYTES;		/* [256] group token -> lane + 1 */
-	lu16 *tb = (lu16 *)(mk + 256);			/* [64] tbase per lane */
-	const u32 own_cnt = valid ? tcnt : 0;
-	tb[lane] = (u16)tbase;
-	wave_sync();
-	/* ---- execute the tokens: up to 256 tokens / PAR_GBYTES bytes a group ----
-	 * The copies of a group are resolved per output BYTE, not per token, 64
-	 * bytes (a slot) at a time and in output order: byte b is a literal, or
-	 * a copy of the byte dist before it.  That byte is final - in the LDS
-	 * mirror of the recent output, or in the output itself when it is further
-	 * back than the mirror reaches - unless it lies in the same slot; copies
-	 * inside a slot (runs, short periods) are settled by pointer jumping over
-	 * the 64 lanes, whatever the shape of the dependencies.  The bytes meet
-	 * in the mirror; the output is written from there in whole words once
-	 * per group (flush_ring). */
-	{
-		lu32 *tk = (lu32 *)stage;			/* [256] the group's tokens */
-		/* (a group's tokens are numbered 0 .. 255 and its first byte starts
-		 * token 0, so a cleared entry and "token 0" say the same) */
-		lu8 *R = (lu8 *)((lu32 *)stage + 256);		/* [PAR_GBYTES] byte -> token of the group */
-		gu8 *gout = (gu8 *)outp;
-		u64 gbase = out0;
-		u64 flushed = out0;	/* output below this is in memory */
-		u64 safe_hi = out0;	/* ... and below this its stores have been waited for */
-		u32 g = 0;		/* a multiple of 4: 16-byte token loads */
-		/* four consecutive tokens per lane; the next group's are requested
-		 * as soon as this group's extent is known, so their trip to the
-		 * scratch runs beside the group's LDS work */
-		uint4 tq_next = tok_fetch(tokS, mk, tb, tbase, own_cnt, 0, total_tok, lane);
-		while (g < total_tok) {
-			const u32 ti0 = g + 4 * lane;
-			const uint4 tq = tq_next;
-			const u32 tw4[4] = { tq.x, tq.y, tq.z, tq.w };
-			u32 len4[4], lsum = 0;
-#pragma unroll
-			for (u32 j = 0; j < 4; j++) {
-				len4[j] = ti0 + j >= total_tok ? 0 :
-					  (tw4[j] >> 31) ? (tw4[j] & 0x1FF) : 1;
-				lsum += len4[j];
-			}
-			const u32 incl0 = wave_scan_incl(lsum);
-			/* the lanes whose tokens fit: a prefix */
-			const bool fits = ti0 < total_tok && incl0 <= PAR_GBYTES;
-			const u32 cnt = __builtin_popcountll(__ballot(fits));
-			const u32 gtot = bcast_lane(incl0, cnt - 1);
-			if (g + 4 * cnt < total_tok)
-				tq_next = tok_fetch(tokS, mk, tb, tbase, own_cnt,
-						    g + 4 * cnt, total_tok, lane);
-			/* byte -> token: every token drops its number at its first
-			 * byte, a running maximum over the bytes spreads it */
-			/* (the whole map is cleared with three 16-byte stores per lane
-			 * - 2 x 1024 + 128 bytes - instead of a loop of 2-byte stores
-			 * over the group's bytes: 12 rounds of 8 instructions) */
-			{
-				static_assert(PAR_GBYTES <= PAR_MAP_CLEAR && PAR_MAP_CLEAR == 2176 &&
-					      PAR_GBYTES + 256 <= PAR_RW && PAR_GBYTES >= 4 * 258,
-					      "two full wave stores and one of eight lanes");
-				const uint4 z = make_uint4(0, 0, 0, 0);
-				AS3 uint4 *R16 = (AS3 uint4 *)R;
-				R16[lane] = z;
-				R16[64 + lane] = z;
-				if (lane < 8)
-					R16[128 + lane] = z;
-			}
-			wave_sync();
-			if (lane < cnt) {
-				u32 o = incl0 - lsum;
-				*(AS3 uint4 *)&tk[4 * lane] = tq;	/* the lane's four token words */
-#pragma unroll
-				for (u32 j = 0; j < 4; j++) {
-					if (len4[j])
-						R[o] = (u8)(4 * lane + j);
-					o += len4[j];
-				}
-			}
-			wave_sync();
-			/* a source `rel` bytes before the group is still in the mirror
-			 * when the group's own bytes have not overwritten it and the
-			 * mirror has been kept that far back */
-			const u32 gb = (u32)gbase;
-			u32 ring_rel = PAR_RW - gtot;
-			if (gbase - ring_lo < ring_rel)
-				ring_rel = (u32)(gbase - ring_lo);
-			/* sources further back come from the output itself: base + a
-			 * non-negative 32-bit lane offset (distances are <= 32768) */
-			const gu8 *gfar = (const gu8 *)((uintptr_t)gout + gbase - 32768);
-			/* a distance that reaches back before the stream: possible only
-			 * in the first 32 KiB */
-			const u32 back_max = gbase < 32768 ? (u32)gbase : 32768u;
-			u64 badm = 0;	/* lanes whose distance reaches back before the stream */
-			/* The slots (64 bytes each) are resolved in order, so the
-			 * source of a byte is final in the mirror when its slot is
-			 * reached, unless it lies in the same slot.  The token lookup
-			 * of SB slots is done together (its LDS reads and the reads
-			 * from the output are independent of the mirror); then every
-			 * slot reads its sources, settles the copies inside itself
-			 * (pointer jumping over the 64 lanes, only when there are
-			 * any) and writes its bytes. */
-			enum { SB = 4 };
-			u32 carry = 0;
-			PROF_SEC(2);
-			PROF_SEC_ADD(6, 1);
-			for (u32 s0 = 0; s0 < gtot; s0 += 64 * SB) {
-				u32 own[SB], vfar[SB];
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					/* (an index past the group reads its last entry and is
-					 * masked: as `bi < gtot ? R[bi] : 0` each of the four
-					 * reads sat in an EXEC section of its own with its own
-					 * wait) */
-					const u32 bi = s0 + 64 * k + lane;
-					const u32 r = R[bi < gtot ? bi : gtot - 1];
-					own[k] = bi < gtot ? r : 0;
-				}
-#define DPP_MAX(k, ctrl, rm, bc)                                               \
-	do {                                                                   \
-		u32 t_ = __builtin_amdgcn_update_dpp(0, own[k], ctrl, rm, 0xF, bc); \
-		own[k] = own[k] > t_ ? own[k] : t_;                            \
-	} while (0)
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x111, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x112, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x114, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x118, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x142, 0xA, false);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x143, 0xC, false);
-#undef DPP_MAX
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					own[k] = own[k] > carry ? own[k] : carry;
-					carry = bcast_lane(own[k], 63);
-				}
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					/* (the group's first byte starts token 0 and the running
-					 * maximum carries on) */
-					const u32 bi = s0 + 64 * k + lane;
-					const u32 w = tk[own[k]];	/* token word */
-					own[k] = bi < gtot ? w : 0;
-				}
-				/* bytes whose source is older than the mirror.  The tests are
-				 * one ballot per compare, combined on the scalar unit (a
-				 * ballot of a compound predicate goes through a 0 / 1 detour
-				 * in a vector register), and the four slots share ONE
-				 * section: nothing of it runs when the batch has no such byte */
-				u64 mfar[SB], anyfar = 0, anyneed = 0, tfar = 0;
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 bi = s0 + 64 * k + lane, tw = own[k];
-					const u32 dist = (tw >> 9) & 0xFFFF;
-					const u32 back = dist - bi;	/* bytes in front of the group (when dist > bi) */
-					const u64 before = __ballot((s32)tw < 0) & __ballot(dist > bi);
-					const u64 toofar = before & __ballot(back > back_max);
-					mfar[k] = before & ~toofar & __ballot(back > ring_rel);
-					tfar |= toofar;
-					anyfar |= mfar[k];
-					/* a source at or above safe_hi was stored by this wave
-					 * after its last wait: see below */
-					anyneed |= mfar[k] & __ballot(back <= (u32)(gbase - safe_hi));
-					vfar[k] = 0x100;	/* not a byte: no far source */
-				}
-				if (anyfar) {
-					/* The source may be a byte another lane of this wave
-					 * stored earlier in THIS round (flush_ring); everything
-					 * below safe_hi was stored before a wait.  Only a source
-					 * at or above it - rare: it must be older than the mirror
-					 * and younger than the last wait - makes the wave wait for
-					 * its stores (and for the token rows requested ahead)
-					 * before it loads. */
-					if (anyneed) {
-						global_stores_visible();
-						safe_hi = flushed;
-					}
-#pragma unroll
-					for (u32 k = 0; k < SB; k++) {
-						const u32 bi = s0 + 64 * k + lane;
-						const u32 dist = (own[k] >> 9) & 0xFFFF;
-						if (lane_bit(mfar[k]))
-							vfar[k] = gfar[bi + 32768u - dist];
-					}
-				}
-				if (tfar && dlen) {
-					/* a preset dictionary: sources up to dlen bytes in
-					 * front of the stream are its last bytes */
-					u64 still = 0;
-#pragma unroll
-					for (u32 k = 0; k < SB; k++) {
-						const u32 bi = s0 + 64 * k + lane, tw = own[k];
-						const u32 dist = (tw >> 9) & 0xFFFF;
-						const u32 back = dist - bi;
-						const u64 tf = __ballot((s32)tw < 0) & __ballot(dist > bi) &
-							       __ballot(back > back_max);
-						const u64 ind = tf & __ballot(back - gb <= dlen);
-						if (lane_bit(ind))
-							vfar[k] = dict[dlen - (back - gb)];
-						still |= tf & ~ind;
-					}
-					tfar = still;
-				}
-				badm |= tfar;
-				/* copies inside a slot: where each lane's byte finally comes
-				 * from.  That depends on the tokens alone, so the SB slots'
-				 * pointer chains are jumped together (their latencies
-				 * overlap) before the slots' bytes are settled in order. */
-				u32 root[SB];
-				bool any_intra = false;
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 tw = own[k], dist = (tw >> 9) & 0xFFFF;
-					const bool intra = (tw >> 31) && dist <= lane;
-					root[k] = intra ? lane - dist : lane;
-					any_intra |= intra;
-				}
-				if (__ballot(any_intra)) {
-					for (;;) {
-						/* the four permutes go out together, one wait (as
-						 * `pp = permute; ch |= pp != root` per slot each
-						 * compare waited for its own permute) */
-						u32 pp[SB];
-#pragma unroll
-						for (u32 k = 0; k < SB; k++)
-							pp[k] = (u32)__builtin_amdgcn_ds_bpermute(
-									(int)(root[k] << 2), (int)root[k]);
-						asm volatile("" :: "v"(pp[0]), "v"(pp[1]), "v"(pp[2]), "v"(pp[3]));
-						u64 chm = 0;
-#pragma unroll
-						for (u32 k = 0; k < SB; k++) {
-							chm |= __ballot(pp[k] != root[k]);
-							root[k] = pp[k];
-						}
-						if (!chm)
-							break;
-					}
-				}
-#if defined(LDA_PROFILE) && defined(LDA_PROFILE_COUNTS)
-				/* the wait for the far sources on its own (the profile build
-				 * only: it also waits for the token rows requested ahead) */
-				PROF_SEC(3);
-				asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-				PROF_SEC(4);
-				PROF_SEC_ADD(7, 1);
-#endif
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 bi = s0 + 64 * k + lane, tw = own[k];
-					const u32 dist = (tw >> 9) & 0xFFFF;
-					const bool match = (tw >> 31) != 0;	/* false past gtot */
-					/* every lane reads the mirror (the index is always
-					 * inside it); matches from outside the slot use it */
-					u32 wv = win[(gb + bi - dist) & (PAR_RW - 1)];
-					/* (kept out of the branches below: as part of one the
-					 * read, and its wait, sat inside an EXEC section) */
-					asm volatile("" : "+v"(wv));
-					u32 v = match ? wv : tw & 0xFF;
-					v = vfar[k] < 0x100 ? vfar[k] : v;
-					if (__ballot(root[k] != lane))
-						v = (u32)__builtin_amdgcn_ds_bpermute((int)(root[k] << 2), (int)v);
-					if (bi < gtot)
-						win[(gb + bi) & (PAR_RW - 1)] = (u8)v;
-				}
-			}
-			wave_sync();
-			PROF_SEC(3);
-			if (badm) {
-				/* Invalid stream.  The sequential decoder takes the
-				 * round's bits again and reports it at the token where
-				 * it belongs; what the earlier groups wrote is what it
-				 * will write again, and the mirror is not used across
-				 * an abandoned round. */
-				return PAR_STOP;
-			}
-			gbase += gtot;
-			flushed = flush_ring(gout, win, flushed, gbase, lane);
-			PROF_SEC(5);
-			g += 4 * cnt;
-		}
-		/* the last bytes (less than a word) */
-		if (flushed + lane < gbase)
-			gout[flushed + lane] = win[(u32)(flushed + lane) & (PAR_RW - 1)];
-		wave_sync();
+		const struct copy_bytes X = { (gu8 *)outp, dict, dlen };
+		/* Invalid stream.  The sequential decoder takes the round's bits
+		 * again and reports it at the token where it belongs; what the
+		 * earlier groups wrote is what it will write again, and the mirror
+		 * is not used across an abandoned round. */
+		if (copy_phase(X, tok, win, stage, ring_lo, lane, out0, R.tbase,
+			       R.valid ? R.tcnt : 0, R.total_tok, pf))
+			return PAR_STOP;
+		PAR_SEC_FLUSH8(pf, 16);
 	}
-	PROF_SEC_FLUSH8(16);
 	*bpos_ret = end_bits;
-	*out_ret = out0 + total_bytes;
-	return has_eob ? PAR_EOB : PAR_OK;
-	}	/* !COUNT */
+	*out_ret = out0 + R.total_bytes;
+	return R.has_eob ? PAR_EOB : PAR_OK;
 }
 
 /*

@@ -106,14 +106,54 @@ flush_ring16(u16 *__restrict__ sym, const lsym *win, u64 flushed, u64 end, u32 l
 }
 
 /*
- * One round of a chunk: par_round() of inflate_kernel.hip with
+ * What the copy phase (copy_phase<X>() of inflate_kernel.hip) writes here:
+ * 16-bit symbols at absolute output positions.  A source in front of the
+ * chunk's first byte becomes a MARKER 0x8000 | index into the 32 KiB in front
+ * of the chunk, and the round goes on; a distance that reaches back before
+ * the stream's first byte is reported when the round is done.
+ */
+struct copy_syms {
+	typedef u16 elem;
+	typedef const u16 *far_t;
+	enum { NONE = 0x10000, STOPS = 0 };
+	u16 *__restrict__ sym;
+	u64 chunk_abs;
+	/* bytes of this chunk in front of the group */
+	__device__ __forceinline__ u32 front(u64 gbase) const
+	{
+		const u64 in_chunk = gbase - chunk_abs;
+		return in_chunk < 0x10000 ? (u32)in_chunk : 0x10000u;
+	}
+	__device__ __forceinline__ far_t far_base(u64 gbase) const
+	{
+		return (const u16 *)((uintptr_t)sym + 2 * (gbase - 32768));
+	}
+	__device__ __forceinline__ bool fronts(void) const { return true; }
+	__device__ __forceinline__ u32
+	in_front(u32 v, u64 tf, u32 back, u64 gbase, u32 back_max, u64 *bad) const
+	{
+		const u32 in_stream = gbase < 0x10000 ? (u32)gbase : 0x10000u;
+		if (lane_bit(tf))
+			v = 0x8000u | (32768u - (back - back_max));
+		*bad |= tf & __ballot(back > in_stream);
+		return v;
+	}
+	__device__ __forceinline__ void store(u64 pos, u32 v) const { sym[pos] = (u16)v; }
+	__device__ __forceinline__ u64 flush(const lsym *win, u64 flushed, u64 end, u32 lane) const
+	{
+		return flush_ring16(sym, win, flushed, end, lane);
+	}
+};
+
+/*
+ * One round of a chunk: the stages of inflate_kernel.hip's round with
  *   - a LIMIT: the round (and with it the chunk) ends at the first token
  *     boundary at or after bit `limit_abs`;
  *   - WARM rounds, whose lane 0 starts at a guess like every other lane and
  *     which run over end-of-block symbols (they only look for the boundary);
+ *   - no light first pass: lane 0 records its tokens in pass 0;
  *   - MODE SM_COUNT: no tokens kept, nothing executed, bytes counted;
- *   - MODE SM_MARK: tokens executed into 16-bit symbols at absolute output
- *     positions; a source in front of `chunk_abs` becomes a marker.
+ *   - MODE SM_MARK: tokens executed into 16-bit symbols (struct copy_syms).
  * *bad_ret is set when a distance reaches back before the stream's first byte.
  */
 template <int MODE> static __device__ u32
@@ -126,7 +166,6 @@ chunk_round(const u8 *inp, u64 in_n, const slds_t *S, const shlds_t *SH,
 	const u64 byte0 = bpos_abs >> 3;
 	if (byte0 + 64 > in_n)
 		return PAR_STOP;
-	u32 *__restrict__ tokS = tok;
 	const u32 cb = in_n - byte0 >= 64 * (PAR_CB / 8) ? PAR_CB : 256u;
 	const u64 room = (in_n - byte0 + cb / 8 - 1) / (cb / 8);
 	u32 NL = room < 64 ? (u32)room : 64;
@@ -139,15 +178,7 @@ chunk_round(const u8 *inp, u64 in_n, const slds_t *S, const shlds_t *SH,
 		const u32 need = lim > bpos0 ? (lim - bpos0 + cb - 1) / cb : 1;
 		NL = need < NL ? need : NL;
 	}
-	{
-		const u32 nw = (NL * (cb / 8) + 80) / 8;
-		for (u32 w = lane; w < nw; w += 64) {
-			const u64 pos = byte0 + 8 * w;
-			*(lu64 *)(stage + 8 * w) = pos + 8 <= in_n ? ld8(inp + pos) :
-						  load_in(inp, in_n, pos);
-		}
-		global_stores_visible();	/* as par_round(): the stores of the rounds before */
-	}
+	stage_input(stage, inp, in_n, byte0, (NL * (cb / 8) + 80) & ~7u, lane);
 	const lu8 *span = stage;
 	struct par_long pll, plo;
 	par_long_init<LIT_TB + 1>(&pll, &S->lit, LIT_TB + 1);
@@ -173,56 +204,25 @@ chunk_round(const u8 *inp, u64 in_n, const slds_t *S, const shlds_t *SH,
 
 	for (u32 pass = 0; pass < 64; pass++) {
 		struct par_bits b;
-		bool run = dirty;
-		const bool keep = MODE == SM_MARK && (pass != 0 || lane == 0);
 		pb_init(&b, span, start);
 		if (dirty) {
 			nbytes = 0;
 			ntok = 0;
 			eob = false;
 		}
-		while (__ballot(run)) {
-			run = run && PB_POS(b) < cend;
-			pb_refill(&b, span);
-			struct par_token t = par_decode(S, SH, &pll, &plo, b.buf);
-			const u32 e1 = t.e1;
-			const bool two = t.kind == K_LIT && PB_POS(b) + t.used < cend &&
-					 (e1 & 0xC000) == K_LIT && (e1 & 15) != 0;
-			if (run) {
-				u32 used = t.used;
-				if (t.kind == K_EOB) {
-					if (!warm) {
-						eob = true;
-						run = false;
-					}
-				} else {
-					if (keep && ntok < PAR_LANECAP)
-						tokS[TOK_AT(ntok, lane)] = t.kind == K_LEN ?
-							0x80000000u | t.length | (t.dist << 9) : t.lit;
-					nbytes += t.kind == K_LEN ? t.length : 1;
-					ntok++;
-					if (two) {
-						if (keep && ntok < PAR_LANECAP)
-							tokS[TOK_AT(ntok, lane)] = (e1 >> 4) & 0xFF;
-						nbytes++;
-						ntok++;
-						used += e1 & 15;
-					}
-				}
-				b.buf >>= used;
-				b.cnt -= used;
-			}
-		}
+		const struct tok_rows T = { nbytes, ntok, tok, lane,
+			MODE == SM_MARK && (pass != 0 || lane == 0) };
+		const struct piece_end e = parse_piece(S, SH, &pll, &plo, span, b, cend,
+						       dirty && PB_POS(b) < cend, warm, T);
+		eob = eob || e.eob;
 		if (dirty)
-			end = PB_POS(b);
-		u32 ns = __builtin_amdgcn_update_dpp(end, end, 0x138, 0xF, 0xF, false);
-		if (lane == 0)
-			ns = bpos0;
+			end = e.pos;
+		u32 ns = pass_starts(end, lane, bpos0);
 		dirty = (ns != start || (pass == 0 && lane != 0)) && lane < NL;
-		const u64 dm = __ballot(dirty), em = __ballot(eob);
-		const u64 exact = dm ? (1ull << __builtin_ctzll(dm)) - 1 : ~0ull;
-		if (em & exact) {
-			K = (u32)__builtin_ctzll(em & exact);
+		const struct pass_masks m = pass_settle(dirty, eob);
+		const u64 dm = m.dirty;
+		if (m.eobs) {
+			K = (u32)__builtin_ctzll(m.eobs);
 			has_eob = true;
 			break;
 		}
@@ -252,218 +252,21 @@ chunk_round(const u8 *inp, u64 in_n, const slds_t *S, const shlds_t *SH,
 		}
 		start = ns;
 	}
-	bool valid = lane <= K;
-	u32 tcnt = valid ? ntok : 0;
-	u32 tbase = wave_scan_incl(tcnt) - tcnt;
-	{
-		u64 vm = __ballot(valid);
-		const u64 over = __ballot(lane <= K && ntok > PAR_LANECAP);
-		if (over)
-			vm &= (1ull << __builtin_ctzll(over)) - 1;
-		const u32 nv = __builtin_popcountll(vm);
-		if (nv == 0)
-			return PAR_STOP;
-		if (nv - 1 < K) {
-			K = nv - 1;
-			has_eob = false;
-		}
-		valid = lane <= K;
-	}
-	const u32 bcnt = valid ? nbytes : 0;
-	const u32 obase = wave_scan_incl(bcnt) - bcnt;
-	const u32 total_tok = bcast_lane(tbase + tcnt, K);
-	const u64 total_bytes = bcast_lane(obase + bcnt, K);
-	const u64 end_bits = (u64)bcast_lane(end, K) + 8 * byte0;
+	struct par_sums R;
+	if (!round_offsets<true>(R, lane, ntok, nbytes, K, has_eob))
+		return PAR_STOP;
+	const u64 end_bits = (u64)bcast_lane(end, R.K) + 8 * byte0;
 	if (end_bits > 8 * in_n)
 		return PAR_STOP;
 	*bpos_ret = end_bits;
-	*out_ret = out0 + total_bytes;
-	if (MODE != SM_MARK || warm)
-		return has_eob ? PAR_EOB : PAR_OK;
-
-	lu8 *mk = stage + PAR_STAGE_BYTES;
-	lu16 *tb = (lu16 *)(mk + 256);
-	const u32 own_cnt = valid ? tcnt : 0;
-	tb[lane] = (u16)tbase;
-	wave_sync();
-	{
-		lu32 *tk = (lu32 *)stage;
-		lu16 *R = (lu16 *)((lu32 *)stage + 256);
-		u64 gbase = out0;
-		u64 flushed = out0;
-		u64 safe_hi = out0;	/* symbols below this were stored before a wait (stage_input) */
-		u32 g = 0;
-		bool bad = false;
-		uint4 tq_next = tok_fetch(tokS, mk, tb, tbase, own_cnt, 0, total_tok, lane);
-		while (g < total_tok) {
-			const u32 ti0 = g + 4 * lane;
-			const uint4 tq = tq_next;
-			const u32 tw4[4] = { tq.x, tq.y, tq.z, tq.w };
-			u32 len4[4], lsum = 0;
-#pragma unroll
-			for (u32 j = 0; j < 4; j++) {
-				len4[j] = ti0 + j >= total_tok ? 0 :
-					  (tw4[j] >> 31) ? (tw4[j] & 0x1FF) : 1;
-				lsum += len4[j];
-			}
-			const u32 incl0 = wave_scan_incl(lsum);
-			const bool fits = ti0 < total_tok && incl0 <= PAR_GBYTES;
-			const u32 cnt = __builtin_popcountll(__ballot(fits));
-			const u32 gtot = bcast_lane(incl0, cnt - 1);
-			if (g + 4 * cnt < total_tok)
-				tq_next = tok_fetch(tokS, mk, tb, tbase, own_cnt,
-						    g + 4 * cnt, total_tok, lane);
-			for (u32 b0 = lane; b0 < gtot; b0 += 64)
-				R[b0] = 0;
-			wave_sync();
-			if (lane < cnt) {
-				u32 o = incl0 - lsum;
-#pragma unroll
-				for (u32 j = 0; j < 4; j++) {
-					tk[4 * lane + j] = tw4[j];
-					if (len4[j])
-						R[o] = (u16)(4 * lane + j + 1);
-					o += len4[j];
-				}
-			}
-			wave_sync();
-			const u32 gb = (u32)gbase;
-			u32 ring_rel = PAR_RW - gtot;
-			if (gbase - ring_lo < ring_rel)
-				ring_rel = (u32)(gbase - ring_lo);
-			/* bytes of this chunk in front of the group (a source further
-			 * back is in front of the chunk: a marker), and of the stream */
-			const u64 in_chunk64 = gbase - chunk_abs;
-			const u32 in_chunk = in_chunk64 < 0x10000 ? (u32)in_chunk64 : 0x10000u;
-			const u32 in_stream = gbase < 0x10000 ? (u32)gbase : 0x10000u;
-			enum { SB = 4 };
-			u32 carry = 0;
-			for (u32 s0 = 0; s0 < gtot; s0 += 64 * SB) {
-				u32 own[SB], vfar[SB];
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 bi = s0 + 64 * k + lane;
-					own[k] = bi < gtot ? R[bi] : 0;
-				}
-#define DPP_MAX(k, ctrl, rm, bc)                                               \
-	do {                                                                   \
-		u32 t_ = __builtin_amdgcn_update_dpp(0, own[k], ctrl, rm, 0xF, bc); \
-		own[k] = own[k] > t_ ? own[k] : t_;                            \
-	} while (0)
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x111, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x112, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x114, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x118, 0xF, true);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x142, 0xA, false);
-#pragma unroll
-				for (u32 k = 0; k < SB; k++)
-					DPP_MAX(k, 0x143, 0xC, false);
-#undef DPP_MAX
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					own[k] = own[k] > carry ? own[k] : carry;
-					carry = bcast_lane(own[k], 63);
-				}
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 bi = s0 + 64 * k + lane;
-					own[k] = bi < gtot ? tk[own[k] - 1] : 0;
-				}
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 bi = s0 + 64 * k + lane, tw = own[k];
-					const u32 dist = (tw >> 9) & 0xFFFF;
-					const bool before = (tw >> 31) && dist > bi;
-					const u32 back = dist - bi;	/* bytes in front of the group */
-					const bool outside = before && back > in_chunk;
-					const bool far = before && !outside && back > ring_rel;
-					bad |= before && back > in_stream;
-					vfar[k] = 0x10000;	/* not a symbol: no far source */
-					if (outside)
-						vfar[k] = 0x8000u | (32768u - (back - in_chunk));
-					if (__ballot(far)) {
-						/* a symbol stored in this round, after the last
-						 * wait: see par_round() */
-						if (__ballot(far && back <= (u32)(gbase - safe_hi))) {
-							global_stores_visible();
-							safe_hi = flushed;
-						}
-						if (far)
-							vfar[k] = sym[gbase - back];
-					}
-				}
-				u32 root[SB];
-				bool any_intra = false;
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 tw = own[k], dist = (tw >> 9) & 0xFFFF;
-					const bool intra = (tw >> 31) && dist <= lane;
-					root[k] = intra ? lane - dist : lane;
-					any_intra |= intra;
-				}
-				if (__ballot(any_intra)) {
-					for (;;) {
-						bool ch = false;
-#pragma unroll
-						for (u32 k = 0; k < SB; k++) {
-							const u32 pp = (u32)__builtin_amdgcn_ds_bpermute(
-									(int)(root[k] << 2), (int)root[k]);
-							ch |= pp != root[k];
-							root[k] = pp;
-						}
-						if (!__ballot(ch))
-							break;
-					}
-				}
-#pragma unroll
-				for (u32 k = 0; k < SB; k++) {
-					const u32 bi = s0 + 64 * k + lane, tw = own[k];
-					const u32 dist = (tw >> 9) & 0xFFFF;
-					const bool match = (tw >> 31) != 0;
-					const u32 wv = win[(gb + bi - dist) & (PAR_RW - 1)];
-					u32 v = match ? wv : tw & 0xFF;
-					v = vfar[k] < 0x10000 ? vfar[k] : v;
-					if (__ballot(root[k] != lane))
-						v = (u32)__builtin_amdgcn_ds_bpermute((int)(root[k] << 2), (int)v);
-					if (bi < gtot)
-						win[(gb + bi) & (PAR_RW - 1)] = (u16)v;
-				}
-			}
-			wave_sync();
-			gbase += gtot;
-			flushed = flush_ring16(sym, win, flushed, gbase, lane);
-			g += 4 * cnt;
-		}
-		if (flushed < gbase && lane == 0)
-			sym[flushed] = win[(u32)flushed & (PAR_RW - 1)];
-		wave_sync();
-		if (__ballot(bad))
+	*out_ret = out0 + R.total_bytes;
+	if constexpr (MODE == SM_MARK) {
+		const struct copy_syms X = { sym, chunk_abs };
+		if (!warm && copy_phase(X, tok, win, stage, ring_lo, lane, out0, R.tbase,
+					R.valid ? R.tcnt : 0, R.total_tok))
 			*bad_ret = 1;
 	}
-	return has_eob ? PAR_EOB : PAR_OK;
-}
-
-/* stage `nbytes` (a multiple of 8) of input from byte0 on, zeros past the end */
-static __device__ __forceinline__ void
-stage_input(lu8 *stage, const u8 *inp, u64 in_n, u64 byte0, u32 nbytes, u32 lane)
-{
-	for (u32 w = lane; w < nbytes / 8; w += 64) {
-		const u64 pos = byte0 + 8 * w;
-		*(lu64 *)(stage + 8 * w) = pos + 8 <= in_n ? ld8(inp + pos) :
-					  load_in(inp, in_n, pos);
-	}
-	/* ... and every store of the rounds before has completed (par_round()) */
-	global_stores_visible();
+	return R.has_eob ? PAR_EOB : PAR_OK;
 }
 
 /*
@@ -977,33 +780,12 @@ phase_count(const struct lda_stream_chunk *__restrict__ cd, struct lda_stream_re
 	for (u32 ph = 0; ph < K; ph++) {
 		struct par_bits b;
 		u32 nbytes = 0;
-		bool eob = false;
 		pb_init(&b, stage, ps + ph);
-		bool run = mine && PB_POS(b) < cend;
-		while (__ballot(run)) {
-			pb_refill(&b, stage);
-			const struct par_token t = par_decode(S, SH, &pll, &plo, b.buf, run);
-			const u32 e1 = t.e1;
-			const bool two = t.kind == K_LIT && PB_POS(b) + t.used < cend &&
-					 (e1 & 0xC000) == K_LIT && (e1 & 15) != 0;
-			if (run) {
-				u32 used = t.used;
-				if (t.kind == K_EOB) {
-					eob = true;
-					run = false;
-				} else {
-					nbytes += t.kind == K_LEN ? t.length : 1;
-					if (two) {
-						nbytes++;
-						used += e1 & 15;
-					}
-				}
-				b.buf >>= used;
-				b.cnt -= used;
-			}
-			run = run && PB_POS(b) < cend;
-		}
-		const u32 pos = PB_POS(b);
+		const struct piece_end e = parse_piece(S, SH, &pll, &plo, stage, b, cend,
+						       mine && PB_POS(b) < cend, false,
+						       tok_bytes{ nbytes });
+		const bool eob = e.eob;
+		const u32 pos = e.pos;
 		u32 c = 0;	/* the chain goes on at `pos` */
 		if (eob) {
 			/* the chunk ends with its block when that is the stream's last or
@@ -1065,34 +847,13 @@ phase_count(const struct lda_stream_chunk *__restrict__ cd, struct lda_stream_re
 			break;
 		struct par_bits b;
 		u32 nbytes = 0;
-		bool eob = false;
 		pb_init(&b, stage, need ? pos : 0);
-		bool run = need && PB_POS(b) < pcend;
-		while (__ballot(run)) {
-			pb_refill(&b, stage);
-			const struct par_token t = par_decode(S, SH, &pll, &plo, b.buf, run);
-			const u32 e1 = t.e1;
-			const bool two = t.kind == K_LIT && PB_POS(b) + t.used < pcend &&
-					 (e1 & 0xC000) == K_LIT && (e1 & 15) != 0;
-			if (run) {
-				u32 used = t.used;
-				if (t.kind == K_EOB) {
-					eob = true;
-					run = false;
-				} else {
-					nbytes += t.kind == K_LEN ? t.length : 1;
-					if (two) {
-						nbytes++;
-						used += e1 & 15;
-					}
-				}
-				b.buf >>= used;
-				b.cnt -= used;
-			}
-			run = run && PB_POS(b) < pcend;
-		}
+		const struct piece_end e = parse_piece(S, SH, &pll, &plo, stage, b, pcend,
+						       need && PB_POS(b) < pcend, false,
+						       tok_bytes{ nbytes });
+		const bool eob = e.eob;
 		if (need) {
-			const u32 np = PB_POS(b);
+			const u32 np = e.pos;
 			total += nbytes;
 			if (eob ? final_blk || np >= lim : last) {
 				endv = np | (eob ? 0x80000000u : 0);
