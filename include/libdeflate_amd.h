@@ -680,6 +680,52 @@ libdeflate_amd_bgzf_compress(struct libdeflate_compressor *compressor,
 			     uint64_t *index, size_t index_avail, unsigned flags);
 
 /*
+ * ONE ordinary stream - raw DEFLATE, zlib or .gz, what gzip -d, zlib or a PNG
+ * reader take - from ONE device buffer d_in of in_nbytes bytes, for callers
+ * whose data is in device memory already and who would otherwise copy it to
+ * the host for libdeflate_<format>_compress.  format: LIBDEFLATE_AMD_DEFLATE,
+ * _ZLIB or _GZIP (BGZF has its own writer above).
+ *
+ * The bytes written to d_out and the size written to d_out_nbytes[0] are,
+ * byte for byte, what libdeflate_<format>_compress() of this build returns
+ * for the same bytes, level and LDA_* switches, for every in_nbytes including
+ * 0: an input of 128 KiB or more at level 1 and above is cut into segments of
+ * 16, 32 or 64 KiB that are compressed side by side, each primed with the
+ * tail of its predecessor, anything else is one chunk of the batch.  So
+ * libdeflate_<format>_compress_bound(in_nbytes) is enough room wherever it is
+ * for that call, and there is no bound function of its own.
+ *
+ * d_in, d_out and d_out_nbytes are device pointers on the object's device;
+ * d_out must not overlap d_in.  The call only ENQUEUES on `stream` and
+ * returns: nothing is copied to or from the host and nothing is waited for -
+ * the descriptors, the checksum of the whole buffer (combined on the device
+ * from the segments' checksums), the container's header and footer and the
+ * size are all written by kernels.  Only the object's scratch growing, on its
+ * first call or a larger one, waits for the device, as every other growth of
+ * an object's scratch does.  d_out_nbytes[0] = 0 when the stream does not fit
+ * out_avail (the rule of libdeflate.h:73-74): then no byte is written at or
+ * past d_out + out_avail, and what lies below it is undefined.
+ *
+ * The arguments are checked before any device work: LIBDEFLATE_AMD_BAD_ARG,
+ * with the reason in libdeflate_amd_last_error(), for a NULL object, a NULL
+ * d_in with in_nbytes != 0, a NULL d_out or d_out_nbytes, another format, or
+ * an out_avail that cannot hold the container's header and footer and one
+ * byte more.  Inputs of 4 GiB and more work as in the host call (64 KiB
+ * segments, 64-bit offsets, gzip's ISIZE modulo 2^32), limited by the scratch
+ * alone: LIBDEFLATE_AMD_OOM.  The scratch belongs to the object and goes with
+ * it: per segment a slot of compress_bound(segment) + 32 bytes, seven u64 of
+ * descriptors, its checksum and its offset.  The rule for objects and streams
+ * above holds unchanged.  Preset dictionaries are out of scope:
+ * libdeflate_amd_compress_dict stays the only large-buffer form with one.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_compress_large_batch(struct libdeflate_compressor *compressor,
+				    int format,
+				    const void *d_in, size_t in_nbytes,
+				    void *d_out, size_t out_avail,
+				    uint64_t *d_out_nbytes, void *stream);
+
+/*
  * Reading a BGZF file.  What a member is (htslib's check_header rule): the
  * bytes 1f 8b 08 04, XLEN = 6 at bytes 10..11, the subfield 42 43 02 00 at
  * bytes 12..15 and BSIZE at 16..17; MTIME, XFL and OS are free.  Its size is

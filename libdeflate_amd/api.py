@@ -93,6 +93,20 @@ class Compressor:
             index.data_ptr() if index is not None else None,
             0 if eof else binding.BGZF_NO_EOF, _stream_ptr(stream)), "bgzf_compress_batch")
 
+    def compress_large_batch(self, fmt, data, out, out_nbytes, stream=None, in_nbytes=None,
+                             out_avail=None):
+        """libdeflate_amd_compress_large_batch: ONE "deflate", "zlib" or "gzip"
+        stream of the uint8 torch CUDA tensor `data` (its first in_nbytes
+        bytes) into `out` (out_avail bytes of it, default all), byte for byte
+        what compress(fmt, ...) returns for the same bytes; bound(fmt, n) is
+        room enough.  out_nbytes: int64 CUDA tensor, [0] gets the stream's
+        size (0: does not fit).  Only enqueues on `stream`."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_compress_large_batch(
+            self._h, FORMATS[fmt], data.data_ptr() if n else None, n, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), out_nbytes.data_ptr(),
+            _stream_ptr(stream)), "compress_large_batch")
+
     def compress(self, fmt, data, out_avail=None):
         """Returns the compressed bytes, or None when the reference API would
         return 0 (does not fit in out_avail)."""

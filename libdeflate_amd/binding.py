@@ -64,6 +64,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_bgzf_read_batch", "libdeflate_amd_bgzf_decompress",
     "libdeflate_amd_decompress_sizes_batch", "libdeflate_amd_decompress_sizes_batch_dict",
     "libdeflate_amd_decompress_sizes_batch_host", "libdeflate_amd_decompress_batch_packed",
+    "libdeflate_amd_compress_large_batch",
 ]
 
 _lib = None
@@ -165,6 +166,8 @@ def load():
     sig("libdeflate_amd_decompress_sizes_batch_host", c_int, P, c_int, SZ, P, P, P, P, P, P)
     sig("libdeflate_amd_decompress_batch_packed", c_int, P, c_int, SZ, P, P, P, P, SZ, SZ, P,
         P, P, P, P)
+    # one raw DEFLATE / zlib / gzip stream from one device buffer, enqueue only
+    sig("libdeflate_amd_compress_large_batch", c_int, P, c_int, P, SZ, P, SZ, P, P)
     _lib = lib
     return lib
 

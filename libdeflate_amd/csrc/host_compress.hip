@@ -16,6 +16,7 @@
 
 #include "host_objects.h"
 #include "kernels.h"
+#include "large_plan.h"
 
 using namespace lda;
 
@@ -103,6 +104,7 @@ libdeflate_free_compressor(struct libdeflate_compressor *c)
 	c->pinned.release();
 	c->meta.release();
 	c->bgzf.release();
+	c->large.release();
 	c->streams.release();
 	free_func_t f = c->free_func;
 	c->~libdeflate_compressor();
@@ -595,39 +597,20 @@ libdeflate_amd_compress_batch_host(struct libdeflate_compressor *c, int format,
  * per-piece checksums:
  *   crc(A || B) = crc(A) * x^(8 |B|) mod P  xor  crc(B)
  * (programs/gzip.c:149-185 hands the whole file to one compress call; this
- * is what makes that call use the whole GPU.)
+ * is what makes that call use the whole GPU.)  The sub-range size, the
+ * segments' descriptors and the CRC arithmetic are large_plan.h's, shared with
+ * the device-memory form below (libdeflate_amd_compress_large_batch).
  */
-#define LDA_SEG_BYTES 65536u
-#define LDA_LARGE_MIN (2 * LDA_SEG_BYTES)
-
-/* multiply two reflected polynomials mod the CRC-32 polynomial (bit 31 = x^0) */
-static uint32_t crc_mulmod(uint32_t a, uint32_t b)
-{
-	uint32_t p = 0;
-	for (uint32_t m = 0x80000000u; m; m >>= 1) {
-		if (a & m)
-			p ^= b;
-		b = (b & 1) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-	}
-	return p;
-}
 
 /* x^(8 len) mod P: what appending len bytes multiplies a CRC by */
 uint32_t lda::crc32_shift(uint64_t len)
 {
-	uint32_t xp = 0x80000000u;	/* 1 */
-	uint32_t base = 0x00800000u;	/* x^8 */
-	for (uint64_t k = len; k; k >>= 1) {
-		if (k & 1)
-			xp = crc_mulmod(xp, base);
-		base = crc_mulmod(base, base);
-	}
-	return xp;
+	return lda_crc_powmod(0x00800000u /* x^8 */, len);
 }
 
 uint32_t lda::crc32_concat_shift(uint32_t crc_a, uint32_t crc_b, uint32_t shift_b)
 {
-	return crc_mulmod(crc_a, shift_b) ^ crc_b;
+	return lda_crc_mulmod(crc_a, shift_b) ^ crc_b;
 }
 
 uint32_t lda::crc32_concat(uint32_t crc_a, uint32_t crc_b, uint64_t len_b)
@@ -658,6 +641,21 @@ static size_t large_fail(const char *what)
 	return 0;
 }
 
+/* a segment's bytes: its own and at most dict_window() (whole tiles) in front,
+ * of the previous segment or of the dictionary.  The usable window is 32 KiB
+ * minus two tiles (the kernel inserts one tile ahead) and the lookahead */
+static size_t large_seg_bound(size_t S)
+{
+	const size_t tile = lda_deflate_tile();
+	return S + (dict_window() + tile - 1) / tile * tile;
+}
+
+/* the slot a segment is compressed into */
+static size_t large_slot(struct libdeflate_compressor *c, size_t S)
+{
+	return align_up(libdeflate_deflate_compress_bound(c, S) + 32, 16);
+}
+
 /*
  * The segments go through in SLICES of up to 32 MiB of input on run_slices(),
  * like the host-pointer batches: while the kernels of slice k
@@ -671,27 +669,12 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 			     size_t out_avail, const uint8_t *dict = NULL,
 			     size_t dict_nbytes = 0)
 {
-	/* sub-ranges of 64 KiB; an input that would not fill the CUs with those
-	 * is cut finer (more blocks and sync markers: ~1 % larger at 16 KiB).
-	 * A preset dictionary's call below LDA_LARGE_MIN is one segment. */
-	size_t S = LDA_SEG_BYTES;
-	if (dict && n < LDA_LARGE_MIN)
-		S = n ? n : 1;
-	else if (env_cfg().seg_bytes)
-		S = env_cfg().seg_bytes;
-	else if (n <= ((size_t)4 << 20))
-		S = 16384;
-	else if (n <= ((size_t)8 << 20))
-		S = 32768;
-	const size_t tile = lda_deflate_tile();
-	/* usable window is 32 KiB minus two tiles (the kernel inserts one tile
-	 * ahead) and the lookahead; whole tiles */
-	const size_t D = dict_window();
+	/* a preset dictionary's call below LDA_LARGE_MIN is one segment */
+	const size_t S = dict && n < LDA_LARGE_MIN ? (n ? n : 1) :
+			 (size_t)lda_large_seg_bytes(n, env_cfg().seg_bytes);
 	const size_t nseg = n ? (n + S - 1) / S : 1;
-	/* a segment's bytes: its own and at most D (whole tiles) in front, of the
-	 * previous segment or of the dictionary */
-	const size_t seg_bound = S + (D + tile - 1) / tile * tile;
-	const size_t slot = align_up(libdeflate_deflate_compress_bound(c, S) + 32, 16);
+	const size_t seg_bound = large_seg_bound(S);
+	const size_t slot = large_slot(c, S);
 	/* the caller's dictionary primes the first segment: its prefix (see
 	 * shape_dict()) lies in front of the input in the staging area */
 	const dict_shape dsh = shape_dict(c->level, dict ? dict_nbytes : 0);
@@ -707,7 +690,7 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	if (!ctx || !c->streams.ensure())
 		return large_fail("streams");
 	hipStream_t s_copy = c->streams.copy, s_comp = c->streams.comp;
-	const size_t per_slice = std::max<size_t>(1, ((size_t)32 << 20) / S);
+	const size_t per_slice = (size_t)lda_large_per_slice(S);
 	const size_t ns = (nseg + per_slice - 1) / per_slice;
 	/* device layout: [7 u64 rows: in_off in_n out_off out_av out_n piece_off
 	 * piece_n][seg_info u32][sums u32][compaction offsets of every slice]
@@ -738,16 +721,17 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	std::vector<uint32_t> d32(nseg);
 	uint64_t *in_off = &d64[0], *in_n = &d64[nseg], *out_off = &d64[2 * nseg],
 		 *out_av = &d64[3 * nseg], *pc_off = &d64[5 * nseg], *pc_n = &d64[6 * nseg];
+	const lda_large_shape shape = { n, S, dict_window(), lda_deflate_tile(), nseg, slot,
+					in_at, out_at };
 	for (size_t i = 0; i < nseg; i++) {
-		const size_t prime = i ? std::min(D, i * S) / tile * tile : 0;
-		const size_t len = i + 1 < nseg ? S : n - i * S;
-		in_off[i] = in_at + i * S - prime;
-		in_n[i] = prime + len;
-		out_off[i] = out_at + i * slot;
-		out_av[i] = slot;
-		pc_off[i] = in_at + i * S;
-		pc_n[i] = len;
-		d32[i] = (uint32_t)prime | (i + 1 == nseg ? 0x80000000u : 0);
+		const lda_large_seg s = lda_large_seg_of(shape, i);
+		in_off[i] = s.in_off;
+		in_n[i] = s.in_n;
+		out_off[i] = s.out_off;
+		out_av[i] = s.out_av;
+		pc_off[i] = s.pc_off;
+		pc_n[i] = s.pc_n;
+		d32[i] = s.info;
 	}
 	std::vector<uint8_t> prefix(pre);
 	if (pre) {
@@ -840,8 +824,7 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 			crc = !i ? h_sums[0] :
 			      pc_n[i] == S ? crc32_concat_shift(crc, h_sums[i], shS) :
 					     crc32_concat(crc, h_sums[i], pc_n[i]);
-		const uint8_t xfl = c->level < 2 ? 4 : c->level >= 8 ? 2 : 0;
-		const uint8_t h[10] = { 0x1F, 0x8B, 8, 0, 0, 0, 0, 0, xfl, 0xFF };
+		const uint8_t h[10] = { 0x1F, 0x8B, 8, 0, 0, 0, 0, 0, lda_gzip_xfl(c->level), 0xFF };
 		memcpy(out, h, 10);
 		uint32_t isize = (uint32_t)n;
 		for (int k = 0; k < 4; k++) {
@@ -853,17 +836,14 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 		uint32_t ad = 1;
 		for (size_t i = 0; i < nseg; i++)
 			ad = i ? adler32_concat(ad, h_sums[i], pc_n[i]) : h_sums[0];
-		uint32_t fl = c->level < 2 ? 0 : c->level < 6 ? 1 : c->level < 8 ? 2 : 3;
-		uint32_t hw = (0x78u << 8) | (fl << 6);
+		uint32_t hw = lda_zlib_header(c->level);
 		if (dict) {
 			/* FDICT and DICTID (RFC 1950 2.2) */
-			hw |= 0x20;
+			hw = (hw & 0xFFC0u) | 0x20;
 			hw += (31 - hw % 31) % 31;
 			const uint32_t id = libdeflate_adler32(1, dict, dict_nbytes);
 			for (int k = 0; k < 4; k++)
 				out[2 + k] = (uint8_t)(id >> (8 * (3 - k)));
-		} else {
-			hw |= 31 - (hw % 31);
 		}
 		out[0] = (uint8_t)(hw >> 8);
 		out[1] = (uint8_t)hw;
@@ -884,10 +864,7 @@ static size_t compress_one(struct libdeflate_compressor *c, int format,
 		complain("libdeflate_*_compress", LIBDEFLATE_AMD_NO_DEVICE);
 		return 0;
 	}
-	/* (inputs of 4 GiB and more always take this path: the kernels index a
-	 * chunk with 32 bits, the segments are 64 KiB each) */
-	if (in_nbytes >= LDA_LARGE_MIN && c->level > 0 &&
-	    (!env_cfg().no_segments || in_nbytes >= 0xFFFF0000u))
+	if (lda_large_segmented(in_nbytes, c->level, env_cfg().no_segments))
 		return no_unwind("libdeflate_*_compress", (size_t)0, [&]() {
 			return compress_large(c, format, (const uint8_t *)in, in_nbytes,
 					      (uint8_t *)out, out_avail);
@@ -956,4 +933,121 @@ libdeflate_amd_compress_dict(struct libdeflate_compressor *c, int format,
 		return compress_large(c, format, (const uint8_t *)in, in_nbytes, (uint8_t *)out,
 				      out_avail, (const uint8_t *)dict, dict_nbytes);
 	});
+}
+
+/*
+ * include/libdeflate_amd.h: ONE stream from one DEVICE buffer, enqueue only.
+ * The bytes are compress_one()'s: the same decision between one chunk and
+ * segments, the same S, descriptors and launches of lda_large_per_slice(S)
+ * segments (large_plan.h) - and what compress_large() does on the host
+ * between them is done by the kernels of large_kernels.hip: the descriptors,
+ * the checksum of the whole buffer from the pieces', header, footer, size.
+ * c->large: [7 u64 rows][scan offsets][seg_info u32][sums u32][slots].
+ */
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_compress_large_batch(struct libdeflate_compressor *c, int format,
+				    const void *d_in, size_t in_nbytes, void *d_out,
+				    size_t out_avail, uint64_t *d_out_nbytes, void *stream)
+{
+	const char *what = "compress_large_batch";
+	if (!c || (!d_in && in_nbytes) || !d_out || !d_out_nbytes) {
+		set_error("%s: NULL argument", what);
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	if (format != LIBDEFLATE_AMD_DEFLATE && format != LIBDEFLATE_AMD_ZLIB &&
+	    format != LIBDEFLATE_AMD_GZIP) {
+		set_error("%s: format %d is not DEFLATE, zlib or gzip", what, format);
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	const uint32_t hdr = format == LIBDEFLATE_AMD_GZIP ? 10 : format == LIBDEFLATE_AMD_ZLIB ? 2 : 0;
+	const uint32_t ftr = format == LIBDEFLATE_AMD_GZIP ? 8 : format == LIBDEFLATE_AMD_ZLIB ? 4 : 0;
+	if (out_avail <= hdr + ftr) {
+		set_error("%s: out_avail %zu cannot hold the container and a byte", what, out_avail);
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	DeviceGuard on(c->device);
+	if (!on.ok())
+		return LIBDEFLATE_AMD_NO_DEVICE;
+	DeviceCtx *ctx = device_ctx();
+	if (!ctx)
+		return LIBDEFLATE_AMD_NO_DEVICE;
+	hipStream_t st = (hipStream_t)stream;
+	const size_t n = in_nbytes;
+
+	if (!lda_large_segmented(n, c->level, env_cfg().no_segments)) {
+		/* one chunk of the ordinary batch, straight into d_out, its size
+		 * straight into d_out_nbytes (compress_batch_host_body() gives the
+		 * kernels the same bound) */
+		uint64_t *rows = (uint64_t *)c->large.reserve(4 * 8);
+		if (!rows)
+			return LIBDEFLATE_AMD_OOM;
+		hipLaunchKernelGGL(lda_large_one_desc_kernel, dim3(1), dim3(64), 0, st, (uint64_t)n,
+				   (uint64_t)out_avail, rows);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		return compress_batch_impl(c, format, 1, d_in ? d_in : (const void *)rows, rows,
+					   rows + 1, d_out, rows + 2, rows + 3, d_out_nbytes, stream,
+					   NULL, n);
+	}
+	const size_t S = (size_t)lda_large_seg_bytes(n, env_cfg().seg_bytes);
+	const size_t nseg = (n + S - 1) / S;
+	const size_t seg_bound = large_seg_bound(S), slot = large_slot(c, S);
+	const size_t per_slice = (size_t)lda_large_per_slice(S);
+	const size_t cmp_at = 7 * 8 * nseg;
+	const size_t seg_at = cmp_at + 8 * libdeflate_amd_compact_offsets_len(nseg);
+	const size_t slots_at = align_up(seg_at + 8 * nseg, 256);
+	/* all of the call's scratch before anything is queued: growing frees
+	 * memory (and waits for the device) */
+	uint8_t *ws = (uint8_t *)c->large.reserve(slots_at + nseg * slot);
+	if (!ws || !c->scratch.reserve(plan_batch(c, std::min(per_slice, nseg), seg_bound, true,
+						  false).total))
+		return LIBDEFLATE_AMD_OOM;
+	uint64_t *rows = (uint64_t *)ws, *out_n = rows + 4 * nseg, *cmp = (uint64_t *)(ws + cmp_at);
+	uint32_t *d_seg = (uint32_t *)(ws + seg_at), *d_sums = d_seg + nseg;
+	uint8_t *slots = ws + slots_at;
+	/* offsets into d_in and into the slots */
+	const lda_large_shape shape = { n, S, dict_window(), lda_deflate_tile(), nseg, slot, 0, 0 };
+	hipLaunchKernelGGL(lda_large_desc_kernel, dim3((unsigned)((nseg + 255) / 256)), dim3(256), 0,
+			   st, shape, rows, d_seg);
+	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+	for (size_t lo = 0; lo < nseg; lo += per_slice) {
+		const size_t nk = std::min(per_slice, nseg - lo);
+		int rc = compress_batch_impl(c, LIBDEFLATE_AMD_DEFLATE, nk, d_in, rows + lo,
+					     rows + nseg + lo, slots, rows + 2 * nseg + lo,
+					     rows + 3 * nseg + lo, out_n + lo, stream, d_seg + lo,
+					     seg_bound);
+		if (rc != LIBDEFLATE_AMD_OK)
+			return rc;
+	}
+	if (ftr) {
+		int rc = format == LIBDEFLATE_AMD_GZIP ?
+			libdeflate_amd_crc32_batch(nseg, d_in, rows + 5 * nseg, rows + 6 * nseg, NULL,
+						   d_sums, stream) :
+			libdeflate_amd_adler32_batch(nseg, d_in, rows + 5 * nseg, rows + 6 * nseg, NULL,
+						     d_sums, stream);
+		if (rc != LIBDEFLATE_AMD_OK)
+			return rc;
+	}
+	/* the scans of libdeflate_amd_compact_batch(), a copy that writes nothing
+	 * unless the whole stream fits, and the container around it */
+	const size_t nblocks = (nseg + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
+	uint64_t *block_sums = cmp + nseg + 1;
+	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)nblocks), dim3(256), 0, st,
+			   (uint64_t)nseg, (const uint64_t *)out_n, cmp, block_sums);
+	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)nblocks,
+			   block_sums);
+	const size_t grid = std::min(nseg, (size_t)ctx->num_cus * 8);
+	hipLaunchKernelGGL(lda_large_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
+			   (uint64_t)nseg, (const uint8_t *)slots, (uint64_t)slot,
+			   (const uint64_t *)out_n, (const uint64_t *)cmp,
+			   (const uint64_t *)block_sums, (uint8_t *)d_out, hdr, ftr,
+			   (uint64_t)out_avail);
+	/* every piece but the last is S bytes */
+	const uint32_t xS = format == LIBDEFLATE_AMD_GZIP ? crc32_shift(S) : 0;
+	const uint32_t xL = format == LIBDEFLATE_AMD_GZIP ? crc32_shift(n - (nseg - 1) * S) : 0;
+	hipLaunchKernelGGL(lda_large_finalize_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)nseg,
+			   (uint64_t)n, (uint64_t)S, format, c->level, (const uint64_t *)out_n,
+			   (const uint32_t *)d_sums, (const uint64_t *)(block_sums + nblocks), xS, xL,
+			   (uint8_t *)d_out, (uint64_t)out_avail, d_out_nbytes);
+	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+	return LIBDEFLATE_AMD_OK;
 }

@@ -65,6 +65,9 @@ struct libdeflate_compressor {
 	lda::DevBuf scratch;	/* parse/encode workspace + per-chunk sums */
 	lda::DevBuf stage;
 	lda::DevBuf bgzf;	/* BGZF files: block descriptors, member slots (host_bgzf.hip) */
+	/* one stream from one device buffer (libdeflate_amd_compress_large_batch):
+	 * descriptor rows, seg_info, per-piece sums, scan offsets, segment slots */
+	lda::DevBuf large;
 	lda::PinnedPair pinned;	/* host-pointer entry points */
 	lda::PinnedBuf meta;	/* host-pointer entry points: per-chunk read-backs */
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "large_plan.h"
+
 /* checksum_kernels.hip */
 extern "C" __global__ void
 lda_crc32_batch_kernel(uint64_t n_chunks, const uint8_t *base,
@@ -194,6 +196,22 @@ extern "C" __global__ void
 lda_bgzf_finalize_kernel(uint64_t m, uint64_t n, const uint64_t *sizes,
 			 const uint64_t *total_at, uint8_t *out, uint64_t out_avail,
 			 uint32_t eof_bytes, uint64_t *out_nbytes, uint64_t *index);
+
+/* large_kernels.hip: one raw DEFLATE / zlib / gzip stream from one device
+ * buffer (host_compress.hip, large_plan.h) */
+extern "C" __global__ void
+lda_large_desc_kernel(struct lda_large_shape g, uint64_t *rows, uint32_t *seg_info);
+extern "C" __global__ void
+lda_large_one_desc_kernel(uint64_t n, uint64_t out_avail, uint64_t *rows);
+extern "C" __global__ void
+lda_large_copy_kernel(uint64_t nseg, const uint8_t *slots, uint64_t slot, const uint64_t *sizes,
+		      const uint64_t *offsets, const uint64_t *block_sums, uint8_t *out,
+		      uint32_t hdr, uint32_t ftr, uint64_t out_avail);
+extern "C" __global__ void
+lda_large_finalize_kernel(uint64_t nseg, uint64_t n, uint64_t S, int format, int level,
+			  const uint64_t *sizes, const uint32_t *sums, const uint64_t *total_at,
+			  uint32_t xS, uint32_t xL, uint8_t *out, uint64_t out_avail,
+			  uint64_t *out_nbytes);
 
 /* bgzf_read_kernels.hip: a BGZF file read from device memory (host_bgzf_read.hip) */
 #define LDA_BR_TILE 4096	/* bytes per step of the candidate scan: 256 threads x 16 */
