@@ -577,6 +577,10 @@ libdeflate_amd_decompress_batch_host(struct libdeflate_decompressor *d,
  * count pass + chain, queueing the decode / window / resolve / checksum kernels,
  * footer check, output copy (which waits for those kernels); [14] input windows;
  * [15] chunks the host made itself from runs of stored blocks (no count pass).
+ * libdeflate_amd_decompress_large is described the same way; nothing is copied
+ * in or out there, and [8] is the time for the stream's head bytes (and for
+ * the bits and rows fetched where a window begins at a block boundary), [13]
+ * the wait for the last kernel.
  */
 #define LIBDEFLATE_AMD_STREAM_STATS 16
 LIBDEFLATEAPI void
@@ -724,6 +728,59 @@ libdeflate_amd_compress_large_batch(struct libdeflate_compressor *compressor,
 				    const void *d_in, size_t in_nbytes,
 				    void *d_out, size_t out_avail,
 				    uint64_t *d_out_nbytes, void *stream);
+
+/*
+ * The way back: ONE stream - raw DEFLATE, zlib or .gz - that lies in DEVICE
+ * memory (read by GPUDirect, received from another GPU, written by the call
+ * above) into device memory, on many waves (the decoder behind
+ * libdeflate_<format>_decompress for large host buffers), without the stream
+ * or its output ever crossing to the host.  format: LIBDEFLATE_AMD_DEFLATE,
+ * _ZLIB or _GZIP.  d_in and d_out are device pointers on the object's device,
+ * of any alignment; d_out must not overlap d_in.
+ *
+ * The result, *actual_in_nbytes_ret and *actual_out_nbytes_ret are exactly
+ * those of libdeflate_<format>_decompress_ex for the same bytes and
+ * out_nbytes_avail: a NULL actual_out_nbytes_ret asks for an exact fill,
+ * bytes behind the stream are allowed, and of a gzip buffer the first member
+ * is decoded (the caller loops on actual_in, as with the reference).  Both
+ * result pointers may be NULL.  No byte is written at or past d_out +
+ * out_nbytes_avail; on a result other than LIBDEFLATE_SUCCESS what lies below
+ * that is undefined, as libdeflate.h says.
+ *
+ * The call BLOCKS - it is not one of the enqueue-only _batch calls, hence its
+ * name: the many-wave decoder's chain of chunks is checked by the host.
+ * Before they first read d_in, the object's own streams wait (an event wait,
+ * not a host wait) for what is queued on `stream` (NULL: the default stream),
+ * so d_in may be the product of kernels queued there; when the call returns,
+ * d_out is complete and any stream may read it.  What crosses to the host are
+ * descriptors, per-chunk results, two small tables (the places where a stored
+ * block could lie, the classes of the block headers) and a few dozen bytes of
+ * the stream: its first 4 KiB at most for the container header, the footer,
+ * 8 bytes where an input window begins at a block boundary.
+ *
+ * Which decoder answers follows the host call's rule, so the result cannot
+ * depend on it: the many-wave path answers for a clean success or for a
+ * footer that does not match a cleanly decoded stream; everything else - a
+ * stream under LDA_STREAM_PAR_MIN bytes, LDA_NO_STREAM_PAR, a gzip header that
+ * runs past 4 KiB, damaged data, an output that does not fit or fill - goes
+ * to libdeflate_amd_decompress_batch as a batch of one on the object's
+ * stream.  libdeflate_amd_stream_stats() says which it was.
+ *
+ * The arguments are checked before any device work: LIBDEFLATE_BAD_DATA, with
+ * the reason in libdeflate_amd_last_error(), for a NULL object, a NULL d_in
+ * with in_nbytes != 0, a NULL d_out with out_nbytes_avail != 0, or another
+ * format.  A library-side failure (no device, no memory) is LIBDEFLATE_BAD_DATA
+ * with its reason there too.  Streams of 4 GiB and more are as limited as in
+ * the host call; preset dictionaries are out of scope.  The scratch (16-bit
+ * symbols of the output, finder queues, a row per 64 bytes of an input window)
+ * belongs to the object and goes with it.
+ */
+LIBDEFLATEAPI enum libdeflate_result
+libdeflate_amd_decompress_large(struct libdeflate_decompressor *decompressor, int format,
+				const void *d_in, size_t in_nbytes,
+				void *d_out, size_t out_nbytes_avail,
+				size_t *actual_in_nbytes_ret, size_t *actual_out_nbytes_ret,
+				void *stream);
 
 /*
  * Reading a BGZF file.  What a member is (htslib's check_header rule): the

@@ -319,6 +319,23 @@ class Decompressor:
             return r, got, nm.value, fl.value, rows
         return r, got, nm.value, fl.value
 
+    def decompress_large(self, fmt, data, out, in_nbytes=None, out_avail=None,
+                         want_actual_out=True, stream=None):
+        """libdeflate_amd_decompress_large: ONE "deflate", "zlib" or "gzip"
+        stream in the uint8 torch CUDA tensor `data` (its first in_nbytes
+        bytes) into the uint8 CUDA tensor `out` (out_avail bytes of it,
+        default all), on many waves, with the results of decompress_ex ->
+        (result, actual_in, actual_out); want_actual_out=False asks for an
+        exact fill.  Blocks; ordered behind what is queued on `stream`."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        ai, ao = c_size_t(0), c_size_t(0)
+        r = self._lib.libdeflate_amd_decompress_large(
+            self._h, FORMATS[fmt], data.data_ptr() if n else None, n,
+            out.data_ptr() if avail else None, avail, ctypes.byref(ai),
+            ctypes.byref(ao) if want_actual_out else None, _stream_ptr(stream))
+        return r, ai.value, ao.value
+
     def decompress_batch(self, fmt, data, in_offsets, in_nbytes, out,
                          out_offsets, out_avail, results, actual_in=None,
                          actual_out=None, stream=None):

@@ -64,7 +64,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_bgzf_read_batch", "libdeflate_amd_bgzf_decompress",
     "libdeflate_amd_decompress_sizes_batch", "libdeflate_amd_decompress_sizes_batch_dict",
     "libdeflate_amd_decompress_sizes_batch_host", "libdeflate_amd_decompress_batch_packed",
-    "libdeflate_amd_compress_large_batch",
+    "libdeflate_amd_compress_large_batch", "libdeflate_amd_decompress_large",
 ]
 
 _lib = None
@@ -168,6 +168,8 @@ def load():
         P, P, P, P)
     # one raw DEFLATE / zlib / gzip stream from one device buffer, enqueue only
     sig("libdeflate_amd_compress_large_batch", c_int, P, c_int, P, SZ, P, SZ, P, P)
+    # ... and one such stream from device memory to device memory (blocking)
+    sig("libdeflate_amd_decompress_large", c_int, P, c_int, P, SZ, P, SZ, psz, psz, P)
     _lib = lib
     return lib
 

@@ -45,6 +45,9 @@ struct libdeflate_decompressor {
 	/* one large stream on many waves (host_stream.hip): input + finder
 	 * queues, chunk descriptors / results, 16-bit symbols, output bytes */
 	lda::DevBuf sin, squeue, schunks, srepair, ssym, sout, swin, shdr, shint;
+	/* the same for a stream in device memory (libdeflate_amd_decompress_large):
+	 * the rows of possible stored blocks and the headers' classes */
+	lda::DevBuf sprobe;
 	lda::PinnedPair pinned;	/* host-pointer entry points */
 	lda::PinnedBuf meta;	/* host-pointer entry points: per-chunk read-backs */
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */
@@ -94,11 +97,13 @@ int fanout(Obj *o, size_t n, const size_t *weight,
 	   const std::function<int(Obj *, size_t, size_t)> &body);
 
 /* host_stream.hip: true = answered (result, sizes, output); false = the
- * caller takes the sequential path */
+ * caller takes the sequential path.  on_device: `in` and `out` are device
+ * pointers (libdeflate_amd_decompress_large), the object's streams exist and
+ * are ordered behind whatever produces `in`. */
 bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 				const uint8_t *in, size_t in_nbytes, uint8_t *out,
 				size_t out_avail, bool exact_fill, int32_t *res,
-				size_t *ain, size_t *aout);
+				size_t *ain, size_t *aout, bool on_device = false);
 }
 
 #endif /* LDA_HOST_OBJECTS_H */

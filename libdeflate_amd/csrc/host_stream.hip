@@ -24,6 +24,7 @@
 #include "host_objects.h"
 #include "kernels.h"
 #include "stream_kernels.h"
+#include "stored_rows.h"
 
 namespace lda {
 
@@ -48,12 +49,17 @@ struct planned {
 
 /* gzip / zlib container: offset of the raw stream and the footer's size; false
  * if the sequential path should look at it (lib/gzip_decompress.c:45-107,
- * lib/zlib_decompress.c:45-72) */
-static bool container(int format, const uint8_t *in, size_t n, size_t *hdr, size_t *ftr)
+ * lib/zlib_decompress.c:45-72).  `have`: how many of the buffer's n bytes are
+ * at `in` - all of them, or the head of a stream that lies in device memory:
+ * a header that runs past the head is the sequential path's */
+static bool container(int format, const uint8_t *in, size_t n, size_t have, size_t *hdr,
+		      size_t *ftr)
 {
 	*hdr = *ftr = 0;
 	if (format == LIBDEFLATE_AMD_DEFLATE)
 		return true;
+	if (have < (n < 18 ? n : 18))
+		return false;
 	if (format == LIBDEFLATE_AMD_ZLIB) {
 		if (n < 6)
 			return false;
@@ -77,8 +83,11 @@ static bool container(int format, const uint8_t *in, size_t n, size_t *hdr, size
 	}
 	for (int k = 0; k < 2; k++)
 		if (flg & (k ? 0x10 : 0x08)) {
+			if (p >= have)
+				return false;
 			while (in[p++] != 0 && p != n)
-				;
+				if (p >= have)
+					return false;
 			if (n - p < 8)
 				return false;
 		}
@@ -87,6 +96,8 @@ static bool container(int format, const uint8_t *in, size_t n, size_t *hdr, size
 		if (n - p < 8)
 			return false;
 	}
+	if (p > have)
+		return false;
 	*hdr = p;
 	*ftr = 8;
 	return true;
@@ -111,8 +122,23 @@ static bool launch_count(hipStream_t st, uint32_t n, const lda_stream_chunk *d_c
 bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 				const uint8_t *in, size_t in_nbytes, uint8_t *out,
 				size_t out_avail, bool exact_fill, int32_t *res,
-				size_t *ain, size_t *aout)
+				size_t *ain, size_t *aout, bool on_device)
 {
+	/*
+	 * THE INPUT SOURCE.  on_device == false: `in` is the caller's host
+	 * buffer; it is copied to d->sin window by window, the host reads what it
+	 * decides itself out of `in`, and the output goes through d->sout to the
+	 * host buffer `out`.  on_device == true (libdeflate_amd_decompress_large):
+	 * `in` and `out` are device pointers.  The kernels read the caller's
+	 * buffer in place and write the caller's output, and the five things the
+	 * host reads out of the stream come to it otherwise: (a) the container
+	 * header and the bits at bit 0 from the first 4 KiB, fetched once; (b) the
+	 * footer with the decode pass's results; (c) the bits at a carried-in
+	 * boundary as 8 bytes fetched when a window begins there; (d) runs of
+	 * stored blocks from the rows of lda_stream_find_stored_kernel; (e) blocks
+	 * of one codeword length from lda_stream_hdr_class_kernel.
+	 */
+	const bool dev = on_device;
 	uint64_t *S = g_stats;
 	memset(g_stats, 0, sizeof(g_stats));
 	/* host-side phase clock: S[8..13] = microseconds of copy in, find, count +
@@ -137,21 +163,7 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		S[1] = WHY_DISABLED;
 		return false;
 	}
-	size_t hdr, ftr;
-	if (!container(format, in, in_nbytes, &hdr, &ftr)) {
-		S[1] = WHY_HEADER;
-		return false;
-	}
-	const uint64_t raw_n = in_nbytes - hdr - ftr;
-	const uint64_t raw_bits = 8 * raw_n;
-	if (raw_n < 8) {
-		S[1] = WHY_HEADER;
-		return false;
-	}
-	S[1] = WHY_DEVICE;	/* until something better is known */
-	if (!d->streams.ensure())
-		return false;
-	hipStream_t s_copy = d->streams.copy, s_comp = d->streams.comp;
+	hipStream_t s_copy = nullptr, s_comp = nullptr;
 	/* The small transfers of every phase (descriptors down, results back) go
 	 * through pinned memory: from and to pageable memory each of them would
 	 * be staged by the runtime and cost a host-blocking round trip of its own.
@@ -166,17 +178,17 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		pin_used = 0;
 		return pin_base != nullptr;
 	};
-	auto up = [&](void *dev, const void *src, size_t n) -> hipError_t {
+	auto up = [&](void *dev_p, const void *src, size_t n) -> hipError_t {
 		uint8_t *q = pin_base + pin_used;
 		pin_used += align_up(n, 64);
 		memcpy(q, src, n);
-		return hipMemcpyAsync(dev, q, n, hipMemcpyHostToDevice, s_comp);
+		return hipMemcpyAsync(dev_p, q, n, hipMemcpyHostToDevice, s_comp);
 	};
-	auto back = [&](void *dst, const void *dev, size_t n) -> hipError_t {
+	auto back = [&](void *dst, const void *dev_p, size_t n) -> hipError_t {
 		uint8_t *q = pin_base + pin_used;
 		pin_used += align_up(n, 64);
 		pin_pending.push_back({ dst, q, n });
-		return hipMemcpyAsync(q, dev, n, hipMemcpyDeviceToHost, s_comp);
+		return hipMemcpyAsync(q, dev_p, n, hipMemcpyDeviceToHost, s_comp);
 	};
 	auto pin_sync = [&]() -> hipError_t {
 		const hipError_t e = hipStreamSynchronize(s_comp);
@@ -186,19 +198,133 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		pin_used = 0;
 		return e;
 	};
+	/* (a) a stream in device memory: its first bytes, for the container
+	 * header and the bits at bit 0 */
+	std::vector<uint8_t> head;
+	if (dev) {
+		S[1] = WHY_DEVICE;
+		s_copy = d->streams.copy;
+		s_comp = d->streams.comp;
+		head.resize(std::min<size_t>(in_nbytes, 4096));
+		if (!head.empty()) {
+			if (!pin_phase(head.size()))
+				return false;
+			ST_TRY(back(head.data(), in, head.size()));
+			ST_TRY(pin_sync());
+		}
+		lap(8);
+	}
+	size_t hdr, ftr;
+	if (!container(format, dev ? head.data() : in, in_nbytes, dev ? head.size() : in_nbytes,
+		       &hdr, &ftr) ||
+	    (dev && hdr + 8 > head.size())) {
+		S[1] = WHY_HEADER;
+		return false;
+	}
+	const uint64_t raw_n = in_nbytes - hdr - ftr;
+	const uint64_t raw_bits = 8 * raw_n;
+	if (raw_n < 8) {
+		S[1] = WHY_HEADER;
+		return false;
+	}
+	S[1] = WHY_DEVICE;	/* until something better is known */
+	if (!dev) {
+		if (!d->streams.ensure())
+			return false;
+		s_copy = d->streams.copy;
+		s_comp = d->streams.comp;
+	}
 
-	/* the host has the stream too: bits of it, for what it can decide itself */
-	const uint8_t *raw = in + hdr;
+	/* the host has the stream too: bits of it, for what it can decide itself.
+	 * Of a stream in device memory it has 8 bytes at a time: pk[] holds the
+	 * raw stream's bytes from pk_at on (the head's at first, fetch_pk() for
+	 * the boundary a later window begins at). */
+	const uint8_t *raw = dev ? nullptr : in + hdr;
+	const stored_probe_bytes host_bytes = { raw, raw_n };
+	uint8_t pk[8] = { 0 };
+	uint64_t pk_at = 0;
+	if (dev)
+		memcpy(pk, head.data() + hdr, 8);
 	auto peek = [&](uint64_t bit, unsigned n) -> uint32_t {	/* n <= 24; zeros past the end */
+		if (!dev)
+			return host_bytes.peek(bit, n);
 		uint32_t v = 0;
 		const uint64_t b0 = bit >> 3;
-		if (b0 + 4 <= raw_n)
-			memcpy(&v, raw + b0, 4);	/* (little-endian host, as the HIP runtime's) */
-		else
-			for (unsigned k = 0; k < 4; k++)
-				if (b0 + k < raw_n)
-					v |= (uint32_t)raw[b0 + k] << (8 * k);
+		for (unsigned k = 0; k < 4; k++)
+			if (b0 + k < raw_n && b0 + k >= pk_at && b0 + k < pk_at + 8)
+				v |= (uint32_t)pk[b0 + k - pk_at] << (8 * k);
 		return (v >> (bit & 7)) & ((1u << n) - 1);
+	};
+	/* (pk_queue(): as part of a round trip that is being queued anyway) */
+	auto pk_queue = [&](uint64_t bit) -> hipError_t {
+		const uint64_t b0 = bit >> 3;
+		if (b0 == pk_at)
+			return hipSuccess;
+		memset(pk, 0, sizeof(pk));
+		pk_at = b0;
+		if (hdr + b0 >= in_nbytes)
+			return hipSuccess;
+		return back(pk, in + hdr + b0, std::min<size_t>(8, in_nbytes - hdr - b0));
+	};
+	auto fetch_pk = [&](uint64_t bit) -> bool {
+		if ((bit >> 3) == pk_at)
+			return true;
+		if (!pin_phase(64))
+			return false;
+		ST_TRY(pk_queue(bit));
+		ST_TRY(pin_sync());
+		return true;
+	};
+	/* (d) the rows of the current window: every offset of it at which a stored
+	 * block's LEN / NLEN could lie (stored_rows.h), sorted.  The kernel is
+	 * queued once per window - ahead of everything when the window begins at
+	 * a stored block, otherwise beside the block finder, whose round trip then
+	 * brings the rows too.  Scratch: [count][classes of (e)][rows]. */
+	std::vector<lda_stored_row> rows;
+	bool rows_queued = false;
+	uint32_t rows_cap = 0, rows_cnt = 0;
+	const uint32_t ROWS_FIRST = 4096;	/* rows read back with the count */
+	const size_t cls_at = 64, rows_at = cls_at + (size_t)LDA_STREAM_HDR_SLOTS * 8;
+	uint8_t *d_probe = nullptr;
+	auto rows_queue = [&](const uint8_t *d_in_raw, uint64_t in_n, uint64_t bp0) -> bool {
+		const uint64_t span = in_n > bp0 ? in_n - bp0 : 0;
+		rows_cap = (uint32_t)std::min<uint64_t>(span / 64 + 4096, 1u << 28);
+		d_probe = (uint8_t *)d->sprobe.reserve(rows_at + (size_t)rows_cap * 16 + 64);
+		if (!d_probe)
+			return false;
+		ST_TRY(hipMemsetAsync(d_probe, 0, 16, s_comp));
+		if (span >= 4) {
+			const uint64_t blocks = (span + 15 + 4095) / 4096 + 1;
+			hipLaunchKernelGGL(lda_stream_find_stored_kernel,
+					   dim3((unsigned)std::min<uint64_t>(blocks, 2048)), dim3(256), 0,
+					   s_comp, d_in_raw, in_n, bp0, (uint4 *)(d_probe + rows_at),
+					   (uint32_t *)d_probe, rows_cap);
+			ST_TRY(hipGetLastError());
+		}
+		rows_queued = true;
+		return true;
+	};
+	/* (the two halves of the read-back: queued with a round trip, looked at
+	 * behind it) */
+	auto rows_back = [&]() -> hipError_t {
+		rows.resize(std::min(rows_cap, ROWS_FIRST));
+		hipError_t e = back(&rows_cnt, d_probe, 4);
+		if (e == hipSuccess)
+			e = back(rows.data(), d_probe + rows_at, rows.size() * 16);
+		return e;
+	};
+	auto rows_done = [&]() -> bool {
+		const uint32_t n = std::min(rows_cnt, rows_cap), first = (uint32_t)rows.size();
+		rows.resize(n);
+		if (n > first) {
+			if (!pin_phase((size_t)(n - first) * 16))
+				return false;
+			ST_TRY(back(rows.data() + first, d_probe + rows_at + (size_t)first * 16,
+				    (size_t)(n - first) * 16));
+			ST_TRY(pin_sync());
+		}
+		sort_stored_rows(rows.data(), rows.size());
+		return true;
 	};
 	/*
 	 * A RUN OF STORED BLOCKS from the block boundary `p` on, walked by the
@@ -211,50 +337,32 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 	 * of the first block that is not stored, is not wholly inside the first
 	 * `dev_bytes` of the stream (what the kernels can read), or is invalid
 	 * (the kernels - and after them the sequential path - say what the
-	 * reference says about that one).  Returns the bit it stopped at.
+	 * reference says about that one).  Returns the bit it stopped at.  The
+	 * walk itself is walk_stored_run() of stored_rows.h, over the stream's
+	 * bytes or over the rows.
 	 */
 	auto walk_stored = [&](uint64_t p, uint64_t dev_bytes, uint64_t group,
 			       std::vector<lda_stream_chunk> &oc, std::vector<lda_stream_res> &orr,
 			       bool *fin_ret) -> uint64_t {
-		*fin_ret = false;
-		for (;;) {
+		auto emit = [&](uint64_t from, uint64_t to, uint64_t nout, bool fin) {
 			lda_stream_chunk c = {};
 			lda_stream_res r = {};
 			c.kind = LDA_CHUNK_HEADER;
-			c.hdr_bit = c.start_bit = c.target_bit = p;
-			r.start_bit = p;
-			uint64_t q = p;
-			bool fin = false;
-			while (q + 3 <= raw_bits && !fin && q - p < group) {
-				const uint32_t h = peek(q, 3);
-				if ((h >> 1) != 0)
-					break;
-				const uint64_t bp = (q + 3 + 7) >> 3;
-				if (bp + 4 > raw_n)
-					break;
-				const uint32_t len = raw[bp] | ((uint32_t)raw[bp + 1] << 8);
-				const uint32_t nlen = raw[bp + 2] | ((uint32_t)raw[bp + 3] << 8);
-				if (len != (nlen ^ 0xFFFFu) || bp + 4 + len > raw_n || bp + 4 + len > dev_bytes)
-					break;
-				r.nout += len;
-				q = 8 * (bp + 4 + len);
-				fin = h & 1;
-			}
-			if (q == p)
-				return p;
-			c.limit_bit = q;
-			r.end_bit = r.end_hdr_bit = q;
+			c.hdr_bit = c.start_bit = c.target_bit = from;
+			r.start_bit = from;
+			r.nout = nout;
+			c.limit_bit = to;
+			r.end_bit = r.end_hdr_bit = to;
 			r.status = fin ? LDA_STREAM_FINAL : LDA_STREAM_OK;
 			r.flags = LDA_RES_BOUNDARY;
 			oc.push_back(c);
 			orr.push_back(r);
 			S[15]++;
-			p = q;
-			if (fin) {
-				*fin_ret = true;
-				return p;
-			}
-		}
+		};
+		if (!dev)
+			return walk_stored_run(p, raw_n, dev_bytes, group, host_bytes, emit, fin_ret);
+		const stored_probe_rows by_rows = { rows.data(), rows.size() };
+		return walk_stored_run(p, raw_n, dev_bytes, group, by_rows, emit, fin_ret);
 	};
 
 	/*
@@ -406,6 +514,21 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		const auto it = hdr_slot.find(hdr_bit);
 		return it == hdr_slot.end() ? 0 : it->second;
 	};
+	/* (e) of a stream in device memory the host has no header to read:
+	 * lda_stream_hdr_class_kernel applies one_length_code()'s final rule to
+	 * the lengths in the slots, and hcls[slot] = { longest literal codeword or
+	 * 0, bits from the header to the first token } comes back before the
+	 * plan.  A header without a slot counts as an ordinary block. */
+	struct hdr_class { uint32_t hi, used; };
+	std::vector<hdr_class> hcls;
+	auto one_length_slot = [&](uint64_t hb, uint64_t *first_token) -> uint32_t {
+		const uint32_t slot = cache_of(hb);
+		if (!slot || slot > hcls.size() || !hcls[slot - 1].hi ||
+		    hb + hcls[slot - 1].used >= raw_bits)
+			return 0;
+		*first_token = hb + hcls[slot - 1].used;
+		return hcls[slot - 1].hi;
+	};
 	uint32_t *d_cnt = nullptr;	/* [0] queue, [1] candidates, [2] error flag */
 	uint32_t qcap = 0, ccap = 0;
 
@@ -430,14 +553,20 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		bool cache_queued = false;
 		/* ---- this window's input ---- */
 		const size_t upto = std::min<size_t>(in_nbytes, std::max(copied, hdr) + W);
-		if (!sin || in_at + upto + 64 > d->sin.cap) {
+		if (dev) {
+			/* (in place: the windows only bound what is searched) */
+			d_raw = (uint8_t *)in + hdr;
+			copied = upto;
+			rows.clear();
+			rows_queued = false;
+		} else if (!sin || in_at + upto + 64 > d->sin.cap) {
 			sin = (uint8_t *)d->sin.reserve(in_at + std::min<size_t>(in_nbytes, 2 * upto) + 64);
 			if (!sin)
 				return false;
 			d_raw = sin + in_at + hdr;
 			copied = 0;
 		}
-		if (upto > copied) {
+		if (!dev && upto > copied) {
 			if (span_in(&d->pinned, sin, in_at + copied, in + copied, upto - copied, s_copy) !=
 			    LIBDEFLATE_AMD_OK)
 				return false;
@@ -459,6 +588,22 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		if (carry.kind == LDA_CHUNK_HEADER) {
 			const uint64_t group = 8 * (uint64_t)(env.stream_chunk ? env.stream_chunk : 16384);
 			bool fin = false;
+			/* (in device memory: the bits at the boundary say whether a run
+			 * begins there; only then are the rows made ahead of the finder,
+			 * at the price of a round trip) */
+			if (dev) {
+				if (!fetch_pk(carry.start_bit))
+					return false;
+				if (carry.start_bit + 3 <= raw_bits && (peek(carry.start_bit, 3) >> 1) == 0) {
+					if (!rows_queue(d_raw, win_n, (carry.start_bit + 10) >> 3) ||
+					    !pin_phase(64 + (size_t)ROWS_FIRST * 16))
+						return false;
+					ST_TRY(rows_back());
+					ST_TRY(pin_sync());
+					if (!rows_done())
+						return false;
+				}
+			}
 			const uint64_t q = walk_stored(carry.start_bit, win_n, group, acc, accr, &fin);
 			if (fin) {
 				final_seen = true;
@@ -493,6 +638,9 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		}
 		ST_TRY(hipMemsetAsync(d_cnt, 0, 16, s_comp));
 		if (nbits > fb0) {
+			const bool rows_here = dev && !rows_queued;
+			if (rows_here && !rows_queue(d_raw, win_n, (carry.start_bit + 10) >> 3))
+				return false;
 			for (uint64_t b0 = fb0; b0 < nbits; b0 += 1ull << 31) {
 				const uint64_t nb = std::min<uint64_t>(nbits - b0, 1ull << 31);
 				/* (a workgroup of four waves takes 16 windows of 4 x 64 bytes) */
@@ -510,6 +658,16 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 					   lda_stream_hdr_cache_lds(), s_copy, d_raw, win_n, d_cand, d_cnt + 1,
 					   std::min<uint32_t>(ccap, LDA_STREAM_HDR_SLOTS), d_hlens, d_hinfo);
 			ST_TRY(hipGetLastError());
+			uint2 *d_cls = nullptr;
+			if (dev && !env.stream_chunk) {
+				/* (the scratch exists: the rows of this window were queued) */
+				d_cls = (uint2 *)(d_probe + cls_at);
+				hipLaunchKernelGGL(lda_stream_hdr_class_kernel, dim3(LDA_STREAM_HDR_SLOTS / 64),
+						   dim3(64), 0, s_copy, d_cnt + 1,
+						   std::min<uint32_t>(ccap, LDA_STREAM_HDR_SLOTS), d_hlens, d_hinfo,
+						   d_cls);
+				ST_TRY(hipGetLastError());
+			}
 			ST_TRY(hipEventRecord(d->streams.mark2, s_copy));
 			cache_queued = true;
 			/* the counts and the first candidates in one round trip (a stream
@@ -517,11 +675,17 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 			const uint32_t first = std::min<uint32_t>(ccap, 2048);
 			uint32_t cnt[2];
 			cands.resize(first);
-			if (!pin_phase(64 + (size_t)first * 8))
+			if (!pin_phase(64 + (size_t)first * 8 + (rows_here ? 128 + (size_t)ROWS_FIRST * 16 : 0)))
 				return false;
 			ST_TRY(back(cnt, d_cnt, 8));
 			ST_TRY(back(cands.data(), d_cand, (size_t)first * 8));
+			if (rows_here)
+				ST_TRY(rows_back());
+			if (dev && carry.kind == LDA_CHUNK_HEADER)
+				ST_TRY(pk_queue(carry.start_bit));
 			ST_TRY(pin_sync());
+			if (rows_here && !rows_done())
+				return false;
 			const uint32_t nc = std::min(cnt[1], ccap);
 			cands.resize(nc);
 			if (nc > first) {
@@ -532,6 +696,17 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 			}
 			for (uint32_t i = 0; i < nc && i < LDA_STREAM_HDR_SLOTS; i++)
 				hdr_slot.emplace(cands[i], i + 1);
+			hcls.clear();
+			if (d_cls && nc) {
+				/* the classes of the headers in the slots, behind the kernel that
+				 * parsed them: the plan needs them */
+				hcls.resize(std::min<uint32_t>(nc, LDA_STREAM_HDR_SLOTS));
+				if (!pin_phase(hcls.size() * 8))
+					return false;
+				ST_TRY(hipMemcpyAsync(pin_base, d_cls, hcls.size() * 8, hipMemcpyDeviceToHost, s_copy));
+				ST_TRY(hipStreamSynchronize(s_copy));
+				memcpy(hcls.data(), pin_base, hcls.size() * 8);
+			}
 			std::sort(cands.begin(), cands.end());
 			S[2] += cnt[0];
 			S[3] += nc;
@@ -573,8 +748,9 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 			 * is the true parse; the chain finds it by its key, in the first
 			 * count pass.  (A match across P is not covered: a repair.) */
 			uint64_t tok0 = 0;
-			const uint32_t hi = first.kind == LDA_CHUNK_HEADER && !env.stream_chunk ?
-						    one_length_code(first.hdr_bit, &tok0) : 0;
+			const uint32_t hi = first.kind != LDA_CHUNK_HEADER || env.stream_chunk ? 0 :
+					    dev ? one_length_slot(first.hdr_bit, &tok0) :
+						  one_length_code(first.hdr_bit, &tok0);
 			/* (the starts of one position are counted together by ONE wave,
 			 * phase_count() of inflate_stream.hip, when the chunk is one
 			 * round of input: 1.5 x TN <= 64 pieces of 384 bits) */
@@ -656,6 +832,8 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 					cs.push_back(c);
 			}
 			uint64_t last_at = carry.start_bit;
+			if (dev && carry.kind == LDA_CHUNK_HEADER && !fetch_pk(carry.start_bit))
+				return false;
 			/* a STATIC block at the carried-in state (the host sees the
 			 * header, or the state says so): chunks under the static
 			 * codes up to the next candidate.  They stop at the block's
@@ -1087,6 +1265,14 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 	const size_t consumed = (size_t)((end_bit + 7) / 8);
 	int32_t result = LIBDEFLATE_SUCCESS;
 	uint32_t sum = format == LIBDEFLATE_AMD_GZIP ? 0u : 1u;
+	/* (b) the footer of a stream in device memory: with the last round trip */
+	uint8_t fbytes[8] = { 0 };
+	if (dev && ftr && !total) {
+		if (!pin_phase(64))
+			return false;
+		ST_TRY(back(fbytes, in + hdr + consumed, ftr));
+		ST_TRY(pin_sync());
+	}
 	if (total) {
 		S[1] = WHY_DEVICE;
 		if (!d_cnt) {
@@ -1101,7 +1287,10 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		ST_TRY(hipMemsetAsync(d_cnt, 0, 16, s_comp));
 		const size_t BATCH = 4096;	/* decode waves per launch (their token scratch: 48 KiB each) */
 		uint16_t *d_sym = (uint16_t *)d->ssym.reserve((size_t)total * 2 + 64);
-		uint8_t *d_out = (uint8_t *)d->sout.reserve((size_t)total + 64);
+		/* (the window and resolve kernels write bytes and, guarded by
+		 * i + 8 <= the chunk's end, 8-byte words at any alignment: nothing at or
+		 * past d_out + total, so they can write a caller's device buffer) */
+		uint8_t *d_out = dev ? out : (uint8_t *)d->sout.reserve((size_t)total + 64);
 		uint32_t *d_tok = (uint32_t *)d->tokens.reserve(
 			std::min<size_t>(na, BATCH) * lda_stream_tokcap() * 4 + 64);
 		if (!d_sym || !d_out || !d_tok)
@@ -1212,17 +1401,23 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		ST_TRY(back(&err, d_cnt + 2, 4));
 		if (npc)
 			ST_TRY(back(sums.data(), d_sums, npc * 4));
+		if (dev && ftr)
+			ST_TRY(back(fbytes, in + hdr + consumed, ftr));
 		lap(11);
 		if (debug) {
 			ST_TRY(hipEventSynchronize(d->streams.mark));
 			dbg("decode .. resolve kernels");
 		}
 		/* the output, beside the checksum kernels and the read-backs */
-		ST_TRY(hipStreamWaitEvent(s_copy, d->streams.mark, 0));
-		if (span_out(&d->pinned, d_out, 0, out, (size_t)total, s_copy) != LIBDEFLATE_AMD_OK)
-			return false;
-		lap(13);
+		if (!dev) {
+			ST_TRY(hipStreamWaitEvent(s_copy, d->streams.mark, 0));
+			if (span_out(&d->pinned, d_out, 0, out, (size_t)total, s_copy) != LIBDEFLATE_AMD_OK)
+				return false;
+			lap(13);
+		}
 		ST_TRY(pin_sync());
+		if (dev)
+			lap(13);	/* (nothing to copy: the wait for the last kernel) */
 		bool same = err == 0;
 		for (uint32_t i = 0; i < na && same; i++)
 			same = dr[i].end_bit == accr[i].end_bit && dr[i].nout == accr[i].nout &&
@@ -1239,7 +1434,7 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 						     crc32_concat(sum, sums[i], po[npc + i]);
 	}
 	if (ftr) {
-		const uint8_t *f = in + hdr + consumed;
+		const uint8_t *f = dev ? fbytes : in + hdr + consumed;
 		if (format == LIBDEFLATE_AMD_GZIP) {
 			const uint32_t want = f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) |
 					      ((uint32_t)f[3] << 24);
@@ -1267,6 +1462,128 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 }
 
 } /* namespace lda */
+
+/*
+ * ONE large stream in DEVICE memory -> its bytes in device memory.  The
+ * many-wave path answers for what it decoded cleanly; everything else is the
+ * device batch of one on the same stream, the sequential kernel that follows
+ * the reference's result codes bit for bit - the rule of decompress_one()
+ * (host_decompress.hip).  Blocking: the chain check is the host's.
+ */
+static enum libdeflate_result
+decompress_large_body(struct libdeflate_decompressor *d, int format, const uint8_t *d_in,
+		      size_t in_nbytes, uint8_t *d_out, size_t out_avail, size_t *actual_in_ret,
+		      size_t *actual_out_ret, hipStream_t user)
+{
+	using namespace lda;
+	const char *what = "libdeflate_amd_decompress_large";
+	DeviceGuard on(d->device);
+	if (!on.ok() || !device_ctx() || !d->streams.ensure()) {
+		complain(what, LIBDEFLATE_AMD_NO_DEVICE);
+		return LIBDEFLATE_BAD_DATA;	/* a library-side failure, see decompress_one() */
+	}
+	hipStream_t sc = d->streams.comp;
+	/* the object's streams go on behind what is queued on the caller's: d_in
+	 * may be the product of kernels there */
+	if (hipEventRecord(d->streams.mark, user) != hipSuccess ||
+	    hipStreamWaitEvent(sc, d->streams.mark, 0) != hipSuccess ||
+	    hipStreamWaitEvent(d->streams.copy, d->streams.mark, 0) != hipSuccess) {
+		set_error("%s: %s", what, hipGetErrorString(hipGetLastError()));
+		complain(what, LIBDEFLATE_AMD_NO_DEVICE);
+		return LIBDEFLATE_BAD_DATA;
+	}
+	int32_t res = LIBDEFLATE_BAD_DATA;
+	size_t ain = 0, aout = 0;
+	bool answered = d_in && d_out &&
+			no_unwind("libdeflate_amd_decompress_large (many waves)", false, [&]() {
+				return decompress_stream_parallel(d, format, d_in, in_nbytes, d_out, out_avail,
+								  actual_out_ret == NULL, &res, &ain, &aout,
+								  true);
+			});
+	if (!d_in || !d_out) {
+		memset(g_stats, 0, sizeof(g_stats));
+		g_stats[1] = WHY_DISABLED;
+	}
+	if (!answered) {
+		/* [in_off in_n out_off out_avail ain aout][result]; a NULL buffer of
+		 * size 0 is any valid address */
+		uint8_t *st = (uint8_t *)d->stage.reserve(256);
+		uint64_t *desc = st ? (uint64_t *)d->meta.ensure(256) : nullptr;
+		if (!desc) {
+			(void)hipStreamSynchronize(sc);
+			complain(what, LIBDEFLATE_AMD_OOM);
+			return LIBDEFLATE_BAD_DATA;
+		}
+		uint64_t *dd = (uint64_t *)st;
+		desc[0] = 0;
+		desc[1] = in_nbytes;
+		desc[2] = 0;
+		desc[3] = out_avail;
+		desc[4] = desc[5] = 0;
+		desc[6] = (uint64_t)LIBDEFLATE_BAD_DATA;
+		int rc = LIBDEFLATE_AMD_OK;
+		if (hipMemcpyAsync(st, desc, 56, hipMemcpyHostToDevice, sc) != hipSuccess)
+			rc = LIBDEFLATE_AMD_NO_DEVICE;
+		if (rc == LIBDEFLATE_AMD_OK)
+			rc = libdeflate_amd_decompress_batch(d, format, 1, d_in ? d_in : st, dd, dd + 1,
+							     d_out ? d_out : st + 128, dd + 2, dd + 3,
+							     (int32_t *)(dd + 6), dd + 4,
+							     actual_out_ret ? dd + 5 : NULL, sc);
+		if (rc == LIBDEFLATE_AMD_OK &&
+		    hipMemcpyAsync(desc, st, 56, hipMemcpyDeviceToHost, sc) != hipSuccess)
+			rc = LIBDEFLATE_AMD_NO_DEVICE;
+		if (hipStreamSynchronize(sc) != hipSuccess && rc == LIBDEFLATE_AMD_OK)
+			rc = LIBDEFLATE_AMD_NO_DEVICE;
+		if (rc != LIBDEFLATE_AMD_OK) {
+			if (rc == LIBDEFLATE_AMD_NO_DEVICE)
+				set_error("%s: %s", what, hipGetErrorString(hipGetLastError()));
+			complain(what, rc);
+			return LIBDEFLATE_BAD_DATA;
+		}
+		res = (int32_t)desc[6];
+		ain = (size_t)desc[4];
+		aout = (size_t)desc[5];
+	}
+	if (res == LIBDEFLATE_SUCCESS) {
+		if (actual_in_ret)
+			*actual_in_ret = ain;
+		if (actual_out_ret)
+			*actual_out_ret = aout;
+	}
+	return (enum libdeflate_result)res;
+}
+
+extern "C" LIBDEFLATEAPI enum libdeflate_result
+libdeflate_amd_decompress_large(struct libdeflate_decompressor *d, int format,
+				const void *d_in, size_t in_nbytes, void *d_out,
+				size_t out_nbytes_avail, size_t *actual_in_nbytes_ret,
+				size_t *actual_out_nbytes_ret, void *stream)
+{
+	using namespace lda;
+	if (!d) {
+		set_error("libdeflate_amd_decompress_large: NULL decompressor");
+		return LIBDEFLATE_BAD_DATA;
+	}
+	if (!d_in && in_nbytes) {
+		set_error("libdeflate_amd_decompress_large: NULL d_in with in_nbytes != 0");
+		return LIBDEFLATE_BAD_DATA;
+	}
+	if (!d_out && out_nbytes_avail) {
+		set_error("libdeflate_amd_decompress_large: NULL d_out with out_nbytes_avail != 0");
+		return LIBDEFLATE_BAD_DATA;
+	}
+	if (format != LIBDEFLATE_AMD_DEFLATE && format != LIBDEFLATE_AMD_ZLIB &&
+	    format != LIBDEFLATE_AMD_GZIP) {
+		set_error("libdeflate_amd_decompress_large: format %d is not DEFLATE, zlib or gzip",
+			  format);
+		return LIBDEFLATE_BAD_DATA;
+	}
+	return no_unwind("libdeflate_amd_decompress_large", LIBDEFLATE_BAD_DATA, [&]() {
+		return decompress_large_body(d, format, (const uint8_t *)d_in, in_nbytes,
+					     (uint8_t *)d_out, out_nbytes_avail, actual_in_nbytes_ret,
+					     actual_out_nbytes_ret, (hipStream_t)stream);
+	});
+}
 
 extern "C" LIBDEFLATEAPI void libdeflate_amd_stream_stats(uint64_t *out)
 {

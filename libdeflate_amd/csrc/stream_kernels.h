@@ -95,4 +95,16 @@ extern "C" size_t lda_stream_chunk_lds(void);
 extern "C" size_t lda_stream_find_b_lds(void);
 extern "C" size_t lda_stream_tokcap(void);	/* u32 words of token scratch per decode wave */
 
+/* stream_probe_kernels.hip: what the host reads out of a stream in host memory
+ * itself, for a stream in device memory.  rows[]: struct lda_stored_row
+ * (stored_rows.h) as one 16-byte store each; cls[i] = { longest literal
+ * codeword of a block of one codeword length or 0, bits from the header of
+ * slot i to its first token }. */
+extern "C" __global__ void
+lda_stream_find_stored_kernel(const uint8_t *inp, uint64_t in_n, uint64_t bp0, uint4 *rows,
+			      uint32_t *count, uint32_t cap);
+extern "C" __global__ void
+lda_stream_hdr_class_kernel(const uint32_t *ncand, uint32_t nslots, const uint8_t *hdr_lens,
+			    const uint32_t *hdr_info, uint2 *cls);
+
 #endif /* LDA_STREAM_KERNELS_H */
