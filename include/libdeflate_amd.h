@@ -783,6 +783,117 @@ libdeflate_amd_decompress_large(struct libdeflate_decompressor *decompressor, in
 				void *stream);
 
 /*
+ * A SEEK INDEX over one plain stream, and reads through it: the counterpart
+ * of the BGZF reader below for streams nobody prepared (gzip, pigz, zlib, a
+ * web server, a PNG writer), which have no member boundaries to start at.
+ *
+ * libdeflate_amd_decompress_large_index is libdeflate_amd_decompress_large -
+ * the same arguments, result, *actual_in_nbytes_ret, *actual_out_nbytes_ret,
+ * the same rule for which decoder answers, no byte written at or past d_out +
+ * out_nbytes_avail, blocking - and keeps what the many-wave decoder proved on
+ * the way: POINTS at which a decode can start (a chunk of its chain: output
+ * offset, exact start bit, governing block header), about every `spacing`
+ * bytes of output, each with the 32 KiB of output in front of it.
+ *
+ * `index` (HOST, index_avail u64 entries) receives rows of
+ * LIBDEFLATE_AMD_SEEK_WORDS = 4 u64:
+ *   row 0        { magic / version word, format, byte offset of the raw
+ *                  DEFLATE stream inside d_in (the container header), n }
+ *   rows 1 .. n  the points { out_off, start_bit, hdr_bit, kind }: bits
+ *                  relative to the raw stream; kind 0 = the point is the block
+ *                  header at hdr_bit = start_bit, kind 2 = the token boundary
+ *                  start_bit inside the block whose header is at hdr_bit
+ *   row n + 1    { total output bytes, bytes of the raw stream up to the end
+ *                  of its final block, footer bytes, end marker }
+ * so 4 (n + 2) entries are written and *points_ret = n.  Point 0 is always the
+ * stream's first bit at output offset 0; out_off and start_bit rise strictly.
+ * d_windows (DEVICE, windows_avail bytes, any alignment) receives window k -
+ * the output bytes [out_off - 32768, out_off) of point k, zeros below offset 0
+ * - at d_windows + LIBDEFLATE_AMD_SEEK_WINDOW k.  The index is plain data: it
+ * may be copied and kept as long as the stream's bytes stay what they are.
+ *
+ * Points are taken greedily: the first chunk of the chain at least `spacing`
+ * bytes of output behind the last point.  A chunk that was decoded under the
+ * static codes without its block's header cannot be one (it stops at its
+ * block's end): a Z_FIXED stream of one giant block keeps few or no points
+ * beyond point 0.  The capacity is min(index_avail / 4 - 2, windows_avail /
+ * 32768) points; when the points do not fit, `spacing` is doubled until they
+ * do, so the index always covers the whole stream.  Before the call returns
+ * every interval (point k to point k + 1) is parsed once more from the point's
+ * own row; a point whose interval does not end exactly at the next point with
+ * exactly the bytes between is dropped.  When the sequential decoder answered
+ * with LIBDEFLATE_SUCCESS (a stream under LDA_STREAM_PAR_MIN bytes,
+ * LDA_NO_STREAM_PAR, ...) the index is point 0 and the closing row.  On any
+ * other result *points_ret = 0 and the index is undefined.
+ *
+ * Refused before any device work, LIBDEFLATE_BAD_DATA with the reason in
+ * libdeflate_amd_last_error(): what libdeflate_amd_decompress_large refuses, a
+ * capacity below 1, spacing == 0, a NULL index, points_ret or d_windows.
+ * Nothing is written through the result pointers then.
+ *
+ * What it costs: 32 KiB of device memory and 32 bytes of host memory per
+ * point, one more parse of the stream for the check, one gather kernel.  Out
+ * of scope: preset dictionaries, further gzip members (the first member is
+ * indexed, as libdeflate_amd_decompress_large decodes it), streams of 4 GiB
+ * and more, a host-pointer form, a file format for the index.
+ */
+#define LIBDEFLATE_AMD_SEEK_WINDOW 32768	/* bytes of d_windows per point */
+#define LIBDEFLATE_AMD_SEEK_WORDS 4		/* u64 per row of the index */
+
+LIBDEFLATEAPI enum libdeflate_result
+libdeflate_amd_decompress_large_index(struct libdeflate_decompressor *decompressor, int format,
+				      const void *d_in, size_t in_nbytes,
+				      void *d_out, size_t out_nbytes_avail,
+				      size_t *actual_in_nbytes_ret, size_t *actual_out_nbytes_ret,
+				      size_t spacing,
+				      uint64_t *index, size_t index_avail,
+				      size_t *points_ret,
+				      void *d_windows, size_t windows_avail,
+				      void *stream);
+
+/*
+ * n_ranges pieces of the stream's output through such an index, back to back
+ * into d_out; enqueues on `stream` only.  d_in / in_nbytes: the stream the
+ * index was made from (its first in_nbytes bytes; at least what the closing
+ * row needs).  `index` (index_words u64 entries, at least 4 (n + 2)) and
+ * `ranges` (pairs (offset, length) in output bytes) are HOST arrays and may be
+ * reused when the call returns; d_windows is the build's window array.
+ *
+ * Every interval a range touches is decoded ONCE, however many ranges touch
+ * it: parsed (lda_stream_count_kernel), then - only if that parse ended at
+ * the next point's start bit (the last interval: with the stream's final
+ * block, at the raw stream's last byte) with exactly the bytes the index says
+ * - decoded into 16-bit symbols in the object's scratch, whose slots are sized
+ * from the index; then every range's share of it is resolved against the
+ * interval's window into its place in d_out.  d_results[r] (device) = 0, or
+ * LIBDEFLATE_BAD_DATA when an interval of range r did not parse as indexed or
+ * refers to bytes in front of the stream; a failed range does not affect the
+ * others (its bytes in d_out are undefined).  So a d_in or d_windows that does
+ * not belong to the index cannot make the call write outside the object's
+ * scratch and [d_out, d_out + out_avail).  There is NO CHECKSUM of a partial
+ * read - no format states one: bytes of d_in changed so that an interval still
+ * parses to the same end and length are not detected.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL pointer (d_out may be NULL when the
+ * ranges are all empty), a bad magic word or format, rows that do not rise
+ * strictly in out_off and start_bit, an index whose closing row needs more
+ * input than in_nbytes, a range past the total, ranges that need more than
+ * out_avail.  LIBDEFLATE_AMD_OOM when the scratch for the touched intervals
+ * (2 bytes per byte of them, and 48 KiB per decoding wave) cannot be had.
+ * d_out must not overlap d_in or d_windows.  The cost: two parses per touched
+ * interval and the resolve, whatever part of the interval is wanted.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_seek_read_batch(struct libdeflate_decompressor *decompressor,
+			       const void *d_in, size_t in_nbytes,
+			       const uint64_t *index, size_t index_words,
+			       const void *d_windows,
+			       size_t n_ranges, const uint64_t *ranges,
+			       void *d_out, size_t out_avail, int32_t *d_results,
+			       void *stream);
+
+/*
  * Reading a BGZF file.  What a member is (htslib's check_header rule): the
  * bytes 1f 8b 08 04, XLEN = 6 at bytes 10..11, the subfield 42 43 02 00 at
  * bytes 12..15 and BSIZE at 16..17; MTIME, XFL and OS are free.  Its size is

@@ -336,6 +336,51 @@ class Decompressor:
             ctypes.byref(ao) if want_actual_out else None, _stream_ptr(stream))
         return r, ai.value, ao.value
 
+    def decompress_large_index(self, fmt, data, out, spacing, max_points, in_nbytes=None,
+                               out_avail=None, want_actual_out=True, stream=None):
+        """libdeflate_amd_decompress_large_index: decompress_large, and a
+        seek index over the stream with a point about every `spacing` bytes
+        of output, at most max_points of them (the spacing is doubled until
+        they fit) -> (result, actual_in, actual_out, index, windows): index
+        is a numpy uint64 array of rows of 4 (header row, the points, closing
+        row; None unless result is 0), windows the uint8 CUDA tensor of
+        32768 bytes per point that read through it.  Blocks."""
+        import torch
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        max_points = int(max_points)
+        idx = np.zeros(binding.SEEK_WORDS * (max(max_points, 0) + 2), dtype=np.uint64)
+        win = torch.empty(max(max_points, 0) * binding.SEEK_WINDOW, dtype=torch.uint8,
+                          device=data.device)
+        ai, ao, npts = c_size_t(0), c_size_t(0), c_size_t(0)
+        r = self._lib.libdeflate_amd_decompress_large_index(
+            self._h, FORMATS[fmt], data.data_ptr() if n else None, n,
+            out.data_ptr() if avail else None, avail, ctypes.byref(ai),
+            ctypes.byref(ao) if want_actual_out else None, int(spacing),
+            idx.ctypes.data_as(c_void_p), idx.size, ctypes.byref(npts),
+            win.data_ptr() if max_points > 0 else None, win.numel(), _stream_ptr(stream))
+        if r != 0:
+            return r, ai.value, ao.value, None, None
+        rows = idx[:binding.SEEK_WORDS * (npts.value + 2)].reshape(-1, binding.SEEK_WORDS).copy()
+        return r, ai.value, ao.value, rows, win[:npts.value * binding.SEEK_WINDOW]
+
+    def seek_read_batch(self, data, index, windows, ranges, out, results, stream=None,
+                        in_nbytes=None, out_avail=None):
+        """libdeflate_amd_seek_read_batch: `ranges` (host, rows of (offset,
+        nbytes) of the uncompressed data) of the stream in the CUDA tensor
+        `data`, through the index and windows of decompress_large_index,
+        back to back into `out`; results: int32 CUDA tensor, one per range (0
+        or BAD_DATA).  Only enqueues on `stream`."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1)
+        rng = np.ascontiguousarray(ranges, dtype=np.uint64).reshape(-1, 2)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_seek_read_batch(
+            self._h, data.data_ptr(), n, idx.ctypes.data_as(c_void_p), idx.size,
+            windows.data_ptr(), len(rng), rng.ctypes.data_as(c_void_p),
+            out.data_ptr() if out.numel() else None, avail,
+            results.data_ptr() if len(rng) else None, _stream_ptr(stream)), "seek_read_batch")
+
     def decompress_batch(self, fmt, data, in_offsets, in_nbytes, out,
                          out_offsets, out_avail, results, actual_in=None,
                          actual_out=None, stream=None):

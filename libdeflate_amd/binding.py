@@ -26,6 +26,8 @@ BGZF_BLOCK, BGZF_MEMBER_MAX, BGZF_EOF_BYTES, BGZF_NO_EOF = 65280, 65536, 28, 1
 # the BGZF reader: result[0] beyond enum libdeflate_result, the flag bit of
 # result[4], the words of a result, the read flag for virtual offsets
 BGZF_MORE_MEMBERS, BGZF_HAS_EOF, BGZF_RESULT_WORDS, BGZF_VOFFSETS = 16, 1, 5, 2
+# the seek index: bytes of window per point, u64 per row
+SEEK_WINDOW, SEEK_WORDS = 32768, 4
 # the size query: the limit a NULL d_out_limit stands for
 SIZE_LIMIT_MAX = 0xFFFFFFFF
 
@@ -65,6 +67,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_decompress_sizes_batch", "libdeflate_amd_decompress_sizes_batch_dict",
     "libdeflate_amd_decompress_sizes_batch_host", "libdeflate_amd_decompress_batch_packed",
     "libdeflate_amd_compress_large_batch", "libdeflate_amd_decompress_large",
+    "libdeflate_amd_decompress_large_index", "libdeflate_amd_seek_read_batch",
 ]
 
 _lib = None
@@ -170,6 +173,11 @@ def load():
     sig("libdeflate_amd_compress_large_batch", c_int, P, c_int, P, SZ, P, SZ, P, P)
     # ... and one such stream from device memory to device memory (blocking)
     sig("libdeflate_amd_decompress_large", c_int, P, c_int, P, SZ, P, SZ, psz, psz, P)
+    # ... the same with a seek index (host rows, device windows), and ranged
+    # reads through such an index (index and ranges on the host, enqueue only)
+    sig("libdeflate_amd_decompress_large_index", c_int, P, c_int, P, SZ, P, SZ, psz, psz,
+        SZ, P, SZ, psz, P, SZ, P)
+    sig("libdeflate_amd_seek_read_batch", c_int, P, P, SZ, P, SZ, P, SZ, P, P, SZ, P, P)
     _lib = lib
     return lib
 

@@ -162,6 +162,10 @@ libdeflate_free_decompressor(struct libdeflate_decompressor *d)
 	d->bgzf_desc.release();
 	if (d->bgzf_up)
 		(void)hipEventDestroy(d->bgzf_up);
+	d->seek.release();
+	d->seek_desc.release();
+	if (d->seek_up)
+		(void)hipEventDestroy(d->seek_up);
 	free_func_t f = d->free_func;
 	d->~libdeflate_decompressor();
 	f(d);

@@ -57,6 +57,12 @@ struct libdeflate_decompressor {
 	lda::DevBuf bgzf;
 	lda::PinnedBuf bgzf_desc;
 	hipEvent_t bgzf_up = nullptr;
+	/* the seek index (host_seek.hip): descriptors and results of the intervals
+	 * of a build's verification or of a ranged read; a read's descriptors on
+	 * their way up, and the event behind that copy */
+	lda::DevBuf seek;
+	lda::PinnedBuf seek_desc;
+	hipEvent_t seek_up = nullptr;
 };
 
 struct libdeflate_compressor {
@@ -99,11 +105,24 @@ int fanout(Obj *o, size_t n, const size_t *weight,
 /* host_stream.hip: true = answered (result, sizes, output); false = the
  * caller takes the sequential path.  on_device: `in` and `out` are device
  * pointers (libdeflate_amd_decompress_large), the object's streams exist and
- * are ordered behind whatever produces `in`. */
+ * are ordered behind whatever produces `in`.
+ * `seek` (seek_plan.h; NULL: nobody asks): on a SUCCESS answered here, the
+ * accepted chain and the container's sizes, for a seek index. */
+struct seek_export;
 bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 				const uint8_t *in, size_t in_nbytes, uint8_t *out,
 				size_t out_avail, bool exact_fill, int32_t *res,
-				size_t *ain, size_t *aout, bool on_device = false);
+				size_t *ain, size_t *aout, bool on_device = false,
+				seek_export *seek = nullptr);
+/* host_stream.hip: the body of libdeflate_amd_decompress_large (arguments
+ * checked by the caller, `what` names it in errors); with `seek`, also what
+ * libdeflate_amd_decompress_large_index (host_seek.hip) builds its index from -
+ * of a stream the sequential decoder answered for, point 0 alone */
+enum libdeflate_result
+decompress_large_body(struct libdeflate_decompressor *d, int format, const uint8_t *d_in,
+		      size_t in_nbytes, uint8_t *d_out, size_t out_avail, size_t *actual_in_ret,
+		      size_t *actual_out_ret, hipStream_t user, const char *what,
+		      seek_export *seek);
 }
 
 #endif /* LDA_HOST_OBJECTS_H */

@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "stream_kernels.h"
 #include "stored_rows.h"
+#include "seek_plan.h"
 
 namespace lda {
 
@@ -122,7 +123,7 @@ static bool launch_count(hipStream_t st, uint32_t n, const lda_stream_chunk *d_c
 bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 				const uint8_t *in, size_t in_nbytes, uint8_t *out,
 				size_t out_avail, bool exact_fill, int32_t *res,
-				size_t *ain, size_t *aout, bool on_device)
+				size_t *ain, size_t *aout, bool on_device, seek_export *seek)
 {
 	/*
 	 * THE INPUT SOURCE.  on_device == false: `in` is the caller's host
@@ -1455,6 +1456,17 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 		*ain = hdr + consumed + ftr;
 		*aout = (size_t)total;
 	}
+	if (seek && result == LIBDEFLATE_SUCCESS) {
+		/* the chain that was proved, for a seek index (host_seek.hip) */
+		seek->parallel = seek->known = true;
+		seek->raw_off = hdr;
+		seek->raw_nbytes = consumed;
+		seek->ftr = ftr;
+		seek->total = total;
+		seek->chain.resize(na);
+		for (uint32_t i = 0; i < na; i++)
+			seek->chain[i] = { acc[i].out_off, acc[i].start_bit, acc[i].hdr_bit, acc[i].kind };
+	}
 	S[0] = 1;
 	S[1] = WHY_OK;
 	S[7] = total;
@@ -1470,13 +1482,12 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
  * the reference's result codes bit for bit - the rule of decompress_one()
  * (host_decompress.hip).  Blocking: the chain check is the host's.
  */
-static enum libdeflate_result
+namespace lda {
+enum libdeflate_result
 decompress_large_body(struct libdeflate_decompressor *d, int format, const uint8_t *d_in,
 		      size_t in_nbytes, uint8_t *d_out, size_t out_avail, size_t *actual_in_ret,
-		      size_t *actual_out_ret, hipStream_t user)
+		      size_t *actual_out_ret, hipStream_t user, const char *what, seek_export *seek)
 {
-	using namespace lda;
-	const char *what = "libdeflate_amd_decompress_large";
 	DeviceGuard on(d->device);
 	if (!on.ok() || !device_ctx() || !d->streams.ensure()) {
 		complain(what, LIBDEFLATE_AMD_NO_DEVICE);
@@ -1498,7 +1509,7 @@ decompress_large_body(struct libdeflate_decompressor *d, int format, const uint8
 			no_unwind("libdeflate_amd_decompress_large (many waves)", false, [&]() {
 				return decompress_stream_parallel(d, format, d_in, in_nbytes, d_out, out_avail,
 								  actual_out_ret == NULL, &res, &ain, &aout,
-								  true);
+								  true, seek);
 			});
 	if (!d_in || !d_out) {
 		memset(g_stats, 0, sizeof(g_stats));
@@ -1544,6 +1555,33 @@ decompress_large_body(struct libdeflate_decompressor *d, int format, const uint8
 		ain = (size_t)desc[4];
 		aout = (size_t)desc[5];
 	}
+	if (seek && !answered && res == LIBDEFLATE_SUCCESS) {
+		/* the sequential decoder answered: the index is point 0 alone, and it
+		 * needs the container's sizes (the header from the stream's first
+		 * bytes, fetched here: 4 KiB, or 1 MiB for a gzip header that long) */
+		size_t hdr = 0, ftr = 0;
+		bool have = false;
+		for (size_t want : { (size_t)4096, (size_t)1 << 20 }) {
+			const size_t n = std::min(in_nbytes, want);
+			uint8_t *h = n ? (uint8_t *)d->meta.ensure(n) : nullptr;
+			if (n && (!h || hipMemcpyAsync(h, d_in, n, hipMemcpyDeviceToHost, sc) != hipSuccess ||
+				  hipStreamSynchronize(sc) != hipSuccess))
+				break;
+			if (container(format, h, in_nbytes, n, &hdr, &ftr) && hdr + ftr <= ain) {
+				have = true;
+				break;
+			}
+			if (n == in_nbytes)
+				break;
+		}
+		seek->parallel = false;
+		seek->known = have;
+		seek->raw_off = hdr;
+		seek->raw_nbytes = have ? ain - hdr - ftr : 0;
+		seek->ftr = ftr;
+		seek->total = actual_out_ret ? aout : out_avail;
+		seek->chain.assign(1, seek_link{ 0, 0, 0, LDA_CHUNK_HEADER });
+	}
 	if (res == LIBDEFLATE_SUCCESS) {
 		if (actual_in_ret)
 			*actual_in_ret = ain;
@@ -1552,6 +1590,7 @@ decompress_large_body(struct libdeflate_decompressor *d, int format, const uint8
 	}
 	return (enum libdeflate_result)res;
 }
+} /* namespace lda */
 
 extern "C" LIBDEFLATEAPI enum libdeflate_result
 libdeflate_amd_decompress_large(struct libdeflate_decompressor *d, int format,
@@ -1581,7 +1620,8 @@ libdeflate_amd_decompress_large(struct libdeflate_decompressor *d, int format,
 	return no_unwind("libdeflate_amd_decompress_large", LIBDEFLATE_BAD_DATA, [&]() {
 		return decompress_large_body(d, format, (const uint8_t *)d_in, in_nbytes,
 					     (uint8_t *)d_out, out_nbytes_avail, actual_in_nbytes_ret,
-					     actual_out_nbytes_ret, (hipStream_t)stream);
+					     actual_out_nbytes_ret, (hipStream_t)stream,
+					     "libdeflate_amd_decompress_large", nullptr);
 	});
 }
 

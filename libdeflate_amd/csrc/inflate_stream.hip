@@ -929,6 +929,51 @@ lda_stream_decode_kernel(u32 nchunks, const struct lda_stream_chunk *chunks,
 }
 
 /*
+ * A ranged read through a seek index (host_seek.hip): interval j of the index
+ * - point to point - as one chunk, decoded into its slot of the symbol scratch
+ * (chunks[j].out_off = the slot's first symbol).  THE GATE: the count pass has
+ * parsed the interval already (counted[j]); only when it ended where the index
+ * says - want[j] = { end, bytes }, end = the next point's start bit, or for
+ * the stream's last interval 2^63 | the raw stream's bytes, and then with the
+ * final block - is anything executed, because only then is the slot, which the
+ * host sized from the index, what the decode fills.  Otherwise fail[j] is set
+ * and nothing is written: the input need not be the stream the index was made
+ * from.  (A distance that reaches back before the stream cannot be seen here -
+ * the slot does not lie at the stream's start; lda_seek_resolve_kernel sees
+ * the marker.)
+ */
+extern "C" __global__ void __launch_bounds__(64)
+lda_seek_decode_kernel(u32 nchunks, const struct lda_stream_chunk *chunks,
+		       const struct lda_stream_res *counted, const u64 *want,
+		       struct lda_stream_res *res, const u8 *inp, u64 in_n, u16 *sym,
+		       u32 *tokscratch, u32 *fail)
+{
+	const u32 j = blockIdx.x;
+	if (j >= nchunks)
+		return;
+	const u64 wend = want[2 * j], wbytes = want[2 * j + 1];
+	const bool last = wend >> 63;
+	auto as_indexed = [&](const struct lda_stream_res *r) -> bool {
+		const u64 end_bit = r->end_bit, nout = r->nout;
+		const u32 status = r->status, flags = r->flags;
+		return nout == wbytes && !(flags & LDA_RES_BAD_DIST) &&
+		       (last ? status == LDA_STREAM_FINAL && (end_bit + 7) / 8 == (wend & ~(1ull << 63)) :
+			       status == LDA_STREAM_OK && end_bit == wend);
+	};
+	if (!as_indexed(counted + j)) {		/* (wave-uniform) */
+		if (threadIdx.x == 0)
+			fail[j] = 1;
+		return;
+	}
+	chunk_run<SM_MARK>(chunks + j, res + j, inp, in_n, sym,
+			   tokscratch + (size_t)j * PAR_SCRATCH, NULL, NULL, NULL);
+	/* the same parse again: lane 0 looks at what it has just stored */
+	__threadfence();
+	if (threadIdx.x == 0 && !as_indexed(res + j))
+		fail[j] = 1;
+}
+
+/*
  * The headers the finder accepted, parsed ONCE each (a wave per header: lane 0
  * decodes the code lengths, all lanes store them) beside the host's planning,
  * for every chunk that starts at or inside the block: slot i belongs to

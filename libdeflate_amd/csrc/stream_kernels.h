@@ -107,4 +107,32 @@ extern "C" __global__ void
 lda_stream_hdr_class_kernel(const uint32_t *ncand, uint32_t nslots, const uint8_t *hdr_lens,
 			    const uint32_t *hdr_info, uint2 *cls);
 
+/*
+ * The seek index and its ranged reads (host_seek.hip, seek_plan.h).
+ * lda_seek_decode_kernel (inflate_stream.hip): interval j into its slot of the
+ * symbol scratch, if the count pass ended where the index says: want[2j] = the
+ * end bit (last interval: 2^63 | bytes of the raw stream), want[2j + 1] = the
+ * bytes; else fail[j] = 1 and nothing is written.
+ * seek_kernels.hip: the 32 KiB in front of every point out of the output; one
+ * piece (a range's share of an interval) from symbols to bytes - piece p is
+ * pieces[4p ..] = { interval | range << 32, first symbol, offset in out, bytes },
+ * lowest[j] = the first marker index that exists in window j; a range's
+ * verdict from its pieces' intervals.
+ */
+extern "C" __global__ void
+lda_seek_decode_kernel(uint32_t nchunks, const struct lda_stream_chunk *chunks,
+		       const struct lda_stream_res *counted, const uint64_t *want,
+		       struct lda_stream_res *res, const uint8_t *inp, uint64_t in_n,
+		       uint16_t *sym, uint32_t *tokscratch, uint32_t *fail);
+extern "C" __global__ void
+lda_seek_window_kernel(uint32_t npoints, const uint64_t *out_off, const uint8_t *out,
+		       uint8_t *windows);
+extern "C" __global__ void
+lda_seek_resolve_kernel(uint32_t npieces, uint32_t piece0, const uint64_t *pieces,
+			const uint64_t *win_of, const uint32_t *lowest, const uint16_t *sym,
+			const uint8_t *windows, uint8_t *out, uint32_t *fail);
+extern "C" __global__ void
+lda_seek_verdict_kernel(uint32_t nranges, const uint64_t *first, const uint64_t *pieces,
+			const uint32_t *fail, int32_t *results);
+
 #endif /* LDA_STREAM_KERNELS_H */
