@@ -1008,6 +1008,110 @@ libdeflate_amd_bgzf_decompress(struct libdeflate_decompressor *decompressor,
 			       size_t *actual_out_ret, size_t *members_ret,
 			       uint64_t *index, size_t index_avail, unsigned *flags_ret);
 
+/*
+ * Reading a file of concatenated gzip members that do not state their size:
+ * `cat a.gz b.gz`, WARC archives, mgzip / pgzip output, BGZF-like writers
+ * other than htslib's.  What a member is: exactly what
+ * libdeflate_gzip_decompress_ex accepts at that offset with the rest of the
+ * file as its input - any MTIME / XFL / OS; FEXTRA, FNAME, FCOMMENT and FHCRC
+ * skipped; reserved flag bits refused - with one limit of this reader's own:
+ * FNAME and FCOMMENT together are at most LIBDEFLATE_AMD_GZM_NAME_MAX bytes,
+ * terminators included; a header with more is no member here
+ * (LIBDEFLATE_BAD_DATA where the chain needs it).  Every look-alike of a
+ * header is parsed on speculation with the rest of the file behind it, and
+ * the limit is what keeps a hostile file from making each of them walk to the
+ * end of the file in search of a name's end.  The file is the chain of such members
+ * from byte 0 that ends exactly at in_nbytes: the loop of
+ * libdeflate_amd_gzip_decompress_members, so trailing bytes that are not a
+ * member (zero padding included) and in_nbytes == 0 are LIBDEFLATE_BAD_DATA,
+ * as they are there.
+ */
+#define LIBDEFLATE_AMD_GZM_MORE_MEMBERS     16	/* result[0]; same value as the BGZF reader's */
+#define LIBDEFLATE_AMD_GZM_MORE_CANDIDATES  17	/* result[0] */
+#define LIBDEFLATE_AMD_GZM_RESULT_WORDS     5
+#define LIBDEFLATE_AMD_GZM_SLACK            1024	/* candidate room = max_members + this */
+#define LIBDEFLATE_AMD_GZM_NAME_MAX         65536	/* bytes of FNAME + FCOMMENT of a member */
+
+/*
+ * The whole file in DEVICE memory -> its bytes in device memory.  Enqueues on
+ * `stream` and returns, with the conventions of
+ * libdeflate_amd_bgzf_decompress_batch: device pointers on the object's
+ * device, scratch of the object, d_out must not overlap d_in, and no byte is
+ * ever written at or past d_out + out_avail.
+ *
+ * A member's end is only known once its DEFLATE stream has been parsed, so the
+ * members are found by speculation: every offset p with 1f 8b 08, FLG & 0xE0
+ * == 0 and p + 18 <= in_nbytes is a CANDIDATE (payloads, names and chance
+ * make false ones); one size query counts all candidates at once, each with
+ * the rest of the file as its input; the candidates that the chain from
+ * offset 0 reaches are the members; a prefix sum of their counted sizes gives
+ * every member its place, and one decompress batch (exact input, exact fill)
+ * decodes all of them there.
+ *
+ * max_members sizes the launches and the scratch on the host: the decode batch
+ * has max_members chunks and the finder has room for max_members +
+ * LIBDEFLATE_AMD_GZM_SLACK candidates.  A generous bound costs empty chunks.
+ *
+ * d_result[0..4] (device memory):
+ *   [0] the verdict, the first of these that applies:
+ *       1. LIBDEFLATE_AMD_GZM_MORE_CANDIDATES: the file has more candidates
+ *          than max_members + LIBDEFLATE_AMD_GZM_SLACK;
+ *       2. a broken chain - some position q < in_nbytes, reached from offset 0,
+ *          starts no successfully counted member: the count's verdict of the
+ *          candidate at q (LIBDEFLATE_BAD_DATA, or
+ *          LIBDEFLATE_INSUFFICIENT_SPACE for a member of 4 GiB or more, the
+ *          size query's limit), LIBDEFLATE_BAD_DATA when no candidate stands
+ *          at q.  The count checks everything the decode checks but the
+ *          CRC-32, a wrong ISIZE included;
+ *       3. LIBDEFLATE_AMD_GZM_MORE_MEMBERS;
+ *       4. LIBDEFLATE_INSUFFICIENT_SPACE: the sum of the sizes exceeds
+ *          out_avail;
+ *       (1 to 4 are decided BEFORE the decode: nothing is decoded then and
+ *       d_out is not written)
+ *       5. otherwise the decode result of the first member in file order that
+ *          failed - a wrong CRC-32 is LIBDEFLATE_BAD_DATA there -, else
+ *          LIBDEFLATE_SUCCESS.
+ *       This is the host loop's result for every good file - where [1], [2]
+ *       and [3] are its members, actual_in and actual_out too - and for every
+ *       file with a single defect.
+ *   [1] members; under MORE_MEMBERS how many the file has, under
+ *       MORE_CANDIDATES how many candidates it has, 0 under a broken chain;
+ *   [2] compressed bytes consumed, [3] uncompressed bytes: both 0 under every
+ *       pre-decode verdict except 4., where they are the totals the file needs;
+ *   [4] 0 (reserved).
+ *
+ * d_index: NULL, or device room for 2 (max_members + 1) u64: the pairs
+ * (compressed offset, uncompressed offset) of every member, empty ones
+ * included, then the closing pair (result[2], result[3]).  Written unless [0]
+ * is one of the verdicts 1 to 3.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL object or pointer (d_out may be NULL
+ * only with out_avail == 0, d_in only with in_nbytes == 0), max_members == 0
+ * or above 2^28, in_nbytes above 2^36.
+ *
+ * Not covered: ranged reads through the index (with the index in hand,
+ * libdeflate_amd_decompress_batch_packed over the chosen members does it); a
+ * host-pointer form; the fallback loop of
+ * libdeflate_amd_gzip_decompress_members, which stays as it is; members large
+ * enough to want the many-wave decoder - every member is decoded by one wave
+ * here, correct but slow for a file of a few huge members, for which
+ * libdeflate_amd_decompress_large in a caller's loop stays the tool; preset
+ * dictionaries; members of 4 GiB and more.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_gzip_members_decompress_batch(struct libdeflate_decompressor *decompressor,
+					     const void *d_in, size_t in_nbytes,
+					     size_t max_members, void *d_out, size_t out_avail,
+					     uint64_t *d_result, uint64_t *d_index, void *stream);
+
+/* The index and the five words alone: everything but the decode (out_avail
+ * counts as unlimited, and checksum failures cannot show). */
+LIBDEFLATEAPI int
+libdeflate_amd_gzip_members_index_batch(struct libdeflate_decompressor *decompressor,
+					const void *d_in, size_t in_nbytes, size_t max_members,
+					uint64_t *d_result, uint64_t *d_index, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -281,6 +281,32 @@ class Decompressor:
             index.data_ptr() if index is not None else None, _stream_ptr(stream)),
             "bgzf_index_batch")
 
+    def decompress_gzip_members_batch(self, data, max_members, out, result, index=None,
+                                      stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_gzip_members_decompress_batch: the file of
+        concatenated gzip members in the uint8 torch CUDA tensor `data` (its
+        first in_nbytes bytes) into `out` (out_avail bytes of it, default
+        all).  result: int64 CUDA tensor of 5 (verdict, members, compressed
+        bytes, uncompressed bytes, 0); index: None or an int64 CUDA tensor of
+        2 (max_members + 1).  Only enqueues on `stream`."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_gzip_members_decompress_batch(
+            self._h, data.data_ptr() if n else None, n, int(max_members),
+            out.data_ptr() if avail else None, avail, result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
+            "gzip_members_decompress_batch")
+
+    def index_gzip_members_batch(self, data, max_members, result, index=None, stream=None,
+                                 in_nbytes=None):
+        """libdeflate_amd_gzip_members_index_batch: result and index as in
+        decompress_gzip_members_batch; nothing is decoded."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_gzip_members_index_batch(
+            self._h, data.data_ptr() if n else None, n, int(max_members), result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
+            "gzip_members_index_batch")
+
     def read_bgzf_batch(self, data, index, ranges, out, results, voffsets=False, stream=None,
                         in_nbytes=None, out_avail=None):
         """libdeflate_amd_bgzf_read_batch: `ranges` (host, rows of (begin,

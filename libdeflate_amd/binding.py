@@ -26,6 +26,10 @@ BGZF_BLOCK, BGZF_MEMBER_MAX, BGZF_EOF_BYTES, BGZF_NO_EOF = 65280, 65536, 28, 1
 # the BGZF reader: result[0] beyond enum libdeflate_result, the flag bit of
 # result[4], the words of a result, the read flag for virtual offsets
 BGZF_MORE_MEMBERS, BGZF_HAS_EOF, BGZF_RESULT_WORDS, BGZF_VOFFSETS = 16, 1, 5, 2
+# the reader of concatenated gzip members: result[0] beyond enum
+# libdeflate_result, the words of a result, candidate room beyond max_members
+GZM_MORE_MEMBERS, GZM_MORE_CANDIDATES, GZM_RESULT_WORDS, GZM_SLACK = 16, 17, 5, 1024
+GZM_NAME_MAX = 65536    # bytes of FNAME + FCOMMENT the member reader accepts
 # the seek index: bytes of window per point, u64 per row
 SEEK_WINDOW, SEEK_WORDS = 32768, 4
 # the size query: the limit a NULL d_out_limit stands for
@@ -68,6 +72,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_decompress_sizes_batch_host", "libdeflate_amd_decompress_batch_packed",
     "libdeflate_amd_compress_large_batch", "libdeflate_amd_decompress_large",
     "libdeflate_amd_decompress_large_index", "libdeflate_amd_seek_read_batch",
+    "libdeflate_amd_gzip_members_decompress_batch", "libdeflate_amd_gzip_members_index_batch",
 ]
 
 _lib = None
@@ -178,6 +183,10 @@ def load():
     sig("libdeflate_amd_decompress_large_index", c_int, P, c_int, P, SZ, P, SZ, psz, psz,
         SZ, P, SZ, psz, P, SZ, P)
     sig("libdeflate_amd_seek_read_batch", c_int, P, P, SZ, P, SZ, P, SZ, P, P, SZ, P, P)
+    # a file of concatenated gzip members: device file -> device bytes, the
+    # index alone (enqueue only)
+    sig("libdeflate_amd_gzip_members_decompress_batch", c_int, P, P, SZ, SZ, P, SZ, P, P, P)
+    sig("libdeflate_amd_gzip_members_index_batch", c_int, P, P, SZ, SZ, P, P, P)
     _lib = lib
     return lib
 

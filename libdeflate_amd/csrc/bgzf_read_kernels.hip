@@ -66,23 +66,6 @@ pre_status(const u32 *__restrict__ state, u64 total, u64 out_avail, u64 max_memb
 	return LDA_SUCCESS;
 }
 
-/* the 16 bytes at in + off as four words; bytes at or past n read as 0 */
-static __device__ __forceinline__ uint4 load16_guard(const u8 *__restrict__ in, u64 off, u64 n)
-{
-	uint4 v = { 0, 0, 0, 0 };
-	if (off + 16 <= n) {
-		__builtin_memcpy(&v, in + off, 16);
-	} else if (off < n) {
-		u32 w[4] = { 0, 0, 0, 0 };
-#pragma unroll
-		for (u32 k = 0; k < 16; k++)
-			if (off + k < n)
-				w[k >> 2] |= (u32)in[off + k] << (8 * (k & 3));
-		v = make_uint4(w[0], w[1], w[2], w[3]);
-	}
-	return v;
-}
-
 /* member size by the header rule from 18 header bytes, 0 = no member: bytes
  * 4..9 (MTIME, XFL, OS) are free.  left = bytes of the file from this offset */
 static __device__ __forceinline__ u32 header_size(const u8 *h, u64 left)

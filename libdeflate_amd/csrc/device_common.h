@@ -185,6 +185,23 @@ copy_span(const u8 *__restrict__ src, u8 *__restrict__ dst, u64 len, u32 tid)
 		dst[tail + tid] = src[tail + tid];
 }
 
+/* the 16 bytes at in + off as four words; bytes at or past n read as 0 */
+static __device__ __forceinline__ uint4 load16_guard(const u8 *__restrict__ in, u64 off, u64 n)
+{
+	uint4 v = { 0, 0, 0, 0 };
+	if (off + 16 <= n) {
+		__builtin_memcpy(&v, in + off, 16);
+	} else if (off < n) {
+		u32 w[4] = { 0, 0, 0, 0 };
+#pragma unroll
+		for (u32 k = 0; k < 16; k++)
+			if (off + k < n)
+				w[k >> 2] |= (u32)in[off + k] << (8 * (k & 3));
+		v = make_uint4(w[0], w[1], w[2], w[3]);
+	}
+	return v;
+}
+
 /*
  * Optional phase profiling (make PROFILE=1 builds libdeflate_amd_prof.so):
  * thread 0 of each workgroup accumulates s_memtime deltas per phase.

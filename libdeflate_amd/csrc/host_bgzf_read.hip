@@ -27,20 +27,6 @@ using namespace lda;
 #define BR_SLOT ((size_t)LIBDEFLATE_AMD_BGZF_MEMBER_MAX)
 #define BR_MIN_MEMBER 28
 
-/* carves arrays out of one device allocation; p == NULL only sizes it */
-struct Carve {
-	uint8_t *p;
-	size_t at = 0;
-	explicit Carve(void *base) : p((uint8_t *)base) {}
-	template <typename T> T *take(size_t count, size_t align = 16)
-	{
-		at = align_up(at, align);
-		T *r = p ? (T *)(p + at) : nullptr;
-		at += count * sizeof(T);
-		return r;
-	}
-};
-
 struct FileScratch {
 	uint64_t *cand_pos, *counts, *offs, *bsum_a, *isize, *bsum_b;
 	uint64_t *in_off, *in_n, *out_off, *out_av, *ain;

@@ -196,6 +196,20 @@ int span_out(PinnedPair *pp, const uint8_t *d_base, uint64_t d_off, uint8_t *dst
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+/* carves arrays out of one device allocation; p == NULL only sizes it */
+struct Carve {
+	uint8_t *p;
+	size_t at = 0;
+	explicit Carve(void *base) : p((uint8_t *)base) {}
+	template <typename T> T *take(size_t count, size_t align = 16)
+	{
+		at = align_up(at, align);
+		T *r = p ? (T *)(p + at) : nullptr;
+		at += count * sizeof(T);
+		return r;
+	}
+};
+
 /*
  * Nothing may unwind through an extern "C" entry point: the reference is C and
  * its callers have no handlers, an exception that reaches them ends the

@@ -53,7 +53,9 @@ struct libdeflate_decompressor {
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */
 	/* BGZF files read on the device (host_bgzf_read.hip): candidates, chain,
 	 * descriptors, edge slots; the descriptors of a ranged read on their way
-	 * up, and the event behind that copy */
+	 * up, and the event behind that copy.  The reader of concatenated gzip
+	 * members (host_gzip_members.hip) keeps its candidates, counts, chain and
+	 * descriptors in the same buffer */
 	lda::DevBuf bgzf;
 	lda::PinnedBuf bgzf_desc;
 	hipEvent_t bgzf_up = nullptr;
@@ -101,6 +103,15 @@ template <typename Obj>
 int fanout(Obj *o, size_t n, const size_t *weight,
 	   const std::function<Obj *(const struct libdeflate_options *)> &alloc,
 	   const std::function<int(Obj *, size_t, size_t)> &body);
+
+/* host_sizes.hip: the size query on a stream (arguments checked by the
+ * callers); s: sizes_scratch_bytes(n) bytes of device memory that stay
+ * untouched until the query has run */
+size_t sizes_scratch_bytes(size_t n);
+int sizes_enqueue(DeviceCtx *c, uint8_t *s, int format, size_t n, const void *d_in,
+		  const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
+		  const uint64_t *d_out_limit, int32_t *d_results, uint64_t *d_actual_in,
+		  uint64_t *d_out_nbytes, hipStream_t st, const void *d_dict, size_t dict_nbytes);
 
 /* host_stream.hip: true = answered (result, sizes, output); false = the
  * caller takes the sequential path.  on_device: `in` and `out` are device

@@ -61,17 +61,17 @@ extern "C" __attribute__((visibility("default"))) void lda_sizes_lds_report(size
 }
 
 /* scratch of one size query: [counter 16][order u32 x n][dictionary block] */
-static size_t sizes_scratch_bytes(size_t n)
+size_t lda::sizes_scratch_bytes(size_t n)
 {
 	return align_up(16 + 4 * n, 64) + LDA_DICT_BLK_HDR;
 }
 
 /* arguments checked by the callers; s: sizes_scratch_bytes(n) of device memory */
-static int sizes_enqueue(DeviceCtx *c, uint8_t *s, int format, size_t n, const void *d_in,
-			 const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
-			 const uint64_t *d_out_limit, int32_t *d_results, uint64_t *d_actual_in,
-			 uint64_t *d_out_nbytes, hipStream_t st, const void *d_dict,
-			 size_t dict_nbytes)
+int lda::sizes_enqueue(DeviceCtx *c, uint8_t *s, int format, size_t n, const void *d_in,
+		       const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
+		       const uint64_t *d_out_limit, int32_t *d_results, uint64_t *d_actual_in,
+		       uint64_t *d_out_nbytes, hipStream_t st, const void *d_dict,
+		       size_t dict_nbytes)
 {
 	uint32_t *next = (uint32_t *)s, *order = NULL, *dict_id = NULL;
 	uint32_t dlen = 0;

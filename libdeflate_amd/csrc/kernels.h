@@ -269,6 +269,42 @@ extern "C" __global__ void
 lda_bgzf_range_kernel(uint64_t n_ranges, const uint64_t *first, const uint64_t *in_n,
 		      const int32_t *results, const uint64_t *actual_in, int32_t *range_results);
 
+/* gzip_members_kernels.hip: a file of concatenated gzip members read from
+ * device memory (host_gzip_members.hip); the chain among the candidates is
+ * found by lda_bgzf_jump_kernel / _top_ / _members_ above, whose state words
+ * LDA_BR_CHAIN and LDA_BR_MEMBERS it shares */
+#define LDA_GZM_BREAK 3		/* state word: the verdict of a broken chain */
+#define LDA_GZM_MORE_CANDIDATES 17	/* LIBDEFLATE_AMD_GZM_MORE_CANDIDATES */
+#define LDA_GZM_RESULT_WORDS 5
+#define LDA_GZM_NAME_MAX 65536u	/* LIBDEFLATE_AMD_GZM_NAME_MAX */
+extern "C" __global__ void
+lda_gzm_scan_kernel(const uint8_t *in, uint64_t n, uint64_t *counts, const uint64_t *offsets,
+		    const uint64_t *block_sums, uint64_t cap, uint64_t *cand_pos);
+extern "C" __global__ void
+lda_gzm_slots_kernel(const uint8_t *in, uint64_t n, const uint64_t *k_at, uint64_t cap, const uint64_t *cand_pos,
+		     uint64_t *in_off, uint64_t *in_n);
+extern "C" __global__ void
+lda_gzm_size32_kernel(const uint64_t *k_at, uint64_t cap, int32_t *results,
+		      const uint64_t *actual_in, uint32_t *cand_size);
+extern "C" __global__ void
+lda_gzm_break_kernel(const uint64_t *k_at, uint64_t cap, const uint64_t *cand_pos,
+		     const uint32_t *next, const uint32_t *exit_at, const int32_t *results,
+		     uint32_t *state);
+extern "C" __global__ void
+lda_gzm_msize_kernel(uint64_t max_members, const uint64_t *k_at, uint64_t cap,
+		     const uint64_t *cand_pos, const uint64_t *cand_out, const uint32_t *state,
+		     const uint64_t *in_off, uint64_t *msize);
+extern "C" __global__ void
+lda_gzm_desc_kernel(uint64_t max_members, uint64_t out_avail, const uint64_t *k_at, uint64_t cap,
+		    const uint32_t *state, const uint64_t *msize, const uint64_t *block_sums,
+		    uint64_t *in_off, uint64_t *in_n, uint64_t *out_off, uint64_t *out_av,
+		    uint64_t *index);
+extern "C" __global__ void
+lda_gzm_final_kernel(uint64_t n, uint64_t max_members, uint64_t out_avail, const uint64_t *k_at,
+		     uint64_t cap, const uint32_t *state, const uint64_t *total_at,
+		     const uint64_t *in_n, const int32_t *results, const uint64_t *actual_in,
+		     uint64_t *result, uint64_t *index);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
