@@ -27,6 +27,8 @@ void set_error(const char *fmt, ...);
 			return failret;                                      \
 		}                                                            \
 	} while (0)
+/* ... in a function that says "not done here" with false */
+#define LDA_TRY(expr) LDA_HIP_TRY(expr, false)
 
 struct DeviceCtx {
 	int device = -1;

@@ -10,6 +10,7 @@
 #define LDA_HOST_OBJECTS_H
 
 #include "host_common.h"
+#include "stream_types.h"
 #include <functional>
 
 namespace lda {
@@ -125,6 +126,16 @@ bool decompress_stream_parallel(struct libdeflate_decompressor *d, int format,
 				size_t out_avail, bool exact_fill, int32_t *res,
 				size_t *ain, size_t *aout, bool on_device = false,
 				seek_export *seek = nullptr);
+/* host_stream.hip: one launch of lda_stream_count_kernel over n chunks on `st`
+ * (the header cache and the hint rows: NULL where there are none) */
+bool launch_count(hipStream_t st, uint32_t n, const lda_stream_chunk *d_chunks,
+		  lda_stream_res *d_res, const uint8_t *d_raw, uint64_t raw_n,
+		  const uint8_t *d_hlens = nullptr, const uint32_t *d_hinfo = nullptr,
+		  uint16_t *d_hints = nullptr);
+/* decode waves per launch of the stream decode kernels, and their token
+ * scratch (48 KiB each; d->tokens): nullptr + error on failure */
+const size_t STREAM_DECODE_BATCH = 4096;
+uint32_t *stream_token_scratch(struct libdeflate_decompressor *d, size_t nwaves);
 /* host_stream.hip: the body of libdeflate_amd_decompress_large (arguments
  * checked by the caller, `what` names it in errors); with `seek`, also what
  * libdeflate_amd_decompress_large_index (host_seek.hip) builds its index from -

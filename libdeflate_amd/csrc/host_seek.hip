@@ -20,21 +20,10 @@
 #include "stream_kernels.h"
 #include "seek_plan.h"
 
-static_assert(LDA_SEEK_KIND_HEADER == LDA_CHUNK_HEADER && LDA_SEEK_KIND_EXACT == LDA_CHUNK_EXACT &&
-	      LDA_SEEK_HDR_STATIC == LDA_HDR_STATIC, "seek_plan.h restates stream_kernels.h");
 static_assert(LDA_SEEK_ROW == LIBDEFLATE_AMD_SEEK_WORDS && LDA_SEEK_WIN == LIBDEFLATE_AMD_SEEK_WINDOW,
 	      "seek_plan.h restates libdeflate_amd.h");
 
 namespace lda {
-
-#define SK_TRY(expr)                                                          \
-	do {                                                                  \
-		hipError_t e_ = (expr);                                       \
-		if (e_ != hipSuccess) {                                       \
-			set_error("%s: %s", #expr, hipGetErrorString(e_));    \
-			return false;                                         \
-		}                                                             \
-	} while (0)
 
 /* interval k of pts[] as a chunk: from the point's state up to the next
  * point's start bit (the last: to the end of the raw stream) */
@@ -84,15 +73,13 @@ static bool verify_points(struct libdeflate_decompressor *d, const uint8_t *d_ra
 			hc[i] = interval_chunk(pts[k].hdr_bit, pts[k].start_bit, pts[k].kind,
 					       k + 1 < n ? pts[k + 1].start_bit : 8 * x.raw_nbytes, 0);
 		}
-		SK_TRY(hipMemcpyAsync(dv, h, nw * sizeof(lda_stream_chunk), hipMemcpyHostToDevice, sc));
-		hipLaunchKernelGGL(lda_stream_count_kernel, dim3((unsigned)nw), dim3(64),
-				   lda_stream_chunk_lds(), sc, (uint32_t)nw, (const lda_stream_chunk *)dv,
-				   (lda_stream_res *)(dv + res_at), d_raw, x.raw_nbytes, (uint32_t *)NULL,
-				   (const uint8_t *)NULL, (const uint32_t *)NULL, (uint16_t *)NULL);
-		SK_TRY(hipGetLastError());
-		SK_TRY(hipMemcpyAsync(h + res_at, dv + res_at, nw * sizeof(lda_stream_res),
-				      hipMemcpyDeviceToHost, sc));
-		SK_TRY(hipStreamSynchronize(sc));
+		LDA_TRY(hipMemcpyAsync(dv, h, nw * sizeof(lda_stream_chunk), hipMemcpyHostToDevice, sc));
+		if (!launch_count(sc, (uint32_t)nw, (const lda_stream_chunk *)dv,
+				  (lda_stream_res *)(dv + res_at), d_raw, x.raw_nbytes))
+			return false;
+		LDA_TRY(hipMemcpyAsync(h + res_at, dv + res_at, nw * sizeof(lda_stream_res),
+				       hipMemcpyDeviceToHost, sc));
+		LDA_TRY(hipStreamSynchronize(sc));
 		const lda_stream_res *hr = (const lda_stream_res *)(h + res_at);
 		std::vector<uint8_t> failed(n, 0);
 		bool any = false;
@@ -195,7 +182,7 @@ static int read_body(struct libdeflate_decompressor *d, const uint8_t *d_in, con
 		     uint8_t *d_out, int32_t *d_results, hipStream_t st)
 {
 	const size_t N = pl.iv.size(), P = pl.pieces.size();
-	const size_t BATCH = 4096;	/* decode waves per launch, as the stream path's */
+	const size_t BATCH = STREAM_DECODE_BATCH;
 	Lay lay;
 	const size_t chunks_at = lay.take(N * sizeof(lda_stream_chunk));
 	const size_t want_at = lay.take(2 * N * 8);
@@ -216,8 +203,7 @@ static int read_body(struct libdeflate_decompressor *d, const uint8_t *d_in, con
 	uint8_t *ws = (uint8_t *)d->seek.reserve(lay.at + 64);
 	uint8_t *h = (uint8_t *)d->seek_desc.ensure(up_bytes + 64);
 	uint16_t *d_sym = N ? (uint16_t *)d->ssym.reserve((size_t)pl.sym_words * 2 + 64) : nullptr;
-	uint32_t *d_tok = N ? (uint32_t *)d->tokens.reserve(std::min(N, BATCH) * lda_stream_tokcap() * 4 + 64) :
-			      nullptr;
+	uint32_t *d_tok = N ? stream_token_scratch(d, N) : nullptr;
 	if (!ws || !h || (N && (!d_sym || !d_tok)))
 		return LIBDEFLATE_AMD_OOM;
 	memset(h, 0, up_bytes);
@@ -256,10 +242,8 @@ static int read_body(struct libdeflate_decompressor *d, const uint8_t *d_in, con
 	const uint8_t *d_raw = d_in + v.raw_off;
 	if (N) {
 		/* count: nothing written but results */
-		hipLaunchKernelGGL(lda_stream_count_kernel, dim3((unsigned)N), dim3(64),
-				   lda_stream_chunk_lds(), st, (uint32_t)N, g_chunks, g_counted, d_raw,
-				   v.raw_nbytes, (uint32_t *)NULL, (const uint8_t *)NULL,
-				   (const uint32_t *)NULL, (uint16_t *)NULL);
+		if (!launch_count(st, (uint32_t)N, g_chunks, g_counted, d_raw, v.raw_nbytes))
+			return LIBDEFLATE_AMD_NO_DEVICE;
 		/* the gated decode, into the slots */
 		for (size_t lo = 0; lo < N; lo += BATCH) {
 			const uint32_t nk = (uint32_t)std::min(BATCH, N - lo);

@@ -26,16 +26,14 @@
 #include <string>
 #include <vector>
 
+#include "stream_types.h"
+
 namespace lda {
 
 #define LDA_SEEK_MAGIC 0x314B45455341444Cull	/* "LDASEEK1" */
 #define LDA_SEEK_END 0x21444E454B454553ull	/* "SEEKEND!" */
 #define LDA_SEEK_ROW 4u				/* = LIBDEFLATE_AMD_SEEK_WORDS */
 #define LDA_SEEK_WIN 32768u			/* = LIBDEFLATE_AMD_SEEK_WINDOW */
-/* stream_kernels.h's values (host_seek.hip asserts that they are the same) */
-#define LDA_SEEK_KIND_HEADER 0u
-#define LDA_SEEK_KIND_EXACT 2u
-#define LDA_SEEK_HDR_STATIC (~(uint64_t)1)
 /* the first slot of the symbol scratch: copy_syms::in_front() takes absolute
  * positions below 65536 for the start of a stream, far_base() reads 32768
  * symbols in front of a position */
@@ -61,7 +59,7 @@ struct seek_export {
  * interval that goes on behind that block. */
 static inline bool seek_eligible(const seek_link &c)
 {
-	return !(c.hdr_bit == LDA_SEEK_HDR_STATIC && c.kind != LDA_SEEK_KIND_HEADER);
+	return !(c.hdr_bit == LDA_HDR_STATIC && c.kind != LDA_CHUNK_HEADER);
 }
 
 static inline size_t seek_capacity(size_t index_avail, size_t windows_avail)
@@ -212,13 +210,13 @@ seek_check_index(const uint64_t *index, size_t index_words, size_t in_nbytes, se
 	}
 	if (raw_n >= ((uint64_t)1 << 60))
 		return "the index's raw stream is too long";
-	if (rows[0] != 0 || rows[1] != 0 || rows[2] != 0 || rows[3] != LDA_SEEK_KIND_HEADER)
+	if (rows[0] != 0 || rows[1] != 0 || rows[2] != 0 || rows[3] != LDA_CHUNK_HEADER)
 		return "point 0 is not the stream's first bit at output offset 0";
 	for (uint64_t k = 0; k < n; k++) {
 		const uint64_t *r = rows + LDA_SEEK_ROW * k;
-		const bool hdr = r[3] == LDA_SEEK_KIND_HEADER;
+		const bool hdr = r[3] == LDA_CHUNK_HEADER;
 		const bool state_ok = hdr ? r[2] == r[1] :
-				      r[3] == LDA_SEEK_KIND_EXACT && r[2] < r[1] && r[2] != LDA_SEEK_HDR_STATIC;
+				      r[3] == LDA_CHUNK_EXACT && r[2] < r[1] && r[2] != LDA_HDR_STATIC;
 		const bool rising = k == 0 || (r[0] > r[0 - (ptrdiff_t)LDA_SEEK_ROW] &&
 					       r[1] > r[1 - (ptrdiff_t)LDA_SEEK_ROW]);
 		if (!state_ok || !rising || r[1] >= 8 * raw_n + (k == 0) || r[0] > total ||

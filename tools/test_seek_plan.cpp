@@ -39,14 +39,14 @@ static std::vector<seek_link> random_chain(std::mt19937_64 &rng, size_t n, uint6
 		c.start_bit = bit;
 		const unsigned what = i == 0 ? 0 : (unsigned)(rng() % 10);
 		if (what < 3) {			/* a block header */
-			c.kind = LDA_SEEK_KIND_HEADER;
+			c.kind = LDA_CHUNK_HEADER;
 			c.hdr_bit = hdr = bit;
 		} else if (what < 8) {		/* inside the block of the last header */
-			c.kind = bit > hdr ? LDA_SEEK_KIND_EXACT : LDA_SEEK_KIND_HEADER;
-			c.hdr_bit = hdr = c.kind == LDA_SEEK_KIND_HEADER ? bit : hdr;
+			c.kind = bit > hdr ? LDA_CHUNK_EXACT : LDA_CHUNK_HEADER;
+			c.hdr_bit = hdr = c.kind == LDA_CHUNK_HEADER ? bit : hdr;
 		} else {			/* under the static codes, no header: never a point */
-			c.kind = LDA_SEEK_KIND_EXACT;
-			c.hdr_bit = LDA_SEEK_HDR_STATIC;
+			c.kind = LDA_CHUNK_EXACT;
+			c.hdr_bit = LDA_HDR_STATIC;
 		}
 		ch.push_back(c);
 		out += rng() % 5 == 0 ? 0 : rng() % 40000;
@@ -146,7 +146,7 @@ static std::vector<uint64_t> make_index(const std::vector<uint64_t> &offs, uint6
 		seek_link l = {};
 		l.out_off = offs[k];
 		l.start_bit = k ? 3 + 11 * offs[k] / 4 : 0;
-		l.kind = k % 2 ? LDA_SEEK_KIND_EXACT : LDA_SEEK_KIND_HEADER;
+		l.kind = k % 2 ? LDA_CHUNK_EXACT : LDA_CHUNK_HEADER;
 		l.hdr_bit = k % 2 ? l.start_bit - 1 : l.start_bit;
 		pts.push_back(l);
 	}
@@ -323,7 +323,7 @@ static void test_malformed()
 	CHECK(refused(with(2, ~(uint64_t)0), good.size(), in_n, "in_nbytes"));
 	CHECK(refused(with(R + 0, 1), good.size(), in_n, "point 0"));
 	CHECK(refused(with(R + 1, 1), good.size(), in_n, "point 0"));
-	CHECK(refused(with(R + 3, LDA_SEEK_KIND_EXACT), good.size(), in_n, "point 0"));
+	CHECK(refused(with(R + 3, LDA_CHUNK_EXACT), good.size(), in_n, "point 0"));
 	CHECK(refused(with(2 * R + 0, 0), good.size(), in_n, "row 2"));		/* out_off does not rise */
 	CHECK(refused(with(3 * R + 0, 100), good.size(), in_n, "row 3"));
 	CHECK(refused(with(3 * R + 0, 99), good.size(), in_n, "row 3"));
@@ -342,7 +342,7 @@ static void test_malformed()
 	CHECK(refused(with(2 * R + 3, 1), good.size(), in_n, "row 2"));		/* a kind that is none */
 	CHECK(refused(with(2 * R + 3, 7), good.size(), in_n, "row 2"));
 	CHECK(refused(with(2 * R + 2, good[2 * R + 1]), good.size(), in_n, "row 2"));	/* EXACT at its own header */
-	CHECK(refused(with(2 * R + 2, LDA_SEEK_HDR_STATIC), good.size(), in_n, "row 2"));
+	CHECK(refused(with(2 * R + 2, LDA_HDR_STATIC), good.size(), in_n, "row 2"));
 	CHECK(refused(with(3 * R + 2, 5), good.size(), in_n, "row 3"));		/* HEADER elsewhere */
 }
 
