@@ -1112,6 +1112,164 @@ libdeflate_amd_gzip_members_index_batch(struct libdeflate_decompressor *decompre
 					const void *d_in, size_t in_nbytes, size_t max_members,
 					uint64_t *d_result, uint64_t *d_index, void *stream);
 
+/*
+ * Reading a ZIP archive (.zip, .jar, .whl, .docx, .npz) that lies in device
+ * memory.  The reference has no ZIP reader: a ZIP tool walks the container and
+ * hands raw DEFLATE to libdeflate_deflate_decompress; here the walk happens on
+ * the device too.  What an archive is (tools/models/zip_walk.py restates the
+ * rule on the CPU):
+ *
+ * END RECORD: the highest offset p >= in_nbytes - min(in_nbytes, 65557) that
+ * carries 50 4b 05 06 and has p + 22 + comment_len <= in_nbytes.  Trailing
+ * bytes behind it are tolerated, as Python's zipfile tolerates them; nothing
+ * at or past in_nbytes is part of the file.  Its disk numbers must be 0 and
+ * "entries on this disk" must equal "entries".
+ *
+ * ZIP64: if 50 4b 06 07 stands at p - 20, the ZIP64 end record it points to
+ * supplies the 64-bit entry count, directory size and directory offset, and
+ * LIBDEFLATE_AMD_ZIP_ZIP64 is set: signature 50 4b 06 06 at an offset q with
+ * q + 56 <= p - 20, total disks at most 1 (zipfile's rule); the disk rule above
+ * is then checked on the ZIP64 record's fields instead.  A locator whose
+ * record fails this is LIBDEFLATE_BAD_DATA.
+ *
+ * CENTRAL DIRECTORY: it must end exactly where the (ZIP64) end record begins -
+ * cd_off + cd_size == q with ZIP64, == p without - and cd_size must be below
+ * 4 GiB.  An archive with data in front whose offsets need shifting (a
+ * self-extractor) is therefore LIBDEFLATE_BAD_DATA.  The directory is the
+ * chain of records 50 4b 01 02 of 46 + name_len + extra_len + comment_len
+ * bytes that runs from cd_off, ends exactly at cd_off + cd_size and has
+ * exactly the stated number of entries.  Every offset of the directory that
+ * carries the signature with 46 bytes of directory behind it is a CANDIDATE -
+ * names, extras and comments may carry it -; the chain decides which are
+ * entries.
+ *
+ * PER ENTRY, from the central record: a 32-bit field equal to 0xFFFFFFFF is
+ * replaced from the ZIP64 extra (the first extra record with id 0x0001) in the
+ * order uncompressed size, compressed size, local header offset, and a disk
+ * field of 0xFFFF from the 4 bytes behind them; a needed value that is
+ * missing, or a disk other than 0, is LIBDEFLATE_BAD_DATA for that entry.
+ * Then: a method other than 0 and 8, flag bit 0, 5, 6 or 13 (encryption,
+ * patches, masked headers) or a size of 4 GiB or more is
+ * LIBDEFLATE_AMD_ZIP_UNSUPPORTED for that entry alone.  Then the local header:
+ * it must carry 50 4b 03 04 and lie wholly below cd_off, its own name and
+ * extra lengths give data_off, and data_off + csize <= cd_off must hold, else
+ * LIBDEFLATE_BAD_DATA.  Sizes and CRC-32 are the central directory's, so
+ * entries written with data descriptors (flag bit 3) need nothing special.
+ * Method 0 (stored) requires csize == usize (LIBDEFLATE_BAD_DATA); method 8 is
+ * raw DEFLATE that must use exactly csize bytes and give exactly usize bytes.
+ * Overlapping entries are allowed: the output is bounded by the sum of the
+ * stated sizes against out_avail, whatever the file says.
+ */
+#define LIBDEFLATE_AMD_ZIP_MORE_ENTRIES     16	/* result[0]; same value as the BGZF / gzip readers' */
+#define LIBDEFLATE_AMD_ZIP_MORE_CANDIDATES  17	/* result[0] */
+#define LIBDEFLATE_AMD_ZIP_UNSUPPORTED      18	/* a per-entry result */
+#define LIBDEFLATE_AMD_ZIP_RESULT_WORDS     5
+#define LIBDEFLATE_AMD_ZIP_WORDS            8	/* u64 per index row */
+#define LIBDEFLATE_AMD_ZIP_SLACK            1024	/* candidate room = max_entries + this */
+#define LIBDEFLATE_AMD_ZIP_ZIP64            1	/* result[4] bit */
+
+/*
+ * The whole archive in DEVICE memory -> every entry's bytes in device memory.
+ * Enqueues on `stream` and returns, with the conventions of
+ * libdeflate_amd_gzip_members_decompress_batch: device pointers on the
+ * object's device, scratch of the object, d_out must not overlap d_in, and no
+ * byte is ever written at or past d_out + out_avail.  max_entries sizes the
+ * launches and the scratch on the host, because the host never learns the
+ * entry count: the decode batch has max_entries chunks and the finder has room
+ * for max_entries + LIBDEFLATE_AMD_ZIP_SLACK candidates.
+ *
+ * d_result[0..4] (device memory):
+ *   [0] the verdict, the first of these that applies:
+ *       1. LIBDEFLATE_BAD_DATA: no end record, an inconsistent one, or a
+ *          directory out of bounds; in_nbytes == 0 falls here;
+ *       2. LIBDEFLATE_AMD_ZIP_MORE_ENTRIES: the stated count exceeds
+ *          max_entries ([1] is the count);
+ *       3. LIBDEFLATE_AMD_ZIP_MORE_CANDIDATES: the directory holds more
+ *          candidates than max_entries + LIBDEFLATE_AMD_ZIP_SLACK ([1] is how
+ *          many);
+ *       4. LIBDEFLATE_BAD_DATA: a broken chain, or a chain of another length
+ *          than the stated count;
+ *       5. LIBDEFLATE_INSUFFICIENT_SPACE: the output needed exceeds out_avail;
+ *       (1 to 5 are decided BEFORE the decode, and d_out is then not written;
+ *       under 5 the index, d_results - pre-decode values - and [1] to [4] are
+ *       written, so the caller can allocate and call again)
+ *       6. the result of the first entry in directory order that did not
+ *          succeed;
+ *       7. LIBDEFLATE_SUCCESS.
+ *   [1] entries (0 under verdicts 1 and 4), [2] cd_off, [3] bytes of output
+ *   needed, alignment included, [4] flags (LIBDEFLATE_AMD_ZIP_ZIP64); under
+ *   verdicts 1 to 4 words [2] to [4] are 0 and d_index and d_results are not
+ *   written.
+ *
+ * d_index: NULL, or device room for max_entries rows of LIBDEFLATE_AMD_ZIP_WORDS
+ * u64; row k of entry k in directory order:
+ *   { offset of the central record (the name is at + 46), name_len,
+ *     method | flags << 16, CRC-32, data_off, csize, usize, out_off }
+ * data_off is 0 for an entry that is refused before its local header told it.
+ * out_off is the exclusive prefix sum of the usizes, each rounded up to
+ * out_align (a power of two in 1 .. 256); an entry refused before the decode
+ * counts 0.  Entry k's bytes are at d_out + out_off.
+ *
+ * d_results[k] (int32, room for max_entries; written for the archive's
+ * entries): 0, LIBDEFLATE_BAD_DATA (ZIP64 extra, disk, local header, bounds,
+ * stored size mismatch, damaged DEFLATE, input not used up, CRC-32 mismatch),
+ * the decoder's LIBDEFLATE_SHORT_OUTPUT / LIBDEFLATE_INSUFFICIENT_SPACE when
+ * usize lies, LIBDEFLATE_AMD_ZIP_UNSUPPORTED.  A failed entry never affects
+ * its neighbours; an entry whose CRC fails keeps its slot.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL object or pointer (d_out may be NULL
+ * only with out_avail == 0, d_in only with in_nbytes == 0, d_index always),
+ * max_entries == 0 or above 2^28, in_nbytes above 2^36, an out_align that is
+ * not a power of two in 1 .. 256.
+ *
+ * Not covered: writing archives; encrypted entries and methods other than 0
+ * and 8; multi-disk archives; archives with prepended data; entries of 4 GiB
+ * or more; entries large enough to want the many-wave decoder (each entry is
+ * decoded by one wave, and a stored entry is copied by one workgroup: correct,
+ * but slow for a few huge entries); a host-pointer form.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_zip_decompress_batch(struct libdeflate_decompressor *decompressor,
+				    const void *d_in, size_t in_nbytes, size_t max_entries,
+				    void *d_out, size_t out_avail, size_t out_align,
+				    uint64_t *d_result, uint64_t *d_index, int32_t *d_results,
+				    void *stream);
+
+/* The index, the per-entry pre-decode results and the five words alone:
+ * everything but the decode (out_avail counts as unlimited; damaged DEFLATE
+ * and CRC failures cannot show).  The same out_off as the call above. */
+LIBDEFLATEAPI int
+libdeflate_amd_zip_index_batch(struct libdeflate_decompressor *decompressor,
+			       const void *d_in, size_t in_nbytes, size_t max_entries,
+			       size_t out_align, uint64_t *d_result, uint64_t *d_index,
+			       int32_t *d_results, void *stream);
+
+/*
+ * Extract a selection.  index: HOST memory, `entries` rows as
+ * libdeflate_amd_zip_index_batch returned them; sel: HOST memory, n_sel entry
+ * numbers in any order, duplicates allowed.  Only those entries are decoded,
+ * back to back in sel order with out_align, the CRC-32 checked against the
+ * row; out_offsets: NULL, or HOST room for n_sel + 1 u64 - where selection r
+ * starts, and where the last one ends - filled in before the call returns.
+ * d_results[r] (device, int32) as above; a row with an unsupported method or
+ * flag yields LIBDEFLATE_AMD_ZIP_UNSUPPORTED, a stored row whose sizes differ
+ * LIBDEFLATE_BAD_DATA, and both take no room.  Enqueues on `stream`; the host
+ * arrays may be reused when the call returns.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work: a NULL argument, out_align
+ * as above, a selected row that does not lie inside in_nbytes (central record
+ * and name, data_off + csize), a size of 4 GiB or more, a sel at or above
+ * entries, a selection that needs more than out_avail.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_zip_read_batch(struct libdeflate_decompressor *decompressor,
+			      const void *d_in, size_t in_nbytes,
+			      const uint64_t *index, size_t entries,
+			      size_t n_sel, const uint64_t *sel,
+			      void *d_out, size_t out_avail, size_t out_align,
+			      uint64_t *out_offsets, int32_t *d_results, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -307,6 +307,56 @@ class Decompressor:
             index.data_ptr() if index is not None else None, _stream_ptr(stream)),
             "gzip_members_index_batch")
 
+    def index_zip_batch(self, data, max_entries, result, results, index=None, out_align=1,
+                        stream=None, in_nbytes=None):
+        """libdeflate_amd_zip_index_batch: the ZIP archive in the uint8 torch
+        CUDA tensor `data` (its first in_nbytes bytes) -> result: int64 CUDA
+        tensor of 5 (verdict, entries, cd_off, bytes of output needed, flags);
+        results: int32 CUDA tensor of max_entries (per-entry pre-decode
+        results); index: None or an int64 CUDA tensor of 8 max_entries (rows
+        of central record, name_len, method | flags << 16, CRC-32, data_off,
+        csize, usize, out_off).  Nothing is decoded.  Only enqueues."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_zip_index_batch(
+            self._h, data.data_ptr() if n else None, n, int(max_entries), int(out_align),
+            result.data_ptr(), index.data_ptr() if index is not None else None,
+            results.data_ptr(), _stream_ptr(stream)), "zip_index_batch")
+
+    def decompress_zip_batch(self, data, max_entries, out, result, results, index=None,
+                             out_align=1, stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_zip_decompress_batch: every entry of the ZIP archive
+        in `data` into `out` (out_avail bytes of it, default all), entry k at
+        out_off of row k; result, results and index as in index_zip_batch,
+        results with the decode's and the CRC-32's verdicts.  Only enqueues
+        on `stream`."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_zip_decompress_batch(
+            self._h, data.data_ptr() if n else None, n, int(max_entries),
+            out.data_ptr() if avail else None, avail, int(out_align), result.data_ptr(),
+            index.data_ptr() if index is not None else None, results.data_ptr(),
+            _stream_ptr(stream)), "zip_decompress_batch")
+
+    def read_zip_batch(self, data, index, sel, out, results, out_align=1, stream=None,
+                       in_nbytes=None, out_avail=None):
+        """libdeflate_amd_zip_read_batch: the entries `sel` (host, any order,
+        duplicates allowed) of the archive in the CUDA tensor `data`, back to
+        back into `out` with out_align; index: host rows as index_zip_batch
+        wrote them; results: int32 CUDA tensor, one per selection.  Returns
+        the numpy uint64 offsets (len(sel) + 1) of the selections in `out`.
+        Only enqueues."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.ZIP_WORDS)
+        s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+        offs = np.zeros(len(s) + 1, dtype=np.uint64)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_zip_read_batch(
+            self._h, data.data_ptr() if n else None, n, idx.ctypes.data_as(c_void_p), len(idx),
+            len(s), s.ctypes.data_as(c_void_p), out.data_ptr() if avail else None, avail,
+            int(out_align), offs.ctypes.data_as(c_void_p), results.data_ptr(),
+            _stream_ptr(stream)), "zip_read_batch")
+        return offs
+
     def read_bgzf_batch(self, data, index, ranges, out, results, voffsets=False, stream=None,
                         in_nbytes=None, out_avail=None):
         """libdeflate_amd_bgzf_read_batch: `ranges` (host, rows of (begin,
@@ -548,6 +598,26 @@ def bgzf_gzi_parse(blob):
     count = int(np.frombuffer(blob[:8], dtype="<u8")[0])
     assert len(blob) == 8 + 16 * count, "truncated .gzi"
     return np.frombuffer(blob[8:], dtype="<u8").reshape(count, 2)
+
+
+def zip_entry_names(data, result, index):
+    """The entries' names of the archive in the CUDA tensor `data`, from the
+    result words and index rows of index_zip_batch / decompress_zip_batch
+    (CUDA tensors or host arrays): the directory region is fetched once.
+    Bytes that are no UTF-8 decode as CP437, as zipfile reads them."""
+    words = [int(x) for x in (result.cpu().tolist() if hasattr(result, "cpu") else result)]
+    rows = index.cpu().numpy() if hasattr(index, "cpu") else np.asarray(index)
+    entries, cd_off = words[1], words[2]
+    rows = rows.reshape(-1, binding.ZIP_WORDS)[:entries].astype(np.uint64)
+    if not entries:
+        return []
+    cd_end = int((rows[:, 0] + np.uint64(46) + rows[:, 1]).max())
+    cd = data[cd_off:cd_end].cpu().numpy().tobytes()
+    names = []
+    for rec, name_len, mf in zip(rows[:, 0].tolist(), rows[:, 1].tolist(), rows[:, 2].tolist()):
+        raw = cd[rec + 46 - cd_off:rec + 46 - cd_off + name_len]
+        names.append(raw.decode("utf-8" if (mf >> 16) & 0x800 else "cp437"))
+    return names
 
 
 def _stream_ptr(stream):

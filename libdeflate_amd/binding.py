@@ -30,6 +30,11 @@ BGZF_MORE_MEMBERS, BGZF_HAS_EOF, BGZF_RESULT_WORDS, BGZF_VOFFSETS = 16, 1, 5, 2
 # libdeflate_result, the words of a result, candidate room beyond max_members
 GZM_MORE_MEMBERS, GZM_MORE_CANDIDATES, GZM_RESULT_WORDS, GZM_SLACK = 16, 17, 5, 1024
 GZM_NAME_MAX = 65536    # bytes of FNAME + FCOMMENT the member reader accepts
+# the ZIP reader: result[0] beyond enum libdeflate_result, a per-entry result,
+# the words of a result, u64 per index row, candidate room beyond max_entries,
+# the flag bit of result[4]
+ZIP_MORE_ENTRIES, ZIP_MORE_CANDIDATES, ZIP_UNSUPPORTED = 16, 17, 18
+ZIP_RESULT_WORDS, ZIP_WORDS, ZIP_SLACK, ZIP_ZIP64 = 5, 8, 1024, 1
 # the seek index: bytes of window per point, u64 per row
 SEEK_WINDOW, SEEK_WORDS = 32768, 4
 # the size query: the limit a NULL d_out_limit stands for
@@ -73,6 +78,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_compress_large_batch", "libdeflate_amd_decompress_large",
     "libdeflate_amd_decompress_large_index", "libdeflate_amd_seek_read_batch",
     "libdeflate_amd_gzip_members_decompress_batch", "libdeflate_amd_gzip_members_index_batch",
+    "libdeflate_amd_zip_index_batch", "libdeflate_amd_zip_decompress_batch",
+    "libdeflate_amd_zip_read_batch",
 ]
 
 _lib = None
@@ -187,6 +194,11 @@ def load():
     # index alone (enqueue only)
     sig("libdeflate_amd_gzip_members_decompress_batch", c_int, P, P, SZ, SZ, P, SZ, P, P, P)
     sig("libdeflate_amd_gzip_members_index_batch", c_int, P, P, SZ, SZ, P, P, P)
+    # a ZIP archive: the index alone, device file -> every entry's bytes, a
+    # selection of entries (index rows and entry numbers on the host)
+    sig("libdeflate_amd_zip_index_batch", c_int, P, P, SZ, SZ, SZ, P, P, P, P)
+    sig("libdeflate_amd_zip_decompress_batch", c_int, P, P, SZ, SZ, P, SZ, SZ, P, P, P, P)
+    sig("libdeflate_amd_zip_read_batch", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, P, P, P)
     _lib = lib
     return lib
 

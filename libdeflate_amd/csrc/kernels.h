@@ -305,6 +305,64 @@ lda_gzm_final_kernel(uint64_t n, uint64_t max_members, uint64_t out_avail, const
 		     const uint64_t *in_n, const int32_t *results, const uint64_t *actual_in,
 		     uint64_t *result, uint64_t *index);
 
+/* zip_kernels.hip: a ZIP archive read from device memory (host_zip.hip); the
+ * chain among the directory's candidates is found by lda_bgzf_jump_kernel /
+ * _top_ / _members_ above, whose state words LDA_BR_CHAIN and LDA_BR_MEMBERS it
+ * shares.  Copies of the header's constants (static_assert in host_zip.hip) */
+#define LDA_ZIP_MORE_ENTRIES 16		/* LIBDEFLATE_AMD_ZIP_MORE_ENTRIES */
+#define LDA_ZIP_MORE_CANDIDATES 17	/* LIBDEFLATE_AMD_ZIP_MORE_CANDIDATES */
+#define LDA_ZIP_UNSUPPORTED 18		/* LIBDEFLATE_AMD_ZIP_UNSUPPORTED */
+#define LDA_ZIP_RESULT_WORDS 5
+#define LDA_ZIP_WORDS 8
+#define LDA_ZIP_ZIP64 1
+#define LDA_ZIP_WINDOW 65557u	/* an end record and the longest comment */
+/* the chain's end as the chain kernels are told it: cd_size is below 2^32 */
+#define LDA_ZIP_CHAIN_END 0xFFFFFFFFull
+/* what the end record says (u64 words) */
+#define LDA_ZS_BAD 0		/* 1: no end record, an inconsistent one, a directory out of bounds */
+#define LDA_ZS_ENTRIES 1
+#define LDA_ZS_CD_OFF 2
+#define LDA_ZS_CD_SIZE 3
+#define LDA_ZS_FLAGS 4
+#define LDA_ZS_WORDS 8
+/* meta[k] >> 40 (zip_plan.h builds the same words for a selection) */
+#define LDA_ZIP_KIND_NONE 0
+#define LDA_ZIP_KIND_STORED 1
+#define LDA_ZIP_KIND_DEFLATE 2
+extern "C" __global__ void
+lda_zip_end_kernel(const uint8_t *in, uint64_t n, uint64_t *zs);
+extern "C" __global__ void
+lda_zip_scan_kernel(const uint8_t *in, const uint64_t *zs, uint64_t *counts,
+		    const uint64_t *offsets, const uint64_t *block_sums, uint64_t cap,
+		    uint64_t *cand_pos);
+extern "C" __global__ void
+lda_zip_size_kernel(const uint8_t *in, const uint64_t *zs, const uint64_t *k_at, uint64_t cap,
+		    const uint64_t *cand_pos, uint32_t *cand_size);
+extern "C" __global__ void
+lda_zip_resolve_kernel(const uint8_t *in, uint64_t max_entries, uint64_t align_mask,
+		       const uint64_t *zs, const uint32_t *state, const uint64_t *k_at,
+		       uint64_t cap, const uint64_t *rel, uint64_t *rows, int32_t *results,
+		       uint64_t *sizes);
+extern "C" __global__ void
+lda_zip_desc_kernel(uint64_t max_entries, uint64_t out_avail, const uint64_t *zs,
+		    const uint32_t *state, const uint64_t *k_at, uint64_t cap,
+		    const uint64_t *block_sums, uint64_t *rows, const int32_t *results,
+		    uint64_t *in_off, uint64_t *in_n, uint64_t *out_off, uint64_t *out_av,
+		    uint64_t *cp_src, uint64_t *cp_len, uint64_t *crc_n, uint64_t *meta);
+extern "C" __global__ void
+lda_zip_copy_kernel(uint64_t n_chunks, const uint64_t *src, const uint64_t *dst,
+		    const uint64_t *len, const uint8_t *in, uint8_t *out);
+extern "C" __global__ void
+lda_zip_final_kernel(uint64_t max_entries, uint64_t out_avail, const uint64_t *zs,
+		     const uint32_t *state, const uint64_t *k_at, uint64_t cap,
+		     const uint64_t *total_at, const uint64_t *meta, const uint64_t *in_n,
+		     const int32_t *batch_res, const uint64_t *actual_in, const uint32_t *crcs,
+		     int32_t *results, uint64_t *result);
+extern "C" __global__ void
+lda_zip_rfinal_kernel(uint64_t n_sel, const uint64_t *meta, const uint64_t *in_n,
+		      const int32_t *batch_res, const uint64_t *actual_in, const uint32_t *crcs,
+		      int32_t *results);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
