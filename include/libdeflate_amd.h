@@ -1223,11 +1223,12 @@ libdeflate_amd_gzip_members_index_batch(struct libdeflate_decompressor *decompre
  * max_entries == 0 or above 2^28, in_nbytes above 2^36, an out_align that is
  * not a power of two in 1 .. 256.
  *
- * Not covered: writing archives; encrypted entries and methods other than 0
- * and 8; multi-disk archives; archives with prepended data; entries of 4 GiB
- * or more; entries large enough to want the many-wave decoder (each entry is
- * decoded by one wave, and a stored entry is copied by one workgroup: correct,
- * but slow for a few huge entries); a host-pointer form.
+ * Not covered: encrypted entries and methods other than 0 and 8 (archives are
+ * written by libdeflate_amd_zip_compress_batch below); multi-disk archives;
+ * archives with prepended data; entries of 4 GiB or more; entries large enough
+ * to want the many-wave decoder (each entry is decoded by one wave, and a
+ * stored entry is copied by one workgroup: correct, but slow for a few huge
+ * entries); a host-pointer form.
  */
 LIBDEFLATEAPI int
 libdeflate_amd_zip_decompress_batch(struct libdeflate_decompressor *decompressor,
@@ -1269,6 +1270,89 @@ libdeflate_amd_zip_read_batch(struct libdeflate_decompressor *decompressor,
 			      size_t n_sel, const uint64_t *sel,
 			      void *d_out, size_t out_avail, size_t out_align,
 			      uint64_t *out_offsets, int32_t *d_results, void *stream);
+
+/*
+ * ---- ZIP archives written on the device ----
+ *
+ * n_entries named byte ranges of one DEVICE buffer -> one ZIP archive in device
+ * memory: every entry compressed (method 8) or stored (method 0), local
+ * headers, central directory and end records placed by kernels.  Enqueues on
+ * `stream` and returns: nothing comes back to the host and the device is not
+ * waited for, with two exceptions: scratch of the object grows on the host, as
+ * everywhere else, and the plan goes up through one pinned block per object,
+ * so a call waits until the previous call on the same object has had its plan
+ * uploaded (its stream has reached that copy, not its kernels).
+ *
+ * names / name_offsets (n_entries + 1, ascending), in_offsets and in_nbytes
+ * are HOST arrays - a ZIP writer's caller knows them - and may be reused when
+ * the call returns.  Entry k is bytes [in_offsets[k], + in_nbytes[k]) of d_in
+ * and is called names[name_offsets[k] .. name_offsets[k + 1]).  Entries may
+ * overlap one another; d_out must not overlap d_in.
+ *
+ * An entry gets method 8 when its raw DEFLATE stream - byte for byte what
+ * libdeflate_deflate_compress() of this build returns for the entry's bytes at
+ * the object's level and LDA_* switches - is shorter than the entry; otherwise
+ * method 0 with the entry's own bytes.  Empty entries, a level-0 object and
+ * LIBDEFLATE_AMD_ZIP_STORE always store, and under the last two no compress
+ * kernel runs.
+ *
+ * The archive: per entry a local header (30 bytes, version needed 20 - 45 in
+ * ZIP64 mode -, general-purpose bit 11 iff the name holds a byte >= 0x80 and
+ * no other flag, time / date the low / high half of dos_datetime - 0 stands
+ * for 0x00210000, 1980-01-01 00:00 -, the real CRC-32 and sizes, no extra
+ * field, no data descriptor), the name and the data, back to back from offset
+ * 0 in the caller's order; then the central directory (version made by 20 /
+ * 45, attributes 0, no comment; in ZIP64 mode the offset field is 0xFFFFFFFF
+ * and the extra field 01 00 08 00 + the u64 offset); then the 22-byte end
+ * record without a comment - in ZIP64 mode the 56-byte ZIP64 end record, its
+ * 20-byte locator and an end record whose counts, size and offset are
+ * 0xFFFF / 0xFFFFFFFF.  ZIP64 mode is decided on the host:
+ * LIBDEFLATE_AMD_ZIP_FORCE_ZIP64, n_entries >= 65535, or a plain bound of
+ * 0xFFFFFFFF or more.
+ *
+ * libdeflate_amd_zip_compress_bound() is exact arithmetic on the host arrays:
+ *   Sum(30 + name + in_nbytes) + Sum(46 + name + 12 z64) + 22 + 76 z64
+ * No archive of these entries is larger, because csize <= usize.
+ *
+ * d_result[0 .. LIBDEFLATE_AMD_ZIPW_RESULT_WORDS) (device memory):
+ *   [0] 0, or LIBDEFLATE_INSUFFICIENT_SPACE: the archive does not fit
+ *       out_avail - then no byte of d_out and no row of d_index is written;
+ *   [1] the archive's size, [2] cd_off, [3] the entries that got method 8
+ *   ([1] to [3] are valid either way).
+ * d_index: NULL, or device room for n_entries rows of LIBDEFLATE_AMD_ZIP_WORDS
+ * u64: exactly the rows libdeflate_amd_zip_index_batch returns for the written
+ * archive with out_align 1, so the archive can go straight into
+ * libdeflate_amd_zip_read_batch.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL object or pointer (d_in may be NULL with
+ * in_avail == 0, the host arrays with n_entries == 0, d_index always), unknown
+ * flags, n_entries above 2^28, a name of 0 or more than 65535 bytes or
+ * decreasing name_offsets, an entry of 4 GiB or more, an entry that does not
+ * lie inside in_avail, out_avail below the size of the directory and end
+ * records alone.  n_entries == 0 writes the 22-byte empty archive.
+ *
+ * Limits: the object's scratch is about the sum of the entries' sizes plus
+ * descriptors; with LDA_NO_SEGMENTS a huge entry is one piece and one
+ * workgroup; no host-pointer form; no per-entry method, time or alignment
+ * padding; no archive comment; no encryption.
+ */
+#define LIBDEFLATE_AMD_ZIP_STORE         1	/* flag: every entry method 0, nothing compressed */
+#define LIBDEFLATE_AMD_ZIP_FORCE_ZIP64   2	/* flag: ZIP64 records whatever the sizes */
+#define LIBDEFLATE_AMD_ZIPW_RESULT_WORDS 4
+
+LIBDEFLATEAPI size_t
+libdeflate_amd_zip_compress_bound(size_t n_entries, const uint64_t *name_offsets,
+				  const uint64_t *in_nbytes, unsigned flags);
+
+LIBDEFLATEAPI int
+libdeflate_amd_zip_compress_batch(struct libdeflate_compressor *compressor,
+				  size_t n_entries, const void *names,
+				  const uint64_t *name_offsets, const void *d_in, size_t in_avail,
+				  const uint64_t *in_offsets, const uint64_t *in_nbytes,
+				  void *d_out, size_t out_avail, uint64_t *d_result,
+				  uint64_t *d_index, uint32_t dos_datetime, unsigned flags,
+				  void *stream);
 
 #ifdef __cplusplus
 }

@@ -107,6 +107,59 @@ class Compressor:
             out.numel() if out_avail is None else int(out_avail), out_nbytes.data_ptr(),
             _stream_ptr(stream)), "compress_large_batch")
 
+    @staticmethod
+    def _zip_names(names):
+        """names (str -> UTF-8, or bytes) -> (blob, uint64 offsets (n + 1));
+        a caller that makes many archives of the same names passes that pair
+        itself and skips the encoding"""
+        if isinstance(names, tuple):
+            blob, offs = names
+            assert blob.dtype == np.uint8 and offs.dtype == np.uint64
+            return blob, offs
+        raw = [x.encode("utf-8") if isinstance(x, str) else bytes(x) for x in names]
+        offs = np.zeros(len(raw) + 1, dtype=np.uint64)
+        if raw:
+            offs[1:] = np.cumsum([len(x) for x in raw], dtype=np.uint64)
+        return np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8), offs
+
+    def zip_bound(self, names, sizes, flags=0):
+        """libdeflate_amd_zip_compress_bound: the exact upper bound of the
+        archive compress_zip_batch writes for entries of these names (str or
+        bytes) and sizes."""
+        _, offs = self._zip_names(names)
+        sz = np.ascontiguousarray(sizes, dtype=np.uint64)
+        assert sz.size == offs.size - 1
+        return self._lib.libdeflate_amd_zip_compress_bound(
+            sz.size, offs.ctypes.data_as(c_void_p), sz.ctypes.data_as(c_void_p), int(flags))
+
+    def compress_zip_batch(self, names, data, in_offsets, in_nbytes, out, result, index=None,
+                           dos_datetime=0, flags=0, stream=None, in_avail=None, out_avail=None):
+        """libdeflate_amd_zip_compress_batch: a ZIP archive of the entries
+        data[in_offsets[k] : + in_nbytes[k]] (data: uint8 torch CUDA tensor, its
+        first in_avail bytes; names, offsets and sizes: host lists or arrays,
+        names also as the (blob, offsets) pair of _zip_names())
+        into `out` (out_avail bytes of it, default all; zip_bound() is room
+        enough).  result: int64 CUDA tensor of ZIPW_RESULT_WORDS - [0] 0 or
+        INSUFFICIENT_SPACE, [1] the archive's size, [2] cd_off, [3] entries
+        deflated; index: None or an int64 CUDA tensor of ZIP_WORDS per entry,
+        the rows index_zip_batch returns for the archive.  flags: ZIP_STORE,
+        ZIP_FORCE_ZIP64.  Only enqueues on `stream`."""
+        blob, offs = self._zip_names(names)
+        ino = np.ascontiguousarray(in_offsets, dtype=np.uint64)
+        inn = np.ascontiguousarray(in_nbytes, dtype=np.uint64)
+        n = offs.size - 1
+        assert ino.size == n and inn.size == n
+        assert result.numel() >= binding.ZIPW_RESULT_WORDS
+        assert index is None or index.numel() >= binding.ZIP_WORDS * n
+        avail = data.numel() if in_avail is None else int(in_avail)
+        check(self._lib.libdeflate_amd_zip_compress_batch(
+            self._h, n, blob.ctypes.data_as(c_void_p), offs.ctypes.data_as(c_void_p),
+            data.data_ptr() if avail else None, avail, ino.ctypes.data_as(c_void_p),
+            inn.ctypes.data_as(c_void_p), out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
+            index.data_ptr() if index is not None else None, int(dos_datetime), int(flags),
+            _stream_ptr(stream)), "zip_compress_batch")
+
     def compress(self, fmt, data, out_avail=None):
         """Returns the compressed bytes, or None when the reference API would
         return 0 (does not fit in out_avail)."""

@@ -27,19 +27,6 @@
 #define SCAN_PER_THREAD 8
 #define SCAN_BLOCK (SCAN_THREADS * SCAN_PER_THREAD)
 
-static __device__ __forceinline__ u64 wave_scan_incl64(u64 v)
-{
-	const u32 lane = lane_id();
-#pragma unroll
-	for (int off = 1; off < 64; off <<= 1) {
-		u32 lo = __shfl_up((u32)v, off, 64);
-		u32 hi = __shfl_up((u32)(v >> 32), off, 64);
-		if (lane >= (u32)off)
-			v += ((u64)hi << 32) | lo;
-	}
-	return v;
-}
-
 extern "C" __global__ void __launch_bounds__(SCAN_THREADS)
 lda_scan_local_kernel(u64 n, const u64 *__restrict__ sizes,
 		      u64 *__restrict__ offsets, u64 *__restrict__ block_sums)

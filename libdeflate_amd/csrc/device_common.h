@@ -116,6 +116,20 @@ static __device__ __forceinline__ u64 wave_sum64(u64 v)
 	return v;
 }
 
+/* inclusive prefix sum of 64-bit values across the 64 lanes */
+static __device__ __forceinline__ u64 wave_scan_incl64(u64 v)
+{
+	const u32 lane = lane_id();
+#pragma unroll
+	for (int off = 1; off < 64; off <<= 1) {
+		u32 lo = __shfl_up((u32)v, off, 64);
+		u32 hi = __shfl_up((u32)(v >> 32), off, 64);
+		if (lane >= (u32)off)
+			v += ((u64)hi << 32) | lo;
+	}
+	return v;
+}
+
 /* inclusive prefix sum across the 64 lanes: DPP row shifts inside the rows of
  * 16, then row_bcast15 / row_bcast31 carry the row totals (no LDS permutes) */
 static __device__ __forceinline__ u32 wave_scan_incl(u32 v)

@@ -105,6 +105,10 @@ libdeflate_free_compressor(struct libdeflate_compressor *c)
 	c->meta.release();
 	c->bgzf.release();
 	c->large.release();
+	c->zipw.release();
+	c->zipw_desc.release();
+	if (c->zipw_up)
+		(void)hipEventDestroy(c->zipw_up);
 	c->streams.release();
 	free_func_t f = c->free_func;
 	c->~libdeflate_compressor();
@@ -391,6 +395,29 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
 	return LIBDEFLATE_AMD_OK;
+}
+
+/* host_objects.h: what the ZIP writer launches its pieces through */
+int lda::compress_deflate_pieces(struct libdeflate_compressor *c, size_t n, const void *d_in,
+				 const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
+				 void *d_out, const uint64_t *d_out_offsets,
+				 const uint64_t *d_out_avail, uint64_t *d_out_nbytes, void *stream,
+				 const uint32_t *d_seg_info, size_t max_in)
+{
+	return compress_batch_impl(c, LIBDEFLATE_AMD_DEFLATE, n, d_in, d_in_offsets, d_in_nbytes,
+				   d_out, d_out_offsets, d_out_avail, d_out_nbytes, stream,
+				   d_seg_info, max_in);
+}
+
+size_t lda::compress_pieces_scratch(const struct libdeflate_compressor *c, size_t n,
+				    size_t max_in, bool seg)
+{
+	return plan_batch(c, n, max_in, seg, false).total;
+}
+
+size_t lda::compress_prime_window(void)
+{
+	return dict_window();
 }
 
 extern "C" LIBDEFLATEAPI int

@@ -80,6 +80,12 @@ struct libdeflate_compressor {
 	/* one stream from one device buffer (libdeflate_amd_compress_large_batch):
 	 * descriptor rows, seg_info, per-piece sums, scan offsets, segment slots */
 	lda::DevBuf large;
+	/* a ZIP archive written on the device (host_zip_write.hip): the plan's
+	 * columns and the names, per-piece and per-entry results, the slots; the
+	 * columns on their way up, and the event behind that copy */
+	lda::DevBuf zipw;
+	lda::PinnedBuf zipw_desc;
+	hipEvent_t zipw_up = nullptr;
 	lda::PinnedPair pinned;	/* host-pointer entry points */
 	lda::PinnedBuf meta;	/* host-pointer entry points: per-chunk read-backs */
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */
@@ -104,6 +110,21 @@ template <typename Obj>
 int fanout(Obj *o, size_t n, const size_t *weight,
 	   const std::function<Obj *(const struct libdeflate_options *)> &alloc,
 	   const std::function<int(Obj *, size_t, size_t)> &body);
+
+/* host_compress.hip, for the ZIP writer (host_zip_write.hip): one compress
+ * batch of raw DEFLATE as the batch entry points launch it - seg_info NULL or
+ * one word per chunk (large_plan.h), max_in the size bound of the chunks - the
+ * kernels' scratch such a launch reserves in the object (reserve the largest
+ * before the first of several is queued: growing frees memory), and the bytes
+ * in front of a segment that prime it (lda_large_shape's D) */
+int compress_deflate_pieces(struct libdeflate_compressor *c, size_t n, const void *d_in,
+			    const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes, void *d_out,
+			    const uint64_t *d_out_offsets, const uint64_t *d_out_avail,
+			    uint64_t *d_out_nbytes, void *stream, const uint32_t *d_seg_info,
+			    size_t max_in);
+size_t compress_pieces_scratch(const struct libdeflate_compressor *c, size_t n, size_t max_in,
+			       bool seg);
+size_t compress_prime_window(void);
 
 /* host_sizes.hip: the size query on a stream (arguments checked by the
  * callers); s: sizes_scratch_bytes(n) bytes of device memory that stay

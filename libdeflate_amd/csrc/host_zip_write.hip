@@ -1,0 +1,235 @@
+/*
+ * host_zip_write.hip - C-ABI of writing a ZIP archive in device memory
+ * (include/libdeflate_amd.h: libdeflate_amd_zip_compress_batch).
+ *
+ * zip_write_plan.h checks the host arrays, decides ZIP64 and cuts the entries
+ * into pieces; its columns and the names go up through a pinned block in ONE
+ * copy, as the descriptors of libdeflate_amd_zip_read_batch do.  ONE CRC-32
+ * batch runs over the pieces, the compress batches of every launch group run
+ * into slots in the object's scratch (compress_deflate_pieces(): the launches
+ * of the batch entry points, sliced like the segmented single-buffer path),
+ * and the kernels of zip_write_kernels.hip decide deflate or stored per entry
+ * and place headers, data, directory and end records.  Nothing comes back, and
+ * the device is waited for only where the pinned block is still on its way up
+ * from the previous call on the same object (and where scratch grows).
+ * c->zipw: [entry columns][piece columns][seg_info][names] (what goes up),
+ * [out_n][cp_src cp_dst cp_len][sizes][offsets][block sums][e_info][crcs][slots].
+ */
+#include <string.h>
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "host_objects.h"
+#include "kernels.h"
+#include "zip_write_plan.h"
+
+using namespace lda;
+
+static_assert(LIBDEFLATE_AMD_ZIP_STORE == ZIPW_STORE &&
+	      LIBDEFLATE_AMD_ZIP_FORCE_ZIP64 == ZIPW_FORCE_ZIP64 &&
+	      LIBDEFLATE_AMD_ZIPW_RESULT_WORDS == ZIPW_RESULT_WORDS &&
+	      ZIPW_MAX_ENTRIES == (uint64_t)1 << 28,
+	      "zip_write_plan.h holds copies of the header's constants");
+
+extern "C" LIBDEFLATEAPI size_t
+libdeflate_amd_zip_compress_bound(size_t n_entries, const uint64_t *name_offsets,
+				  const uint64_t *in_nbytes, unsigned flags)
+{
+	if (n_entries && (!name_offsets || !in_nbytes)) {
+		set_error("zip_compress_bound: NULL argument");
+		return 0;
+	}
+	return (size_t)zipw_bound(n_entries, name_offsets, in_nbytes, flags, NULL, NULL, NULL);
+}
+
+struct ZipwScratch {
+	/* what goes up */
+	uint64_t *ecols, *pcols;
+	uint32_t *seg;
+	uint8_t *names;
+	size_t up_bytes;
+	/* what the kernels leave */
+	uint64_t *out_n, *cp_src, *cp_dst, *cp_len, *sizes, *offs, *bsum, *e_info;
+	uint32_t *crcs;
+	uint8_t *slots;
+	size_t nblocks, bytes;
+};
+
+static ZipwScratch zipw_scratch(void *base, const zipw_plan &p, size_t names_bytes)
+{
+	ZipwScratch s;
+	Carve c(base);
+	const size_t n = (size_t)p.n, np = (size_t)p.np;
+
+	s.nblocks = (n + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
+	s.ecols = c.take<uint64_t>(ZIPW_ECOLS * n);
+	s.pcols = c.take<uint64_t>(ZIPW_PCOLS * np);
+	s.seg = c.take<uint32_t>(np);
+	s.names = c.take<uint8_t>(names_bytes);
+	s.up_bytes = c.at;
+	s.out_n = c.take<uint64_t>(np);
+	s.cp_src = c.take<uint64_t>(np);
+	s.cp_dst = c.take<uint64_t>(np);
+	s.cp_len = c.take<uint64_t>(np);
+	s.sizes = c.take<uint64_t>(n);
+	s.offs = c.take<uint64_t>(n);
+	s.bsum = c.take<uint64_t>(s.nblocks + 1);
+	s.e_info = c.take<uint64_t>(n);
+	s.crcs = c.take<uint32_t>(np);
+	s.slots = c.take<uint8_t>((size_t)p.slots_bytes, 256);
+	s.bytes = c.at + 16;
+	return s;
+}
+
+/* pieces per compress launch of a group: segments as the segmented
+ * single-buffer path slices them, whole entries in one call (which slices
+ * itself where its token lists need it) */
+static size_t zipw_per_launch(const zipw_group &g)
+{
+	return g.S ? (size_t)lda_large_per_slice(g.S) : (size_t)(g.hi - g.lo);
+}
+
+static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, const uint8_t *names,
+			size_t names_bytes, const uint8_t *d_in, uint8_t *d_out, uint64_t out_avail,
+			uint64_t *d_result, uint64_t *d_index, uint32_t dos_datetime, hipStream_t st)
+{
+	DeviceCtx *ctx = device_ctx();
+	if (!ctx)
+		return LIBDEFLATE_AMD_NO_DEVICE;
+	const size_t n = (size_t)p.n, np = (size_t)p.np;
+	const uint64_t tail = p.cd_size + p.end_bytes;
+	const ZipwScratch sz = zipw_scratch(NULL, p, names_bytes);
+
+	/* the pinned block of the last call may still be on its way up */
+	if (c->zipw_up)
+		LDA_HIP_TRY(hipEventSynchronize(c->zipw_up), LIBDEFLATE_AMD_NO_DEVICE);
+	else
+		LDA_HIP_TRY(hipEventCreateWithFlags(&c->zipw_up, hipEventDisableTiming),
+			    LIBDEFLATE_AMD_NO_DEVICE);
+	/* all of the call's scratch before anything is queued: growing frees
+	 * memory (and waits for the device) */
+	size_t kernels = 0;
+	for (const zipw_group &g : p.groups)
+		kernels = std::max(kernels, compress_pieces_scratch(
+			c, std::min(zipw_per_launch(g), (size_t)(g.hi - g.lo)), (size_t)g.max_in,
+			g.S != 0));
+	uint8_t *ws = (uint8_t *)c->zipw.reserve(sz.bytes);
+	uint8_t *h = (uint8_t *)c->zipw_desc.ensure(std::max(sz.up_bytes, (size_t)64));
+	if (!ws || !h || (kernels && !c->scratch.reserve(kernels)))
+		return LIBDEFLATE_AMD_OOM;
+	const ZipwScratch s = zipw_scratch(ws, p, names_bytes), hs = zipw_scratch(h, p, names_bytes);
+	if (sz.up_bytes) {
+		memcpy(hs.ecols, p.ecols.data(), p.ecols.size() * 8);
+		memcpy(hs.pcols, p.pcols.data(), p.pcols.size() * 8);
+		memcpy(hs.seg, p.seg_info.data(), p.seg_info.size() * 4);
+		memcpy(hs.names, names, names_bytes);
+		LDA_HIP_TRY(hipMemcpyAsync(ws, h, sz.up_bytes, hipMemcpyHostToDevice, st),
+			    LIBDEFLATE_AMD_NO_DEVICE);
+		LDA_HIP_TRY(hipEventRecord(c->zipw_up, st), LIBDEFLATE_AMD_NO_DEVICE);
+	}
+	const uint64_t *ecol[ZIPW_ECOLS], *pcol[ZIPW_PCOLS];
+	for (size_t a = 0; a < ZIPW_ECOLS; a++)
+		ecol[a] = s.ecols + a * n;
+	for (size_t a = 0; a < ZIPW_PCOLS; a++)
+		pcol[a] = s.pcols + a * np;
+	const bool compressed = !p.groups.empty();
+
+	int rc = libdeflate_amd_crc32_batch(np, d_in, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N], NULL,
+					    s.crcs, st);
+	if (rc != LIBDEFLATE_AMD_OK)
+		return rc;
+	for (const zipw_group &g : p.groups) {
+		const size_t per = zipw_per_launch(g);
+		for (size_t lo = (size_t)g.lo; lo < g.hi; lo += per) {
+			const size_t nk = std::min(per, (size_t)g.hi - lo);
+			rc = compress_deflate_pieces(c, nk, d_in, pcol[ZIPW_P_IN_OFF] + lo,
+						     pcol[ZIPW_P_IN_N] + lo, s.slots,
+						     pcol[ZIPW_P_SLOT_OFF] + lo,
+						     pcol[ZIPW_P_SLOT_AV] + lo, s.out_n + lo, st,
+						     g.S ? s.seg + lo : NULL, (size_t)g.max_in);
+			if (rc != LIBDEFLATE_AMD_OK)
+				return rc;
+		}
+	}
+	const unsigned wave_grid = (unsigned)std::max((size_t)1, std::min((n + 3) / 4, (size_t)ctx->num_cus * 16));
+	if (n) {
+		hipLaunchKernelGGL(lda_zipw_entry_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+				   ecol[ZIPW_E_FIRST], ecol[ZIPW_E_COUNT], ecol[ZIPW_E_NAME_LEN],
+				   ecol[ZIPW_E_USIZE], pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
+				   (const uint64_t *)(compressed ? s.out_n : NULL),
+				   (const uint32_t *)s.crcs, s.e_info, s.sizes);
+		hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nblocks), dim3(256), 0, st,
+				   (uint64_t)n, (const uint64_t *)s.sizes, s.offs, s.bsum);
+	}
+	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)s.nblocks,
+			   s.bsum);
+	if (n)
+		hipLaunchKernelGGL(lda_zipw_place_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+				   (uint32_t)p.zip64, dos_datetime, out_avail, tail, ecol[ZIPW_E_FIRST],
+				   ecol[ZIPW_E_COUNT], ecol[ZIPW_E_NAME_OFF], ecol[ZIPW_E_NAME_LEN],
+				   ecol[ZIPW_E_CEN], ecol[ZIPW_E_USIZE], ecol[ZIPW_E_UOFF],
+				   (const uint8_t *)s.names, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
+				   pcol[ZIPW_P_SLOT_OFF], (const uint64_t *)s.out_n,
+				   (const uint64_t *)s.e_info, (const uint64_t *)s.offs,
+				   (const uint64_t *)s.bsum, d_out, s.cp_src, s.cp_dst, s.cp_len,
+				   d_index);
+	if (np) {
+		const size_t grid = std::min(np, (size_t)ctx->num_cus * 8);
+		hipLaunchKernelGGL(lda_zipw_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
+				   (uint64_t)np, (const uint64_t *)(s.bsum + s.nblocks), out_avail, tail,
+				   (const uint64_t *)s.cp_src, (const uint64_t *)s.cp_dst,
+				   (const uint64_t *)s.cp_len, d_in, (const uint8_t *)s.slots, d_out);
+	}
+	hipLaunchKernelGGL(lda_zipw_final_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)n,
+			   (uint32_t)p.zip64, out_avail, p.cd_size, tail, ecol[ZIPW_E_USIZE],
+			   (const uint64_t *)s.e_info, (const uint64_t *)(s.bsum + s.nblocks), d_out,
+			   d_result);
+	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+	return LIBDEFLATE_AMD_OK;
+}
+
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_zip_compress_batch(struct libdeflate_compressor *c, size_t n_entries,
+				  const void *names, const uint64_t *name_offsets,
+				  const void *d_in, size_t in_avail, const uint64_t *in_offsets,
+				  const uint64_t *in_nbytes, void *d_out, size_t out_avail,
+				  uint64_t *d_result, uint64_t *d_index, uint32_t dos_datetime,
+				  unsigned flags, void *stream)
+{
+	const char *what = "zip_compress_batch";
+	if (!c || !d_out || !d_result || (!d_in && in_avail) ||
+	    (n_entries && (!names || !name_offsets || !in_offsets || !in_nbytes))) {
+		set_error("%s: NULL argument", what);
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
+		std::string err;
+		/* (before the count is known to be sane, no array is walked past it) */
+		if (!zipw_check(n_entries, name_offsets, in_offsets, in_nbytes, in_avail, out_avail,
+				flags, err)) {
+			set_error("%s: %s", what, err.c_str());
+			return LIBDEFLATE_AMD_BAD_ARG;
+		}
+		DeviceGuard on(c->device);
+		if (!on.ok() || !device_ctx())
+			return LIBDEFLATE_AMD_NO_DEVICE;
+		const EnvCfg &env = env_cfg();
+		zipw_params pr;
+		pr.level = c->level;
+		pr.store = c->level == 0 || (flags & LIBDEFLATE_AMD_ZIP_STORE);
+		pr.no_segments = env.no_segments;
+		pr.env_seg = env.seg_bytes;
+		pr.D = compress_prime_window();
+		pr.tile = lda_deflate_tile();
+		pr.small_max = c->level <= 9 && !env.no_small ? lda_deflate_small_max() : 0;
+		zipw_plan p;
+		const uint8_t *nm = n_entries ? (const uint8_t *)names + name_offsets[0] : NULL;
+		zipw_plan_build(pr, n_entries, (const uint8_t *)names, name_offsets, in_offsets,
+				in_nbytes, flags, p);
+		return zipw_enqueue(c, p, nm,
+				    n_entries ? (size_t)(name_offsets[n_entries] - name_offsets[0]) : 0,
+				    (const uint8_t *)d_in, (uint8_t *)d_out, out_avail, d_result, d_index,
+				    dos_datetime ? dos_datetime : 0x00210000u, (hipStream_t)stream);
+	});
+}

@@ -363,6 +363,31 @@ lda_zip_rfinal_kernel(uint64_t n_sel, const uint64_t *meta, const uint64_t *in_n
 		      const int32_t *batch_res, const uint64_t *actual_in, const uint32_t *crcs,
 		      int32_t *results);
 
+/* zip_write_kernels.hip: a ZIP archive assembled in device memory
+ * (host_zip_write.hip, zip_write_plan.h) */
+extern "C" __global__ void
+lda_zipw_entry_kernel(uint64_t n, const uint64_t *first, const uint64_t *count,
+		      const uint64_t *name_len, const uint64_t *usize, const uint64_t *pc_off,
+		      const uint64_t *pc_n, const uint64_t *out_n, const uint32_t *crcs,
+		      uint64_t *e_info, uint64_t *sizes);
+extern "C" __global__ void
+lda_zipw_place_kernel(uint64_t n, uint32_t zip64, uint32_t dos_datetime, uint64_t out_avail,
+		      uint64_t tail, const uint64_t *first, const uint64_t *count,
+		      const uint64_t *name_off, const uint64_t *name_len, const uint64_t *cen,
+		      const uint64_t *usize, const uint64_t *uoff, const uint8_t *names,
+		      const uint64_t *pc_off, const uint64_t *pc_n, const uint64_t *slot_off,
+		      const uint64_t *out_n, const uint64_t *e_info, const uint64_t *offsets,
+		      const uint64_t *block_sums, uint8_t *out, uint64_t *cp_src, uint64_t *cp_dst,
+		      uint64_t *cp_len, uint64_t *index);
+extern "C" __global__ void
+lda_zipw_copy_kernel(uint64_t np, const uint64_t *total_at, uint64_t out_avail, uint64_t tail,
+		     const uint64_t *cp_src, const uint64_t *cp_dst, const uint64_t *cp_len,
+		     const uint8_t *in, const uint8_t *slots, uint8_t *out);
+extern "C" __global__ void
+lda_zipw_final_kernel(uint64_t n, uint32_t zip64, uint64_t out_avail, uint64_t cd_size,
+		      uint64_t tail, const uint64_t *usize, const uint64_t *e_info,
+		      const uint64_t *total_at, uint8_t *out, uint64_t *result);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */

@@ -9,7 +9,17 @@
 #ifndef LDA_LARGE_PLAN_H
 #define LDA_LARGE_PLAN_H
 
+/* (a host compiler takes the arithmetic alone: tools/test_zip_write_plan.cpp) */
+#if defined(__HIPCC__) || defined(__HIP__)
 #include <hip/hip_runtime.h>
+#else
+#ifndef __host__
+#define __host__
+#endif
+#ifndef __device__
+#define __device__
+#endif
+#endif
 #include <stdint.h>
 
 #define LDA_SEG_BYTES 65536u
