@@ -6,7 +6,10 @@
  * of the finder, and the tests run it on the same files).
  *
  * The members form a linked list (next = pos + BSIZE + 1).  Walked by one
- * lane that is a dependent load per member, so the list is found in parallel:
+ * lane that is a dependent load per member, so the list is found in parallel
+ * (host_finder.h launches the finder, for this reader and for those of
+ * concatenated gzip members and ZIP directories, whose candidates the chain
+ * kernels below link as well):
  *
  *   lda_bgzf_scan_kernel     every byte offset against htslib's header rule
  *                            (1f 8b 08 04, XLEN 6, "BC" 2 0) with a size that
@@ -91,7 +94,7 @@ lda_bgzf_scan_kernel(const u8 *__restrict__ in, u64 n, u64 *__restrict__ counts,
 {
 	__shared__ __attribute__((aligned(16))) u32 tile[LDA_BR_TILE / 4 + 8];
 	__shared__ u32 wsum[4];
-	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const u32 tid = threadIdx.x;
 	const u64 wg0 = (u64)blockIdx.x * LDA_BR_SCAN_WG;
 	u64 at = 0;	/* candidates of this workgroup so far / where they go */
 
@@ -133,19 +136,8 @@ lda_bgzf_scan_kernel(const u8 *__restrict__ in, u64 n, u64 *__restrict__ counts,
 			}
 			mask = keep;
 		}
-		const u32 cnt = (u32)__builtin_popcount(mask);
-		const u32 incl = wave_scan_incl(cnt);
-		if (lane == 63)
-			wsum[wave] = incl;
-		__syncthreads();
-		u32 pre = incl - cnt, tot = 0;
-#pragma unroll
-		for (u32 k = 0; k < 4; k++) {
-			const u32 v = wsum[k];
-			if (k < wave)
-				pre += v;
-			tot += v;
-		}
+		u32 tot;
+		const u32 pre = wg_count_excl((u32)__builtin_popcount(mask), wsum, &tot);
 		if (offsets && mask && at + pre < cap) {
 			cand_pos[at + pre] = base + 16 * tid + (u32)__builtin_ctz(mask);
 			cand_size[at + pre] = size;

@@ -143,6 +143,28 @@ static __device__ __forceinline__ u32 wave_scan_incl(u32 v)
 	return v;
 }
 
+/* a workgroup of four waves: the sum of cnt over the threads below this one,
+ * *tot the sum over all.  One __syncthreads(); wsum[] is free again behind the
+ * caller's next one */
+static __device__ __forceinline__ u32 wg_count_excl(u32 cnt, u32 *wsum, u32 *tot)
+{
+	const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const u32 incl = wave_scan_incl(cnt);
+	if (lane == 63)
+		wsum[wave] = incl;
+	__syncthreads();
+	u32 pre = incl - cnt, t = 0;
+#pragma unroll
+	for (u32 k = 0; k < 4; k++) {
+		const u32 v = wsum[k];
+		if (k < wave)
+			pre += v;
+		t += v;
+	}
+	*tot = t;
+	return pre;
+}
+
 /* sum over lanes 0..15 (the first row), wave-uniform; the caller's lanes 16..63
  * take no part */
 static __device__ __forceinline__ u32 row16_sum(u32 v)

@@ -13,7 +13,8 @@
  *   lda_gzm_scan_kernel     every byte offset p against the candidate rule -
  *                           1f 8b 08, FLG & 0xE0 == 0, p + 18 <= n -: counted
  *                           per 16 KiB of file, then - after the scan kernels
- *                           of compact_kernels.hip - written in file order.
+ *                           of compact_kernels.hip - written in file order
+ *                           (host_finder.h launches the passes).
  *                           Candidates are not members: a stored block, a
  *                           FNAME or plain chance carries the three bytes.
  *   lda_gzm_slots_kernel    one size query (lda_inflate_sizes_kernel, GZIP)
@@ -27,8 +28,9 @@
  *   lda_gzm_size32_kernel   a candidate's size as the chain kernels want it:
  *                           actual_in as u32, 0 where the count failed.
  *   lda_bgzf_jump_kernel / lda_bgzf_top_kernel / lda_bgzf_members_kernel
- *                           (bgzf_read_kernels.hip, unchanged) keep the
- *                           candidates that the chain from offset 0 reaches.
+ *                           (bgzf_read_kernels.hip, launched by host_finder.h)
+ *                           keep the candidates that the chain from offset 0
+ *                           reaches.
  *   lda_gzm_break_kernel    where a broken chain stopped, and so its verdict.
  *   lda_gzm_msize_kernel    the counted size of every member.
  *   lda_gzm_desc_kernel     behind the scan of the sizes: the batch's
@@ -84,7 +86,7 @@ lda_gzm_scan_kernel(const u8 *__restrict__ in, u64 n, u64 *__restrict__ counts,
 {
 	__shared__ __attribute__((aligned(16))) u32 tile[LDA_BR_TILE / 4 + 4];
 	__shared__ u32 wsum[4];
-	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const u32 tid = threadIdx.x;
 	const u64 wg0 = (u64)blockIdx.x * LDA_BR_SCAN_WG;
 	u64 at = 0;	/* candidates of this workgroup so far / where they go */
 
@@ -127,19 +129,8 @@ lda_gzm_scan_kernel(const u8 *__restrict__ in, u64 n, u64 *__restrict__ counts,
 				if (p0 + j + MIN_MEMBER > n)
 					mask &= ~(1u << j);
 		}
-		const u32 cnt = (u32)__builtin_popcount(mask);
-		const u32 incl = wave_scan_incl(cnt);
-		if (lane == 63)
-			wsum[wave] = incl;
-		__syncthreads();
-		u32 pre = incl - cnt, tot = 0;
-#pragma unroll
-		for (u32 k = 0; k < 4; k++) {
-			const u32 v = wsum[k];
-			if (k < wave)
-				pre += v;
-			tot += v;
-		}
+		u32 tot;
+		const u32 pre = wg_count_excl((u32)__builtin_popcount(mask), wsum, &tot);
 		if (offsets) {
 			u64 dst = at + pre;
 			for (u32 m = mask; m && dst < cap; m &= m - 1, dst++)

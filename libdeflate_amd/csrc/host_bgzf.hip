@@ -103,12 +103,8 @@ static int bgzf_enqueue(struct libdeflate_compressor *c, const uint8_t *d_in, si
 			return rc;
 		/* the scans of libdeflate_amd_compact_batch(), then a copy that
 		 * writes nothing unless the whole file fits */
-		const size_t nblocks = (m + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
 		uint64_t *block_sums = cmp + m + 1;
-		hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)nblocks), dim3(256), 0, st,
-				   (uint64_t)m, (const uint64_t *)out_n, cmp, block_sums);
-		hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st,
-				   (uint64_t)nblocks, block_sums);
+		const size_t nblocks = scan_enqueue(st, m, out_n, cmp, block_sums);
 		const size_t grid = std::min(m, (size_t)ctx->num_cus * 8);
 		hipLaunchKernelGGL(lda_bgzf_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
 				   (uint64_t)m, (const uint8_t *)slots, (const uint64_t *)out_n,

@@ -1,8 +1,8 @@
 /*
  * host_bgzf_read.hip - C-ABI of reading BGZF files (include/libdeflate_amd.h).
  *
- * A file in device memory: the kernels of bgzf_read_kernels.hip find its
- * members, a prefix sum of their ISIZEs gives every member its place in one
+ * A file in device memory: the shared finder (host_finder.h) with the scan
+ * kernel of bgzf_read_kernels.hip finds its members, a prefix sum of their ISIZEs gives every member its place in one
  * contiguous output, and ONE decompress batch of max_members chunks (format
  * GZIP, exact fill) decodes there directly; the chunks behind the file's last
  * member are empty, and so are all of them when the file is refused before
@@ -17,22 +17,19 @@
 #include <algorithm>
 #include <vector>
 
+#include "host_finder.h"
 #include "host_objects.h"
-#include "kernels.h"
 
 using namespace lda;
 
-#define BR_MAX_MEMBERS ((size_t)1 << 28)	/* candidate indices are 32 bits */
-#define BR_MAX_FILE ((size_t)1 << 36)		/* member counts are 32 bits */
 #define BR_SLOT ((size_t)LIBDEFLATE_AMD_BGZF_MEMBER_MAX)
 #define BR_MIN_MEMBER 28
 
 struct FileScratch {
-	uint64_t *cand_pos, *counts, *offs, *bsum_a, *isize, *bsum_b;
-	uint64_t *in_off, *in_n, *out_off, *out_av, *ain;
-	uint32_t *cand_size, *next, *exit_at, *hops, *entry, *base, *state;
+	Finder f;
+	uint64_t *isize, *bsum_b, *in_off, *in_n, *out_off, *out_av, *ain;
 	int32_t *results;
-	size_t cap, nwg, nsb_a, nsb_b, nblk, bytes;
+	size_t bytes;
 };
 
 static FileScratch file_scratch(void *base, size_t n, size_t M)
@@ -40,53 +37,22 @@ static FileScratch file_scratch(void *base, size_t n, size_t M)
 	FileScratch s;
 	Carve c(base);
 	/* two members start 16 bytes apart at least (bgzf_read_kernels.hip) */
-	s.cap = std::min(4 * M + 1024, n / 16 + 1);
-	s.nwg = (n + LDA_BR_SCAN_WG - 1) / LDA_BR_SCAN_WG;
-	s.nsb_a = (s.nwg + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
-	s.nsb_b = (M + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
-	s.nblk = (s.cap + LDA_BR_JUMP - 1) / LDA_BR_JUMP;
-	s.state = c.take<uint32_t>(LDA_BR_STATE_WORDS);
-	s.cand_pos = c.take<uint64_t>(s.cap);
-	s.counts = c.take<uint64_t>(s.nwg);
-	s.offs = c.take<uint64_t>(s.nwg);
-	s.bsum_a = c.take<uint64_t>(s.nsb_a + 1);
+	s.f.carve(c, n, std::min(4 * M + 1024, n / 16 + 1));
 	s.isize = c.take<uint64_t>(M);
-	s.bsum_b = c.take<uint64_t>(s.nsb_b + 1);
+	s.bsum_b = c.take<uint64_t>(scan_blocks(M) + 1);
 	s.in_off = c.take<uint64_t>(M);
 	s.in_n = c.take<uint64_t>(M);
 	s.out_off = c.take<uint64_t>(M);
 	s.out_av = c.take<uint64_t>(M);
 	s.ain = c.take<uint64_t>(M);
-	s.cand_size = c.take<uint32_t>(s.cap);
-	s.next = c.take<uint32_t>(s.cap);
-	s.exit_at = c.take<uint32_t>(s.cap);
-	s.hops = c.take<uint32_t>(s.cap);
-	s.entry = c.take<uint32_t>(s.nblk);
-	s.base = c.take<uint32_t>(s.nblk);
+	s.f.carve_chain(c);
 	s.results = c.take<int32_t>(M);
 	s.bytes = c.at;
 	return s;
 }
 
-/* what the device calls check before they touch a device */
-static bool read_args_ok(const char *what, const struct libdeflate_decompressor *d,
-			 const void *d_in, size_t n, size_t max_members, const void *d_result)
-{
-	if (!d || (!d_in && n) || !d_result) {
-		set_error("%s: NULL argument", what);
-		return false;
-	}
-	if ((n && !max_members) || max_members > BR_MAX_MEMBERS) {
-		set_error("%s: max_members %zu (1 .. 2^28 for a file of %zu bytes)", what,
-			  max_members, n);
-		return false;
-	}
-	if (n > BR_MAX_FILE) {
-		set_error("%s: in_nbytes %zu above 2^36", what, n);
-		return false;
-	}
-	return true;
-}
+/* a file of no bytes may have room for no member */
+#define BR_MAX_MEMBERS_MSG "%s: max_members %zu (1 .. 2^28 for a file of %zu bytes)"
 
 static int read_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, size_t n,
 			size_t M, uint8_t *d_out, uint64_t out_avail, uint64_t *d_result,
@@ -107,55 +73,35 @@ static int read_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, 
 	if (!ws)
 		return LIBDEFLATE_AMD_OOM;
 	const FileScratch s = file_scratch(ws, n, M);
+	const Finder &f = s.f;
 	const bool serial = env_cfg().bgzf_serial;
 	const uint64_t *k_at = NULL;
 	const unsigned per256 = (unsigned)((M + 255) / 256);
 
-	LDA_HIP_TRY(hipMemsetAsync(s.state, 0, LDA_BR_STATE_WORDS * 4, st), LIBDEFLATE_AMD_NO_DEVICE);
-	if (!serial) {
-		/* candidates: count, scan, write in file order */
-		hipLaunchKernelGGL(lda_bgzf_scan_kernel, dim3((unsigned)s.nwg), dim3(256), 0, st, d_in,
-				   (uint64_t)n, s.counts, (const uint64_t *)NULL,
-				   (const uint64_t *)NULL, (uint64_t)s.cap, s.cand_pos, s.cand_size);
-		hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nsb_a), dim3(256), 0, st,
-				   (uint64_t)s.nwg, (const uint64_t *)s.counts, s.offs, s.bsum_a);
-		hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st,
-				   (uint64_t)s.nsb_a, s.bsum_a);
-		hipLaunchKernelGGL(lda_bgzf_scan_kernel, dim3((unsigned)s.nwg), dim3(256), 0, st, d_in,
-				   (uint64_t)n, s.counts, (const uint64_t *)s.offs,
-				   (const uint64_t *)s.bsum_a, (uint64_t)s.cap, s.cand_pos,
-				   s.cand_size);
-		k_at = s.bsum_a + s.nsb_a;
-		/* the chain: none of these does anything when the candidates
-		 * overflowed their space - then the walk below runs */
-		hipLaunchKernelGGL(lda_bgzf_jump_kernel, dim3((unsigned)s.nblk), dim3(LDA_BR_JUMP), 0,
-				   st, (uint64_t)n, k_at, (uint64_t)s.cap,
-				   (const uint64_t *)s.cand_pos, (const uint32_t *)s.cand_size, s.next,
-				   s.exit_at, s.hops, s.entry);
-		hipLaunchKernelGGL(lda_bgzf_top_kernel, dim3(1), dim3(64), 0, st, k_at,
-				   (uint64_t)s.cap, (const uint64_t *)s.cand_pos,
-				   (const uint32_t *)s.exit_at, (const uint32_t *)s.hops, s.entry,
-				   s.base, s.state);
-		hipLaunchKernelGGL(lda_bgzf_members_kernel, dim3((unsigned)s.nblk), dim3(LDA_BR_JUMP),
-				   0, st, k_at, (uint64_t)s.cap, (uint64_t)M,
-				   (const uint64_t *)s.cand_pos, (const uint32_t *)s.cand_size,
-				   (const uint32_t *)s.next, (const uint32_t *)s.hops,
-				   (const uint32_t *)s.entry, (const uint32_t *)s.base,
-				   (const uint32_t *)s.state, s.in_off, s.in_n);
+	if (serial) {
+		LDA_HIP_TRY(hipMemsetAsync(f.state, 0, LDA_BR_STATE_WORDS * 4, st),
+			    LIBDEFLATE_AMD_NO_DEVICE);
+	} else {
+		LDA_OK_TRY(finder_list(f, st, [&](const uint64_t *offs, const uint64_t *bsum) {
+			hipLaunchKernelGGL(lda_bgzf_scan_kernel, dim3((unsigned)f.nwg), dim3(256), 0, st,
+					   d_in, (uint64_t)n, f.counts, offs, bsum, (uint64_t)f.cap,
+					   f.cand_pos, f.cand_size);
+		}));
+		k_at = f.k_at();
+		/* when the candidates overflowed their room the chain does nothing
+		 * and the walk below runs */
+		finder_chain(f, st, n, M, s.in_off, s.in_n);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
 	hipLaunchKernelGGL(lda_bgzf_walk_kernel, dim3(1), dim3(64), 0, st, d_in, (uint64_t)n,
-			   (uint64_t)M, k_at, (uint64_t)s.cap, (int)serial, s.in_off, s.in_n, s.state);
+			   (uint64_t)M, k_at, (uint64_t)f.cap, (int)serial, s.in_off, s.in_n, f.state);
 	/* ISIZEs -> places in the output -> descriptors and index */
 	hipLaunchKernelGGL(lda_bgzf_isize_kernel, dim3(per256), dim3(256), 0, st, d_in, (uint64_t)n,
-			   (uint64_t)M, (const uint64_t *)s.in_off, (const uint64_t *)s.in_n, s.state,
+			   (uint64_t)M, (const uint64_t *)s.in_off, (const uint64_t *)s.in_n, f.state,
 			   s.isize);
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nsb_b), dim3(256), 0, st,
-			   (uint64_t)M, (const uint64_t *)s.isize, s.out_off, s.bsum_b);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)s.nsb_b,
-			   s.bsum_b);
+	const uint64_t *total_at = s.bsum_b + scan_enqueue(st, M, s.isize, s.out_off, s.bsum_b);
 	hipLaunchKernelGGL(lda_bgzf_rdesc_kernel, dim3(per256), dim3(256), 0, st, (uint64_t)M,
-			   out_avail, (const uint32_t *)s.state, (const uint64_t *)s.isize,
+			   out_avail, (const uint32_t *)f.state, (const uint64_t *)s.isize,
 			   (const uint64_t *)s.bsum_b, s.in_off, s.in_n, s.out_off, s.out_av, d_index);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	if (decode) {
@@ -168,9 +114,9 @@ static int read_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, 
 			return rc;
 	}
 	hipLaunchKernelGGL(lda_bgzf_rfinal_kernel, dim3(1), dim3(256), 0, st, d_in, (uint64_t)n,
-			   (uint64_t)M, out_avail, (const uint32_t *)s.state,
-			   (const uint64_t *)(s.bsum_b + s.nsb_b), (const uint64_t *)s.in_off,
-			   (const uint64_t *)s.in_n, (const int32_t *)(decode ? s.results : NULL),
+			   (uint64_t)M, out_avail, (const uint32_t *)f.state, total_at,
+			   (const uint64_t *)s.in_off, (const uint64_t *)s.in_n,
+			   (const int32_t *)(decode ? s.results : NULL),
 			   (const uint64_t *)s.ain, d_result, d_index);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	return LIBDEFLATE_AMD_OK;
@@ -183,7 +129,8 @@ libdeflate_amd_bgzf_decompress_batch(struct libdeflate_decompressor *d, const vo
 				     void *stream)
 {
 	const char *what = "bgzf_decompress_batch";
-	if (!read_args_ok(what, d, d_in, in_nbytes, max_members, d_result))
+	if (!finder_args_ok(what, d, d_in, in_nbytes, BR_MAX_MEMBERS_MSG, max_members, !!in_nbytes,
+			    d_result))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	if (!d_out && in_nbytes) {
 		set_error("%s: NULL argument", what);
@@ -201,7 +148,8 @@ libdeflate_amd_bgzf_index_batch(struct libdeflate_decompressor *d, const void *d
 				size_t in_nbytes, size_t max_members, uint64_t *d_result,
 				uint64_t *d_index, void *stream)
 {
-	if (!read_args_ok("bgzf_index_batch", d, d_in, in_nbytes, max_members, d_result))
+	if (!finder_args_ok("bgzf_index_batch", d, d_in, in_nbytes, BR_MAX_MEMBERS_MSG, max_members, !!in_nbytes,
+			    d_result))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	DeviceGuard on(d->device);
 	if (!on.ok())
@@ -355,14 +303,9 @@ static int read_ranges(struct libdeflate_decompressor *d, const uint8_t *d_in,
 		g_slots = cv->take<uint8_t>(T * BR_SLOT + 16, 256);
 	};
 	lay(&sizes);
-	/* the pinned block of the last call may still be on its way up */
-	if (d->bgzf_up)
-		LDA_HIP_TRY(hipEventSynchronize(d->bgzf_up), LIBDEFLATE_AMD_NO_DEVICE);
-	else
-		LDA_HIP_TRY(hipEventCreateWithFlags(&d->bgzf_up, hipEventDisableTiming),
-			    LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_OK_TRY(d->bgzf_up.begin());
 	uint8_t *ws = (uint8_t *)d->bgzf.reserve(sizes.at);
-	uint64_t *h = (uint64_t *)d->bgzf_desc.ensure(std::max(up_bytes, (size_t)64));
+	uint64_t *h = (uint64_t *)d->bgzf_up.pinned(up_bytes);
 	if (!ws || !h)
 		return LIBDEFLATE_AMD_OOM;
 	Carve real(ws);
@@ -378,13 +321,11 @@ static int read_ranges(struct libdeflate_decompressor *d, const uint8_t *d_in,
 	memcpy(h + 4 * N, first.data(), (n_ranges + 1) * 8);
 	if (T)
 		memcpy(h + 4 * N + n_ranges + 1, trims.data(), 3 * T * 8);
-	LDA_HIP_TRY(hipMemcpyAsync(ws, h, up_bytes, hipMemcpyHostToDevice, st),
-		    LIBDEFLATE_AMD_NO_DEVICE);
-	LDA_HIP_TRY(hipEventRecord(d->bgzf_up, st), LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_OK_TRY(d->bgzf_up.send(ws, up_bytes, st));
 	if (N) {
-		int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_GZIP, N, d_in, g_desc,
-							 g_desc + N, d_out, g_desc + 2 * N,
-							 g_desc + 3 * N, g_res, g_ain, NULL, st);
+		int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_GZIP, N, d_in, g_desc, g_desc + N,
+						     d_out, g_desc + 2 * N, g_desc + 3 * N, g_res, g_ain,
+						     NULL, st);
 		if (rc != LIBDEFLATE_AMD_OK)
 			return rc;
 	}
@@ -418,7 +359,7 @@ libdeflate_amd_bgzf_read_batch(struct libdeflate_decompressor *d, const void *d_
 		set_error("%s: unknown flags 0x%x", what, flags);
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
-	if (members > BR_MAX_MEMBERS || !index_ok(what, index, members, in_nbytes))
+	if (members > LDA_FINDER_MAX_RECORDS || !index_ok(what, index, members, in_nbytes))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
 		std::vector<uint64_t> rb, re;

@@ -27,6 +27,13 @@ void set_error(const char *fmt, ...);
 			return failret;                                      \
 		}                                                            \
 	} while (0)
+/* ... for a call of ours that returns a LIBDEFLATE_AMD_* status */
+#define LDA_OK_TRY(expr)                                                     \
+	do {                                                                 \
+		int rc_ = (expr);                                            \
+		if (rc_ != LIBDEFLATE_AMD_OK)                                \
+			return rc_;                                          \
+	} while (0)
 /* ... in a function that says "not done here" with false */
 #define LDA_TRY(expr) LDA_HIP_TRY(expr, false)
 
@@ -132,6 +139,21 @@ struct PinnedBuf {
 	void *ensure(size_t want);	/* nullptr + error on failure */
 	void release();
 };
+/*
+ * Host arrays on their way to an object's device scratch, through a pinned
+ * block in one asynchronous copy.  The block of the last call may still be on
+ * its way up, so begin() waits for the event behind that copy (and makes the
+ * event on first use); the caller then reserves its device scratch, fills
+ * pinned(bytes) and hands it to send().
+ */
+struct Upload {
+	PinnedBuf desc;
+	hipEvent_t up = nullptr;
+	int begin();					/* OK or NO_DEVICE */
+	void *pinned(size_t bytes) { return desc.ensure(bytes < 64 ? 64 : bytes); }	/* nullptr + error on failure */
+	int send(void *d_dst, size_t bytes, hipStream_t st);	/* OK or NO_DEVICE */
+	void release();
+};
 #define LDA_PINNED_SLICE ((size_t)32 << 20)
 #define LDA_PINNED_MIN ((size_t)64 << 10)
 
@@ -211,6 +233,15 @@ struct Carve {
 		return r;
 	}
 };
+
+/* host_compact.hip: the exclusive prefix sum of n sizes on `st`, in blocks of
+ * LDA_SCAN_BLOCK: the place of size i is offsets[i] + block_sums[i /
+ * LDA_SCAN_BLOCK], and the total is at block_sums + the block count, which
+ * scan_enqueue() returns (block_sums: scan_blocks(n) + 1 words).  n == 0
+ * writes the total alone */
+size_t scan_blocks(size_t n);
+size_t scan_enqueue(hipStream_t st, size_t n, const uint64_t *sizes, uint64_t *offsets,
+		    uint64_t *block_sums);
 
 /*
  * Nothing may unwind through an extern "C" entry point: the reference is C and

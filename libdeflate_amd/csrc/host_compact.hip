@@ -1,16 +1,34 @@
 /*
  * host_compact.hip - C-ABI of the device-side output compaction
- * (compact_kernels.hip): prefix sum of the per-chunk sizes + one gather copy.
+ * (compact_kernels.hip): prefix sum of the per-chunk sizes + one gather copy,
+ * and the prefix sum alone for every other caller (scan_enqueue()).
  */
 #include "host_common.h"
 #include "kernels.h"
 
 using namespace lda;
 
+size_t lda::scan_blocks(size_t n)
+{
+	return (n + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
+}
+
+size_t lda::scan_enqueue(hipStream_t st, size_t n, const uint64_t *sizes, uint64_t *offsets,
+			 uint64_t *block_sums)
+{
+	const size_t nblocks = scan_blocks(n);
+	if (nblocks)
+		hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)nblocks), dim3(256), 0, st,
+				   (uint64_t)n, sizes, offsets, block_sums);
+	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)nblocks,
+			   block_sums);
+	return nblocks;
+}
+
 extern "C" LIBDEFLATEAPI size_t
 libdeflate_amd_compact_offsets_len(size_t n_chunks)
 {
-	return n_chunks + 2 + (n_chunks + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
+	return n_chunks + 2 + scan_blocks(n_chunks);
 }
 
 extern "C" LIBDEFLATEAPI int
@@ -32,12 +50,8 @@ libdeflate_amd_compact_batch(size_t n, const void *d_in,
 		LDA_HIP_TRY(hipMemsetAsync(d_out_offsets, 0, 8, st), LIBDEFLATE_AMD_NO_DEVICE);
 		return LIBDEFLATE_AMD_OK;
 	}
-	const size_t nblocks = (n + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
-	uint64_t *block_sums = d_out_offsets + n + 1;	/* nblocks + 1 entries */
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)nblocks), dim3(256),
-			   0, st, (uint64_t)n, d_nbytes, d_out_offsets, block_sums);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st,
-			   (uint64_t)nblocks, block_sums);
+	uint64_t *block_sums = d_out_offsets + n + 1;	/* scan_blocks(n) + 1 entries */
+	scan_enqueue(st, n, d_nbytes, d_out_offsets, block_sums);
 	size_t grid = (size_t)c->num_cus * 8;
 	if (grid > n)
 		grid = n;

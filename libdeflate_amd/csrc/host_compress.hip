@@ -106,9 +106,7 @@ libdeflate_free_compressor(struct libdeflate_compressor *c)
 	c->bgzf.release();
 	c->large.release();
 	c->zipw.release();
-	c->zipw_desc.release();
-	if (c->zipw_up)
-		(void)hipEventDestroy(c->zipw_up);
+	c->zipw_up.release();
 	c->streams.release();
 	free_func_t f = c->free_func;
 	c->~libdeflate_compressor();
@@ -1056,12 +1054,8 @@ libdeflate_amd_compress_large_batch(struct libdeflate_compressor *c, int format,
 	}
 	/* the scans of libdeflate_amd_compact_batch(), a copy that writes nothing
 	 * unless the whole stream fits, and the container around it */
-	const size_t nblocks = (nseg + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
 	uint64_t *block_sums = cmp + nseg + 1;
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)nblocks), dim3(256), 0, st,
-			   (uint64_t)nseg, (const uint64_t *)out_n, cmp, block_sums);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)nblocks,
-			   block_sums);
+	const size_t nblocks = scan_enqueue(st, nseg, out_n, cmp, block_sums);
 	const size_t grid = std::min(nseg, (size_t)ctx->num_cus * 8);
 	hipLaunchKernelGGL(lda_large_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
 			   (uint64_t)nseg, (const uint8_t *)slots, (uint64_t)slot,

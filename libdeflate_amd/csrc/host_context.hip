@@ -169,6 +169,31 @@ void PinnedBuf::release()
 	cap = 0;
 }
 
+int Upload::begin()
+{
+	if (up)
+		LDA_HIP_TRY(hipEventSynchronize(up), LIBDEFLATE_AMD_NO_DEVICE);
+	else
+		LDA_HIP_TRY(hipEventCreateWithFlags(&up, hipEventDisableTiming), LIBDEFLATE_AMD_NO_DEVICE);
+	return LIBDEFLATE_AMD_OK;
+}
+
+int Upload::send(void *d_dst, size_t bytes, hipStream_t st)
+{
+	LDA_HIP_TRY(hipMemcpyAsync(d_dst, desc.p, bytes, hipMemcpyHostToDevice, st),
+		    LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_HIP_TRY(hipEventRecord(up, st), LIBDEFLATE_AMD_NO_DEVICE);
+	return LIBDEFLATE_AMD_OK;
+}
+
+void Upload::release()
+{
+	desc.release();
+	if (up)
+		(void)hipEventDestroy(up);
+	up = nullptr;
+}
+
 bool StreamPair::ensure()
 {
 	if (copy && comp && mark && mark2)

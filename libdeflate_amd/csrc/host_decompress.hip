@@ -159,13 +159,9 @@ libdeflate_free_decompressor(struct libdeflate_decompressor *d)
 	d->meta.release();
 	d->streams.release();
 	d->bgzf.release();
-	d->bgzf_desc.release();
-	if (d->bgzf_up)
-		(void)hipEventDestroy(d->bgzf_up);
+	d->bgzf_up.release();
 	d->seek.release();
-	d->seek_desc.release();
-	if (d->seek_up)
-		(void)hipEventDestroy(d->seek_up);
+	d->seek_up.release();
 	free_func_t f = d->free_func;
 	d->~libdeflate_decompressor();
 	f(d);

@@ -2,11 +2,11 @@
  * host_gzip_members.hip - C-ABI of reading a file of concatenated gzip members
  * from device memory (include/libdeflate_amd.h).
  *
- * The kernels of gzip_members_kernels.hip list every offset that looks like a
- * gzip header, ONE size query (host_sizes.hip) count-parses all of them at
- * once, the chain kernels of the BGZF reader keep the candidates reachable
- * from offset 0, a prefix sum of their counted sizes gives every member its
- * place in one contiguous output, and ONE decompress batch of max_members
+ * The shared finder (host_finder.h) lists every offset that looks like a gzip
+ * header and, once ONE size query (host_sizes.hip) has count-parsed all of
+ * them, keeps the candidates reachable from offset 0; a prefix sum of their
+ * counted sizes gives every member its place in one contiguous output, and
+ * ONE decompress batch of max_members
  * chunks (format GZIP, exact input, exact fill) decodes there directly; the
  * chunks behind the file's last member are empty, and so are all of them when
  * the file is refused before the decode.  Nothing waits for the device and
@@ -15,13 +15,13 @@
  */
 #include <algorithm>
 
+#include "host_finder.h"
 #include "host_objects.h"
-#include "kernels.h"
 
 using namespace lda;
 
-#define GZM_MAX_MEMBERS ((size_t)1 << 28)	/* candidate indices are 32 bits */
-#define GZM_MAX_FILE ((size_t)1 << 36)
+
+#define GZM_MAX_MEMBERS_MSG "%s: max_members %zu (1 .. 2^28)"
 
 static_assert(LIBDEFLATE_AMD_GZM_MORE_MEMBERS == LDA_BR_MORE &&
 	      LIBDEFLATE_AMD_GZM_MORE_CANDIDATES == LDA_GZM_MORE_CANDIDATES &&
@@ -30,17 +30,15 @@ static_assert(LIBDEFLATE_AMD_GZM_MORE_MEMBERS == LDA_BR_MORE &&
 	      "kernels.h holds copies of the header's constants");
 
 struct MembersScratch {
-	uint32_t *state;
-	/* the candidates: positions, the size query's descriptors and answers,
-	 * the chain */
-	uint64_t *cand_pos, *counts, *offs, *bsum_a, *c_in_off, *c_in_n, *c_ain, *c_out;
+	Finder f;
+	/* the candidates: the size query's descriptors and answers */
+	uint64_t *c_in_off, *c_in_n, *c_ain, *c_out;
 	int32_t *c_res;
-	uint32_t *cand_size, *next, *exit_at, *hops, *entry, *base;
 	/* the members: sizes, the decode batch */
 	uint64_t *msize, *bsum_b, *in_off, *in_n, *out_off, *out_av, *ain;
 	int32_t *results;
 	uint8_t *sizes;		/* the size query's own scratch */
-	size_t cap, nwg, nsb_a, nsb_b, nblk, bytes;
+	size_t bytes;
 };
 
 static MembersScratch members_scratch(void *base, size_t n, size_t M)
@@ -48,57 +46,25 @@ static MembersScratch members_scratch(void *base, size_t n, size_t M)
 	MembersScratch s;
 	Carve c(base);
 	/* two candidates start 3 bytes apart at least */
-	s.cap = std::min(M + LIBDEFLATE_AMD_GZM_SLACK, n / 3 + 1);
-	s.nwg = (n + LDA_BR_SCAN_WG - 1) / LDA_BR_SCAN_WG;
-	s.nsb_a = (s.nwg + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
-	s.nsb_b = (M + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
-	s.nblk = (s.cap + LDA_BR_JUMP - 1) / LDA_BR_JUMP;
-	s.state = c.take<uint32_t>(LDA_BR_STATE_WORDS);
-	s.cand_pos = c.take<uint64_t>(s.cap);
-	s.counts = c.take<uint64_t>(s.nwg);
-	s.offs = c.take<uint64_t>(s.nwg);
-	s.bsum_a = c.take<uint64_t>(s.nsb_a + 1);
-	s.c_in_off = c.take<uint64_t>(s.cap);
-	s.c_in_n = c.take<uint64_t>(s.cap);
-	s.c_ain = c.take<uint64_t>(s.cap);
-	s.c_out = c.take<uint64_t>(s.cap);
+	s.f.carve(c, n, std::min(M + LIBDEFLATE_AMD_GZM_SLACK, n / 3 + 1));
+	const size_t cap = s.f.cap;
+	s.c_in_off = c.take<uint64_t>(cap);
+	s.c_in_n = c.take<uint64_t>(cap);
+	s.c_ain = c.take<uint64_t>(cap);
+	s.c_out = c.take<uint64_t>(cap);
 	s.msize = c.take<uint64_t>(M);
-	s.bsum_b = c.take<uint64_t>(s.nsb_b + 1);
+	s.bsum_b = c.take<uint64_t>(scan_blocks(M) + 1);
 	s.in_off = c.take<uint64_t>(M);
 	s.in_n = c.take<uint64_t>(M);
 	s.out_off = c.take<uint64_t>(M);
 	s.out_av = c.take<uint64_t>(M);
 	s.ain = c.take<uint64_t>(M);
-	s.c_res = c.take<int32_t>(s.cap);
-	s.cand_size = c.take<uint32_t>(s.cap);
-	s.next = c.take<uint32_t>(s.cap);
-	s.exit_at = c.take<uint32_t>(s.cap);
-	s.hops = c.take<uint32_t>(s.cap);
-	s.entry = c.take<uint32_t>(s.nblk);
-	s.base = c.take<uint32_t>(s.nblk);
+	s.c_res = c.take<int32_t>(cap);
+	s.f.carve_chain(c);
 	s.results = c.take<int32_t>(M);
-	s.sizes = c.take<uint8_t>(sizes_scratch_bytes(s.cap), 64);
+	s.sizes = c.take<uint8_t>(sizes_scratch_bytes(cap), 64);
 	s.bytes = c.at;
 	return s;
-}
-
-/* what both calls check before they touch a device */
-static bool members_args_ok(const char *what, const struct libdeflate_decompressor *d,
-			    const void *d_in, size_t n, size_t max_members, const void *d_result)
-{
-	if (!d || (!d_in && n) || !d_result) {
-		set_error("%s: NULL argument", what);
-		return false;
-	}
-	if (!max_members || max_members > GZM_MAX_MEMBERS) {
-		set_error("%s: max_members %zu (1 .. 2^28)", what, max_members);
-		return false;
-	}
-	if (n > GZM_MAX_FILE) {
-		set_error("%s: in_nbytes %zu above 2^36", what, n);
-		return false;
-	}
-	return true;
 }
 
 static int members_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, size_t n,
@@ -121,60 +87,39 @@ static int members_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_i
 	if (!ws)
 		return LIBDEFLATE_AMD_OOM;
 	const MembersScratch s = members_scratch(ws, n, M);
-	const uint64_t *k_at = s.bsum_a + s.nsb_a;
-	const uint64_t cap = s.cap;
+	const Finder &f = s.f;
+	const uint64_t *k_at = f.k_at();
+	const uint64_t cap = f.cap;
 	const unsigned per256 = (unsigned)((M + 255) / 256);
-	const unsigned cap256 = (unsigned)((s.cap + 255) / 256);
+	const unsigned cap256 = (unsigned)((f.cap + 255) / 256);
 
-	LDA_HIP_TRY(hipMemsetAsync(s.state, 0, LDA_BR_STATE_WORDS * 4, st), LIBDEFLATE_AMD_NO_DEVICE);
-	/* candidates: count, scan, write in file order */
-	hipLaunchKernelGGL(lda_gzm_scan_kernel, dim3((unsigned)s.nwg), dim3(256), 0, st, d_in,
-			   (uint64_t)n, s.counts, (const uint64_t *)NULL, (const uint64_t *)NULL, cap,
-			   s.cand_pos);
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nsb_a), dim3(256), 0, st,
-			   (uint64_t)s.nwg, (const uint64_t *)s.counts, s.offs, s.bsum_a);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)s.nsb_a,
-			   s.bsum_a);
-	hipLaunchKernelGGL(lda_gzm_scan_kernel, dim3((unsigned)s.nwg), dim3(256), 0, st, d_in,
-			   (uint64_t)n, s.counts, (const uint64_t *)s.offs, (const uint64_t *)s.bsum_a,
-			   cap, s.cand_pos);
+	LDA_OK_TRY(finder_list(f, st, [&](const uint64_t *offs, const uint64_t *bsum) {
+		hipLaunchKernelGGL(lda_gzm_scan_kernel, dim3((unsigned)f.nwg), dim3(256), 0, st, d_in,
+				   (uint64_t)n, f.counts, offs, bsum, cap, f.cand_pos);
+	}));
 	/* the speculation: every candidate whose header is bounded counted as a
 	 * member that runs to the end of the file at most (none of what follows
 	 * does anything when the candidates overflowed their room) */
 	hipLaunchKernelGGL(lda_gzm_slots_kernel, dim3(cap256), dim3(256), 0, st, d_in, (uint64_t)n, k_at,
-			   cap, (const uint64_t *)s.cand_pos, s.c_in_off, s.c_in_n);
+			   cap, (const uint64_t *)f.cand_pos, s.c_in_off, s.c_in_n);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	int rc = sizes_enqueue(ctx, s.sizes, LIBDEFLATE_AMD_GZIP, s.cap, d_in, s.c_in_off, s.c_in_n,
-			       NULL, s.c_res, s.c_ain, s.c_out, st, NULL, 0);
+	int rc = sizes_enqueue(ctx, s.sizes, LIBDEFLATE_AMD_GZIP, f.cap, d_in, s.c_in_off, s.c_in_n, NULL,
+			   s.c_res, s.c_ain, s.c_out, st, NULL, 0);
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
 	hipLaunchKernelGGL(lda_gzm_size32_kernel, dim3(cap256), dim3(256), 0, st, k_at, cap,
-			   s.c_res, (const uint64_t *)s.c_ain, s.cand_size);
-	/* the chain among the candidates */
-	hipLaunchKernelGGL(lda_bgzf_jump_kernel, dim3((unsigned)s.nblk), dim3(LDA_BR_JUMP), 0, st,
-			   (uint64_t)n, k_at, cap, (const uint64_t *)s.cand_pos,
-			   (const uint32_t *)s.cand_size, s.next, s.exit_at, s.hops, s.entry);
-	hipLaunchKernelGGL(lda_bgzf_top_kernel, dim3(1), dim3(64), 0, st, k_at, cap,
-			   (const uint64_t *)s.cand_pos, (const uint32_t *)s.exit_at,
-			   (const uint32_t *)s.hops, s.entry, s.base, s.state);
-	hipLaunchKernelGGL(lda_bgzf_members_kernel, dim3((unsigned)s.nblk), dim3(LDA_BR_JUMP), 0, st,
-			   k_at, cap, (uint64_t)M, (const uint64_t *)s.cand_pos,
-			   (const uint32_t *)s.cand_size, (const uint32_t *)s.next,
-			   (const uint32_t *)s.hops, (const uint32_t *)s.entry,
-			   (const uint32_t *)s.base, (const uint32_t *)s.state, s.in_off, s.in_n);
+			   s.c_res, (const uint64_t *)s.c_ain, f.cand_size);
+	finder_chain(f, st, n, M, s.in_off, s.in_n);
 	hipLaunchKernelGGL(lda_gzm_break_kernel, dim3(1), dim3(64), 0, st, k_at, cap,
-			   (const uint64_t *)s.cand_pos, (const uint32_t *)s.next,
-			   (const uint32_t *)s.exit_at, (const int32_t *)s.c_res, s.state);
+			   (const uint64_t *)f.cand_pos, (const uint32_t *)f.next,
+			   (const uint32_t *)f.exit_at, (const int32_t *)s.c_res, f.state);
 	/* counted sizes -> places in the output -> descriptors and index */
 	hipLaunchKernelGGL(lda_gzm_msize_kernel, dim3(per256), dim3(256), 0, st, (uint64_t)M, k_at,
-			   cap, (const uint64_t *)s.cand_pos, (const uint64_t *)s.c_out,
-			   (const uint32_t *)s.state, (const uint64_t *)s.in_off, s.msize);
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nsb_b), dim3(256), 0, st,
-			   (uint64_t)M, (const uint64_t *)s.msize, s.out_off, s.bsum_b);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)s.nsb_b,
-			   s.bsum_b);
+			   cap, (const uint64_t *)f.cand_pos, (const uint64_t *)s.c_out,
+			   (const uint32_t *)f.state, (const uint64_t *)s.in_off, s.msize);
+	const uint64_t *total_at = s.bsum_b + scan_enqueue(st, M, s.msize, s.out_off, s.bsum_b);
 	hipLaunchKernelGGL(lda_gzm_desc_kernel, dim3(per256), dim3(256), 0, st, (uint64_t)M,
-			   out_avail, k_at, cap, (const uint32_t *)s.state, (const uint64_t *)s.msize,
+			   out_avail, k_at, cap, (const uint32_t *)f.state, (const uint64_t *)s.msize,
 			   (const uint64_t *)s.bsum_b, s.in_off, s.in_n, s.out_off, s.out_av, d_index);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	if (decode) {
@@ -187,8 +132,8 @@ static int members_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_i
 			return rc;
 	}
 	hipLaunchKernelGGL(lda_gzm_final_kernel, dim3(1), dim3(256), 0, st, (uint64_t)n, (uint64_t)M,
-			   out_avail, k_at, cap, (const uint32_t *)s.state,
-			   (const uint64_t *)(s.bsum_b + s.nsb_b), (const uint64_t *)s.in_n,
+			   out_avail, k_at, cap, (const uint32_t *)f.state, total_at,
+			   (const uint64_t *)s.in_n,
 			   (const int32_t *)(decode ? s.results : NULL), (const uint64_t *)s.ain,
 			   d_result, d_index);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -202,7 +147,7 @@ libdeflate_amd_gzip_members_decompress_batch(struct libdeflate_decompressor *d, 
 					     void *stream)
 {
 	const char *what = "gzip_members_decompress_batch";
-	if (!members_args_ok(what, d, d_in, in_nbytes, max_members, d_result))
+	if (!finder_args_ok(what, d, d_in, in_nbytes, GZM_MAX_MEMBERS_MSG, max_members, 1, d_result))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	if (!d_out && out_avail) {
 		set_error("%s: NULL argument", what);
@@ -220,7 +165,8 @@ libdeflate_amd_gzip_members_index_batch(struct libdeflate_decompressor *d, const
 					size_t in_nbytes, size_t max_members, uint64_t *d_result,
 					uint64_t *d_index, void *stream)
 {
-	if (!members_args_ok("gzip_members_index_batch", d, d_in, in_nbytes, max_members, d_result))
+	if (!finder_args_ok("gzip_members_index_batch", d, d_in, in_nbytes, GZM_MAX_MEMBERS_MSG,
+			    max_members, 1, d_result))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	DeviceGuard on(d->device);
 	if (!on.ok())
@@ -234,7 +180,7 @@ libdeflate_amd_gzip_members_index_batch(struct libdeflate_decompressor *d, const
 extern "C" __attribute__((visibility("default"))) int
 lda_gzm_scan_bench(const void *d_in, size_t n, uint64_t *d_counts, void *stream)
 {
-	if (!d_in || !n || !d_counts || n > GZM_MAX_FILE)
+	if (!d_in || !n || !d_counts || n > LDA_FINDER_MAX_FILE)
 		return LIBDEFLATE_AMD_BAD_ARG;
 	hipLaunchKernelGGL(lda_gzm_scan_kernel,
 			   dim3((unsigned)((n + LDA_BR_SCAN_WG - 1) / LDA_BR_SCAN_WG)), dim3(256), 0,

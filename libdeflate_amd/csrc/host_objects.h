@@ -54,18 +54,16 @@ struct libdeflate_decompressor {
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */
 	/* BGZF files read on the device (host_bgzf_read.hip): candidates, chain,
 	 * descriptors, edge slots; the descriptors of a ranged read on their way
-	 * up, and the event behind that copy.  The reader of concatenated gzip
+	 * up.  The reader of concatenated gzip
 	 * members (host_gzip_members.hip) keeps its candidates, counts, chain and
 	 * descriptors in the same buffer */
 	lda::DevBuf bgzf;
-	lda::PinnedBuf bgzf_desc;
-	hipEvent_t bgzf_up = nullptr;
+	lda::Upload bgzf_up;
 	/* the seek index (host_seek.hip): descriptors and results of the intervals
 	 * of a build's verification or of a ranged read; a read's descriptors on
-	 * their way up, and the event behind that copy */
+	 * their way up */
 	lda::DevBuf seek;
-	lda::PinnedBuf seek_desc;
-	hipEvent_t seek_up = nullptr;
+	lda::Upload seek_up;
 };
 
 struct libdeflate_compressor {
@@ -82,10 +80,9 @@ struct libdeflate_compressor {
 	lda::DevBuf large;
 	/* a ZIP archive written on the device (host_zip_write.hip): the plan's
 	 * columns and the names, per-piece and per-entry results, the slots; the
-	 * columns on their way up, and the event behind that copy */
+	 * columns on their way up */
 	lda::DevBuf zipw;
-	lda::PinnedBuf zipw_desc;
-	hipEvent_t zipw_up = nullptr;
+	lda::Upload zipw_up;
 	lda::PinnedPair pinned;	/* host-pointer entry points */
 	lda::PinnedBuf meta;	/* host-pointer entry points: per-chunk read-backs */
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */

@@ -194,14 +194,9 @@ static int read_body(struct libdeflate_decompressor *d, const uint8_t *d_in, con
 	const size_t up_bytes = lay.at;
 	const size_t counted_at = lay.take(N * sizeof(lda_stream_res));
 	const size_t res_at = lay.take(N * sizeof(lda_stream_res));
-	/* the pinned block of the last call may still be on its way up */
-	if (d->seek_up)
-		LDA_HIP_TRY(hipEventSynchronize(d->seek_up), LIBDEFLATE_AMD_NO_DEVICE);
-	else
-		LDA_HIP_TRY(hipEventCreateWithFlags(&d->seek_up, hipEventDisableTiming),
-			    LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_OK_TRY(d->seek_up.begin());
 	uint8_t *ws = (uint8_t *)d->seek.reserve(lay.at + 64);
-	uint8_t *h = (uint8_t *)d->seek_desc.ensure(up_bytes + 64);
+	uint8_t *h = (uint8_t *)d->seek_up.pinned(up_bytes + 64);
 	uint16_t *d_sym = N ? (uint16_t *)d->ssym.reserve((size_t)pl.sym_words * 2 + 64) : nullptr;
 	uint32_t *d_tok = N ? stream_token_scratch(d, N) : nullptr;
 	if (!ws || !h || (N && (!d_sym || !d_tok)))
@@ -231,8 +226,7 @@ static int read_body(struct libdeflate_decompressor *d, const uint8_t *d_in, con
 		longest = std::max(longest, pc.len);
 	}
 	memcpy(hf, pl.first.data(), (n_ranges + 1) * 8);
-	LDA_HIP_TRY(hipMemcpyAsync(ws, h, up_bytes, hipMemcpyHostToDevice, st), LIBDEFLATE_AMD_NO_DEVICE);
-	LDA_HIP_TRY(hipEventRecord(d->seek_up, st), LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_OK_TRY(d->seek_up.send(ws, up_bytes, st));
 	const lda_stream_chunk *g_chunks = (const lda_stream_chunk *)(ws + chunks_at);
 	lda_stream_res *g_counted = (lda_stream_res *)(ws + counted_at);
 	lda_stream_res *g_res = (lda_stream_res *)(ws + res_at);

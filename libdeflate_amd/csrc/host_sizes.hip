@@ -328,7 +328,7 @@ libdeflate_amd_decompress_batch_packed(struct libdeflate_decompressor *d, int fo
 		LDA_HIP_TRY(hipMemsetAsync(d_out_offsets, 0, 8, st), LIBDEFLATE_AMD_NO_DEVICE);
 		return LIBDEFLATE_AMD_OK;
 	}
-	const size_t nblocks = (n + 1 + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
+	const size_t nblocks = scan_blocks(n + 1);
 	size_t front = align_up(n * 4, 16) + 16 * n + 4 * n + 16;	/* decompress_batch */
 	if (front < sizes_scratch_bytes(n))
 		front = sizes_scratch_bytes(n);
@@ -354,10 +354,7 @@ libdeflate_amd_decompress_batch_packed(struct libdeflate_decompressor *d, int fo
 	const unsigned g1 = (unsigned)((n + 1 + 255) / 256);
 	hipLaunchKernelGGL(lda_packed_round_kernel, dim3(g1), dim3(256), 0, st, (uint64_t)n,
 			   (uint64_t)out_align - 1, (const uint64_t *)d_actual_out, rounded);
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)nblocks), dim3(256), 0, st,
-			   (uint64_t)(n + 1), (const uint64_t *)rounded, d_out_offsets, block_sums);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st,
-			   (uint64_t)nblocks, block_sums);
+	scan_enqueue(st, n + 1, rounded, d_out_offsets, block_sums);
 	hipLaunchKernelGGL(lda_packed_desc_kernel, dim3(g1), dim3(256), 0, st, (uint64_t)n,
 			   (uint64_t)out_capacity, d_in_nbytes, (const uint64_t *)d_actual_out,
 			   (const uint64_t *)block_sums, d_out_offsets, verdict, dec_in, dec_av);

@@ -2,9 +2,10 @@
  * host_zip.hip - C-ABI of reading a ZIP archive from device memory
  * (include/libdeflate_amd.h).
  *
- * The kernels of zip_kernels.hip find the end record, list every offset of the
- * central directory that looks like a directory record and size it; the chain
- * kernels of the BGZF reader keep the candidates reachable from cd_off; every
+ * The kernels of zip_kernels.hip find the end record; the shared finder
+ * (host_finder.h) lists every offset of the central directory that looks like
+ * a directory record and, once they are sized, keeps the candidates reachable
+ * from cd_off; every
  * entry is resolved against its local header; a prefix sum of the stated sizes
  * gives every entry its place in one contiguous output; ONE decompress batch
  * of max_entries chunks (format DEFLATE, exact input, exact fill) decodes the
@@ -24,14 +25,12 @@
 #include <string>
 #include <vector>
 
+#include "host_finder.h"
 #include "host_objects.h"
-#include "kernels.h"
 #include "zip_plan.h"
 
 using namespace lda;
 
-#define ZIP_MAX_ENTRIES ((size_t)1 << 28)	/* candidate indices are 32 bits */
-#define ZIP_MAX_FILE ((size_t)1 << 36)
 #define ZIP_END_BYTES 22
 
 static_assert(LIBDEFLATE_AMD_ZIP_MORE_ENTRIES == LDA_ZIP_MORE_ENTRIES &&
@@ -48,17 +47,14 @@ static_assert(ZIP_UNSUPPORTED == LDA_ZIP_UNSUPPORTED && ZIP_BAD_DATA == LIBDEFLA
 	      "zip_plan.h holds copies of them too");
 
 struct ZipScratch {
-	uint32_t *state;
+	Finder f;
 	uint64_t *zs;
-	/* the candidates and their chain */
-	uint64_t *cand_pos, *counts, *offs, *bsum_a;
-	uint32_t *cand_size, *next, *exit_at, *hops, *entry, *base;
 	/* the entries: rows (when the caller wants no index), rooms, the batches */
 	uint64_t *rows, *sizes, *bsum_b, *in_off, *in_n, *out_off, *out_av, *ain;
 	uint64_t *cp_src, *cp_len, *crc_n, *meta;
 	int32_t *bres;
 	uint32_t *crcs;
-	size_t cap, nwg, nsb_a, nsb_b, nblk, bytes;
+	size_t bytes;
 };
 
 static ZipScratch zip_scratch(void *base, size_t n, size_t M, bool own_rows)
@@ -66,20 +62,11 @@ static ZipScratch zip_scratch(void *base, size_t n, size_t M, bool own_rows)
 	ZipScratch s;
 	Carve c(base);
 	/* two signatures start 4 bytes apart at least */
-	s.cap = std::min(M + LIBDEFLATE_AMD_ZIP_SLACK, n / 4 + 1);
-	s.nwg = (n + LDA_BR_SCAN_WG - 1) / LDA_BR_SCAN_WG;
-	s.nsb_a = (s.nwg + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
-	s.nsb_b = (M + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
-	s.nblk = (s.cap + LDA_BR_JUMP - 1) / LDA_BR_JUMP;
-	s.state = c.take<uint32_t>(LDA_BR_STATE_WORDS);
+	s.f.carve(c, n, std::min(M + LIBDEFLATE_AMD_ZIP_SLACK, n / 4 + 1));
 	s.zs = c.take<uint64_t>(LDA_ZS_WORDS);
-	s.cand_pos = c.take<uint64_t>(s.cap);
-	s.counts = c.take<uint64_t>(s.nwg);
-	s.offs = c.take<uint64_t>(s.nwg);
-	s.bsum_a = c.take<uint64_t>(s.nsb_a + 1);
 	s.rows = c.take<uint64_t>(own_rows ? LDA_ZIP_WORDS * M : 0);
 	s.sizes = c.take<uint64_t>(M);
-	s.bsum_b = c.take<uint64_t>(s.nsb_b + 1);
+	s.bsum_b = c.take<uint64_t>(scan_blocks(M) + 1);
 	s.in_off = c.take<uint64_t>(M);
 	s.in_n = c.take<uint64_t>(M);
 	s.out_off = c.take<uint64_t>(M);
@@ -89,12 +76,7 @@ static ZipScratch zip_scratch(void *base, size_t n, size_t M, bool own_rows)
 	s.cp_len = c.take<uint64_t>(M);
 	s.crc_n = c.take<uint64_t>(M);
 	s.meta = c.take<uint64_t>(M);
-	s.cand_size = c.take<uint32_t>(s.cap);
-	s.next = c.take<uint32_t>(s.cap);
-	s.exit_at = c.take<uint32_t>(s.cap);
-	s.hops = c.take<uint32_t>(s.cap);
-	s.entry = c.take<uint32_t>(s.nblk);
-	s.base = c.take<uint32_t>(s.nblk);
+	s.f.carve_chain(c);
 	s.bres = c.take<int32_t>(M);
 	s.crcs = c.take<uint32_t>(M);
 	s.bytes = c.at;
@@ -115,19 +97,13 @@ static bool zip_args_ok(const char *what, const struct libdeflate_decompressor *
 			const void *d_in, size_t n, size_t max_entries, size_t out_align,
 			const void *d_result, const void *d_results)
 {
-	if (!d || (!d_in && n) || !d_result || !d_results) {
+	if (!d_results) {
 		set_error("%s: NULL argument", what);
 		return false;
 	}
-	if (!max_entries || max_entries > ZIP_MAX_ENTRIES) {
-		set_error("%s: max_entries %zu (1 .. 2^28)", what, max_entries);
-		return false;
-	}
-	if (n > ZIP_MAX_FILE) {
-		set_error("%s: in_nbytes %zu above 2^36", what, n);
-		return false;
-	}
-	return align_ok(what, out_align);
+	return finder_args_ok(what, d, d_in, n, "%s: max_entries %zu (1 .. 2^28)", max_entries, 1,
+			      d_result) &&
+	       align_ok(what, out_align);
 }
 
 static unsigned copy_grid(const DeviceCtx *ctx, size_t n_chunks)
@@ -156,54 +132,33 @@ static int zip_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, s
 	if (!ws)
 		return LIBDEFLATE_AMD_OOM;
 	const ZipScratch s = zip_scratch(ws, n, M, !d_index);
-	const uint64_t *k_at = s.bsum_a + s.nsb_a;
-	const uint64_t cap = s.cap;
+	const Finder &f = s.f;
+	const uint64_t *k_at = f.k_at();
+	const uint64_t cap = f.cap;
 	uint64_t *rows = d_index ? d_index : s.rows;
 	const unsigned per256 = (unsigned)((M + 255) / 256);
-	const unsigned cap256 = (unsigned)((s.cap + 255) / 256);
+	const unsigned cap256 = (unsigned)((f.cap + 255) / 256);
 
-	LDA_HIP_TRY(hipMemsetAsync(s.state, 0, LDA_BR_STATE_WORDS * 4, st), LIBDEFLATE_AMD_NO_DEVICE);
 	hipLaunchKernelGGL(lda_zip_end_kernel, dim3(1), dim3(1024), 0, st, d_in, (uint64_t)n, s.zs);
-	/* candidates of the directory: count, scan, write in file order */
-	hipLaunchKernelGGL(lda_zip_scan_kernel, dim3((unsigned)s.nwg), dim3(256), 0, st, d_in,
-			   (const uint64_t *)s.zs, s.counts, (const uint64_t *)NULL,
-			   (const uint64_t *)NULL, cap, s.cand_pos);
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nsb_a), dim3(256), 0, st,
-			   (uint64_t)s.nwg, (const uint64_t *)s.counts, s.offs, s.bsum_a);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)s.nsb_a,
-			   s.bsum_a);
-	hipLaunchKernelGGL(lda_zip_scan_kernel, dim3((unsigned)s.nwg), dim3(256), 0, st, d_in,
-			   (const uint64_t *)s.zs, s.counts, (const uint64_t *)s.offs,
-			   (const uint64_t *)s.bsum_a, cap, s.cand_pos);
+	/* the candidates of the directory */
+	LDA_OK_TRY(finder_list(f, st, [&](const uint64_t *offs, const uint64_t *bsum) {
+		hipLaunchKernelGGL(lda_zip_scan_kernel, dim3((unsigned)f.nwg), dim3(256), 0, st, d_in,
+				   (const uint64_t *)s.zs, f.counts, offs, bsum, cap, f.cand_pos);
+	}));
 	hipLaunchKernelGGL(lda_zip_size_kernel, dim3(cap256), dim3(256), 0, st, d_in,
-			   (const uint64_t *)s.zs, k_at, cap, (const uint64_t *)s.cand_pos,
-			   s.cand_size);
-	/* the chain among the candidates, in positions relative to cd_off: it
-	 * starts at 0 and ends at LDA_ZIP_CHAIN_END (lda_zip_size_kernel); entry k's
-	 * position lands in in_off[k] (none of these does anything when the
-	 * candidates overflowed their room) */
-	hipLaunchKernelGGL(lda_bgzf_jump_kernel, dim3((unsigned)s.nblk), dim3(LDA_BR_JUMP), 0, st,
-			   (uint64_t)LDA_ZIP_CHAIN_END, k_at, cap, (const uint64_t *)s.cand_pos,
-			   (const uint32_t *)s.cand_size, s.next, s.exit_at, s.hops, s.entry);
-	hipLaunchKernelGGL(lda_bgzf_top_kernel, dim3(1), dim3(64), 0, st, k_at, cap,
-			   (const uint64_t *)s.cand_pos, (const uint32_t *)s.exit_at,
-			   (const uint32_t *)s.hops, s.entry, s.base, s.state);
-	hipLaunchKernelGGL(lda_bgzf_members_kernel, dim3((unsigned)s.nblk), dim3(LDA_BR_JUMP), 0, st,
-			   k_at, cap, (uint64_t)M, (const uint64_t *)s.cand_pos,
-			   (const uint32_t *)s.cand_size, (const uint32_t *)s.next,
-			   (const uint32_t *)s.hops, (const uint32_t *)s.entry,
-			   (const uint32_t *)s.base, (const uint32_t *)s.state, s.in_off, s.in_n);
+			   (const uint64_t *)s.zs, k_at, cap, (const uint64_t *)f.cand_pos,
+			   f.cand_size);
+	/* the chain in positions relative to cd_off: it starts at 0 and ends at
+	 * LDA_ZIP_CHAIN_END (lda_zip_size_kernel) */
+	finder_chain(f, st, LDA_ZIP_CHAIN_END, M, s.in_off, s.in_n);
 	/* entries -> rooms -> places in the output -> descriptors and index */
 	hipLaunchKernelGGL(lda_zip_resolve_kernel, dim3(per256), dim3(256), 0, st, d_in, (uint64_t)M,
 			   (uint64_t)(out_align - 1), (const uint64_t *)s.zs,
-			   (const uint32_t *)s.state, k_at, cap, (const uint64_t *)s.in_off, rows,
+			   (const uint32_t *)f.state, k_at, cap, (const uint64_t *)s.in_off, rows,
 			   d_results, s.sizes);
-	hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nsb_b), dim3(256), 0, st,
-			   (uint64_t)M, (const uint64_t *)s.sizes, s.out_off, s.bsum_b);
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)s.nsb_b,
-			   s.bsum_b);
+	const uint64_t *total_at = s.bsum_b + scan_enqueue(st, M, s.sizes, s.out_off, s.bsum_b);
 	hipLaunchKernelGGL(lda_zip_desc_kernel, dim3(per256), dim3(256), 0, st, (uint64_t)M,
-			   out_avail, (const uint64_t *)s.zs, (const uint32_t *)s.state, k_at, cap,
+			   out_avail, (const uint64_t *)s.zs, (const uint32_t *)f.state, k_at, cap,
 			   (const uint64_t *)s.bsum_b, rows, (const int32_t *)d_results, s.in_off,
 			   s.in_n, s.out_off, s.out_av, s.cp_src, s.cp_len, s.crc_n, s.meta);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -212,8 +167,8 @@ static int zip_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, s
 		 * is written and nothing is read) */
 		uint8_t *out = d_out ? d_out : (uint8_t *)ws;
 		int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_DEFLATE, M, d_in, s.in_off,
-							 s.in_n, out, s.out_off, s.out_av, s.bres,
-							 s.ain, NULL, st);
+						     s.in_n, out, s.out_off, s.out_av, s.bres, s.ain,
+						     NULL, st);
 		if (rc != LIBDEFLATE_AMD_OK)
 			return rc;
 		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, M)), dim3(256), 0, st,
@@ -225,8 +180,8 @@ static int zip_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, s
 			return rc;
 	}
 	hipLaunchKernelGGL(lda_zip_final_kernel, dim3(1), dim3(256), 0, st, (uint64_t)M, out_avail,
-			   (const uint64_t *)s.zs, (const uint32_t *)s.state, k_at, cap,
-			   (const uint64_t *)(s.bsum_b + s.nsb_b), (const uint64_t *)s.meta,
+			   (const uint64_t *)s.zs, (const uint32_t *)f.state, k_at, cap, total_at,
+			   (const uint64_t *)s.meta,
 			   (const uint64_t *)s.in_n, (const int32_t *)(decode ? s.bres : NULL),
 			   (const uint64_t *)s.ain, (const uint32_t *)s.crcs, d_results, d_result);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -291,31 +246,24 @@ static int zip_read(struct libdeflate_decompressor *d, const uint8_t *d_in, size
 	};
 	Carve sizes(NULL);
 	lay(&sizes);
-	/* the pinned block of the last call may still be on its way up */
-	if (d->bgzf_up)
-		LDA_HIP_TRY(hipEventSynchronize(d->bgzf_up), LIBDEFLATE_AMD_NO_DEVICE);
-	else
-		LDA_HIP_TRY(hipEventCreateWithFlags(&d->bgzf_up, hipEventDisableTiming),
-			    LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_OK_TRY(d->bgzf_up.begin());
 	uint8_t *ws = (uint8_t *)d->bgzf.reserve(sizes.at + 16);
-	uint64_t *h = (uint64_t *)d->bgzf_desc.ensure(std::max(up_bytes, (size_t)64));
+	void *h = d->bgzf_up.pinned(up_bytes);
 	if (!ws || !h)
 		return LIBDEFLATE_AMD_OOM;
 	Carve real(ws);
 	lay(&real);
 	memcpy(h, cols.data(), up_bytes);
-	LDA_HIP_TRY(hipMemcpyAsync(ws, h, up_bytes, hipMemcpyHostToDevice, st),
-		    LIBDEFLATE_AMD_NO_DEVICE);
-	LDA_HIP_TRY(hipEventRecord(d->bgzf_up, st), LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_OK_TRY(d->bgzf_up.send(ws, up_bytes, st));
 	const uint64_t *col[ZIP_COLS];
 	for (size_t a = 0; a < ZIP_COLS; a++)
 		col[a] = g_cols + a * n_sel;
 	/* (a NULL d_out has out_avail 0: nothing is written, nothing is read) */
 	uint8_t *out = d_out ? d_out : ws;
 	int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_DEFLATE, n_sel, d_in,
-						 col[ZIP_COL_IN_OFF], col[ZIP_COL_IN_N], out,
-						 col[ZIP_COL_OUT_OFF], col[ZIP_COL_OUT_AV], g_res,
-						 g_ain, NULL, st);
+					     col[ZIP_COL_IN_OFF], col[ZIP_COL_IN_N], out,
+					     col[ZIP_COL_OUT_OFF], col[ZIP_COL_OUT_AV], g_res, g_ain, NULL,
+					     st);
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
 	hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, n_sel)), dim3(256), 0, st,
@@ -346,11 +294,11 @@ libdeflate_amd_zip_read_batch(struct libdeflate_decompressor *d, const void *d_i
 		set_error("%s: NULL argument", what);
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
-	if (entries > ZIP_MAX_ENTRIES || n_sel > ZIP_MAX_ENTRIES) {
+	if (entries > LDA_FINDER_MAX_RECORDS || n_sel > LDA_FINDER_MAX_RECORDS) {
 		set_error("%s: entries %zu, n_sel %zu (at most 2^28)", what, entries, n_sel);
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
-	if (in_nbytes > ZIP_MAX_FILE) {
+	if (in_nbytes > LDA_FINDER_MAX_FILE) {
 		set_error("%s: in_nbytes %zu above 2^36", what, in_nbytes);
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}

@@ -4,7 +4,8 @@
  *
  * zip_write_plan.h checks the host arrays, decides ZIP64 and cuts the entries
  * into pieces; its columns and the names go up through a pinned block in ONE
- * copy, as the descriptors of libdeflate_amd_zip_read_batch do.  ONE CRC-32
+ * copy (Upload, host_common.h), as the descriptors of
+ * libdeflate_amd_zip_read_batch do.  ONE CRC-32
  * batch runs over the pieces, the compress batches of every launch group run
  * into slots in the object's scratch (compress_deflate_pieces(): the launches
  * of the batch entry points, sliced like the segmented single-buffer path),
@@ -53,7 +54,7 @@ struct ZipwScratch {
 	uint64_t *out_n, *cp_src, *cp_dst, *cp_len, *sizes, *offs, *bsum, *e_info;
 	uint32_t *crcs;
 	uint8_t *slots;
-	size_t nblocks, bytes;
+	size_t bytes;
 };
 
 static ZipwScratch zipw_scratch(void *base, const zipw_plan &p, size_t names_bytes)
@@ -62,7 +63,6 @@ static ZipwScratch zipw_scratch(void *base, const zipw_plan &p, size_t names_byt
 	Carve c(base);
 	const size_t n = (size_t)p.n, np = (size_t)p.np;
 
-	s.nblocks = (n + LDA_SCAN_BLOCK - 1) / LDA_SCAN_BLOCK;
 	s.ecols = c.take<uint64_t>(ZIPW_ECOLS * n);
 	s.pcols = c.take<uint64_t>(ZIPW_PCOLS * np);
 	s.seg = c.take<uint32_t>(np);
@@ -74,7 +74,7 @@ static ZipwScratch zipw_scratch(void *base, const zipw_plan &p, size_t names_byt
 	s.cp_len = c.take<uint64_t>(np);
 	s.sizes = c.take<uint64_t>(n);
 	s.offs = c.take<uint64_t>(n);
-	s.bsum = c.take<uint64_t>(s.nblocks + 1);
+	s.bsum = c.take<uint64_t>(scan_blocks(n) + 1);
 	s.e_info = c.take<uint64_t>(n);
 	s.crcs = c.take<uint32_t>(np);
 	s.slots = c.take<uint8_t>((size_t)p.slots_bytes, 256);
@@ -101,12 +101,7 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 	const uint64_t tail = p.cd_size + p.end_bytes;
 	const ZipwScratch sz = zipw_scratch(NULL, p, names_bytes);
 
-	/* the pinned block of the last call may still be on its way up */
-	if (c->zipw_up)
-		LDA_HIP_TRY(hipEventSynchronize(c->zipw_up), LIBDEFLATE_AMD_NO_DEVICE);
-	else
-		LDA_HIP_TRY(hipEventCreateWithFlags(&c->zipw_up, hipEventDisableTiming),
-			    LIBDEFLATE_AMD_NO_DEVICE);
+	LDA_OK_TRY(c->zipw_up.begin());
 	/* all of the call's scratch before anything is queued: growing frees
 	 * memory (and waits for the device) */
 	size_t kernels = 0;
@@ -115,7 +110,7 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 			c, std::min(zipw_per_launch(g), (size_t)(g.hi - g.lo)), (size_t)g.max_in,
 			g.S != 0));
 	uint8_t *ws = (uint8_t *)c->zipw.reserve(sz.bytes);
-	uint8_t *h = (uint8_t *)c->zipw_desc.ensure(std::max(sz.up_bytes, (size_t)64));
+	uint8_t *h = (uint8_t *)c->zipw_up.pinned(sz.up_bytes);
 	if (!ws || !h || (kernels && !c->scratch.reserve(kernels)))
 		return LIBDEFLATE_AMD_OOM;
 	const ZipwScratch s = zipw_scratch(ws, p, names_bytes), hs = zipw_scratch(h, p, names_bytes);
@@ -124,9 +119,7 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 		memcpy(hs.pcols, p.pcols.data(), p.pcols.size() * 8);
 		memcpy(hs.seg, p.seg_info.data(), p.seg_info.size() * 4);
 		memcpy(hs.names, names, names_bytes);
-		LDA_HIP_TRY(hipMemcpyAsync(ws, h, sz.up_bytes, hipMemcpyHostToDevice, st),
-			    LIBDEFLATE_AMD_NO_DEVICE);
-		LDA_HIP_TRY(hipEventRecord(c->zipw_up, st), LIBDEFLATE_AMD_NO_DEVICE);
+		LDA_OK_TRY(c->zipw_up.send(ws, sz.up_bytes, st));
 	}
 	const uint64_t *ecol[ZIPW_ECOLS], *pcol[ZIPW_PCOLS];
 	for (size_t a = 0; a < ZIPW_ECOLS; a++)
@@ -153,17 +146,14 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 		}
 	}
 	const unsigned wave_grid = (unsigned)std::max((size_t)1, std::min((n + 3) / 4, (size_t)ctx->num_cus * 16));
-	if (n) {
+	if (n)
 		hipLaunchKernelGGL(lda_zipw_entry_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
 				   ecol[ZIPW_E_FIRST], ecol[ZIPW_E_COUNT], ecol[ZIPW_E_NAME_LEN],
 				   ecol[ZIPW_E_USIZE], pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
 				   (const uint64_t *)(compressed ? s.out_n : NULL),
 				   (const uint32_t *)s.crcs, s.e_info, s.sizes);
-		hipLaunchKernelGGL(lda_scan_local_kernel, dim3((unsigned)s.nblocks), dim3(256), 0, st,
-				   (uint64_t)n, (const uint64_t *)s.sizes, s.offs, s.bsum);
-	}
-	hipLaunchKernelGGL(lda_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)s.nblocks,
-			   s.bsum);
+	/* (of no entries, the total alone: cd_off 0) */
+	const uint64_t *total_at = s.bsum + scan_enqueue(st, n, s.sizes, s.offs, s.bsum);
 	if (n)
 		hipLaunchKernelGGL(lda_zipw_place_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
 				   (uint32_t)p.zip64, dos_datetime, out_avail, tail, ecol[ZIPW_E_FIRST],
@@ -177,13 +167,13 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 	if (np) {
 		const size_t grid = std::min(np, (size_t)ctx->num_cus * 8);
 		hipLaunchKernelGGL(lda_zipw_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
-				   (uint64_t)np, (const uint64_t *)(s.bsum + s.nblocks), out_avail, tail,
+				   (uint64_t)np, total_at, out_avail, tail,
 				   (const uint64_t *)s.cp_src, (const uint64_t *)s.cp_dst,
 				   (const uint64_t *)s.cp_len, d_in, (const uint8_t *)s.slots, d_out);
 	}
 	hipLaunchKernelGGL(lda_zipw_final_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)n,
 			   (uint32_t)p.zip64, out_avail, p.cd_size, tail, ecol[ZIPW_E_USIZE],
-			   (const uint64_t *)s.e_info, (const uint64_t *)(s.bsum + s.nblocks), d_out,
+			   (const uint64_t *)s.e_info, total_at, d_out,
 			   d_result);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	return LIBDEFLATE_AMD_OK;

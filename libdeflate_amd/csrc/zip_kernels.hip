@@ -26,8 +26,9 @@
  *                           ends exactly at cd_end the size that ends it at
  *                           LDA_ZIP_CHAIN_END, the one end the host knows.
  *   lda_bgzf_jump_kernel / lda_bgzf_top_kernel / lda_bgzf_members_kernel
- *                           (bgzf_read_kernels.hip, unchanged) keep the
- *                           candidates that the chain from cd_off reaches.
+ *                           (bgzf_read_kernels.hip, launched by host_finder.h)
+ *                           keep the candidates that the chain from cd_off
+ *                           reaches.
  *   lda_zip_resolve_kernel  per entry: the central fields, the ZIP64 extra,
  *                           the local header, the checks; seven words of its
  *                           index row, its pre-decode result, its room.
@@ -215,7 +216,7 @@ lda_zip_scan_kernel(const u8 *__restrict__ in, const u64 *__restrict__ zs,
 {
 	__shared__ __attribute__((aligned(16))) u32 tile[LDA_BR_TILE / 4 + 4];
 	__shared__ u32 wsum[4];
-	const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const u32 tid = threadIdx.x;
 	const u64 wg0 = (u64)blockIdx.x * LDA_BR_SCAN_WG;
 	const u64 cd_off = zs[LDA_ZS_CD_OFF], cd_end = cd_off + zs[LDA_ZS_CD_SIZE];
 	u64 at = 0;	/* candidates of this workgroup so far / where they go */
@@ -263,19 +264,8 @@ lda_zip_scan_kernel(const u8 *__restrict__ in, const u64 *__restrict__ zs,
 				if (p0 + j < cd_off || p0 + j + CEN_BYTES > cd_end)
 					mask &= ~(1u << j);
 		}
-		const u32 cnt = (u32)__builtin_popcount(mask);
-		const u32 incl = wave_scan_incl(cnt);
-		if (lane == 63)
-			wsum[wave] = incl;
-		__syncthreads();
-		u32 pre = incl - cnt, tot = 0;
-#pragma unroll
-		for (u32 k = 0; k < 4; k++) {
-			const u32 v = wsum[k];
-			if (k < wave)
-				pre += v;
-			tot += v;
-		}
+		u32 tot;
+		const u32 pre = wg_count_excl((u32)__builtin_popcount(mask), wsum, &tot);
 		if (offsets) {
 			u64 dst = at + pre;
 			for (u32 m = mask; m && dst < cap; m &= m - 1, dst++)

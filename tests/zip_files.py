@@ -202,13 +202,35 @@ def lookalikes():
     return Good("lookalikes", b.getvalue(), b.getvalue(), False)
 
 
+BOUNDARIES = (4093, 4094, 4095, 4096, 16381, 16382, 16383, 16384)
+
+
+@_once
+def boundary(at):
+    """the central directory starts exactly at file offset `at`, around the 4 KiB
+    steps and the 16 KiB workgroups of the candidate scan: a stored first entry
+    padded to put it there, and right below it a stored last entry of
+    look-alike signatures, which lie outside the directory"""
+    def build(pad):
+        b = io.BytesIO()
+        with zipfile.ZipFile(b, "w") as zf:
+            zf.writestr(_info("pad", zipfile.ZIP_STORED), payload(pad, 30))
+            zf.writestr(_info("a", zipfile.ZIP_DEFLATED, 6), payload(700, 31))
+            zf.writestr(_info("b", zipfile.ZIP_DEFLATED, 9), payload(33, 32))
+            zf.writestr(_info("sigs", zipfile.ZIP_STORED), b"PK\1\2" * 9)
+        return b.getvalue()
+    data = build(at - _layout(build(0))[1])
+    assert _layout(data)[1] == at and data[at - 4:at + 4] == b"PK\1\2PK\1\2"
+    return Good(f"boundary{at}", data, data, False)
+
+
 GOOD_NAMES = ("mixed0", "mixed1", "mixed65535", "descriptor", "zip64", "many", "trailing1",
-              "trailing2", "trailing3", "false", "empty")
+              "trailing2", "trailing3", "false", "empty") + tuple(f"boundary{at}" for at in BOUNDARIES)
 
 
 def good(name):
     """the good file of that name, built on first use"""
-    for stem, fn in (("mixed", mixed), ("trailing", trailing)):
+    for stem, fn in (("mixed", mixed), ("trailing", trailing), ("boundary", boundary)):
         if name.startswith(stem):
             return fn(int(name[len(stem):]))
     return {"descriptor": descriptor, "zip64": zip64, "many": many, "false": false,
