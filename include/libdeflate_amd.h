@@ -1354,6 +1354,86 @@ libdeflate_amd_zip_compress_batch(struct libdeflate_compressor *compressor,
 				  uint64_t *d_index, uint32_t dos_datetime, unsigned flags,
 				  void *stream);
 
+/*
+ * ---- Files of concatenated gzip members written on the device ----
+ *
+ * n_records byte ranges of one DEVICE buffer -> one file of n_records ordinary
+ * gzip members back to back (a WARC archive, `cat a.gz b.gz`, an mgzip / pgzip
+ * shard): what libdeflate_amd_gzip_members_decompress_batch reads.  The
+ * conventions are those of libdeflate_amd_zip_compress_batch above: the call
+ * enqueues on `stream` and returns, the plan goes up through the object's
+ * pinned block, scratch belongs to the object (the ZIP writer's), names /
+ * name_offsets (n_records + 1, ascending), in_offsets and in_nbytes are HOST
+ * arrays that may be reused when the call returns, records may overlap one
+ * another, d_out must not overlap d_in, and no byte is ever written at or past
+ * d_out + out_avail.
+ *
+ * Unlike libdeflate_amd_compress_batch in gzip format, a record is not one
+ * workgroup whatever its size: records of 128 KiB and more are cut into primed
+ * segments that fill the GPU (large_plan.h), exactly as the single-buffer call
+ * cuts them, and records of at most 4 KiB go to the small-buffer kernel.
+ *
+ * names and name_offsets may both be NULL: no member has a name.  A record
+ * whose name range is empty has none either.
+ *
+ * THE FILE: record k's member stands behind record k - 1's, from offset 0.  An
+ * unnamed member written with mtime == 0 is byte for byte what
+ * libdeflate_gzip_compress() of this build returns for the record's bytes at
+ * the object's level and LDA_* switches - the record of 0 bytes, the records
+ * under the level's pass-through size, level 0 and the segmented records
+ * included.  A named member differs in three places: FLG has FNAME set, the
+ * name and a 0 byte follow the 10 fixed header bytes, and mtime sits in bytes
+ * 4..7 (as it does in an unnamed member when it is not 0).  DEFLATE stream,
+ * CRC-32 and ISIZE are the same.  No FEXTRA, FCOMMENT or FHCRC.
+ *
+ * libdeflate_amd_gzip_members_compress_bound() is arithmetic on the host
+ * arrays (name_offsets may be NULL): the sum of
+ * libdeflate_gzip_compress_bound(in_nbytes[k]), plus the name's length and 1
+ * for every named record.  No file of these records is larger.
+ *
+ * d_result[0 .. LIBDEFLATE_AMD_GZMW_RESULT_WORDS) (device memory):
+ *   [0] 0, or LIBDEFLATE_INSUFFICIENT_SPACE: the file does not fit out_avail -
+ *       then no byte of d_out and no row of d_index is written;
+ *   [1] the file's size, [2] the records' bytes in all, [3] the members
+ *   ([1] to [3] are valid either way).
+ * d_index: NULL, or device room for 2 (n_records + 1) u64: exactly what
+ * libdeflate_amd_gzip_members_index_batch returns for the written file - the
+ * pairs (compressed offset, uncompressed offset) of every member, then the
+ * closing pair - so the file and its index can go straight to
+ * libdeflate_amd_decompress_batch_packed over chosen members.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL object or pointer (d_in may be NULL with
+ * in_avail == 0, the host arrays with n_records == 0, names and name_offsets
+ * together, d_index always), unknown flags (none is defined yet), n_records
+ * above 2^28, decreasing name_offsets, a name that holds a 0 byte or has more
+ * than 65 534 bytes (with its terminator the reader's
+ * LIBDEFLATE_AMD_GZM_NAME_MAX), a record of 4 GiB or more, a record that does
+ * not lie inside in_avail - and, with a level-0 object, a record above
+ * 0xFFFFFF00 bytes, for which libdeflate_gzip_compress() itself returns 0.
+ * n_records == 0 writes nothing and reports a file of size 0.
+ *
+ * Limits: the object's scratch is about the sum of the records' bounds plus
+ * descriptors; a level-0 record, and with LDA_NO_SEGMENTS any record, is one
+ * piece and one workgroup; one level and one mtime per call; no FEXTRA /
+ * FCOMMENT / FHCRC; no host-pointer form; no preset dictionary.
+ */
+#define LIBDEFLATE_AMD_GZMW_RESULT_WORDS 4
+
+LIBDEFLATEAPI size_t
+libdeflate_amd_gzip_members_compress_bound(struct libdeflate_compressor *compressor,
+					   size_t n_records, const uint64_t *name_offsets,
+					   const uint64_t *in_nbytes);
+
+LIBDEFLATEAPI int
+libdeflate_amd_gzip_members_compress_batch(struct libdeflate_compressor *compressor,
+					   size_t n_records, const void *names,
+					   const uint64_t *name_offsets, const void *d_in,
+					   size_t in_avail, const uint64_t *in_offsets,
+					   const uint64_t *in_nbytes, void *d_out, size_t out_avail,
+					   uint64_t *d_result, uint64_t *d_index, uint32_t mtime,
+					   unsigned flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,71 @@ class Compressor:
             index.data_ptr() if index is not None else None, int(dos_datetime), int(flags),
             _stream_ptr(stream)), "zip_compress_batch")
 
+    @staticmethod
+    def _gzm_names(names, n):
+        """None, or names (str -> UTF-8, bytes, None / empty for no name) ->
+        (blob, uint64 offsets (n + 1)), or that pair itself"""
+        if names is None:
+            return None, None
+        if isinstance(names, tuple):
+            return Compressor._zip_names(names)
+        assert len(names) == n
+        return Compressor._zip_names([b"" if x is None else x for x in names])
+
+    def gzip_members_compress_bound(self, sizes, names=None):
+        """libdeflate_amd_gzip_members_compress_bound: room enough for the file
+        gzip_members_compress writes for records of these sizes and names."""
+        sz = np.ascontiguousarray(sizes, dtype=np.uint64)
+        _, offs = self._gzm_names(names, sz.size)
+        return self._lib.libdeflate_amd_gzip_members_compress_bound(
+            self._h, sz.size, offs.ctypes.data_as(c_void_p) if offs is not None else None,
+            sz.ctypes.data_as(c_void_p))
+
+    def gzip_members_compress(self, records, names=None, mtime=0, out=None, result=None,
+                              index=True, flags=0, stream=None, in_avail=None, out_avail=None):
+        """libdeflate_amd_gzip_members_compress_batch: a file of gzip members,
+        one per record.  records: (data, in_offsets, in_nbytes) - a uint8 torch
+        CUDA tensor (its first in_avail bytes) and host lists or arrays; record
+        k is data[in_offsets[k] : + in_nbytes[k]].  names: None, or per record
+        a str, bytes or None (also the (blob, offsets) pair of _zip_names()).
+        out: a uint8 CUDA tensor (out_avail bytes of it, default all), or None
+        for a new one of gzip_members_compress_bound() bytes.  Returns (out,
+        result, index): result an int64 CUDA tensor of GZMW_RESULT_WORDS - [0]
+        0 or INSUFFICIENT_SPACE, [1] the file's size, [2] the records' bytes,
+        [3] the members; index an int64 CUDA tensor of n + 1 pairs (compressed
+        offset, uncompressed offset), what index_gzip_members_batch returns
+        for the file, or None with index=False.  result and index may be the
+        caller's tensors.  Only enqueues on `stream`: the tensors are valid in
+        stream order."""
+        import torch
+        data, in_offsets, in_nbytes = records
+        ino = np.ascontiguousarray(in_offsets, dtype=np.uint64)
+        inn = np.ascontiguousarray(in_nbytes, dtype=np.uint64)
+        n = inn.size
+        assert ino.size == n
+        blob, offs = self._gzm_names(names, n)
+        assert offs is None or offs.size == n + 1
+        dev = data.device
+        if out is None:
+            out = torch.empty(max(1, self.gzip_members_compress_bound(
+                inn, (blob, offs) if offs is not None else None)), dtype=torch.uint8, device=dev)
+        if result is None:
+            result = torch.zeros(binding.GZMW_RESULT_WORDS, dtype=torch.int64, device=dev)
+        idx = index if isinstance(index, torch.Tensor) else \
+            torch.zeros((n + 1, 2), dtype=torch.int64, device=dev) if index else None
+        assert result.numel() >= binding.GZMW_RESULT_WORDS
+        assert idx is None or idx.numel() >= 2 * (n + 1)
+        avail = data.numel() if in_avail is None else int(in_avail)
+        check(self._lib.libdeflate_amd_gzip_members_compress_batch(
+            self._h, n, blob.ctypes.data_as(c_void_p) if blob is not None else None,
+            offs.ctypes.data_as(c_void_p) if offs is not None else None,
+            data.data_ptr() if avail else None, avail, ino.ctypes.data_as(c_void_p),
+            inn.ctypes.data_as(c_void_p), out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
+            idx.data_ptr() if idx is not None else None, int(mtime), int(flags),
+            _stream_ptr(stream)), "gzip_members_compress_batch")
+        return out, result, idx
+
     def compress(self, fmt, data, out_avail=None):
         """Returns the compressed bytes, or None when the reference API would
         return 0 (does not fit in out_avail)."""

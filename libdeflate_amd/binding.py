@@ -37,6 +37,9 @@ ZIP_MORE_ENTRIES, ZIP_MORE_CANDIDATES, ZIP_UNSUPPORTED = 16, 17, 18
 ZIP_RESULT_WORDS, ZIP_WORDS, ZIP_SLACK, ZIP_ZIP64 = 5, 8, 1024, 1
 # the ZIP writer: the two flags, the words of its result
 ZIP_STORE, ZIP_FORCE_ZIP64, ZIPW_RESULT_WORDS = 1, 2, 4
+# the writer of concatenated gzip members: the words of its result, the longest
+# name (GZM_NAME_MAX with its terminator and one byte to spare)
+GZMW_RESULT_WORDS, GZMW_NAME_MAX = 4, 65534
 # the seek index: bytes of window per point, u64 per row
 SEEK_WINDOW, SEEK_WORDS = 32768, 4
 # the size query: the limit a NULL d_out_limit stands for
@@ -83,6 +86,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_zip_index_batch", "libdeflate_amd_zip_decompress_batch",
     "libdeflate_amd_zip_read_batch",
     "libdeflate_amd_zip_compress_bound", "libdeflate_amd_zip_compress_batch",
+    "libdeflate_amd_gzip_members_compress_bound", "libdeflate_amd_gzip_members_compress_batch",
 ]
 
 _lib = None
@@ -207,6 +211,11 @@ def load():
     sig("libdeflate_amd_zip_compress_bound", SZ, SZ, P, P, c_uint32)
     sig("libdeflate_amd_zip_compress_batch", c_int, P, SZ, P, P, P, SZ, P, P, P, SZ, P, P,
         c_uint32, c_uint32, P)
+    # a file of gzip members written: the bound (host arithmetic), and ranges of
+    # a device buffer -> file (names, offsets and sizes on the host)
+    sig("libdeflate_amd_gzip_members_compress_bound", SZ, P, SZ, P, P)
+    sig("libdeflate_amd_gzip_members_compress_batch", c_int, P, SZ, P, P, P, SZ, P, P, P, SZ,
+        P, P, c_uint32, c_uint32, P)
     _lib = lib
     return lib
 

@@ -388,6 +388,27 @@ lda_zipw_final_kernel(uint64_t n, uint32_t zip64, uint64_t out_avail, uint64_t c
 		      uint64_t tail, const uint64_t *usize, const uint64_t *e_info,
 		      const uint64_t *total_at, uint8_t *out, uint64_t *result);
 
+/* gzip_members_write_kernels.hip: a file of gzip members assembled in device
+ * memory (host_gzip_members_write.hip, gzip_members_write_plan.h); the pieces
+ * are copied by lda_zipw_copy_kernel */
+extern "C" __global__ void
+lda_gzmw_member_kernel(uint64_t n, const uint64_t *first, const uint64_t *count,
+		       const uint64_t *name_len, const uint64_t *usize, const uint64_t *pc_off,
+		       const uint64_t *pc_n, const uint64_t *out_n, const uint32_t *crcs,
+		       uint64_t *csize, uint32_t *crc, uint64_t *sizes);
+extern "C" __global__ void
+lda_gzmw_place_kernel(uint64_t n, int level, uint32_t mtime, uint64_t out_avail,
+		      const uint64_t *first, const uint64_t *count, const uint64_t *name_off,
+		      const uint64_t *name_len, const uint64_t *usize, const uint64_t *uoff,
+		      const uint8_t *names, const uint64_t *pc_off, const uint64_t *pc_n,
+		      const uint64_t *slot_off, const uint64_t *out_n, const uint64_t *csize,
+		      const uint32_t *crc, const uint64_t *offsets, const uint64_t *block_sums,
+		      uint8_t *out, uint64_t *cp_src, uint64_t *cp_dst, uint64_t *cp_len,
+		      uint64_t *index);
+extern "C" __global__ void
+lda_gzmw_final_kernel(uint64_t n, uint64_t usize_total, uint64_t out_avail,
+		      const uint64_t *total_at, uint64_t *result, uint64_t *index);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */

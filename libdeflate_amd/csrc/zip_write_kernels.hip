@@ -23,11 +23,8 @@
  */
 #include "device_common.h"
 #include "kernels.h"
-#include "large_plan.h"
+#include "zip_write_device.h"
 
-#define ZW_X8 0x00800000u		/* x^8: what appending one byte multiplies a CRC by */
-#define ZW_WAVES 4			/* entries per 256-thread workgroup */
-#define ZW_FROM_SLOT ((u64)1 << 63)	/* cp_src: an offset into the slots, not into d_in */
 #define ZW_FIN_THREADS 1024
 
 /* does the archive - cd_off bytes of local records, then tail bytes of
@@ -37,14 +34,6 @@ static __device__ __forceinline__ bool zw_fits(u64 cd_off, u64 tail, u64 out_ava
 	return cd_off <= out_avail && out_avail - cd_off >= tail;
 }
 
-/* nbytes of v, little endian, at any alignment */
-template <u32 NBYTES> static __device__ __forceinline__ void zw_put(u8 *p, u64 v)
-{
-#pragma unroll
-	for (u32 i = 0; i < NBYTES; i++)
-		p[i] = (u8)(v >> (8 * i));
-}
-
 /*
  * Entry k, pieces first[k] .. + count[k]: e_info[k] = csize | CRC-32 << 32 and
  * sizes[k] = 30 + name + csize.  Method 8 - csize < usize, which is how the
@@ -52,10 +41,7 @@ template <u32 NBYTES> static __device__ __forceinline__ void zw_put(u8 *p, u64 v
  * sum is shorter than the entry; else stored, csize = usize.  out_n NULL:
  * nothing was compressed.
  *
- * The CRC-32 as lda_large_finalize_kernel combines it: every lane takes a
- * contiguous run of the pieces in Horner form - a multiply by x^(8 len) per
- * piece, xS for the pieces as long as the first - and one multiply by
- * x^(8 bytes behind the run); XOR over the lanes.
+ * The sums and the CRC-32 are zw_combine()'s (zip_write_device.h).
  */
 extern "C" __global__ void __launch_bounds__(256)
 lda_zipw_entry_kernel(u64 n, const u64 *__restrict__ first, const u64 *__restrict__ count,
@@ -69,33 +55,10 @@ lda_zipw_entry_kernel(u64 n, const u64 *__restrict__ first, const u64 *__restric
 	for (u64 k = (u64)blockIdx.x * ZW_WAVES + (threadIdx.x >> 6); k < n;
 	     k += (u64)gridDim.x * ZW_WAVES) {
 		const u64 f = first[k], np = count[k], us = usize[k];
-		const u64 run = (np + 63) / 64;
-		const u64 a = lane * run < np ? lane * run : np;
-		const u64 b = a + run < np ? a + run : np;
-		const u64 S = np ? pc_n[f] : 0;
-		const u32 xS = lda_crc_powmod(ZW_X8, S);
-		u64 csum = 0;
-		u32 acc = 0;
-		bool missing = false;
-
-		for (u64 i = a; i < b; i++) {
-			const u64 len = pc_n[f + i];
-			acc = lda_crc_mulmod(acc, len == S ? xS : lda_crc_powmod(ZW_X8, len)) ^
-			      crcs[f + i];
-			if (out_n) {
-				const u64 o = out_n[f + i];
-				csum += o;
-				missing |= o == 0;
-			}
-		}
-		if (a < b) {
-			const u64 behind = us - (pc_off[f + b - 1] + pc_n[f + b - 1] - pc_off[f]);
-			if (behind)
-				acc = lda_crc_mulmod(acc, lda_crc_powmod(ZW_X8, behind));
-		}
-		const u32 crc = wave_xor(acc);
-		csum = wave_sum64(csum);
-		const bool deflated = out_n && np && !__ballot(missing) && csum < us;
+		u64 csum;
+		bool missing;
+		const u32 crc = zw_combine(lane, f, np, us, pc_off, pc_n, out_n, crcs, &csum, &missing);
+		const bool deflated = out_n && np && !missing && csum < us;
 		if (lane == 0) {
 			const u64 cs = deflated ? csum : us;
 			e_info[k] = cs | (u64)crc << 32;
@@ -187,19 +150,8 @@ lda_zipw_place_kernel(u64 n, u32 zip64, u32 dos_datetime, u64 out_avail, u64 tai
 			rec[46 + i] = ch;
 		}
 		/* the pieces back to back behind the name */
-		u64 at = lho + 30 + nl;
-		for (u64 base = 0; base < np; base += 64) {
-			const u64 j = f + base + lane;
-			const bool live = base + lane < np;
-			const u64 len = !live ? 0 : method ? out_n[j] : pc_n[j];
-			const u64 incl = wave_scan_incl64(len);
-			if (live) {
-				cp_src[j] = method ? slot_off[j] | ZW_FROM_SLOT : pc_off[j];
-				cp_dst[j] = at + incl - len;
-				cp_len[j] = len;
-			}
-			at += wave_sum64(len);
-		}
+		zw_place_pieces(lane, f, np, lho + 30 + nl, method != 0, pc_off, pc_n, slot_off, out_n,
+				cp_src, cp_dst, cp_len);
 	}
 }
 

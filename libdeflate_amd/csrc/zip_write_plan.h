@@ -154,13 +154,19 @@ struct zipw_group {
 	uint64_t S;		/* segment size, 0: whole entries (no seg_info) */
 };
 
-struct zipw_plan {
-	bool zip64;
-	uint64_t n, np, cd_size, end_bytes, bound, slots_bytes;
-	std::vector<uint64_t> ecols;	/* ZIPW_ECOLS x n */
+/* the pieces of many entries: what zipw_cut_pieces() leaves, for this plan and
+ * for the gzip-members writer's (gzip_members_write_plan.h) */
+struct zipw_pieces {
+	uint64_t np, slots_bytes;
 	std::vector<uint64_t> pcols;	/* ZIPW_PCOLS x np */
 	std::vector<uint32_t> seg_info;	/* np */
 	std::vector<zipw_group> groups;	/* empty where nothing is compressed */
+};
+
+struct zipw_plan : zipw_pieces {
+	bool zip64;
+	uint64_t n, cd_size, end_bytes, bound;
+	std::vector<uint64_t> ecols;	/* ZIPW_ECOLS x n */
 };
 
 /* the slot a piece of len bytes is compressed into: room for
@@ -188,35 +194,22 @@ static inline uint64_t zipw_seg_bound(const zipw_params &pr, uint64_t S)
 	return S + (pr.D + pr.tile - 1) / pr.tile * pr.tile;
 }
 
-/* the arguments have passed zipw_check() */
+/*
+ * Entries of in_nbytes[k] bytes at in_offsets[k], cut into pieces: first[k] and
+ * cnt[k] (n words each) get every entry's piece range, p the pieces' columns in
+ * launch-group order, their slots and the groups.
+ */
 static inline void
-zipw_plan_build(const zipw_params &pr, uint64_t n, const uint8_t *names,
-		const uint64_t *name_offsets, const uint64_t *in_offsets,
-		const uint64_t *in_nbytes, unsigned flags, zipw_plan &p)
+zipw_cut_pieces(const zipw_params &pr, uint64_t n, const uint64_t *in_offsets,
+		const uint64_t *in_nbytes, uint64_t *first, uint64_t *cnt, zipw_pieces &p)
 {
 	enum { G_SMALL = 0, G_WHOLE = 1, G_SEG = 2 };
 	std::vector<uint64_t> seg_sizes;	/* the distinct S, in the order met */
 	std::vector<uint64_t> count(G_SEG);
 	std::vector<uint32_t> group_of((size_t)n);
 
-	p.n = n;
-	p.bound = zipw_bound(n, name_offsets, in_nbytes, flags, &p.zip64, &p.cd_size, &p.end_bytes);
-	p.ecols.assign((size_t)(ZIPW_ECOLS * n), 0);
-	uint64_t *first = p.ecols.data() + ZIPW_E_FIRST * n, *cnt = p.ecols.data() + ZIPW_E_COUNT * n;
-	uint64_t cen = 0, uoff = 0;
 	for (uint64_t k = 0; k < n; k++) {
-		const uint64_t nl = name_offsets[k + 1] - name_offsets[k], usize = in_nbytes[k];
-		uint64_t utf8 = 0;
-		for (uint64_t b = name_offsets[k]; b < name_offsets[k + 1]; b++)
-			if (names[b] >= 0x80)
-				utf8 = ZIPW_NAME_UTF8;
-		p.ecols[ZIPW_E_NAME_OFF * n + k] = name_offsets[k] - name_offsets[0];
-		p.ecols[ZIPW_E_NAME_LEN * n + k] = nl | utf8;
-		p.ecols[ZIPW_E_CEN * n + k] = cen;
-		p.ecols[ZIPW_E_USIZE * n + k] = usize;
-		p.ecols[ZIPW_E_UOFF * n + k] = uoff;
-		cen += ZIPW_CEN_BYTES + nl + (p.zip64 ? ZIPW_CEN64_EXTRA : 0);
-		uoff += usize;
+		const uint64_t usize = in_nbytes[k];
 		const uint64_t S = zipw_seg_bytes(pr, usize);
 		uint32_t g = G_SMALL;
 		if (pr.store) {
@@ -296,6 +289,34 @@ zipw_plan_build(const zipw_params &pr, uint64_t n, const uint8_t *names,
 			for (uint64_t j = gr.lo; j < gr.hi; j++)
 				if (p.pcols[ZIPW_P_IN_N * np + j] > gr.max_in)
 					gr.max_in = p.pcols[ZIPW_P_IN_N * np + j];
+}
+
+/* the arguments have passed zipw_check() */
+static inline void
+zipw_plan_build(const zipw_params &pr, uint64_t n, const uint8_t *names,
+		const uint64_t *name_offsets, const uint64_t *in_offsets,
+		const uint64_t *in_nbytes, unsigned flags, zipw_plan &p)
+{
+	p.n = n;
+	p.bound = zipw_bound(n, name_offsets, in_nbytes, flags, &p.zip64, &p.cd_size, &p.end_bytes);
+	p.ecols.assign((size_t)(ZIPW_ECOLS * n), 0);
+	uint64_t cen = 0, uoff = 0;
+	for (uint64_t k = 0; k < n; k++) {
+		const uint64_t nl = name_offsets[k + 1] - name_offsets[k], usize = in_nbytes[k];
+		uint64_t utf8 = 0;
+		for (uint64_t b = name_offsets[k]; b < name_offsets[k + 1]; b++)
+			if (names[b] >= 0x80)
+				utf8 = ZIPW_NAME_UTF8;
+		p.ecols[ZIPW_E_NAME_OFF * n + k] = name_offsets[k] - name_offsets[0];
+		p.ecols[ZIPW_E_NAME_LEN * n + k] = nl | utf8;
+		p.ecols[ZIPW_E_CEN * n + k] = cen;
+		p.ecols[ZIPW_E_USIZE * n + k] = usize;
+		p.ecols[ZIPW_E_UOFF * n + k] = uoff;
+		cen += ZIPW_CEN_BYTES + nl + (p.zip64 ? ZIPW_CEN64_EXTRA : 0);
+		uoff += usize;
+	}
+	zipw_cut_pieces(pr, n, in_offsets, in_nbytes, p.ecols.data() + ZIPW_E_FIRST * n,
+			p.ecols.data() + ZIPW_E_COUNT * n, p);
 }
 
 } /* namespace lda */
