@@ -1434,6 +1434,131 @@ libdeflate_amd_gzip_members_compress_batch(struct libdeflate_compressor *compres
 					   uint64_t *d_result, uint64_t *d_index, uint32_t mtime,
 					   unsigned flags, void *stream);
 
+/*
+ * Prefix decompress: the first bytes of every stream of a batch - zlib's
+ * inflate() with avail_out below the stream's size, Python's
+ * decompressobj().decompress(data, max_length) - which the whole-buffer calls
+ * above answer with LIBDEFLATE_INSUFFICIENT_SPACE and an undefined buffer.
+ *
+ * d_limits[i] is stream i's limit; d_out + d_out_offsets[i] has room for that
+ * many bytes.  d_results[i] is what
+ *   libdeflate_<format>_decompress_ex(in_i, out_avail = d_limits[i],
+ *                                     &actual_in, &actual_out)
+ * returns, with one substitution: where that call returns
+ * LIBDEFLATE_INSUFFICIENT_SPACE the result here is LIBDEFLATE_AMD_PREFIX
+ * (subject to the one exception below), and then
+ *   - d_out[d_out_offsets[i] .. + d_limits[i]) holds the first d_limits[i]
+ *     bytes of what the stream decodes to;
+ *   - d_actual_out[i] = d_limits[i] and d_actual_in[i] = 0;
+ *   - the footer is not looked at (a wrong checksum cannot show).
+ * The one exception is the match that the limit cuts: the reference stops
+ * before it reads that match's offset, this call needs the offset and decodes
+ * it by the rules of a match that fits.  An offset that reaches before the
+ * stream (or its dictionary), and one whose bits do not lie inside the input,
+ * make the stream LIBDEFLATE_BAD_DATA with d_actual_out[i] = 0.  Nothing else
+ * about an offset is bad: an offset code without codewords, or with one, is
+ * read as the reference reads it for a match that fits (an empty code stands
+ * for symbol 0, distance 1 - bad at the stream's first byte only).  (A stored
+ * block that the limit cuts is checked against the input in the same spirit:
+ * a LEN that runs past the input is LIBDEFLATE_BAD_DATA, not a prefix.)
+ *
+ * LIBDEFLATE_SUCCESS means that the stream ended within its limit and was
+ * checked in full, checksum and ISIZE included; d_actual_in[i] and
+ * d_actual_out[i] are then the reference's.  d_limits[i] == 0 is legal.  A
+ * stream that fails or is cut never affects its neighbours, and no byte is
+ * written at or past a stream's limit.  Under every other result the bytes
+ * below the limit are undefined and the two figures mean nothing (0 and 0
+ * where the decoder itself refused the stream; what the raw decoder counted
+ * where only the footer did not match, as with
+ * libdeflate_amd_decompress_batch).
+ *
+ * The calls only enqueue on `stream`; object, scratch and stream follow
+ * libdeflate_amd_decompress_batch, and so does LIBDEFLATE_AMD_BAD_ARG, which
+ * comes before any device work: a NULL object or pointer (d_actual_in alone
+ * may be NULL) or an unknown format; n_chunks == 0 does nothing.  The _dict
+ * form follows libdeflate_amd_decompress_batch_dict: it refuses gzip, and a
+ * distance may reach into the dictionary.
+ *
+ * Cost: a stream runs on one wave.  Whole rounds of the decode run below the
+ * limit, the last of them clipped to it; behind that lane 0 walks less than
+ * one lane's piece of tokens (48 bytes of input) to the cut.  A prefix of many MiB of ONE huge stream therefore runs
+ * at the one-wave rate (libdeflate_amd_decompress_large has no prefix form).
+ * In zlib and gzip format the checksum batch runs over every stream's
+ * d_actual_out bytes, a cut stream's prefix included, though only the streams
+ * that ended are compared with their footer.
+ */
+#define LIBDEFLATE_AMD_PREFIX 19	/* a per-stream result: cut at its limit */
+
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_prefix_batch(struct libdeflate_decompressor *decompressor, int format,
+				       size_t n_chunks, const void *d_in,
+				       const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
+				       void *d_out, const uint64_t *d_out_offsets,
+				       const uint64_t *d_limits, int32_t *d_results,
+				       uint64_t *d_actual_in /* may be NULL */,
+				       uint64_t *d_actual_out, void *stream);
+
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_prefix_batch_dict(struct libdeflate_decompressor *decompressor,
+					    int format, size_t n_chunks, const void *d_dict,
+					    size_t dict_nbytes, const void *d_in,
+					    const uint64_t *d_in_offsets,
+					    const uint64_t *d_in_nbytes, void *d_out,
+					    const uint64_t *d_out_offsets, const uint64_t *d_limits,
+					    int32_t *d_results,
+					    uint64_t *d_actual_in /* may be NULL */,
+					    uint64_t *d_actual_out, void *stream);
+
+/*
+ * One stream, HOST pointers, blocking: `out` has room for `limit` bytes.
+ * Returns an enum libdeflate_result value or LIBDEFLATE_AMD_PREFIX, as
+ * d_results[] above; *actual_out_ret (required) is set on LIBDEFLATE_SUCCESS
+ * and on LIBDEFLATE_AMD_PREFIX (to `limit`), and that many bytes of `out` are
+ * written.  A bad argument or a library-side failure is LIBDEFLATE_BAD_DATA
+ * with the reason in libdeflate_amd_last_error(), as with the single-buffer
+ * calls.  The object's staging buffer grows to in_nbytes + limit bytes of
+ * device memory: `limit` is the room the caller has, not a way to say "no
+ * limit" (a value above SIZE_MAX / 4 is a bad argument).
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_decompress_prefix(struct libdeflate_decompressor *decompressor, int format,
+				 const void *in, size_t in_nbytes, void *out, size_t limit,
+				 size_t *actual_out_ret);
+
+/*
+ * The heads of the members of a file of concatenated gzip members: the first
+ * head_nbytes bytes of every member in one enqueue, with nothing crossing to
+ * the host - libdeflate_amd_gzip_members_index_batch, this call, the caller's
+ * filter over the heads, then libdeflate_amd_decompress_batch_packed over the
+ * chosen members, all on one stream.
+ *
+ * d_result and d_index are DEVICE memory as
+ * libdeflate_amd_gzip_members_index_batch wrote them for (d_in, in_nbytes)
+ * with at least max_members rows.  Row r < min(d_result[1], max_members) is
+ * member r: d_heads[r * head_nbytes ..] gets the first head_nbytes bytes of
+ * what it decodes to (all of it where it is shorter), d_head_nbytes[r] how
+ * many they are and d_results[r] LIBDEFLATE_SUCCESS (the member ended within
+ * head_nbytes and was checked in full), LIBDEFLATE_AMD_PREFIX, or the
+ * member's failure (d_head_nbytes[r] is then meaningless, as d_actual_out of
+ * libdeflate_amd_decompress_prefix_batch).  The rows at and beyond the member
+ * count are empty: d_head_nbytes[r] = 0, d_results[r] = 0, no byte of their
+ * d_heads row written.  So are ALL rows when d_result[0] is not
+ * LIBDEFLATE_SUCCESS - a verdict under which the index is not written - and
+ * every row whose index pair does not lie inside in_nbytes.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work: a NULL object or pointer
+ * (d_in may be NULL with in_nbytes == 0, d_heads with head_nbytes == 0),
+ * max_members == 0 or above 2^28, head_nbytes above 2^32 - 1.  No ZIP
+ * counterpart: a ZIP selection goes through host rows, from which a caller
+ * builds prefix descriptors itself.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_gzip_members_peek_batch(struct libdeflate_decompressor *decompressor,
+				       const void *d_in, size_t in_nbytes,
+				       const uint64_t *d_result, const uint64_t *d_index,
+				       size_t max_members, size_t head_nbytes, void *d_heads,
+				       uint64_t *d_head_nbytes, int32_t *d_results, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ from ctypes import c_size_t, c_void_p
 import numpy as np
 
 from . import binding
-from .binding import FORMATS, check
+from .binding import FORMATS, PREFIX, check  # noqa: F401  (PREFIX: a per-stream result)
 
 
 def _buf(b):
@@ -600,6 +600,59 @@ class Decompressor:
             actual_in.data_ptr() if actual_in is not None else None,
             actual_out.data_ptr() if actual_out is not None else None,
             _stream_ptr(stream)), "decompress_batch_dict")
+
+    def decompress_prefix_batch(self, fmt, data, in_offsets, in_nbytes, out, out_offsets,
+                                limits, results, actual_out, actual_in=None, stream=None):
+        """libdeflate_amd_decompress_prefix_batch: the first limits[i] bytes
+        of every stream.  results[i] is SUCCESS (the stream ended within its
+        limit and was checked in full), PREFIX (cut: exactly limits[i] bytes
+        written, actual_out[i] = limits[i]) or the stream's failure.  Tensors
+        as in decompress_batch; limits and actual_out int64.  Only enqueues."""
+        check(self._lib.libdeflate_amd_decompress_prefix_batch(
+            self._h, FORMATS[fmt], in_offsets.numel(), data.data_ptr(),
+            in_offsets.data_ptr(), in_nbytes.data_ptr(), out.data_ptr(),
+            out_offsets.data_ptr(), limits.data_ptr(), results.data_ptr(),
+            actual_in.data_ptr() if actual_in is not None else None,
+            actual_out.data_ptr(), _stream_ptr(stream)), "decompress_prefix_batch")
+
+    def decompress_prefix_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
+                                     out_offsets, limits, results, actual_out, actual_in=None,
+                                     stream=None):
+        """libdeflate_amd_decompress_prefix_batch_dict: the same with the
+        preset dictionary (a uint8 torch CUDA tensor) of decompress_batch_dict."""
+        check(self._lib.libdeflate_amd_decompress_prefix_batch_dict(
+            self._h, FORMATS[fmt], in_offsets.numel(),
+            dictionary.data_ptr() if dictionary.numel() else None, dictionary.numel(),
+            data.data_ptr(), in_offsets.data_ptr(), in_nbytes.data_ptr(), out.data_ptr(),
+            out_offsets.data_ptr(), limits.data_ptr(), results.data_ptr(),
+            actual_in.data_ptr() if actual_in is not None else None,
+            actual_out.data_ptr(), _stream_ptr(stream)), "decompress_prefix_batch_dict")
+
+    def decompress_prefix(self, fmt, data, limit):
+        """libdeflate_amd_decompress_prefix: host bytes -> (result,
+        actual_out, bytes); result is SUCCESS, PREFIX (bytes are the first
+        `limit` of the stream) or the stream's failure (no bytes)."""
+        p, n = _buf(data)
+        out = np.zeros(max(limit, 1), dtype=np.uint8)
+        ao = c_size_t(0)
+        r = self._lib.libdeflate_amd_decompress_prefix(
+            self._h, FORMATS[fmt], p, n, out.ctypes.data_as(c_void_p), limit, ctypes.byref(ao))
+        return r, ao.value, out[:ao.value].tobytes()
+
+    def peek_gzip_members_batch(self, data, result, index, max_members, head_nbytes, heads,
+                                head_sizes, results, stream=None, in_nbytes=None):
+        """libdeflate_amd_gzip_members_peek_batch: the first head_nbytes bytes
+        of every member of the file in `data`, from `result` and `index` as
+        index_gzip_members_batch wrote them (CUDA tensors, nothing crosses to
+        the host).  heads: uint8 CUDA tensor of max_members * head_nbytes;
+        head_sizes: int64, results: int32, max_members each.  Only enqueues."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_gzip_members_peek_batch(
+            self._h, data.data_ptr() if n else None, n, result.data_ptr(), index.data_ptr(),
+            int(max_members), int(head_nbytes),
+            heads.data_ptr() if heads is not None and heads.numel() else None,
+            head_sizes.data_ptr(), results.data_ptr(), _stream_ptr(stream)),
+            "gzip_members_peek_batch")
 
     def decompress_sizes_batch(self, fmt, data, in_offsets, in_nbytes, results, out_nbytes,
                                limits=None, actual_in=None, stream=None):

@@ -44,6 +44,8 @@ GZMW_RESULT_WORDS, GZMW_NAME_MAX = 4, 65534
 SEEK_WINDOW, SEEK_WORDS = 32768, 4
 # the size query: the limit a NULL d_out_limit stands for
 SIZE_LIMIT_MAX = 0xFFFFFFFF
+# the prefix decompress: the per-stream result of a stream cut at its limit
+PREFIX = 19
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -87,6 +89,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_zip_read_batch",
     "libdeflate_amd_zip_compress_bound", "libdeflate_amd_zip_compress_batch",
     "libdeflate_amd_gzip_members_compress_bound", "libdeflate_amd_gzip_members_compress_batch",
+    "libdeflate_amd_decompress_prefix_batch", "libdeflate_amd_decompress_prefix_batch_dict",
+    "libdeflate_amd_decompress_prefix", "libdeflate_amd_gzip_members_peek_batch",
 ]
 
 _lib = None
@@ -216,6 +220,14 @@ def load():
     sig("libdeflate_amd_gzip_members_compress_bound", SZ, P, SZ, P, P)
     sig("libdeflate_amd_gzip_members_compress_batch", c_int, P, SZ, P, P, P, SZ, P, P, P, SZ,
         P, P, c_uint32, c_uint32, P)
+    # the first bytes of every stream: device batch (with a dictionary), one
+    # host buffer (blocking), the heads of an indexed gzip-members file
+    sig("libdeflate_amd_decompress_prefix_batch", c_int, P, c_int, SZ, P, P, P, P, P, P, P, P,
+        P, P)
+    sig("libdeflate_amd_decompress_prefix_batch_dict", c_int, P, c_int, SZ, P, SZ, P, P, P, P,
+        P, P, P, P, P, P)
+    sig("libdeflate_amd_decompress_prefix", c_int, P, c_int, P, SZ, P, SZ, psz)
+    sig("libdeflate_amd_gzip_members_peek_batch", c_int, P, P, SZ, P, P, SZ, SZ, P, P, P, P)
     _lib = lib
     return lib
 

@@ -37,6 +37,9 @@
  *                           descriptors and the index.
  *   lda_gzm_final_kernel    one workgroup: the five result words, the closing
  *                           index pair.
+ * (The heads of the members, libdeflate_amd_gzip_members_peek_batch, are a
+ * prefix batch over the index this reader wrote: lda_gzm_peek_desc_kernel in
+ * inflate_prefix.hip.)
  *
  * The input is hostile by definition: every load is checked against n, every
  * index against the candidate count, and no loop of these kernels takes its

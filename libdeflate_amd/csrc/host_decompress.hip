@@ -70,19 +70,19 @@ using namespace lda;
  * every wave of the grid, 16 bytes of counters */
 /* waves (= streams in flight) per CU: what the kernel's LDS leaves room for, at
  * most LDA_INFLATE_WAVES_PER_CU (16: four per SIMD at 128 VGPRs) */
-static size_t inflate_wave_lds(void)
+size_t lda::inflate_wave_lds(void)
 {
 	return lda_inflate_lds_per_stream() + lda_inflate_lds_shared() + lda_inflate_window_bytes();
 }
 
-static size_t inflate_waves_per_cu(void)
+size_t lda::inflate_waves_per_cu(void)
 {
 	const size_t fit = 163840 / inflate_wave_lds(), want = (size_t)env_cfg().inflate_waves_per_cu;
 
 	return want < fit ? want : fit;
 }
 
-static size_t inflate_tokens_bytes(size_t n, int num_cus)
+size_t lda::inflate_tokens_bytes(size_t n, int num_cus)
 {
 	size_t grid = (size_t)num_cus * inflate_waves_per_cu();
 

@@ -125,6 +125,15 @@ size_t compress_pieces_scratch(const struct libdeflate_compressor *c, size_t n, 
 			       bool seg);
 size_t compress_prime_window(void);
 
+/* host_decompress.hip, for the prefix batch (host_prefix.hip), which launches
+ * the wave kernel's geometry: dynamic LDS of a wave, waves per CU (LDS and
+ * LDA_INFLATE_WAVES_PER_CU), and the bytes of d->tokens for a batch of n
+ * streams - the token rows of every wave of the grid, then 16 bytes of
+ * counters */
+size_t inflate_wave_lds(void);
+size_t inflate_waves_per_cu(void);
+size_t inflate_tokens_bytes(size_t n, int num_cus);
+
 /* host_sizes.hip: the size query on a stream (arguments checked by the
  * callers); s: sizes_scratch_bytes(n) bytes of device memory that stay
  * untouched until the query has run */

@@ -644,6 +644,17 @@ ring_fill(lu8 *ring, const u8 *inp, u64 in_n, u64 at)
 #define PAR_SCRATCH (64u * PAR_LANECAP)	/* u32 words per wave */
 #define PAR_MAP_BYTES (256u + 128u)	/* tok_fetch: marks + tbase table */
 enum { PAR_STOP = 0, PAR_OK = 1, PAR_EOB = 2 };
+/* A round whose bytes do not fit the output is abandoned: PAR_STOP.  In the
+ * translation unit of the prefix kernel (inflate_prefix.hip), where a stream
+ * cut at its limit is the rule, such a round is clipped instead to the lanes
+ * whose bytes fit - as round_offsets() clips a round to the token scratch -
+ * and reports it: PAR_OK_LIMIT, or PAR_STOP_LIMIT when not even lane 0's
+ * fit.  The caller ends the stream's rounds on either, and lane 0 walks what
+ * is left in front of the limit: less than one lane's piece. */
+#ifndef LDA_INFLATE_PREFIX
+#define LDA_INFLATE_PREFIX 0	/* the PREFIX mode of inflate_block(), see there */
+#endif
+enum { PAR_STOP_LIMIT = 3, PAR_OK_LIMIT = 4 };
 
 struct par_bits {
 	u64 buf;
@@ -1771,8 +1782,25 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	struct par_sums R;
 	if (!round_offsets<!COUNT>(R, lane, ntok, nbytes, K, has_eob))
 		return PAR_STOP;
+#if LDA_INFLATE_PREFIX
+	bool clipped = false;
+	if (R.total_bytes > out_avail - out0) {
+		/* (obase + nbytes grows with the lane: the lanes that fit are a
+		 * prefix of the round's) */
+		const u64 fit = __ballot(R.valid && (u64)R.obase + nbytes <= out_avail - out0);
+		if (!fit)
+			return PAR_STOP_LIMIT;
+		R.K = (u32)__builtin_popcountll(fit) - 1;
+		R.has_eob = false;
+		R.valid = lane <= R.K;
+		R.total_tok = bcast_lane(R.tbase + R.tcnt, R.K);
+		R.total_bytes = bcast_lane(R.obase + nbytes, R.K);
+		clipped = true;
+	}
+#else
 	if (R.total_bytes > out_avail - out0)
 		return PAR_STOP;
+#endif
 	const u64 end_bits = bcast_lane(end, R.K) - bpos0 + bpos_abs;
 	if (end_bits > 8 * in_n)
 		return PAR_STOP;
@@ -1794,6 +1822,10 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
 	}
 	*bpos_ret = end_bits;
 	*out_ret = out0 + R.total_bytes;
+#if LDA_INFLATE_PREFIX
+	if (clipped)
+		return PAR_OK_LIMIT;
+#endif
 	return R.has_eob ? PAR_EOB : PAR_OK;
 }
 
@@ -1812,8 +1844,19 @@ par_round(const u8 *inp, u64 in_n, u8 *outp, u64 out_avail,
  * dictionary's length.  Every store to the output, every read from it and the
  * copy phase of a round do not exist; every check stays, `distance > bytes
  * produced` against the count.
+ *
+ * PREFIX (LDA_INFLATE_PREFIX, a constant of the translation unit, so that
+ * nothing of it reaches the other kernels' code, not even to be folded away;
+ * lda_inflate_prefix_kernel, inflate_prefix.hip): the decode, but a stream
+ * that would end in LDA_INSUFFICIENT_SPACE ends as LDA_PREFIX with exactly
+ * out_avail bytes written - the token that does not fit is cut at the limit.
+ * The three places that say LDA_INSUFFICIENT_SPACE are the three cuts: the
+ * stored block, the literal, the match (whose offset is then decoded, which
+ * the reference does not do for a match without room).
  */
 #define LDA_SIZE_LIMIT_MAX 0xFFFFFFFFull
+#define LDA_PREFIX 19	/* LIBDEFLATE_AMD_PREFIX */
+#define PREFIX_ROUND_MIN 512u	/* bytes of room below which no round is tried */
 static __device__ __forceinline__ void
 inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	      u64 n_chunks, int format, u32 lpw,
@@ -1834,6 +1877,12 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	       * mode's branches fold) */
 	      const bool COUNT = false)
 {
+	constexpr bool PREFIX = LDA_INFLATE_PREFIX;
+	/* PREFIX: lane 0's short copies are not split into loads now and stores
+	 * at the next token (pv0..pv3 and what goes with them: a dozen VGPRs,
+	 * which is what this kernel lacks under the cap of 128; its rounds do
+	 * not use them) */
+	constexpr bool PREFIX_NO_PENDING = PREFIX;
 	slds_t *SL = (slds_t *)lds_raw;
 	const u32 lane = threadIdx.x;
 	const u64 c = blk * lpw + lane;
@@ -1975,6 +2024,11 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 	u32 hist_n = 0;
 	const u64 limit_bits = 8 * in_n + 8;	/* see header comment */
 	(void)limit_bits;
+	/* PREFIX: the stream's rounds are over (wave-uniform).  An abandoned round
+	 * is tried again after the next few tokens of lane 0, which is right where
+	 * it was abandoned for something rare; a round that crosses the limit will
+	 * cross it again, and a stream cut at its limit is no rare thing here */
+	[[maybe_unused]] bool rounds_off = false;
 
 	while (__ballot(state != ST_DONE)) {
 		/* ------------ block headers (lanes that need one) ------------ */
@@ -2011,7 +2065,7 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 						if (len != (nlen ^ 0xFFFF)) {
 							result = LDA_BAD_DATA;
 							state = ST_DONE;
-						} else if (len > out_avail - out_pos) {
+						} else if (!PREFIX && len > out_avail - out_pos) {
 							result = LDA_INSUFFICIENT_SPACE;
 							state = ST_DONE;
 						} else if (len > in_n - pos) {
@@ -2020,6 +2074,13 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 						} else {
 							rpos = pos;
 							stored_left = len;
+							/* cut: the bytes that fit are copied as
+							 * a block of that length, which then
+							 * ends the stream */
+							if (PREFIX && len > out_avail - out_pos) {
+								stored_left = out_avail - out_pos;
+								result = LDA_PREFIX;
+							}
 							state = ST_STORED;
 						}
 					}
@@ -2221,6 +2282,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 					bitcnt = 0;
 					filled = rpos & ~(u64)63;	/* restart the input ring */
 					state = final_block ? ST_DONE : ST_HDR;
+					if (PREFIX && result == LDA_PREFIX)
+						state = ST_DONE;
 				}
 			}
 		} else if (state == ST_STORED) {	/* lane per stream: the lane copies its bytes */
@@ -2244,6 +2307,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			bitcnt = 0;
 			filled = rpos & ~(u64)63;	/* restart the input ring */
 			state = final_block ? ST_DONE : ST_HDR;
+			if (PREFIX && result == LDA_PREFIX)
+				state = ST_DONE;
 		}
 
 		/* ------------ sub-block parallel rounds (wave per stream) ------------ */
@@ -2254,12 +2319,22 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			for (;;) {
 				if (!bcast_first(state == ST_TOK ? 1u : 0u))
 					break;
+				if (PREFIX && rounds_off)
+					break;
 				if (!COUNT) {
 					if (lane == 0)
 						FLUSH_PENDING();
 				}
 				const u64 bpos0 = bcast64(CONSUMED());
 				const u64 o0 = bcast64(out_pos);
+				if (PREFIX) {
+					/* no round fits in less room than this (a round
+					 * of 64 pieces is 3 KiB of input): lane 0 walks */
+					if (bcast64(out_avail) - o0 < PREFIX_ROUND_MIN) {
+						rounds_off = true;
+						break;
+					}
+				}
 				const u8 *inp0 = (const u8 *)bcast64((u64)(uintptr_t)inp);
 				u8 *outp0 = (u8 *)bcast64((u64)(uintptr_t)outp);
 				u64 nb = 0, no = 0;
@@ -2304,6 +2379,15 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 						   dict, bcast_first(dlen));
 
 				PROF_COUNT(12 + pr, 1);
+				if (PREFIX && (pr == PAR_STOP_LIMIT || pr == PAR_OK_LIMIT)) {
+					/* the round's bytes cross the limit and it was
+					 * clipped to the lanes that fit: lane 0 walks the
+					 * rest, less than one lane's piece.  A round
+					 * abandoned for anything else is tried again as
+					 * ever */
+					rounds_off = true;
+					pr = pr == PAR_OK_LIMIT ? PAR_OK : PAR_STOP;
+				}
 				if (pr == PAR_STOP)
 					break;
 				if (lane == 0) {
@@ -2421,7 +2505,7 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 							hist_n = hist_n + length > 8 ? 8 : hist_n + length;
 						} else {
 							u32 nwords = (length + 7) >> 3;
-							if (nwords <= 4 && nwords <= (dist >> 3)) {
+							if (!PREFIX_NO_PENDING && nwords <= 4 && nwords <= (dist >> 3)) {
 								const u8 *src = outp + out_pos - dist;
 								pend_dst = outp + out_pos;
 								pend_n = nwords;
@@ -2493,7 +2577,7 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 #endif
 			if (kind == K_LIT) {
 				if (out_pos == out_avail) {
-					result = LDA_INSUFFICIENT_SPACE;
+					result = PREFIX ? LDA_PREFIX : LDA_INSUFFICIENT_SPACE;
 					state = ST_DONE;
 					continue;
 				}
@@ -2527,7 +2611,7 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			len_sym(pay, &base, &xb);
 			u32 length = base + ((u32)bitbuf & ((1u << xb) - 1));
 			CONSUME(xb);
-			if (length > out_avail - out_pos) {
+			if (!PREFIX && length > out_avail - out_pos) {
 				result = LDA_INSUFFICIENT_SPACE;
 				state = ST_DONE;
 				continue;
@@ -2540,6 +2624,28 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			off_sym(osym, &base, &xb);
 			u32 dist = base + ((u32)bitbuf & ((1u << xb) - 1));
 			CONSUME(xb);
+			if (PREFIX && length > out_avail - out_pos) {
+				/* the cut match.  Its offset was decoded by the rules of a
+				 * match that fits, and its bits must lie inside the input
+				 * (a match that fits and runs into the implicit padding
+				 * fails at the next refill or at the end of the stream:
+				 * this stream has neither).  Byte by byte: the source may
+				 * begin in the dictionary and overlap the destination */
+				const u32 nd = dist > out_pos ? (u32)(dist - out_pos) : 0;
+				if ((CONSUMED() + 7) / 8 > in_n || nd > dlen) {
+					result = LDA_BAD_DATA;
+					state = ST_DONE;
+					continue;
+				}
+				const u32 room = (u32)(out_avail - out_pos);
+				for (u32 j = 0; j < room; j++)
+					outp[out_pos + j] = j < nd ? dict[dlen - nd + j] :
+								     outp[out_pos + j - dist];
+				out_pos = out_avail;
+				result = LDA_PREFIX;
+				state = ST_DONE;
+				continue;
+			}
 			if (dist > out_pos) {
 				if (dist - out_pos > dlen) {
 					result = LDA_BAD_DATA;
@@ -2588,7 +2694,7 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			} else {
 				u32 nwords = (length + 7) >> 3;
 				u32 maxw = dist >> 3;
-				if (nwords <= 4 && nwords <= maxw &&
+				if (!PREFIX_NO_PENDING && nwords <= 4 && nwords <= maxw &&
 				    out_pos + 8ull * nwords <= out_avail) {
 					const u8 *src = outp + out_pos - dist;
 					pend_dst = outp + out_pos;
@@ -2663,7 +2769,8 @@ inflate_block(u64 blk, lu8 *lds_raw, u32 par, u32 *__restrict__ tok,
 			return;
 		}
 		results[c] = result;
-		actual_out[c] = result == LDA_SUCCESS ? out_pos : 0;
+		actual_out[c] = result == LDA_SUCCESS ? out_pos :
+				PREFIX && result == LDA_PREFIX ? out_avail : 0;
 		if (result != LDA_SUCCESS)
 			actual_in[c] = 0;
 	}

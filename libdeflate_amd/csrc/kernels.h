@@ -67,6 +67,19 @@ lda_packed_desc_kernel(uint64_t n, uint64_t capacity, const uint64_t *in_nbytes,
 extern "C" __global__ void
 lda_packed_merge_kernel(uint64_t n, const int32_t *verdict, int32_t *results,
 			uint64_t *actual_in, uint64_t *actual_out);
+/* inflate_prefix.hip: the decode cut at every stream's limit */
+extern "C" __global__ void
+lda_inflate_prefix_kernel(uint64_t n_chunks, int format, uint32_t par, uint32_t *tokscratch,
+			  uint32_t *next_stream, const uint32_t *order, const uint8_t *in_base,
+			  const uint64_t *in_offsets, const uint64_t *in_nbytes,
+			  uint8_t *out_base, const uint64_t *out_offsets, const uint64_t *limits,
+			  int32_t *results, uint64_t *actual_in, uint64_t *actual_out,
+			  const uint8_t *dict, uint32_t dict_len, const uint32_t *dict_id);
+/* ... and the descriptors of the heads of an indexed gzip-members file */
+extern "C" __global__ void
+lda_gzm_peek_desc_kernel(uint64_t max_members, uint64_t n, uint64_t head, const uint64_t *result,
+			 const uint64_t *index, uint64_t *in_off, uint64_t *in_n, uint64_t *out_off,
+			 uint64_t *limits, int32_t *results, uint64_t *head_nbytes);
 extern "C" size_t lda_inflate_tokcap(void);
 extern "C" size_t lda_inflate_window_bytes(void);
 extern "C" __global__ void
