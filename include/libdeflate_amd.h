@@ -1272,6 +1272,182 @@ libdeflate_amd_zip_read_batch(struct libdeflate_decompressor *decompressor,
 			      uint64_t *out_offsets, int32_t *d_results, void *stream);
 
 /*
+ * Reading a tar archive (.tar, and with libdeflate_amd_decompress_large_index
+ * in front a .tar.gz: source releases, container layers, sdists, WebDataset
+ * shards) that lies in device memory.  The reference has nothing to do with
+ * tar; the oracle is Python's tarfile, and tools/models/tar_walk.py restates
+ * the rule on the CPU.  The rule is defined by a serial walk, and the device
+ * result is exactly the walk's, whatever finds it.
+ *
+ * THE WALK: blocks are 512 bytes, nb = in_nbytes / 512 (a trailing partial
+ * block is ignored), pos = 0 in blocks.
+ *   1. nb == 0: LIBDEFLATE_BAD_DATA (tarfile's "empty file").
+ *   2. pos == nb: the archive ends without an end marker; it is accepted and
+ *      LIBDEFLATE_AMD_TAR_EOF is not set.
+ *   3. The block at pos is all zero: the archive ends, LIBDEFLATE_AMD_TAR_EOF
+ *      is set, and what lies behind is not examined (tarfile without
+ *      ignore_zeros).  Block 0 being zero is an empty archive: SUCCESS with 0
+ *      entries.
+ *   4. Otherwise the block must be a HEADER.  An octal field skips leading
+ *      spaces, reads octal digits, and must then be at the field's end or at a
+ *      NUL or a space.  The checksum field (bytes 148..155, at least one digit)
+ *      must equal the sum of the block's 512 bytes with those 8 counted as
+ *      spaces, the bytes taken as unsigned or as signed chars (both accepted,
+ *      as in tarfile).  The size field (124..135) is such an octal number, no
+ *      digits meaning 0; with byte 124 == 0x80 it is the big-endian number in
+ *      bytes 125..135, any other byte 124 with bit 7 set is invalid.  A size of
+ *      2^36 or more is no header.  Data blocks d = ceil(size / 512), but d = 0
+ *      for typeflags '1'..'6' (links, devices, directories, FIFOs) whatever the
+ *      field says, which is tarfile's rule.  pos + 1 + d <= nb must hold.  No
+ *      magic is required (V7 archives).  Anything else at a position the walk
+ *      reaches is a broken chain: LIBDEFLATE_BAD_DATA.
+ *   5. The record is 1 + d blocks; pos += 1 + d.
+ * Every block that passes rule 4 is a CANDIDATE - a file's data may hold
+ * headers, a tar inside a tar does -; the chain from block 0 decides which are
+ * records.
+ *
+ * ENTRIES: records of typeflag L, K, x, X, g are EXTENSION RECORDS.  Every
+ * other record is an ENTRY, and the extension records directly in front of it
+ * belong to it; extension records behind the last entry are dropped.  An
+ * entry's name is the first of these that applies: the value of the last
+ * path= record of its x / X records (pax records are "%d %s=%s\n"; of several
+ * x / X records the last one that has a path=); else the data of its (last) L
+ * record up to the first NUL; else the header's name field up to the first
+ * NUL, preceded, when the magic is "ustar\0" and the prefix field (345..499)
+ * is not empty, by the prefix and a '/'.  K and g records and pax keys other
+ * than path and size are walked over and ignored.
+ *
+ * An entry is LIBDEFLATE_AMD_TAR_UNSUPPORTED for itself alone when it has more
+ * than 8 extension records in front of it, an L, x or X record of more than
+ * 1 MiB, a pax record that does not parse, a pax size= key, or typeflag S, M
+ * or D.  Such an entry is listed with its header's own name and usize 0 and
+ * takes no room.  Unknown typeflags are regular files (POSIX, tarfile): only
+ * typeflags '0', NUL, '7' and unknown ones have bytes to extract, the others
+ * are listed with usize 0.
+ */
+#define LIBDEFLATE_AMD_TAR_MORE_RECORDS     16	/* result[0]; same value as the other readers' */
+#define LIBDEFLATE_AMD_TAR_MORE_CANDIDATES  17	/* result[0] */
+#define LIBDEFLATE_AMD_TAR_UNSUPPORTED      18	/* a per-entry result */
+#define LIBDEFLATE_AMD_TAR_RESULT_WORDS     5
+#define LIBDEFLATE_AMD_TAR_WORDS            8	/* u64 per index row */
+#define LIBDEFLATE_AMD_TAR_SLACK            1024	/* candidate room = max_records + this */
+#define LIBDEFLATE_AMD_TAR_EOF              1	/* result[4]: the walk ended at a zero block */
+#define LIBDEFLATE_AMD_TAR_HAS_L            2	/* result[4]: an L record was seen */
+#define LIBDEFLATE_AMD_TAR_HAS_PAX          4	/* result[4]: an x, X or g record was seen */
+
+/*
+ * The whole archive in DEVICE memory -> every entry's bytes in device memory.
+ * Enqueues on `stream` and returns, with the conventions of
+ * libdeflate_amd_zip_decompress_batch: device pointers on the object's device,
+ * scratch of the object, d_out must not overlap d_in, and no byte is ever
+ * written at or past d_out + out_avail, nor into an entry's alignment padding.
+ * max_records bounds the chain's records of every kind - entries and extension
+ * records - and sizes the launches and the scratch on the host, because the
+ * host never learns the counts; the finder has room for max_records +
+ * LIBDEFLATE_AMD_TAR_SLACK candidates (and never for more than nb).
+ *
+ * d_result[0..4] (device memory):
+ *   [0] the verdict, the first of these that applies:
+ *       1. LIBDEFLATE_BAD_DATA: nb == 0;
+ *       2. LIBDEFLATE_AMD_TAR_MORE_CANDIDATES: more blocks pass the header rule
+ *          than there is room for ([1] is how many);
+ *       3. LIBDEFLATE_BAD_DATA: a broken chain;
+ *       4. LIBDEFLATE_AMD_TAR_MORE_RECORDS: the chain has more than
+ *          max_records records ([1] is how many);
+ *       5. LIBDEFLATE_INSUFFICIENT_SPACE: the output needed exceeds out_avail;
+ *       (1 to 5 are decided BEFORE any byte of d_out is written; under 5 the
+ *       index, d_results and [1] to [4] are written, so the caller can
+ *       allocate and call again)
+ *       6. the result of the first entry that did not succeed;
+ *       7. LIBDEFLATE_SUCCESS.
+ *   [1] entries (0 under verdicts 1 and 3), [2] the byte offset where the walk
+ *   ended - the zero block, or 512 nb -, [3] bytes of output needed, alignment
+ *   included, [4] flags (LIBDEFLATE_AMD_TAR_EOF, _HAS_L, _HAS_PAX); under
+ *   verdicts 1 to 4 words [2] to [4] are 0 and d_index and d_results are not
+ *   written.
+ *
+ * d_index: NULL, or device room for max_records rows of
+ * LIBDEFLATE_AMD_TAR_WORDS u64; row k of entry k in file order:
+ *   { offset of the entry's own header, name_off, name_len | prefix_len << 32,
+ *     typeflag | name source << 8, data_off, usize, mtime, out_off }
+ * name_off is absolute in the file: the pax value (name source 2), the L data
+ * (1) or the header (0).  prefix_len is non-zero only for a header name with a
+ * ustar prefix, which stands at header + 345.  mtime is the header's field, 0
+ * if it does not parse.  out_off is the exclusive prefix sum of the usizes,
+ * each rounded up to out_align (a power of two in 1 .. 256).  Entry k's bytes
+ * are at d_out + out_off.
+ *
+ * d_results[k] (int32, room for max_records; written for the archive's
+ * entries): 0 or LIBDEFLATE_AMD_TAR_UNSUPPORTED.  A refused entry never
+ * affects its neighbours.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL object or pointer (d_out may be NULL
+ * only with out_avail == 0, d_in only with in_nbytes == 0, d_index always),
+ * max_records == 0 or above 2^28, in_nbytes above 2^36, an out_align that is
+ * not a power of two in 1 .. 256.
+ *
+ * Not covered: GNU sparse entries with extended header blocks, and pax size=
+ * overrides that make the header's size field wrong (both usually break the
+ * chain and end as LIBDEFLATE_BAD_DATA); ignore_zeros; link names and pax
+ * attributes other than the path; files of 2^36 bytes and more; a host-pointer
+ * form.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_tar_extract_batch(struct libdeflate_decompressor *decompressor,
+				 const void *d_in, size_t in_nbytes, size_t max_records,
+				 void *d_out, size_t out_avail, size_t out_align,
+				 uint64_t *d_result, uint64_t *d_index, int32_t *d_results,
+				 void *stream);
+
+/* The index, the per-entry results and the five words alone: everything but
+ * the copy (out_avail counts as unlimited).  The same out_off as the call
+ * above. */
+LIBDEFLATEAPI int
+libdeflate_amd_tar_index_batch(struct libdeflate_decompressor *decompressor,
+			       const void *d_in, size_t in_nbytes, size_t max_records,
+			       size_t out_align, uint64_t *d_result, uint64_t *d_index,
+			       int32_t *d_results, void *stream);
+
+/*
+ * Extract a selection.  index: HOST memory, `entries` rows as
+ * libdeflate_amd_tar_index_batch returned them; sel: HOST memory, n_sel entry
+ * numbers in any order, duplicates allowed.  Only those entries are copied,
+ * back to back in sel order with out_align; out_offsets: NULL, or HOST room for
+ * n_sel + 1 u64 - where selection r starts, and where the last one ends -
+ * filled in before the call returns.  d_results[r] (device, int32): 0, or
+ * LIBDEFLATE_AMD_TAR_UNSUPPORTED for a row of typeflag S, M or D, which takes
+ * no room.  Enqueues on `stream`; the host arrays may be reused when the call
+ * returns.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work: a NULL argument, out_align as
+ * above, a selected row that does not lie inside in_nbytes (header, name,
+ * data_off + usize; data_off must be header + 512), a size of 2^36 or more, a
+ * sel at or above entries, a selection that needs more than out_avail.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_tar_read_batch(struct libdeflate_decompressor *decompressor,
+			      const void *d_in, size_t in_nbytes,
+			      const uint64_t *index, size_t entries,
+			      size_t n_sel, const uint64_t *sel,
+			      void *d_out, size_t out_avail, size_t out_align,
+			      uint64_t *out_offsets, int32_t *d_results, void *stream);
+
+/*
+ * The same checks and arithmetic without a device: ranges (HOST, 2 n_sel u64)
+ * receives (data_off, usize) of every selection - (data_off, 0) for a row of
+ * typeflag S, M or D - and *total_ret (may be NULL) the sum of the lengths.
+ * That is what libdeflate_amd_seek_read_batch takes as `ranges` for the seek
+ * index of the .gz the archive came out of, so a selection of a .tar.gz is
+ * read from the compressed bytes.  The rows are checked against a file of
+ * 2^36 bytes; libdeflate_amd_seek_read_batch checks the ranges against the
+ * stream's own size.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_tar_ranges(const uint64_t *index, size_t entries, size_t n_sel,
+			  const uint64_t *sel, uint64_t *ranges, uint64_t *total_ret);
+
+/*
  * ---- ZIP archives written on the device ----
  *
  * n_entries named byte ranges of one DEVICE buffer -> one ZIP archive in device

@@ -8,6 +8,7 @@ functions take torch CUDA tensors that already live in HBM and only pass
 their device pointers through; torch is plumbing (memory, streams), never
 compute.
 """
+import collections
 import ctypes
 from ctypes import c_size_t, c_void_p
 
@@ -26,6 +27,10 @@ def _buf(b):
         arr = np.frombuffer(b, dtype=np.uint8)
         return arr.ctypes.data_as(c_void_p), arr.size
     raise TypeError(type(b))
+
+
+# what Decompressor.read_targz returns
+TarGz = collections.namedtuple("TarGz", "result nbytes seek_index windows words rows results")
 
 
 class Compressor:
@@ -475,6 +480,97 @@ class Decompressor:
             _stream_ptr(stream)), "zip_read_batch")
         return offs
 
+    def index_tar_batch(self, data, max_records, result, results, index=None, out_align=1,
+                        stream=None, in_nbytes=None):
+        """libdeflate_amd_tar_index_batch: the tar archive in the uint8 torch
+        CUDA tensor `data` (its first in_nbytes bytes) -> result: int64 CUDA
+        tensor of 5 (verdict, entries, the offset where the walk ended, bytes
+        of output needed, flags); results: int32 CUDA tensor of max_records
+        (per-entry results); index: None or an int64 CUDA tensor of 8
+        max_records (rows of header, name_off, name_len | prefix_len << 32,
+        typeflag | name source << 8, data_off, usize, mtime, out_off).
+        max_records bounds entries and extension records together.  Nothing
+        is copied.  Only enqueues."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        check(self._lib.libdeflate_amd_tar_index_batch(
+            self._h, data.data_ptr() if n else None, n, int(max_records), int(out_align),
+            result.data_ptr(), index.data_ptr() if index is not None else None,
+            results.data_ptr(), _stream_ptr(stream)), "tar_index_batch")
+
+    def extract_tar_batch(self, data, max_records, out, result, results, index=None,
+                          out_align=1, stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_tar_extract_batch: every entry of the tar archive in
+        `data` into `out` (out_avail bytes of it, default all), entry k at
+        out_off of row k; result, results and index as in index_tar_batch.
+        Only enqueues on `stream`."""
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_tar_extract_batch(
+            self._h, data.data_ptr() if n else None, n, int(max_records),
+            out.data_ptr() if avail else None, avail, int(out_align), result.data_ptr(),
+            index.data_ptr() if index is not None else None, results.data_ptr(),
+            _stream_ptr(stream)), "tar_extract_batch")
+
+    def read_tar_batch(self, data, index, sel, out, results, out_align=1, stream=None,
+                       in_nbytes=None, out_avail=None):
+        """libdeflate_amd_tar_read_batch: the entries `sel` (host, any order,
+        duplicates allowed) of the archive in the CUDA tensor `data`, back to
+        back into `out` with out_align; index: host rows as index_tar_batch
+        wrote them; results: int32 CUDA tensor, one per selection.  Returns
+        the numpy uint64 offsets (len(sel) + 1) of the selections in `out`.
+        Only enqueues."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.TAR_WORDS)
+        s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+        offs = np.zeros(len(s) + 1, dtype=np.uint64)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_tar_read_batch(
+            self._h, data.data_ptr() if n else None, n, idx.ctypes.data_as(c_void_p), len(idx),
+            len(s), s.ctypes.data_as(c_void_p), out.data_ptr() if avail else None, avail,
+            int(out_align), offs.ctypes.data_as(c_void_p), results.data_ptr(),
+            _stream_ptr(stream)), "tar_read_batch")
+        return offs
+
+    def read_targz(self, data, out, max_records, spacing=1 << 20, max_points=1024,
+                   in_nbytes=None, out_avail=None, stream=None):
+        """A .tar.gz in the CUDA tensor `data`: decompress_large_index("gzip")
+        into `out`, then index_tar_batch on the decoded bytes -> TarGz(result,
+        nbytes, seek_index, windows, words, rows, results): the gzip result
+        and the archive's size, the seek index and its windows, and on the
+        host the five words, the index rows (numpy uint64, entries x 8) and
+        the per-entry results of the tar index (None unless result is 0).
+        Any selection is then read from the compressed bytes with
+        read_targz_entries.  Blocks."""
+        import torch
+        r, _, nbytes, seek_index, windows = self.decompress_large_index(
+            "gzip", data, out, spacing, max_points, in_nbytes=in_nbytes, out_avail=out_avail,
+            stream=stream)
+        if r != 0:
+            return TarGz(r, nbytes, None, None, None, None, None)
+        m = int(max_records)
+        res = torch.zeros(binding.TAR_RESULT_WORDS, dtype=torch.int64, device=data.device)
+        idx = torch.zeros(binding.TAR_WORDS * m, dtype=torch.int64, device=data.device)
+        per = torch.zeros(m, dtype=torch.int32, device=data.device)
+        self.index_tar_batch(out, m, res, per, index=idx, stream=stream, in_nbytes=nbytes)
+        words = [int(x) for x in res.cpu().tolist()]    # (waits for the stream's work)
+        known = words[0] not in (binding.BAD_DATA, binding.TAR_MORE_RECORDS,
+                                 binding.TAR_MORE_CANDIDATES)
+        entries = words[1] if known else 0
+        rows = idx.cpu().numpy().astype(np.uint64).reshape(-1, binding.TAR_WORDS)[:entries]
+        return TarGz(r, nbytes, seek_index, windows, words, rows, per.cpu().numpy()[:entries])
+
+    def read_targz_entries(self, data, targz, sel, out, results, stream=None, in_nbytes=None,
+                           out_avail=None):
+        """The entries `sel` of the .tar.gz in `data` out of its compressed
+        bytes: tar_ranges of the rows read_targz returned, then
+        seek_read_batch through its seek index, back to back into `out`;
+        results: int32 CUDA tensor, one per selection.  Returns the numpy
+        uint64 offsets (len(sel) + 1) in `out`.  Only enqueues."""
+        rng, _ = tar_ranges(targz.rows, sel)
+        self.seek_read_batch(data, targz.seek_index, targz.windows, rng, out, results,
+                             stream=stream, in_nbytes=in_nbytes, out_avail=out_avail)
+        return np.concatenate(([0], np.cumsum(rng[:, 1]))).astype(np.uint64)
+
     def read_bgzf_batch(self, data, index, ranges, out, results, voffsets=False, stream=None,
                         in_nbytes=None, out_avail=None):
         """libdeflate_amd_bgzf_read_batch: `ranges` (host, rows of (begin,
@@ -789,6 +885,48 @@ def zip_entry_names(data, result, index):
         raw = cd[rec + 46 - cd_off:rec + 46 - cd_off + name_len]
         names.append(raw.decode("utf-8" if (mf >> 16) & 0x800 else "cp437"))
     return names
+
+
+def tar_entry_names(data, result, index):
+    """The entries' names of the tar archive in the CUDA tensor `data`, from
+    the result words and index rows of index_tar_batch / extract_tar_batch
+    (CUDA tensors or host arrays): a ustar prefix, '/' and the name joined,
+    the pax value or the L data as they stand.  The name bytes are gathered on
+    the device and fetched once; they decode as UTF-8 with surrogateescape, as
+    tarfile reads them."""
+    import torch
+    words = [int(x) for x in (result.cpu().tolist() if hasattr(result, "cpu") else result)]
+    rows = index.cpu().numpy() if hasattr(index, "cpu") else np.asarray(index)
+    rows = rows.reshape(-1, binding.TAR_WORDS)[:words[1]].astype(np.int64)
+    if not len(rows):
+        return []
+    name_len, prefix_len = rows[:, 2] & 0xFFFFFFFF, rows[:, 2] >> 32
+    starts = np.stack([rows[:, 0] + 345, rows[:, 1]], axis=1).reshape(-1)
+    lens = np.stack([prefix_len, name_len], axis=1).reshape(-1)
+    ends = np.cumsum(lens)
+    where = np.repeat(starts - (ends - lens), lens) + np.arange(ends[-1])
+    raw = data[torch.from_numpy(where).to(data.device)].cpu().numpy().tobytes() if ends[-1] else b""
+    names = []
+    for k in range(len(rows)):
+        p0 = int(ends[2 * k] - lens[2 * k])
+        prefix, name = raw[p0:int(ends[2 * k])], raw[int(ends[2 * k]):int(ends[2 * k + 1])]
+        names.append(((prefix + b"/" if prefix else b"") + name).decode("utf-8", "surrogateescape"))
+    return names
+
+
+def tar_ranges(index, sel):
+    """libdeflate_amd_tar_ranges: (data_off, usize) of the entries `sel` of
+    the host index rows `index` -> (numpy uint64 rows of 2, total bytes): what
+    seek_read_batch takes as `ranges` for the .gz the archive came out of.  No
+    device is touched."""
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.TAR_WORDS)
+    s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+    rng = np.zeros((len(s), 2), dtype=np.uint64)
+    total = ctypes.c_uint64(0)
+    check(binding.load().libdeflate_amd_tar_ranges(
+        idx.ctypes.data_as(c_void_p), len(idx), len(s), s.ctypes.data_as(c_void_p),
+        rng.ctypes.data_as(c_void_p), ctypes.byref(total)), "tar_ranges")
+    return rng, total.value
 
 
 def _stream_ptr(stream):

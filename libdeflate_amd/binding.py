@@ -35,6 +35,12 @@ GZM_NAME_MAX = 65536    # bytes of FNAME + FCOMMENT the member reader accepts
 # the flag bit of result[4]
 ZIP_MORE_ENTRIES, ZIP_MORE_CANDIDATES, ZIP_UNSUPPORTED = 16, 17, 18
 ZIP_RESULT_WORDS, ZIP_WORDS, ZIP_SLACK, ZIP_ZIP64 = 5, 8, 1024, 1
+# the tar reader: result[0] beyond enum libdeflate_result, a per-entry result,
+# the words of a result, u64 per index row, candidate room beyond max_records,
+# the flag bits of result[4]
+TAR_MORE_RECORDS, TAR_MORE_CANDIDATES, TAR_UNSUPPORTED = 16, 17, 18
+TAR_RESULT_WORDS, TAR_WORDS, TAR_SLACK = 5, 8, 1024
+TAR_EOF, TAR_HAS_L, TAR_HAS_PAX = 1, 2, 4
 # the ZIP writer: the two flags, the words of its result
 ZIP_STORE, ZIP_FORCE_ZIP64, ZIPW_RESULT_WORDS = 1, 2, 4
 # the writer of concatenated gzip members: the words of its result, the longest
@@ -91,6 +97,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_gzip_members_compress_bound", "libdeflate_amd_gzip_members_compress_batch",
     "libdeflate_amd_decompress_prefix_batch", "libdeflate_amd_decompress_prefix_batch_dict",
     "libdeflate_amd_decompress_prefix", "libdeflate_amd_gzip_members_peek_batch",
+    "libdeflate_amd_tar_index_batch", "libdeflate_amd_tar_extract_batch",
+    "libdeflate_amd_tar_read_batch", "libdeflate_amd_tar_ranges",
 ]
 
 _lib = None
@@ -210,6 +218,12 @@ def load():
     sig("libdeflate_amd_zip_index_batch", c_int, P, P, SZ, SZ, SZ, P, P, P, P)
     sig("libdeflate_amd_zip_decompress_batch", c_int, P, P, SZ, SZ, P, SZ, SZ, P, P, P, P)
     sig("libdeflate_amd_zip_read_batch", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, P, P, P)
+    # a tar archive: the index alone, device file -> every entry's bytes, a
+    # selection through host index rows, and the ranges of a selection (host)
+    sig("libdeflate_amd_tar_index_batch", c_int, P, P, SZ, SZ, SZ, P, P, P, P)
+    sig("libdeflate_amd_tar_extract_batch", c_int, P, P, SZ, SZ, P, SZ, SZ, P, P, P, P)
+    sig("libdeflate_amd_tar_read_batch", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, P, P, P)
+    sig("libdeflate_amd_tar_ranges", c_int, P, SZ, SZ, P, P, P)
     # a ZIP archive written: the exact bound (host arithmetic), and named ranges
     # of a device buffer -> archive (names, offsets and sizes on the host)
     sig("libdeflate_amd_zip_compress_bound", SZ, SZ, P, P, c_uint32)

@@ -99,6 +99,7 @@ struct EnvCfg {
 	int devices = 1;		/* LDA_DEVICES: GPUs a host-pointer batch is spread over (N, or "all" = -1) */
 	bool no_selfcheck = false;	/* LDA_NO_SELFCHECK: skip the per-device hardware self-check */
 	bool bgzf_serial = false;	/* LDA_BGZF_SERIAL: the BGZF reader finds the members by the serial walk */
+	bool tar_serial = false;	/* LDA_TAR_SERIAL: the tar reader finds the records by the serial walk */
 	bool fanout_oversub = false;	/* LDA_FANOUT_OVERSUB: more shards than visible devices (a test aid: several shards share a GPU) */
 };
 const EnvCfg &env_cfg();

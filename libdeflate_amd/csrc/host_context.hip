@@ -97,6 +97,7 @@ static EnvCfg read_env()
 	c.fanout_oversub = getenv("LDA_FANOUT_OVERSUB") != nullptr;
 	c.no_selfcheck = getenv("LDA_NO_SELFCHECK") != nullptr;
 	c.bgzf_serial = getenv("LDA_BGZF_SERIAL") != nullptr;
+	c.tar_serial = getenv("LDA_TAR_SERIAL") != nullptr;
 	return c;
 }
 

@@ -376,6 +376,60 @@ lda_zip_rfinal_kernel(uint64_t n_sel, const uint64_t *meta, const uint64_t *in_n
 		      const int32_t *batch_res, const uint64_t *actual_in, const uint32_t *crcs,
 		      int32_t *results);
 
+/* tar_kernels.hip: a tar archive read from device memory (host_tar.hip).  The
+ * candidates are (position, size) in blocks of 512 bytes, and the chain among
+ * them is found by lda_bgzf_jump_kernel / _top_ / _members_ above, launched
+ * with the block count as the end; the state words LDA_BR_CHAIN and
+ * LDA_BR_MEMBERS are theirs, the other two this reader's.  Copies of the
+ * header's constants (static_assert in host_tar.hip) */
+#define LDA_TAR_MORE_RECORDS 16		/* LIBDEFLATE_AMD_TAR_MORE_RECORDS */
+#define LDA_TAR_MORE_CANDIDATES 17	/* LIBDEFLATE_AMD_TAR_MORE_CANDIDATES */
+#define LDA_TAR_UNSUPPORTED 18		/* LIBDEFLATE_AMD_TAR_UNSUPPORTED */
+#define LDA_TAR_RESULT_WORDS 5
+#define LDA_TAR_WORDS 8
+#define LDA_TAR_EOF 1
+#define LDA_TAR_HAS_L 2
+#define LDA_TAR_HAS_PAX 4
+#define LDA_TAR_NAME_HEADER 0	/* row word 3 >> 8: where the name stands */
+#define LDA_TAR_NAME_L 1
+#define LDA_TAR_NAME_PAX 2
+#define LDA_TAR_EXT_MAX 8	/* extension records in front of one entry */
+#define LDA_TAR_EXT_BYTES 1048576	/* the largest L or x record that is read */
+#define LDA_TAR_SCAN_BLOCKS 32	/* blocks per scan workgroup: LDA_BR_SCAN_WG / 512 */
+#define LDA_TAR_COPY_TILE 65536	/* bytes per tile of the gather copy */
+#define LDA_TAR_FLAGS 2		/* state word: LDA_TAR_HAS_L | LDA_TAR_HAS_PAX */
+#define LDA_TAR_ZERO0 3		/* state word: block 0 is all zero, an empty archive */
+#define LDA_TS_END 0		/* ts[]: where the last record ends by its own size, in blocks */
+#define LDA_TS_WORDS 2
+extern "C" __global__ void
+lda_tar_scan_kernel(const uint8_t *in, uint64_t nb, uint64_t *counts, const uint64_t *offsets,
+		    const uint64_t *block_sums, uint64_t cap, uint64_t *cand_pos,
+		    uint32_t *cand_size, uint32_t *state);
+extern "C" __global__ void
+lda_tar_walk_kernel(const uint8_t *in, uint64_t nb, uint64_t max_records, uint64_t *rec_pos,
+		    uint64_t *rec_n, uint32_t *state, uint64_t *k_out);
+extern "C" __global__ void
+lda_tar_resolve_kernel(const uint8_t *in, uint64_t nb, uint64_t max_records, uint64_t align_mask,
+		       uint32_t *state, const uint64_t *k_at, uint64_t cap,
+		       const uint64_t *rec_pos, uint64_t *ts, uint64_t *tmp, int32_t *res,
+		       uint64_t *flag, uint64_t *room);
+extern "C" __global__ void
+lda_tar_desc_kernel(uint64_t max_records, uint64_t out_avail, const uint32_t *state,
+		    const uint64_t *k_at, uint64_t cap, const uint64_t *tmp, const int32_t *res,
+		    const uint64_t *flag, const uint64_t *f_off, const uint64_t *f_sums,
+		    const uint64_t *r_off, const uint64_t *r_sums, uint64_t *rows,
+		    int32_t *results, uint64_t *cp_src, uint64_t *cp_dst, uint64_t *cp_len,
+		    uint64_t *tiles);
+extern "C" __global__ void
+lda_tar_copy_kernel(uint64_t n_chunks, const uint64_t *t_off, const uint64_t *t_sums,
+		    const uint64_t *total_at, const uint64_t *src, const uint64_t *dst,
+		    const uint64_t *len, const uint8_t *in, uint8_t *out);
+extern "C" __global__ void
+lda_tar_final_kernel(uint64_t nb, uint64_t max_records, uint64_t out_avail,
+		     const uint32_t *state, const uint64_t *k_at, uint64_t cap,
+		     const uint64_t *ts, const uint64_t *entries_at, const uint64_t *total_at,
+		     const int32_t *results, uint64_t *result);
+
 /* zip_write_kernels.hip: a ZIP archive assembled in device memory
  * (host_zip_write.hip, zip_write_plan.h) */
 extern "C" __global__ void
