@@ -1611,6 +1611,118 @@ libdeflate_amd_gzip_members_compress_batch(struct libdeflate_compressor *compres
 					   unsigned flags, void *stream);
 
 /*
+ * ---- tar archives written on the device ----
+ *
+ * n_entries named byte ranges of one DEVICE buffer -> one tar archive in device
+ * memory (a WebDataset shard, a checkpoint bundle), or that archive compressed
+ * into one gzip / zlib / DEFLATE stream (.tar.gz): what
+ * libdeflate_amd_tar_extract_batch reads.  The conventions are those of
+ * libdeflate_amd_zip_compress_batch above: the calls enqueue on `stream` and
+ * return, the plan goes up through the object's pinned block, scratch belongs
+ * to the object (the ZIP writer's), names / name_offsets (n_entries + 1,
+ * ascending), in_offsets and in_nbytes are HOST arrays that may be reused when
+ * the call returns, entry k is bytes [in_offsets[k], + in_nbytes[k]) of d_in,
+ * entries may overlap one another, d_out must not overlap d_in and may have
+ * any alignment.
+ *
+ * A tar archive's layout follows from the names and sizes alone, so the host
+ * knows every offset and the exact size before anything runs: nothing comes
+ * back from the device, there is no verdict word, and one kernel writes every
+ * byte of the archive exactly once - headers, data and all padding, d_out need
+ * not be clear.
+ *
+ * THE ARCHIVE, in blocks of 512 bytes:
+ *   Per entry one header block, the entry's bytes, and zeros up to the next
+ *   block boundary.  The header: name at 0 (100 bytes, NUL-padded, not
+ *   terminated when it fills the field); mode "0000644\0" at 100; uid and gid
+ *   "0000000\0" at 108 and 116; the size at 124 and mtime at 136, each 11
+ *   octal digits and a NUL; the checksum at 148, six octal digits, a NUL and a
+ *   space - the sum of the block's 512 bytes with these eight counted as
+ *   spaces -; typeflag '0' at 156; linkname (100 bytes at 157) NUL; the magic
+ *   "ustar\0" and version "00" at 257; uname, gname, devmajor, devminor and
+ *   prefix, the rest of the block, NUL.  The ustar prefix split is never used.
+ *
+ *   A name of more than 100 characters (names are UTF-8), or with a byte >=
+ *   0x80, has a pax extension record in front of the entry's header: a header
+ *   block as above with the name "././@PaxHeader", mode "0000000\0", mtime 0,
+ *   typeflag 'x' and the length of the pax data as its size; then the pax
+ *   data, the one record "%d path=%s\n" - the decimal is the record's own
+ *   length, itself included - zero-padded to a block boundary.  The entry's own
+ *   header then carries the first 100 characters of the name with every
+ *   character that is not ASCII replaced by one '?'.
+ *
+ *   Behind the last entry two zero blocks, then zeros up to a multiple of
+ *   10 240 bytes.  n_entries == 0 writes 10 240 zero bytes.
+ * Byte for byte this is what Python's tarfile writes in its default (pax)
+ * format for regular files with size and an integer mtime set and every other
+ * attribute at its default.
+ *
+ * libdeflate_amd_tar_write_size() is that archive's exact size, arithmetic on
+ * the host arrays without a device (0, with the reason in
+ * libdeflate_amd_last_error(), for a NULL array and for every count, name,
+ * entry size and archive size that the calls below refuse: one check serves
+ * all three).  libdeflate_amd_tar_write_batch writes
+ * every byte of d_out[0 .. size) and no byte at or past d_out + size.
+ *
+ * index: NULL, or HOST room for n_entries rows of LIBDEFLATE_AMD_TAR_WORDS u64,
+ * filled in before the call returns: exactly the rows
+ * libdeflate_amd_tar_index_batch returns for the written archive with
+ * out_align 1 - name source 0 (the header) or 2 (the pax value), name_off
+ * absolute in the archive, out_off the exclusive prefix sum of the sizes - so
+ * they go straight into libdeflate_amd_tar_read_batch and
+ * libdeflate_amd_tar_ranges, which take host rows.
+ *
+ * libdeflate_amd_targz_compress_batch writes the archive into the object's
+ * scratch and enqueues libdeflate_amd_compress_large_batch on it: d_out and
+ * d_out_nbytes[0] (device memory) get exactly what that call gives for the
+ * archive's bytes at the object's level - d_out_nbytes[0] = 0 and no byte
+ * written when the stream does not fit out_avail.  format is
+ * LIBDEFLATE_AMD_GZIP, _ZLIB or _DEFLATE;
+ * libdeflate_gzip_compress_bound(libdeflate_amd_tar_write_size(...)) is room
+ * enough.  The index rows are the archive's: with the seek index of
+ * libdeflate_amd_decompress_large_index and libdeflate_amd_tar_ranges a
+ * selection is read from the compressed bytes.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL object or pointer (d_in may be NULL with
+ * in_avail == 0, the host arrays with n_entries == 0, index always), unknown
+ * flags (none is defined yet), n_entries above 2^28, decreasing name_offsets, a
+ * name that is empty, longer than 65 535 bytes, holds a 0 byte or is not valid
+ * UTF-8, an entry of 8^11 bytes (8 GiB) or more - it would need a pax size=
+ * record, which the reader refuses -, mtime of 8^11 or more, an entry that
+ * does not lie inside in_avail, out_avail below the archive's size, an archive
+ * above 2^40 - 65 536 bytes (1 TiB: what one launch of the kernel can hold);
+ * for the .tar.gz call what
+ * libdeflate_amd_compress_large_batch refuses of format and out_avail instead
+ * of the room for the archive.
+ *
+ * Limits: regular files only, one mtime and mode 0644 per call; no
+ * directories, links or devices; no uid / gid / uname / gname; no GNU or
+ * ustar-prefix format; no appending to an archive; no host-pointer form.  The
+ * .tar.gz call's scratch holds the whole archive.
+ */
+LIBDEFLATEAPI size_t
+libdeflate_amd_tar_write_size(size_t n_entries, const uint64_t *name_offsets,
+			      const void *names, const uint64_t *in_nbytes);
+
+LIBDEFLATEAPI int
+libdeflate_amd_tar_write_batch(struct libdeflate_compressor *compressor,
+			       size_t n_entries, const void *names,
+			       const uint64_t *name_offsets, const void *d_in, size_t in_avail,
+			       const uint64_t *in_offsets, const uint64_t *in_nbytes,
+			       void *d_out, size_t out_avail, uint64_t *index,
+			       uint64_t mtime, unsigned flags, void *stream);
+
+LIBDEFLATEAPI int
+libdeflate_amd_targz_compress_batch(struct libdeflate_compressor *compressor, int format,
+				    size_t n_entries, const void *names,
+				    const uint64_t *name_offsets, const void *d_in,
+				    size_t in_avail, const uint64_t *in_offsets,
+				    const uint64_t *in_nbytes, void *d_out, size_t out_avail,
+				    uint64_t *d_out_nbytes, uint64_t *index, uint64_t mtime,
+				    unsigned flags, void *stream);
+
+/*
  * Prefix decompress: the first bytes of every stream of a batch - zlib's
  * inflate() with avail_out below the stream's size, Python's
  * decompressobj().decompress(data, max_length) - which the whole-buffer calls

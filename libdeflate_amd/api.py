@@ -230,6 +230,74 @@ class Compressor:
             _stream_ptr(stream)), "gzip_members_compress_batch")
         return out, result, idx
 
+    def tar_write_size(self, names, sizes):
+        """libdeflate_amd_tar_write_size: the exact size of the tar archive
+        write_tar_batch writes for entries of these names (str or bytes, or
+        the (blob, offsets) pair of _zip_names()) and sizes.  No device is
+        touched."""
+        blob, offs = self._zip_names(names)
+        sz = np.ascontiguousarray(sizes, dtype=np.uint64)
+        assert sz.size == offs.size - 1
+        size = self._lib.libdeflate_amd_tar_write_size(
+            sz.size, offs.ctypes.data_as(c_void_p), blob.ctypes.data_as(c_void_p),
+            sz.ctypes.data_as(c_void_p))
+        if not size:
+            raise ValueError(binding.last_error())
+        return size
+
+    def _tar_entries(self, names, data, in_offsets, in_nbytes, index, in_avail):
+        blob, offs = self._zip_names(names)
+        ino = np.ascontiguousarray(in_offsets, dtype=np.uint64)
+        inn = np.ascontiguousarray(in_nbytes, dtype=np.uint64)
+        n = offs.size - 1
+        assert ino.size == n and inn.size == n
+        rows = np.zeros((n, binding.TAR_WORDS), dtype=np.uint64) if index else None
+        avail = data.numel() if in_avail is None else int(in_avail)
+        args = (n, blob.ctypes.data_as(c_void_p), offs.ctypes.data_as(c_void_p),
+                data.data_ptr() if avail else None, avail, ino.ctypes.data_as(c_void_p),
+                inn.ctypes.data_as(c_void_p))
+        # (the arrays stay alive with the tuple until the call has returned)
+        return args, (blob, offs, ino, inn), rows
+
+    def write_tar_batch(self, names, data, in_offsets, in_nbytes, out, index=True, mtime=0,
+                        flags=0, stream=None, in_avail=None, out_avail=None):
+        """libdeflate_amd_tar_write_batch: a tar archive (pax format, byte for
+        byte tarfile's) of the entries data[in_offsets[k] : + in_nbytes[k]]
+        (data: uint8 torch CUDA tensor, its first in_avail bytes; names,
+        offsets and sizes: host lists or arrays, names also as the (blob,
+        offsets) pair of _zip_names()) into out[:tar_write_size()] (out_avail
+        bytes of `out` are there, default all).  Returns the index rows
+        (numpy uint64, entries x TAR_WORDS: what index_tar_batch returns for
+        the archive, ready for read_tar_batch and tar_ranges), or None with
+        index=False.  Only enqueues on `stream`."""
+        args, keep, rows = self._tar_entries(names, data, in_offsets, in_nbytes, index, in_avail)
+        check(self._lib.libdeflate_amd_tar_write_batch(
+            self._h, *args, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail),
+            rows.ctypes.data_as(c_void_p) if rows is not None else None, int(mtime),
+            int(flags), _stream_ptr(stream)), "tar_write_batch")
+        del keep
+        return rows
+
+    def compress_targz_batch(self, fmt, names, data, in_offsets, in_nbytes, out, out_nbytes,
+                             index=True, mtime=0, flags=0, stream=None, in_avail=None,
+                             out_avail=None):
+        """libdeflate_amd_targz_compress_batch: the archive write_tar_batch
+        writes for these entries, compressed into ONE "gzip", "zlib" or
+        "deflate" stream in `out` (out_avail bytes of it, default all;
+        bound(fmt, tar_write_size()) is room enough) - byte for byte what
+        compress_large_batch gives for the archive.  out_nbytes: int64 CUDA
+        tensor, [0] gets the stream's size (0: does not fit).  Returns the
+        archive's index rows as write_tar_batch does.  Only enqueues."""
+        args, keep, rows = self._tar_entries(names, data, in_offsets, in_nbytes, index, in_avail)
+        check(self._lib.libdeflate_amd_targz_compress_batch(
+            self._h, FORMATS[fmt], *args, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), out_nbytes.data_ptr(),
+            rows.ctypes.data_as(c_void_p) if rows is not None else None, int(mtime),
+            int(flags), _stream_ptr(stream)), "targz_compress_batch")
+        del keep
+        return rows
+
     def compress(self, fmt, data, out_avail=None):
         """Returns the compressed bytes, or None when the reference API would
         return 0 (does not fit in out_avail)."""

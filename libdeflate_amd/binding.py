@@ -99,6 +99,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_decompress_prefix", "libdeflate_amd_gzip_members_peek_batch",
     "libdeflate_amd_tar_index_batch", "libdeflate_amd_tar_extract_batch",
     "libdeflate_amd_tar_read_batch", "libdeflate_amd_tar_ranges",
+    "libdeflate_amd_tar_write_size", "libdeflate_amd_tar_write_batch",
+    "libdeflate_amd_targz_compress_batch",
 ]
 
 _lib = None
@@ -229,6 +231,14 @@ def load():
     sig("libdeflate_amd_zip_compress_bound", SZ, SZ, P, P, c_uint32)
     sig("libdeflate_amd_zip_compress_batch", c_int, P, SZ, P, P, P, SZ, P, P, P, SZ, P, P,
         c_uint32, c_uint32, P)
+    # a tar archive written: the exact size (host arithmetic), named ranges of a
+    # device buffer -> archive, and -> one compressed stream of that archive
+    # (names, offsets and sizes on the host; the index rows come back on the host)
+    sig("libdeflate_amd_tar_write_size", SZ, SZ, P, P, P)
+    sig("libdeflate_amd_tar_write_batch", c_int, P, SZ, P, P, P, SZ, P, P, P, SZ, P,
+        c_uint64, c_uint32, P)
+    sig("libdeflate_amd_targz_compress_batch", c_int, P, c_int, SZ, P, P, P, SZ, P, P, P, SZ,
+        P, P, c_uint64, c_uint32, P)
     # a file of gzip members written: the bound (host arithmetic), and ranges of
     # a device buffer -> file (names, offsets and sizes on the host)
     sig("libdeflate_amd_gzip_members_compress_bound", SZ, P, SZ, P, P)

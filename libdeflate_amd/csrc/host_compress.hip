@@ -968,28 +968,86 @@ libdeflate_amd_compress_dict(struct libdeflate_compressor *c, int format,
  * between them is done by the kernels of large_kernels.hip: the descriptors,
  * the checksum of the whole buffer from the pieces', header, footer, size.
  * c->large: [7 u64 rows][scan offsets][seg_info u32][sums u32][slots].
+ * The check and the body are apart for libdeflate_amd_targz_compress_batch
+ * (host_tar_write.hip), whose input is an archive it writes first.
  */
-extern "C" LIBDEFLATEAPI int
-libdeflate_amd_compress_large_batch(struct libdeflate_compressor *c, int format,
-				    const void *d_in, size_t in_nbytes, void *d_out,
-				    size_t out_avail, uint64_t *d_out_nbytes, void *stream)
+bool lda::compress_large_args_ok(const char *what, const struct libdeflate_compressor *c,
+				 int format, const void *d_in, size_t in_nbytes, const void *d_out,
+				 size_t out_avail, const uint64_t *d_out_nbytes)
 {
-	const char *what = "compress_large_batch";
 	if (!c || (!d_in && in_nbytes) || !d_out || !d_out_nbytes) {
 		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
+		return false;
 	}
 	if (format != LIBDEFLATE_AMD_DEFLATE && format != LIBDEFLATE_AMD_ZLIB &&
 	    format != LIBDEFLATE_AMD_GZIP) {
 		set_error("%s: format %d is not DEFLATE, zlib or gzip", what, format);
-		return LIBDEFLATE_AMD_BAD_ARG;
+		return false;
 	}
 	const uint32_t hdr = format == LIBDEFLATE_AMD_GZIP ? 10 : format == LIBDEFLATE_AMD_ZLIB ? 2 : 0;
 	const uint32_t ftr = format == LIBDEFLATE_AMD_GZIP ? 8 : format == LIBDEFLATE_AMD_ZLIB ? 4 : 0;
 	if (out_avail <= hdr + ftr) {
 		set_error("%s: out_avail %zu cannot hold the container and a byte", what, out_avail);
-		return LIBDEFLATE_AMD_BAD_ARG;
+		return false;
 	}
+	return true;
+}
+
+extern "C" LIBDEFLATEAPI int
+libdeflate_amd_compress_large_batch(struct libdeflate_compressor *c, int format,
+				    const void *d_in, size_t in_nbytes, void *d_out,
+				    size_t out_avail, uint64_t *d_out_nbytes, void *stream)
+{
+	if (!compress_large_args_ok("compress_large_batch", c, format, d_in, in_nbytes, d_out,
+				    out_avail, d_out_nbytes))
+		return LIBDEFLATE_AMD_BAD_ARG;
+	return compress_large_enqueue(c, format, d_in, in_nbytes, d_out, out_avail, d_out_nbytes,
+				      stream);
+}
+
+/* the scratch of a stream of n bytes: where the parts of c->large lie (one
+ * chunk: its four descriptor words alone) and what the kernels take of
+ * c->scratch */
+struct large_layout {
+	bool segmented;
+	size_t S, nseg, seg_bound, slot, per_slice, cmp_at, seg_at, slots_at;
+	size_t large_bytes, kernel_bytes;
+};
+
+static large_layout large_layout_of(struct libdeflate_compressor *c, size_t n)
+{
+	large_layout l = {};
+	l.segmented = lda_large_segmented(n, c->level, env_cfg().no_segments);
+	if (!l.segmented) {
+		l.large_bytes = 4 * 8;
+		l.kernel_bytes = plan_batch(c, 1, n, false, false).total;
+		return l;
+	}
+	l.S = (size_t)lda_large_seg_bytes(n, env_cfg().seg_bytes);
+	l.nseg = (n + l.S - 1) / l.S;
+	l.seg_bound = large_seg_bound(l.S);
+	l.slot = large_slot(c, l.S);
+	l.per_slice = (size_t)lda_large_per_slice(l.S);
+	l.cmp_at = 7 * 8 * l.nseg;
+	l.seg_at = l.cmp_at + 8 * libdeflate_amd_compact_offsets_len(l.nseg);
+	l.slots_at = align_up(l.seg_at + 8 * l.nseg, 256);
+	l.large_bytes = l.slots_at + l.nseg * l.slot;
+	l.kernel_bytes = plan_batch(c, std::min(l.per_slice, l.nseg), l.seg_bound, true, false).total;
+	return l;
+}
+
+bool lda::compress_large_reserve(struct libdeflate_compressor *c, size_t in_nbytes)
+{
+	const large_layout l = large_layout_of(c, in_nbytes);
+	return c->large.reserve(l.large_bytes) && c->scratch.reserve(l.kernel_bytes);
+}
+
+int lda::compress_large_enqueue(struct libdeflate_compressor *c, int format, const void *d_in,
+				size_t in_nbytes, void *d_out, size_t out_avail,
+				uint64_t *d_out_nbytes, void *stream)
+{
+	const uint32_t hdr = format == LIBDEFLATE_AMD_GZIP ? 10 : format == LIBDEFLATE_AMD_ZLIB ? 2 : 0;
+	const uint32_t ftr = format == LIBDEFLATE_AMD_GZIP ? 8 : format == LIBDEFLATE_AMD_ZLIB ? 4 : 0;
 	DeviceGuard on(c->device);
 	if (!on.ok())
 		return LIBDEFLATE_AMD_NO_DEVICE;
@@ -998,12 +1056,13 @@ libdeflate_amd_compress_large_batch(struct libdeflate_compressor *c, int format,
 		return LIBDEFLATE_AMD_NO_DEVICE;
 	hipStream_t st = (hipStream_t)stream;
 	const size_t n = in_nbytes;
+	const large_layout l = large_layout_of(c, n);
 
-	if (!lda_large_segmented(n, c->level, env_cfg().no_segments)) {
+	if (!l.segmented) {
 		/* one chunk of the ordinary batch, straight into d_out, its size
 		 * straight into d_out_nbytes (compress_batch_host_body() gives the
 		 * kernels the same bound) */
-		uint64_t *rows = (uint64_t *)c->large.reserve(4 * 8);
+		uint64_t *rows = (uint64_t *)c->large.reserve(l.large_bytes);
 		if (!rows)
 			return LIBDEFLATE_AMD_OOM;
 		hipLaunchKernelGGL(lda_large_one_desc_kernel, dim3(1), dim3(64), 0, st, (uint64_t)n,
@@ -1013,18 +1072,13 @@ libdeflate_amd_compress_large_batch(struct libdeflate_compressor *c, int format,
 					   rows + 1, d_out, rows + 2, rows + 3, d_out_nbytes, stream,
 					   NULL, n);
 	}
-	const size_t S = (size_t)lda_large_seg_bytes(n, env_cfg().seg_bytes);
-	const size_t nseg = (n + S - 1) / S;
-	const size_t seg_bound = large_seg_bound(S), slot = large_slot(c, S);
-	const size_t per_slice = (size_t)lda_large_per_slice(S);
-	const size_t cmp_at = 7 * 8 * nseg;
-	const size_t seg_at = cmp_at + 8 * libdeflate_amd_compact_offsets_len(nseg);
-	const size_t slots_at = align_up(seg_at + 8 * nseg, 256);
+	const size_t S = l.S, nseg = l.nseg, seg_bound = l.seg_bound, slot = l.slot;
+	const size_t per_slice = l.per_slice, cmp_at = l.cmp_at, seg_at = l.seg_at;
+	const size_t slots_at = l.slots_at;
 	/* all of the call's scratch before anything is queued: growing frees
 	 * memory (and waits for the device) */
-	uint8_t *ws = (uint8_t *)c->large.reserve(slots_at + nseg * slot);
-	if (!ws || !c->scratch.reserve(plan_batch(c, std::min(per_slice, nseg), seg_bound, true,
-						  false).total))
+	uint8_t *ws = (uint8_t *)c->large.reserve(l.large_bytes);
+	if (!ws || !c->scratch.reserve(l.kernel_bytes))
 		return LIBDEFLATE_AMD_OOM;
 	uint64_t *rows = (uint64_t *)ws, *out_n = rows + 4 * nseg, *cmp = (uint64_t *)(ws + cmp_at);
 	uint32_t *d_seg = (uint32_t *)(ws + seg_at), *d_sums = d_seg + nseg;

@@ -125,6 +125,20 @@ size_t compress_pieces_scratch(const struct libdeflate_compressor *c, size_t n, 
 			       bool seg);
 size_t compress_prime_window(void);
 
+/* host_compress.hip, for the tar writer (host_tar_write.hip): what
+ * libdeflate_amd_compress_large_batch refuses (false, with the error set under
+ * the name `what`), and what it enqueues once its arguments have passed */
+bool compress_large_args_ok(const char *what, const struct libdeflate_compressor *c, int format,
+			    const void *d_in, size_t in_nbytes, const void *d_out, size_t out_avail,
+			    const uint64_t *d_out_nbytes);
+/* the scratch that compress_large_enqueue() of in_nbytes bytes takes of the
+ * object, reserved ahead: a caller that queues work of its own in front reserves
+ * first, because growing frees memory and waits for the device */
+bool compress_large_reserve(struct libdeflate_compressor *c, size_t in_nbytes);
+int compress_large_enqueue(struct libdeflate_compressor *c, int format, const void *d_in,
+			   size_t in_nbytes, void *d_out, size_t out_avail,
+			   uint64_t *d_out_nbytes, void *stream);
+
 /* host_decompress.hip, for the prefix batch (host_prefix.hip), which launches
  * the wave kernel's geometry: dynamic LDS of a wave, waves per CU (LDS and
  * LDA_INFLATE_WAVES_PER_CU), and the bytes of d->tokens for a batch of n

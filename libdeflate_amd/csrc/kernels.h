@@ -476,6 +476,21 @@ extern "C" __global__ void
 lda_gzmw_final_kernel(uint64_t n, uint64_t usize_total, uint64_t out_avail,
 		      const uint64_t *total_at, uint64_t *result, uint64_t *index);
 
+/* tar_write_kernels.hip: a tar archive written into device memory from the
+ * rows of tar_write_plan.h (host_tar_write.hip), one workgroup per tile */
+#define LDA_TARW_TILE 65536	/* bytes of the archive per tile */
+#define LDA_TARW_E_OFF 0	/* the words of an entry's row: TARW_E_* of tar_write_plan.h */
+#define LDA_TARW_E_PAX 1
+#define LDA_TARW_E_NAME_OFF 2
+#define LDA_TARW_E_NAME_LEN 3
+#define LDA_TARW_E_SRC 4
+#define LDA_TARW_E_SIZE 5
+#define LDA_TARW_ECOLS 6
+extern "C" __global__ void
+lda_tarw_pack_kernel(uint64_t n, uint64_t end, uint64_t total, uint64_t mtime,
+		     const uint64_t *rows, const uint8_t *names, const uint8_t *in,
+		     uint8_t *out);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */

@@ -50,6 +50,7 @@
  */
 #include "device_common.h"
 #include "kernels.h"
+#include "tar_copy.h"	/* copy_tile(): the gather's copy, shared with the writer */
 
 #define BLOCK 512u
 #define SIZE_LIMIT ((u64)1 << 36)
@@ -488,40 +489,6 @@ lda_tar_desc_kernel(u64 max_records, u64 out_avail, const u32 *__restrict__ stat
 	cp_dst[k] = d;
 	cp_len[k] = l;
 	tiles[k] = (l + LDA_TAR_COPY_TILE - 1) / LDA_TAR_COPY_TILE;
-}
-
-/* len bytes src -> dst by a 256-thread workgroup, as copy_span(): bytes up to
- * the first 16-byte boundary of dst, 16-byte stores with four loads in flight
- * per thread, the tail */
-static __device__ __forceinline__ void
-copy_tile(const u8 *__restrict__ src, u8 *__restrict__ dst, u64 len, u32 tid)
-{
-	u64 head = (0 - (uintptr_t)dst) & 15;
-	if (head > len)
-		head = len;
-	if (tid < head)
-		dst[tid] = src[tid];
-	const u64 body = (len - head) & ~(u64)15;
-	const u8 *s = src + head;
-	u8 *d = dst + head;
-	u64 k = 16 * (u64)tid;
-	for (; k + 3 * 4096 < body; k += 4 * 4096) {
-		uint4 v[4];
-#pragma unroll
-		for (u32 i = 0; i < 4; i++)
-			__builtin_memcpy(&v[i], s + k + 4096 * i, 16);	/* source may be unaligned */
-#pragma unroll
-		for (u32 i = 0; i < 4; i++)
-			*(uint4 *)(d + k + 4096 * i) = v[i];
-	}
-	for (; k < body; k += 4096) {
-		uint4 v;
-		__builtin_memcpy(&v, s + k, 16);
-		*(uint4 *)(d + k) = v;
-	}
-	const u64 tail = head + body;
-	if (tail + tid < len)
-		dst[tail + tid] = src[tail + tid];
 }
 
 /*
