@@ -1225,10 +1225,11 @@ libdeflate_amd_gzip_members_index_batch(struct libdeflate_decompressor *decompre
  *
  * Not covered: encrypted entries and methods other than 0 and 8 (archives are
  * written by libdeflate_amd_zip_compress_batch below); multi-disk archives;
- * archives with prepended data; entries of 4 GiB or more; entries large enough
- * to want the many-wave decoder (each entry is decoded by one wave, and a
- * stored entry is copied by one workgroup: correct, but slow for a few huge
- * entries); a host-pointer form.
+ * archives with prepended data; entries of 4 GiB or more; a host-pointer form.
+ * Here each entry is decoded by one wave, and a stored entry is copied by one
+ * workgroup: for archives with a few huge entries, take the index from
+ * libdeflate_amd_zip_index_batch and read through
+ * libdeflate_amd_zip_read_large below.
  */
 LIBDEFLATEAPI int
 libdeflate_amd_zip_decompress_batch(struct libdeflate_decompressor *decompressor,
@@ -1269,6 +1270,60 @@ libdeflate_amd_zip_read_batch(struct libdeflate_decompressor *decompressor,
 			      const uint64_t *index, size_t entries,
 			      size_t n_sel, const uint64_t *sel,
 			      void *d_out, size_t out_avail, size_t out_align,
+			      uint64_t *out_offsets, int32_t *d_results, void *stream);
+
+/*
+ * The same selection for archives with a few HUGE entries (an .npz of large
+ * arrays, a checkpoint, a wheel with shared objects), which the call above
+ * reads correctly but on one wave or one workgroup per entry.  The arguments,
+ * the refusals before any device work, the layout (back to back in sel order,
+ * rounded up to out_align), out_offsets and the values of d_results[r] are
+ * those of libdeflate_amd_zip_read_batch; every output byte is the same.  Two
+ * rules, each read from the index row alone, decide what differs:
+ *
+ * - a method-8 entry with csize >= large_min is decoded by
+ *   libdeflate_amd_decompress_large (format LIBDEFLATE_AMD_DEFLATE, csize
+ *   bytes at d_in + data_off, exactly usize bytes at d_out + out_off); its
+ *   result is the entry's, and a success that did not use up csize bytes is
+ *   LIBDEFLATE_BAD_DATA as above.  Which decoder answers inside that call is
+ *   its own rule - a short stream goes to the one-wave decoder there -, so no
+ *   result depends on large_min.  large_min == 0: the library's default
+ *   (LDA_ZIP_LARGE_MIN);
+ * - an entry of either method with usize > LIBDEFLATE_AMD_ZIP_PIECE is copied
+ *   (if stored) and checksummed in pieces of that many bytes, each an ordinary
+ *   chunk of the copy and of the CRC-32 batch, and its CRC-32 is combined from
+ *   the pieces' on the device before it is compared with the row's.
+ *
+ * Every other entry goes through the call above's one batch.
+ *
+ * The call BLOCKS while its many-wave entries decode - it is not one of the
+ * enqueue-only _batch calls, hence its name: the many-wave decoder's chain of
+ * chunks is checked by the host.  They are decoded first, one after another;
+ * before they first read d_in, the object's own streams wait (an event wait,
+ * not a host wait) for what is queued on `stream`, so d_in may be the product
+ * of kernels queued there, and when the call returns their bytes are complete.
+ * Everything else - the batch, the pieces' copies and CRCs, the results - is
+ * then enqueued on `stream`: d_results and the bytes of the other entries are
+ * ready when `stream` is.  With no many-wave entry in the selection the call
+ * only enqueues, like its sibling.  The host arrays may be reused when the
+ * call returns.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG and LIBDEFLATE_AMD_OOM as in the call above, with
+ * the reason in libdeflate_amd_last_error(); a library-side failure inside a
+ * many-wave decode (no memory for its scratch) is that entry's
+ * LIBDEFLATE_BAD_DATA, as libdeflate_amd_decompress_large reports it.  Not
+ * covered: entries of 4 GiB or more; an enqueue-only form; many-wave entries
+ * decoded side by side.
+ */
+#define LIBDEFLATE_AMD_ZIP_PIECE (1u << 20)	/* bytes per copy / CRC piece */
+
+LIBDEFLATEAPI int
+libdeflate_amd_zip_read_large(struct libdeflate_decompressor *decompressor,
+			      const void *d_in, size_t in_nbytes,
+			      const uint64_t *index, size_t entries,
+			      size_t n_sel, const uint64_t *sel,
+			      void *d_out, size_t out_avail, size_t out_align,
+			      size_t large_min,
 			      uint64_t *out_offsets, int32_t *d_results, void *stream);
 
 /*

@@ -548,6 +548,27 @@ class Decompressor:
             _stream_ptr(stream)), "zip_read_batch")
         return offs
 
+    def read_zip_large(self, data, index, sel, out, results, out_align=1, large_min=0,
+                       stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_zip_read_large: read_zip_batch for archives with a
+        few huge entries - the same arguments, offsets, results and bytes.  A
+        deflated entry of large_min compressed bytes and more (0: the
+        library's default, LDA_ZIP_LARGE_MIN) is decoded on many waves, an
+        entry above binding.ZIP_PIECE bytes is copied and checksummed in
+        pieces.  BLOCKS while the many-wave entries decode; everything else
+        is enqueued on `stream`."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.ZIP_WORDS)
+        s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+        offs = np.zeros(len(s) + 1, dtype=np.uint64)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_zip_read_large(
+            self._h, data.data_ptr() if n else None, n, idx.ctypes.data_as(c_void_p), len(idx),
+            len(s), s.ctypes.data_as(c_void_p), out.data_ptr() if avail else None, avail,
+            int(out_align), int(large_min), offs.ctypes.data_as(c_void_p), results.data_ptr(),
+            _stream_ptr(stream)), "zip_read_large")
+        return offs
+
     def index_tar_batch(self, data, max_records, result, results, index=None, out_align=1,
                         stream=None, in_nbytes=None):
         """libdeflate_amd_tar_index_batch: the tar archive in the uint8 torch

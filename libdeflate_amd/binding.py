@@ -35,6 +35,8 @@ GZM_NAME_MAX = 65536    # bytes of FNAME + FCOMMENT the member reader accepts
 # the flag bit of result[4]
 ZIP_MORE_ENTRIES, ZIP_MORE_CANDIDATES, ZIP_UNSUPPORTED = 16, 17, 18
 ZIP_RESULT_WORDS, ZIP_WORDS, ZIP_SLACK, ZIP_ZIP64 = 5, 8, 1024, 1
+# ... and bytes per copy / CRC piece of libdeflate_amd_zip_read_large
+ZIP_PIECE = 1 << 20
 # the tar reader: result[0] beyond enum libdeflate_result, a per-entry result,
 # the words of a result, u64 per index row, candidate room beyond max_records,
 # the flag bits of result[4]
@@ -92,7 +94,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_decompress_large_index", "libdeflate_amd_seek_read_batch",
     "libdeflate_amd_gzip_members_decompress_batch", "libdeflate_amd_gzip_members_index_batch",
     "libdeflate_amd_zip_index_batch", "libdeflate_amd_zip_decompress_batch",
-    "libdeflate_amd_zip_read_batch",
+    "libdeflate_amd_zip_read_batch", "libdeflate_amd_zip_read_large",
     "libdeflate_amd_zip_compress_bound", "libdeflate_amd_zip_compress_batch",
     "libdeflate_amd_gzip_members_compress_bound", "libdeflate_amd_gzip_members_compress_batch",
     "libdeflate_amd_decompress_prefix_batch", "libdeflate_amd_decompress_prefix_batch_dict",
@@ -220,6 +222,9 @@ def load():
     sig("libdeflate_amd_zip_index_batch", c_int, P, P, SZ, SZ, SZ, P, P, P, P)
     sig("libdeflate_amd_zip_decompress_batch", c_int, P, P, SZ, SZ, P, SZ, SZ, P, P, P, P)
     sig("libdeflate_amd_zip_read_batch", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, P, P, P)
+    # ... the same selection with huge entries on many waves and in pieces
+    # (blocking while those decode; large_min before out_offsets)
+    sig("libdeflate_amd_zip_read_large", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, SZ, P, P, P)
     # a tar archive: the index alone, device file -> every entry's bytes, a
     # selection through host index rows, and the ranges of a selection (host)
     sig("libdeflate_amd_tar_index_batch", c_int, P, P, SZ, SZ, SZ, P, P, P, P)

@@ -94,6 +94,14 @@ struct EnvCfg {
 	size_t seg_bytes = 0;		/* LDA_SEG_BYTES: sub-range of the segmented single-buffer compress (0 = by size) */
 	bool no_stream_par = false;	/* LDA_NO_STREAM_PAR: single streams stay on one wave */
 	size_t stream_par_min = 16384;	/* LDA_STREAM_PAR_MIN: smallest stream (bytes in) for the many-wave path */
+	/* LDA_ZIP_LARGE_MIN: smallest deflated ZIP entry (csize) that
+	 * libdeflate_amd_zip_read_large hands to the many-wave decoder when its
+	 * large_min is 0.  Measured: the smallest value within the spread of the
+	 * best in the sweep of tools/bench_zip_large.py
+	 * (profiles/zip_large_bench.json: 32 KiB to 4 MiB lie within 0.15 ms of
+	 * each other there, 16 KiB - every 64 KiB entry a blocking call of
+	 * 0.62 ms - costs 2.5 s) */
+	size_t zip_large_min = (size_t)128 << 10;
 	size_t stream_window = 0;	/* LDA_STREAM_WINDOW: first input window of that path (0 = 4 MiB) */
 	size_t stream_chunk = 0;	/* LDA_STREAM_CHUNK: input bytes per chunk of that path (0 = by size) */
 	int devices = 1;		/* LDA_DEVICES: GPUs a host-pointer batch is spread over (N, or "all" = -1) */

@@ -78,6 +78,11 @@ static EnvCfg read_env()
 	c.no_stream_par = getenv("LDA_NO_STREAM_PAR") != nullptr;
 	if (const char *e = getenv("LDA_STREAM_PAR_MIN"))
 		c.stream_par_min = (size_t)strtoull(e, nullptr, 0);
+	if (const char *e = getenv("LDA_ZIP_LARGE_MIN")) {
+		size_t v = (size_t)strtoull(e, nullptr, 0);
+		if (v >= 1)
+			c.zip_large_min = v;
+	}
 	if (const char *e = getenv("LDA_STREAM_WINDOW")) {
 		c.stream_window = (size_t)strtoull(e, nullptr, 0);
 		if (c.stream_window && c.stream_window < 32768)

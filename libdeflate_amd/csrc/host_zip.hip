@@ -25,8 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "host_finder.h"
-#include "host_objects.h"
+#include "host_zip_args.h"
 #include "zip_plan.h"
 
 using namespace lda;
@@ -83,15 +82,6 @@ static ZipScratch zip_scratch(void *base, size_t n, size_t M, bool own_rows)
 	return s;
 }
 
-static bool align_ok(const char *what, size_t out_align)
-{
-	if (!out_align || out_align > 256 || (out_align & (out_align - 1))) {
-		set_error("%s: out_align %zu is not a power of two in 1 .. 256", what, out_align);
-		return false;
-	}
-	return true;
-}
-
 /* what the two device-only calls check before they touch a device */
 static bool zip_args_ok(const char *what, const struct libdeflate_decompressor *d,
 			const void *d_in, size_t n, size_t max_entries, size_t out_align,
@@ -103,12 +93,7 @@ static bool zip_args_ok(const char *what, const struct libdeflate_decompressor *
 	}
 	return finder_args_ok(what, d, d_in, n, "%s: max_entries %zu (1 .. 2^28)", max_entries, 1,
 			      d_result) &&
-	       align_ok(what, out_align);
-}
-
-static unsigned copy_grid(const DeviceCtx *ctx, size_t n_chunks)
-{
-	return (unsigned)std::max((size_t)1, std::min(n_chunks, (size_t)ctx->num_cus * 8));
+	       zip_align_ok(what, out_align);
 }
 
 static int zip_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, size_t n, size_t M,
@@ -171,7 +156,7 @@ static int zip_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, s
 						     NULL, st);
 		if (rc != LIBDEFLATE_AMD_OK)
 			return rc;
-		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, M)), dim3(256), 0, st,
+		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(zip_copy_grid(ctx, M)), dim3(256), 0, st,
 				   (uint64_t)M, (const uint64_t *)s.cp_src,
 				   (const uint64_t *)s.out_off, (const uint64_t *)s.cp_len, d_in, out);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -266,7 +251,7 @@ static int zip_read(struct libdeflate_decompressor *d, const uint8_t *d_in, size
 					     st);
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
-	hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, n_sel)), dim3(256), 0, st,
+	hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(zip_copy_grid(ctx, n_sel)), dim3(256), 0, st,
 			   (uint64_t)n_sel, col[ZIP_COL_CP_SRC], col[ZIP_COL_OUT_OFF],
 			   col[ZIP_COL_CP_LEN], d_in, out);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -289,20 +274,8 @@ libdeflate_amd_zip_read_batch(struct libdeflate_decompressor *d, const void *d_i
 			      uint64_t *out_offsets, int32_t *d_results, void *stream)
 {
 	const char *what = "zip_read_batch";
-	if (!d || (!d_in && in_nbytes) || (!index && entries) || (!d_out && out_avail) ||
-	    (n_sel && (!sel || !d_results))) {
-		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	if (entries > LDA_FINDER_MAX_RECORDS || n_sel > LDA_FINDER_MAX_RECORDS) {
-		set_error("%s: entries %zu, n_sel %zu (at most 2^28)", what, entries, n_sel);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	if (in_nbytes > LDA_FINDER_MAX_FILE) {
-		set_error("%s: in_nbytes %zu above 2^36", what, in_nbytes);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	if (!align_ok(what, out_align))
+	if (!zip_read_args_ok(what, d, d_in, in_nbytes, index, entries, n_sel, sel, d_out, out_avail,
+			      out_align, d_results))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
 		std::vector<uint64_t> cols;

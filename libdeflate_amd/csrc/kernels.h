@@ -376,6 +376,21 @@ lda_zip_rfinal_kernel(uint64_t n_sel, const uint64_t *meta, const uint64_t *in_n
 		      const int32_t *batch_res, const uint64_t *actual_in, const uint32_t *crcs,
 		      int32_t *results);
 
+/* zip_large_kernels.hip: the entries of a selection that left the one-wave
+ * batch (host_zip_large.hip; zip_large_plan.h builds the tables and holds
+ * copies of these constants) */
+#define LDA_ZIP_PIECE (1u << 20)	/* LIBDEFLATE_AMD_ZIP_PIECE */
+#define LDA_ZIPL_OWNED 48		/* meta bit: the row's result is lda_zip_lfinal_kernel's */
+#define LDA_ZIPL_MANY_WAVE 1		/* flags of an owned entry */
+#define LDA_ZIPL_PIECED 2
+extern "C" __global__ void
+lda_zip_lfinal_kernel(uint64_t n_own, uint64_t n_sel, uint64_t n_pieces, const uint64_t *l_sel,
+		      const uint64_t *l_flags, const uint64_t *l_in_n, const uint64_t *l_usize,
+		      const uint64_t *l_first, const uint64_t *l_count, const uint64_t *l_res,
+		      const uint64_t *l_ain, const uint64_t *meta, const int32_t *batch_res,
+		      const uint64_t *batch_ain, const uint32_t *batch_crcs, const uint64_t *p_dst,
+		      const uint64_t *p_len, const uint32_t *p_crcs, int32_t *results);
+
 /* tar_kernels.hip: a tar archive read from device memory (host_tar.hip).  The
  * candidates are (position, size) in blocks of 512 bytes, and the chain among
  * them is found by lda_bgzf_jump_kernel / _top_ / _members_ above, launched
