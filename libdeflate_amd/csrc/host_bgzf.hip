@@ -151,7 +151,7 @@ static size_t bgzf_host(struct libdeflate_compressor *c, const uint8_t *in, size
 			uint8_t *out, size_t out_avail, uint64_t *index, unsigned flags)
 {
 	DeviceCtx *ctx = device_ctx();
-	if (!ctx || !c->streams.ensure()) {
+	if (!ctx || !c->streams.enter()) {
 		complain("libdeflate_amd_bgzf_compress", LIBDEFLATE_AMD_NO_DEVICE);
 		return 0;
 	}

@@ -177,6 +177,14 @@ struct StreamPair {
 	hipEvent_t mark = nullptr;	/* a point on `comp` that `copy` may wait for */
 	hipEvent_t mark2 = nullptr;	/* and one on `copy` that `comp` may wait for */
 	bool ensure();
+	/* ensure(), for a call that takes no stream of the caller's (the
+	 * host-pointer entry points): the streams are not ordered behind anything,
+	 * and batches the caller has queued on a stream of their own may still use
+	 * the object's scratch, which such a call is about to reserve and reuse.
+	 * The call blocks anyway, so it waits here, on the host, until the device
+	 * has nothing in flight.  (The blocking calls that do take a stream wait
+	 * for it with an event instead: decompress_large_body().) */
+	bool enter();
 	void release();
 };
 

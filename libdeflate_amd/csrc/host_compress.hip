@@ -526,7 +526,7 @@ static int compress_batch_host_body(struct libdeflate_compressor *c, int format,
 	uint8_t *st = (uint8_t *)c->stage.reserve(cmp_at + total_avail + 64 * ns + 64);
 	if (!st)
 		return LIBDEFLATE_AMD_OOM;
-	if (!c->streams.ensure())
+	if (!c->streams.enter())
 		return LIBDEFLATE_AMD_NO_DEVICE;
 	size_t max_in = 0;
 	for (size_t i = 0; i < n; i++)
@@ -712,7 +712,7 @@ static size_t compress_large(struct libdeflate_compressor *c, int format,
 	if (out_avail <= hdr + ftr)
 		return 0;
 	DeviceCtx *ctx = device_ctx();
-	if (!ctx || !c->streams.ensure())
+	if (!ctx || !c->streams.enter())
 		return large_fail("streams");
 	hipStream_t s_copy = c->streams.copy, s_comp = c->streams.comp;
 	const size_t per_slice = (size_t)lda_large_per_slice(S);

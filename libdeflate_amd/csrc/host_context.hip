@@ -214,6 +214,18 @@ bool StreamPair::ensure()
 	return true;
 }
 
+bool StreamPair::enter()
+{
+	if (!ensure())
+		return false;
+	const hipError_t e = hipDeviceSynchronize();
+	if (e != hipSuccess) {
+		set_error("hipDeviceSynchronize: %s", hipGetErrorString(e));
+		return false;
+	}
+	return true;
+}
+
 void StreamPair::release()
 {
 	if (copy)

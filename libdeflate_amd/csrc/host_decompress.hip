@@ -406,7 +406,7 @@ static int decompress_batch_host_body(struct libdeflate_decompressor *d,
 	uint8_t *st = (uint8_t *)d->stage.reserve(pos + 64);
 	if (!st)
 		return LIBDEFLATE_AMD_OOM;
-	if (!d->streams.ensure())
+	if (!d->streams.enter())
 		return LIBDEFLATE_AMD_NO_DEVICE;
 	/* scratch of the largest launch up front (see the compress side) */
 	if (!d->scratch.reserve(align_up(n * 4, 16) + 16 * n + 4 * n + 16))
@@ -739,7 +739,7 @@ decompress_dict_body(struct libdeflate_decompressor *d, int format, const void *
 	const size_t dict_at = 64, in_at = align_up(dict_at + dict_nbytes, 64);
 	const size_t out_at = align_up(in_at + in_nbytes + 16, 64);
 	uint8_t *st = (uint8_t *)d->stage.reserve(out_at + out_avail + 64);
-	if (!st || !d->streams.ensure()) {
+	if (!st || !d->streams.enter()) {
 		complain("libdeflate_amd_decompress_dict_ex", st ? LIBDEFLATE_AMD_NO_DEVICE :
 									   LIBDEFLATE_AMD_OOM);
 		return LIBDEFLATE_BAD_DATA;

@@ -199,7 +199,7 @@ static int prefix_one_body(struct libdeflate_decompressor *d, int format, const 
 	/* (the staging holds input and limit: checked by the caller not to wrap) */
 	const size_t in_at = 64, out_at = align_up(in_at + in_nbytes + 16, 64);
 	uint8_t *st = (uint8_t *)d->stage.reserve(out_at + limit + 64);
-	if (!st || !d->streams.ensure()) {
+	if (!st || !d->streams.enter()) {
 		complain(what, st ? LIBDEFLATE_AMD_NO_DEVICE : LIBDEFLATE_AMD_OOM);
 		return LIBDEFLATE_BAD_DATA;
 	}

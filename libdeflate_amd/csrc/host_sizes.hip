@@ -210,7 +210,7 @@ static int sizes_batch_host_body(struct libdeflate_decompressor *d, int format, 
 	uint8_t *st = (uint8_t *)d->stage.reserve(pos + 64);
 	if (!st)
 		return LIBDEFLATE_AMD_OOM;
-	if (!d->streams.ensure())
+	if (!d->streams.enter())
 		return LIBDEFLATE_AMD_NO_DEVICE;
 	uint8_t *scr = (uint8_t *)d->scratch.reserve(sizes_scratch_bytes(n));
 	if (!scr)

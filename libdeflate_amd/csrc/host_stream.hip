@@ -469,7 +469,7 @@ struct StreamRun {
 		}
 		S[1] = WHY_DEVICE;	/* until something better is known */
 		if (!dev) {
-			if (!d->streams.ensure())
+			if (!d->streams.enter())
 				return false;
 			s_copy = d->streams.copy;
 			s_comp = d->streams.comp;
