@@ -1503,6 +1503,124 @@ libdeflate_amd_tar_ranges(const uint64_t *index, size_t entries, size_t n_sel,
 			  const uint64_t *sel, uint64_t *ranges, uint64_t *total_ret);
 
 /*
+ * ---- PNG images decoded on the device ----
+ *
+ * A batch of PNG files in device memory -> a batch of pixel arrays in device
+ * memory: the chunks of every file walked and its header checked (the index
+ * call), then for a selection the IDAT payloads gathered into the zlib stream
+ * PNG splits across chunks, that stream decoded by the batch decoder above, and
+ * the five scanline filters undone.  The oracle is the PNG specification as
+ * tools/models/png_model.py restates it, pinned against PIL where PIL is there.
+ * The conventions are those of the ZIP and tar readers: device pointers lie on
+ * the object's device, scratch belongs to the decompressor object (it grows on
+ * the host, as everywhere else, and the plan goes up through one pinned block
+ * per object), and the calls only enqueue on `stream`.
+ *
+ * libdeflate_amd_png_index_batch: n_files files at d_in + d_in_offsets[k],
+ * d_in_nbytes[k] bytes each (device arrays, as in
+ * libdeflate_amd_decompress_batch).  d_results[k] (device, int32) and one row
+ * of LIBDEFLATE_AMD_PNG_WORDS u64 per file in d_index (device):
+ *   { file offset in d_in, file nbytes,
+ *     width | height << 32,
+ *     bit_depth | colour_type << 8 | interlace << 16 | filter unit (bytes per
+ *       pixel, 1 below 8 bits) << 24 | channels << 32,
+ *     offset in d_in of the first IDAT chunk's length field,
+ *     sum of all IDAT data lengths,
+ *     PLTE data offset | entries << 48   (0: none),
+ *     tRNS data offset | length << 48    (0: none, or longer than 65535) }
+ * Only a PLTE and a tRNS in front of the first IDAT are noted.  A failed file's
+ * row is zero beyond words 0 and 1, and it never affects its neighbours.
+ *
+ * LIBDEFLATE_BAD_DATA: a wrong 8-byte signature; a first chunk that is not a
+ * 13-byte IHDR, or an IHDR whose CRC-32 is wrong; width or height 0 or above
+ * 2^31 - 1; a depth and colour type the specification does not pair;
+ * compression or filter method other than 0, interlace other than 0 or 1; a
+ * chunk whose 12 + length bytes do not lie inside the file; no IDAT; an IDAT
+ * after the IDAT run has ended; a second IHDR or PLTE; colour type 3 without a
+ * PLTE before IDAT; a PLTE length that is no multiple of 3 or above 768; no
+ * IEND before the file ends.  LIBDEFLATE_AMD_PNG_UNSUPPORTED, where none of
+ * those applies: interlace 1 (Adam7); an unknown critical chunk (an uppercase
+ * first letter that is not IHDR, PLTE, IDAT or IEND); an image whose height *
+ * (1 + rowbytes) is 2^32 or more.  Bytes behind IEND are ignored.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work: a NULL argument, n_files above
+ * 2^28.
+ */
+#define LIBDEFLATE_AMD_PNG_UNSUPPORTED      18	/* a per-file result; the ZIP and tar readers' value */
+#define LIBDEFLATE_AMD_PNG_WORDS            8	/* u64 per index row */
+#define LIBDEFLATE_AMD_PNG_LE16             1	/* flag: 16-bit samples little-endian */
+
+LIBDEFLATEAPI int
+libdeflate_amd_png_index_batch(struct libdeflate_decompressor *decompressor,
+			       size_t n_files, const void *d_in,
+			       const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
+			       uint64_t *d_index, int32_t *d_results, void *stream);
+
+/*
+ * Host arithmetic only, the counterpart of libdeflate_amd_tar_ranges: index and
+ * sel are HOST memory; out_offsets (HOST, n_sel + 1 u64) receives where
+ * selection r starts in the output of libdeflate_amd_png_decode_batch and where
+ * the last one ends, *total_ret (may be NULL) that end.  Every image takes
+ * height * rowbytes bytes - rowbytes = ceil(width * channels * depth / 8) -
+ * rounded up to out_align, a power of two in 1 .. 256; a zero row (a failed
+ * file) takes none.  LIBDEFLATE_AMD_BAD_ARG: a NULL argument, out_align, a sel
+ * at or above entries, a row whose words 2 and 3 are not a valid IHDR.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_png_out_sizes(const uint64_t *index, size_t entries, size_t n_sel,
+			     const uint64_t *sel, size_t out_align,
+			     uint64_t *out_offsets, uint64_t *total_ret);
+
+/*
+ * Decode a selection.  index: HOST memory, `entries` rows as
+ * libdeflate_amd_png_index_batch wrote them; sel: HOST memory, n_sel row
+ * numbers in any order, duplicates allowed; out_offsets: NULL or HOST room for
+ * n_sel + 1 u64, filled in before the call returns.  Selection r's pixels lie
+ * at d_out + out_offsets[r]: height rows of exactly rowbytes bytes, no filter
+ * bytes and no row padding, the samples as PNG stores them - depths below 8
+ * stay packed most-significant-bit first, palette images stay indices, 16-bit
+ * samples are big-endian.  flags: 0 or LIBDEFLATE_AMD_PNG_LE16, which stores
+ * 16-bit samples little-endian, so that the buffer views as a native uint16
+ * tensor (images of other depths are not changed by it).
+ *
+ * d_results[r] (device, int32) is the first of these that applies:
+ * LIBDEFLATE_AMD_PNG_UNSUPPORTED for a zero row; LIBDEFLATE_BAD_DATA if the
+ * IDAT chain found on the device disagrees with the row (a stale or foreign
+ * index); the zlib decoder's own result - the stream must decode to exactly
+ * height * (1 + rowbytes) bytes and its Adler-32 must hold, so BAD_DATA,
+ * SHORT_OUTPUT and INSUFFICIENT_SPACE mean what they mean in
+ * libdeflate_zlib_decompress; LIBDEFLATE_BAD_DATA for a filter-type byte above
+ * 4; LIBDEFLATE_SUCCESS.  Nothing is written at or past d_out + out_avail, in
+ * alignment padding or in another selection's room, whatever the file holds; a
+ * failed selection's room is undefined, like a failed chunk's in the batch
+ * decompress.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work: a NULL argument (d_out may be
+ * NULL only with out_avail == 0, d_in only with in_nbytes == 0), a bad
+ * out_align or an unknown flag, in_nbytes above 2^36, a sel at or above
+ * entries, a row whose file, first IDAT, IDAT sum or PLTE / tRNS range does not
+ * lie inside in_nbytes or whose fields are not a valid IHDR, a selection that
+ * needs more than out_avail.
+ *
+ * Not covered: Adam7; the CRCs of IDAT, PLTE and ancillary chunks - only the
+ * IHDR's is checked; the zlib stream's Adler-32 vouches for the pixel bytes,
+ * and nothing vouches for a palette; transforms other than LE16 (palette
+ * expansion, tRNS, gamma, depth scaling: the row hands the caller PLTE and
+ * tRNS, so one gather on the device expands them); APNG frames (the default
+ * image alone is decoded); images of 2^32 raw bytes and more; routing a few
+ * huge images to the many-wave decoder, as libdeflate_amd_zip_read_large does
+ * for ZIP (every image is one wave's work here); a host-pointer form; a writer.
+ */
+LIBDEFLATEAPI int
+libdeflate_amd_png_decode_batch(struct libdeflate_decompressor *decompressor,
+				const void *d_in, size_t in_nbytes,
+				const uint64_t *index, size_t entries,
+				size_t n_sel, const uint64_t *sel,
+				void *d_out, size_t out_avail, size_t out_align,
+				unsigned flags, uint64_t *out_offsets,
+				int32_t *d_results, void *stream);
+
+/*
  * ---- ZIP archives written on the device ----
  *
  * n_entries named byte ranges of one DEVICE buffer -> one ZIP archive in device

@@ -620,6 +620,41 @@ class Decompressor:
             _stream_ptr(stream)), "tar_read_batch")
         return offs
 
+    def index_png_batch(self, data, in_offsets, in_nbytes, index, results, stream=None):
+        """libdeflate_amd_png_index_batch: the PNG files data[in_offsets[k] :
+        + in_nbytes[k]] (uint8 CUDA tensor; int64 CUDA tensors) -> index: int64
+        CUDA tensor of 8 per file (rows of file offset, file nbytes, width |
+        height << 32, depth | colour << 8 | interlace << 16 | filter unit << 24
+        | channels << 32, first IDAT, IDAT bytes, PLTE, tRNS; zero beyond the
+        first two words for a refused file); results: int32 CUDA tensor, one
+        per file (0, BAD_DATA, PNG_UNSUPPORTED).  Only enqueues."""
+        n = in_offsets.numel()
+        check(self._lib.libdeflate_amd_png_index_batch(
+            self._h, n, data.data_ptr(), in_offsets.data_ptr(), in_nbytes.data_ptr(),
+            index.data_ptr(), results.data_ptr(), _stream_ptr(stream)), "png_index_batch")
+
+    def decode_png_batch(self, data, index, sel, out, results, out_align=1, flags=0,
+                         stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_png_decode_batch: the images `sel` (host, any order,
+        duplicates allowed) of the files in the CUDA tensor `data`, back to
+        back into `out` with out_align: height rows of rowbytes bytes each, no
+        filter bytes; index: host rows as index_png_batch wrote them; results:
+        int32 CUDA tensor, one per selection; flags: 0 or binding.PNG_LE16
+        (16-bit samples little-endian).  Returns the numpy uint64 offsets
+        (len(sel) + 1) of the selections in `out`; png_shapes(index) gives the
+        shapes to view them with.  Only enqueues."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+        s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+        offs = np.zeros(len(s) + 1, dtype=np.uint64)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_png_decode_batch(
+            self._h, data.data_ptr() if n else None, n, idx.ctypes.data_as(c_void_p), len(idx),
+            len(s), s.ctypes.data_as(c_void_p), out.data_ptr() if avail else None, avail,
+            int(out_align), int(flags), offs.ctypes.data_as(c_void_p), results.data_ptr(),
+            _stream_ptr(stream)), "png_decode_batch")
+        return offs
+
     def read_targz(self, data, out, max_records, spacing=1 << 20, max_points=1024,
                    in_nbytes=None, out_avail=None, stream=None):
         """A .tar.gz in the CUDA tensor `data`: decompress_large_index("gzip")
@@ -1016,6 +1051,32 @@ def tar_ranges(index, sel):
         idx.ctypes.data_as(c_void_p), len(idx), len(s), s.ctypes.data_as(c_void_p),
         rng.ctypes.data_as(c_void_p), ctypes.byref(total)), "tar_ranges")
     return rng, total.value
+
+
+def png_out_sizes(index, sel, out_align=1):
+    """libdeflate_amd_png_out_sizes: where decode_png_batch puts the images
+    `sel` of the host index rows `index` -> (numpy uint64 offsets, len(sel) + 1,
+    total bytes).  An image takes height * rowbytes bytes rounded up to
+    out_align, a zero row (a refused file) none.  No device is touched."""
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+    s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+    offs = np.zeros(len(s) + 1, dtype=np.uint64)
+    total = ctypes.c_uint64(0)
+    check(binding.load().libdeflate_amd_png_out_sizes(
+        idx.ctypes.data_as(c_void_p), len(idx), len(s), s.ctypes.data_as(c_void_p),
+        int(out_align), offs.ctypes.data_as(c_void_p), ctypes.byref(total)), "png_out_sizes")
+    return offs, total.value
+
+
+def png_shapes(index):
+    """(height, width, channels, bit_depth, colour_type) of every host index
+    row of index_png_batch, all zero for a refused file: an 8-bit image's bytes
+    view as a uint8 tensor of height x width x channels, a 16-bit image's
+    (decoded with PNG_LE16) as uint16 of the same shape; below 8 bits a row is
+    ceil(width * bit_depth / 8) packed bytes."""
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+    return [(int(r[2] >> 32), int(r[2] & 0xFFFFFFFF), int(r[3] >> 32), int(r[3] & 0xFF),
+             int(r[3] >> 8 & 0xFF)) for r in idx.tolist()]
 
 
 def _stream_ptr(stream):

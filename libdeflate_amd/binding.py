@@ -43,6 +43,9 @@ ZIP_PIECE = 1 << 20
 TAR_MORE_RECORDS, TAR_MORE_CANDIDATES, TAR_UNSUPPORTED = 16, 17, 18
 TAR_RESULT_WORDS, TAR_WORDS, TAR_SLACK = 5, 8, 1024
 TAR_EOF, TAR_HAS_L, TAR_HAS_PAX = 1, 2, 4
+# the PNG reader: a per-file result (the ZIP and tar readers' value), u64 per
+# index row, the one flag of a decode
+PNG_UNSUPPORTED, PNG_WORDS, PNG_LE16 = 18, 8, 1
 # the ZIP writer: the two flags, the words of its result
 ZIP_STORE, ZIP_FORCE_ZIP64, ZIPW_RESULT_WORDS = 1, 2, 4
 # the writer of concatenated gzip members: the words of its result, the longest
@@ -103,6 +106,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_tar_read_batch", "libdeflate_amd_tar_ranges",
     "libdeflate_amd_tar_write_size", "libdeflate_amd_tar_write_batch",
     "libdeflate_amd_targz_compress_batch",
+    "libdeflate_amd_png_index_batch", "libdeflate_amd_png_out_sizes",
+    "libdeflate_amd_png_decode_batch",
 ]
 
 _lib = None
@@ -231,6 +236,13 @@ def load():
     sig("libdeflate_amd_tar_extract_batch", c_int, P, P, SZ, SZ, P, SZ, SZ, P, P, P, P)
     sig("libdeflate_amd_tar_read_batch", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, P, P, P)
     sig("libdeflate_amd_tar_ranges", c_int, P, SZ, SZ, P, P, P)
+    # PNG files: the index of a batch of files, the output offsets of a
+    # selection (host arithmetic), and a selection through host index rows ->
+    # pixels (flags before out_offsets)
+    sig("libdeflate_amd_png_index_batch", c_int, P, SZ, P, P, P, P, P, P)
+    sig("libdeflate_amd_png_out_sizes", c_int, P, SZ, SZ, P, SZ, P, P)
+    sig("libdeflate_amd_png_decode_batch", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, c_uint32,
+        P, P, P)
     # a ZIP archive written: the exact bound (host arithmetic), and named ranges
     # of a device buffer -> archive (names, offsets and sizes on the host)
     sig("libdeflate_amd_zip_compress_bound", SZ, SZ, P, P, c_uint32)

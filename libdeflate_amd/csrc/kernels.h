@@ -506,6 +506,30 @@ lda_tarw_pack_kernel(uint64_t n, uint64_t end, uint64_t total, uint64_t mtime,
 		     const uint64_t *rows, const uint8_t *names, const uint8_t *in,
 		     uint8_t *out);
 
+/* png_kernels.hip: PNG files read from device memory (host_png.hip): the chunk
+ * walk, one lane per file; the IDAT payloads of a selection gathered into one
+ * zlib stream, one workgroup per selection; the scanline filters undone behind
+ * the zlib batch decode, one wave per selection; the verdicts merged.  The
+ * c_* columns are those of png_plan.h.  Copies of the header's constants
+ * (static_assert in host_png.hip) */
+#define LDA_PNG_UNSUPPORTED 18		/* LIBDEFLATE_AMD_PNG_UNSUPPORTED */
+#define LDA_PNG_WORDS 8
+#define LDA_PNG_META_LE16 0x100		/* meta: LIBDEFLATE_AMD_PNG_LE16 << 8, 16-bit images */
+extern "C" __global__ void
+lda_png_index_kernel(uint64_t n_files, const uint8_t *in, const uint64_t *in_off,
+		     const uint64_t *in_n, uint64_t *rows, int32_t *results);
+extern "C" __global__ void
+lda_png_gather_kernel(uint64_t n_sel, const uint64_t *c_idat, const uint64_t *c_end,
+		      const uint64_t *c_zsum, const uint64_t *c_zoff, const uint8_t *in,
+		      uint8_t *ws, int32_t *flags);
+extern "C" __global__ void
+lda_png_unfilter_kernel(uint64_t n_sel, const uint64_t *c_raw_off, const uint64_t *c_raw_n,
+			const uint64_t *c_out_off, const uint64_t *c_geom, const uint64_t *c_meta,
+			const uint8_t *ws, uint8_t *out_base, int32_t *flags);
+extern "C" __global__ void
+lda_png_final_kernel(uint64_t n_sel, const uint64_t *c_meta, const int32_t *gather,
+		     const int32_t *decode, const int32_t *unfilter, int32_t *results);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
