@@ -1609,7 +1609,7 @@ libdeflate_amd_png_out_sizes(const uint64_t *index, size_t entries, size_t n_sel
  * tRNS, so one gather on the device expands them); APNG frames (the default
  * image alone is decoded); images of 2^32 raw bytes and more; routing a few
  * huge images to the many-wave decoder, as libdeflate_amd_zip_read_large does
- * for ZIP (every image is one wave's work here); a host-pointer form; a writer.
+ * for ZIP (every image is one wave's work here); a host-pointer form.
  */
 LIBDEFLATEAPI int
 libdeflate_amd_png_decode_batch(struct libdeflate_decompressor *decompressor,
@@ -1894,6 +1894,96 @@ libdeflate_amd_targz_compress_batch(struct libdeflate_compressor *compressor, in
 				    const uint64_t *in_nbytes, void *d_out, size_t out_avail,
 				    uint64_t *d_out_nbytes, uint64_t *index, uint64_t mtime,
 				    unsigned flags, void *stream);
+
+/*
+ * ---- PNG images written on the device ----
+ *
+ * n_images pixel arrays of one DEVICE buffer -> n_images PNG files back to
+ * back in device memory: the scanlines filtered by a kernel, compressed into
+ * one zlib stream per image, and signature, IHDR, PLTE, tRNS, ONE IDAT and
+ * IEND placed around it with their CRC-32s: what
+ * libdeflate_amd_png_decode_batch reads.  The conventions are those of
+ * libdeflate_amd_gzip_members_compress_batch above: the object is a
+ * compressor and the level is the object's, the call enqueues on `stream` and
+ * returns, the plan goes up through the object's pinned block, scratch belongs
+ * to the object (the ZIP writer's), `images` is a HOST array that may be
+ * reused when the call returns, d_out must not overlap d_in, and no byte is
+ * ever written at or past d_out + out_avail.
+ *
+ * images: LIBDEFLATE_AMD_PNG_WORDS u64 per image, the reader's index row read
+ * the other way - a decoded row with words 0 and 1 replaced is a valid input:
+ *   { offset of the pixels in d_in, their size (height * rowbytes),
+ *     width | height << 32,
+ *     bit_depth | colour_type << 8 (bits 16..23, interlace, must be 0; bits 24
+ *       and up are ignored),
+ *     ignored, ignored,
+ *     PLTE data offset in d_in | entries << 48 (0: none; required for colour
+ *       type 3, allowed for 2 and 6, refused for 0 and 4; 1 .. 256 entries, for
+ *       type 3 at most 1 << depth),
+ *     tRNS data offset in d_in | length << 48 (0: none; the length 2 for type
+ *       0, 6 for type 2, 1 .. PLTE entries for type 3; refused for 4 and 6) }
+ * The pixels are what the reader writes: height rows of exactly rowbytes bytes,
+ * depths below 8 packed most-significant-bit first, 16-bit samples big-endian -
+ * or, with LIBDEFLATE_AMD_PNG_LE16 in flags, little-endian (a native uint16
+ * tensor): they are swapped as they are loaded, so the filters see PNG's order.
+ *
+ * THE FILES: image k's file stands behind image k - 1's, from offset 0.  The
+ * IDAT payload is byte for byte what libdeflate_zlib_compress() of this build
+ * returns for the image's filtered scanlines at the object's level and LDA_*
+ * switches; every chunk's CRC-32 is right.  Scanline y is a filter-type byte
+ * and rowbytes filtered bytes (PNG specification 9.2; the row above row 0 is
+ * zeros, the filter unit is max(1, channels * depth / 8) bytes, Average takes
+ * the 9-bit sum, Paeth resolves ties a, b, c).  filter 0 .. 4: that type on
+ * every row.  LIBDEFLATE_AMD_PNG_FILTER_ADAPTIVE: per row the type whose
+ * filtered bytes, read as signed, have the least sum of absolute values, the
+ * lowest type on a tie (libpng's heuristic).
+ *
+ * libdeflate_amd_png_encode_bound() is arithmetic on the host rows: per image
+ * 8 + 25 + (12 + 3 entries, with a PLTE) + (12 + length, with a tRNS) + 12 +
+ * libdeflate_zlib_compress_bound(height * (1 + rowbytes)) + 12.  No files of
+ * these images are larger.  0 for rows the batch call refuses (what needs
+ * in_avail apart).
+ *
+ * d_result[0 .. LIBDEFLATE_AMD_PNGW_RESULT_WORDS) (device memory):
+ *   [0] 0, or LIBDEFLATE_INSUFFICIENT_SPACE: the files do not fit out_avail -
+ *       then no byte of d_out and no row of d_index is written;
+ *   [1] the files' bytes in all, [2] the pixels' bytes in all, [3] the images
+ *   ([1] to [3] are valid either way).
+ * d_index: NULL, or device room for n_images rows of LIBDEFLATE_AMD_PNG_WORDS
+ * u64: exactly the rows libdeflate_amd_png_index_batch returns for the written
+ * files, word 0 the file's offset in d_out, so d_out and the rows can go
+ * straight to libdeflate_amd_png_decode_batch.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the reason in
+ * libdeflate_amd_last_error(): a NULL object or pointer (d_in may be NULL with
+ * in_avail == 0, images with n_images == 0, d_index always), a filter above 5,
+ * an unknown flag, n_images above 2^28, words 2 and 3 that are no valid
+ * non-interlaced IHDR (the reader's rule), word 1 not height * rowbytes,
+ * height * (1 + rowbytes) of 2^32 or more, a zlib bound above 2^31 - 1 (one
+ * IDAT's length field; it also excludes every image for which a level-0
+ * libdeflate_zlib_compress() returns 0), pixels, PLTE or tRNS that do not lie
+ * inside in_avail, a PLTE or tRNS rule above broken.  n_images == 0 writes
+ * d_result alone.
+ *
+ * Limits: the object's scratch is about twice the pixels' bytes (the scanlines
+ * and the slots) plus descriptors; one filter mode and one level per call; no
+ * Adam7; one IDAT per image; no ancillary chunk but tRNS; no filter choice by
+ * trial compression; no host-pointer form.
+ */
+#define LIBDEFLATE_AMD_PNG_FILTER_ADAPTIVE 5	/* filter: 0..4 = that type on every row */
+#define LIBDEFLATE_AMD_PNGW_RESULT_WORDS   4
+
+LIBDEFLATEAPI size_t
+libdeflate_amd_png_encode_bound(struct libdeflate_compressor *compressor,
+				size_t n_images, const uint64_t *images);
+
+LIBDEFLATEAPI int
+libdeflate_amd_png_encode_batch(struct libdeflate_compressor *compressor,
+				size_t n_images, const uint64_t *images,
+				const void *d_in, size_t in_avail,
+				void *d_out, size_t out_avail,
+				uint64_t *d_result, uint64_t *d_index,
+				unsigned filter, unsigned flags, void *stream);
 
 /*
  * Prefix decompress: the first bytes of every stream of a batch - zlib's

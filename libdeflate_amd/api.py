@@ -230,6 +230,44 @@ class Compressor:
             _stream_ptr(stream)), "gzip_members_compress_batch")
         return out, result, idx
 
+    def png_encode_bound(self, images):
+        """libdeflate_amd_png_encode_bound: room enough for the files
+        encode_png_batch writes for these image rows (png_image_rows()).  No
+        device is touched; ValueError for rows the call would refuse."""
+        rows = np.ascontiguousarray(images, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+        size = self._lib.libdeflate_amd_png_encode_bound(
+            self._h, len(rows), rows.ctypes.data_as(c_void_p))
+        if len(rows) and not size:
+            raise ValueError("png_encode_bound: a row the encode call refuses")
+        return size
+
+    def encode_png_batch(self, images, data, out, result, index=None,
+                         filter=binding.PNG_FILTER_ADAPTIVE, flags=0, stream=None,
+                         in_avail=None, out_avail=None):
+        """libdeflate_amd_png_encode_batch: one PNG file per image row, back to
+        back from out[0].  images: host rows of PNG_WORDS u64 (png_image_rows(),
+        or the rows of index_png_batch with words 0 and 1 replaced); data: the
+        uint8 torch CUDA tensor the rows' offsets point into (its first in_avail
+        bytes) - pixels as decode_png_batch writes them, PLTE and tRNS data;
+        out: uint8 CUDA tensor (out_avail bytes of it, default all;
+        png_encode_bound() is room enough); result: int64 CUDA tensor of
+        PNGW_RESULT_WORDS - [0] 0 or INSUFFICIENT_SPACE, [1] the files' bytes,
+        [2] the pixels' bytes, [3] the images; index: None or an int64 CUDA
+        tensor of images x PNG_WORDS, the rows index_png_batch returns for the
+        files.  filter: 0..4 or PNG_FILTER_ADAPTIVE; flags: 0 or PNG_LE16 (the
+        16-bit samples in `data` are little-endian).  Only enqueues on
+        `stream`."""
+        rows = np.ascontiguousarray(images, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+        n = len(rows)
+        assert result.numel() >= binding.PNGW_RESULT_WORDS
+        assert index is None or index.numel() >= binding.PNG_WORDS * n
+        avail = data.numel() if in_avail is None else int(in_avail)
+        check(self._lib.libdeflate_amd_png_encode_batch(
+            self._h, n, rows.ctypes.data_as(c_void_p), data.data_ptr() if avail else None,
+            avail, out.data_ptr(), out.numel() if out_avail is None else int(out_avail),
+            result.data_ptr(), index.data_ptr() if index is not None else None, int(filter),
+            int(flags), _stream_ptr(stream)), "png_encode_batch")
+
     def tar_write_size(self, names, sizes):
         """libdeflate_amd_tar_write_size: the exact size of the tar archive
         write_tar_batch writes for entries of these names (str or bytes, or
@@ -1077,6 +1115,43 @@ def png_shapes(index):
     idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
     return [(int(r[2] >> 32), int(r[2] & 0xFFFFFFFF), int(r[3] >> 32), int(r[3] & 0xFF),
              int(r[3] >> 8 & 0xFF)) for r in idx.tolist()]
+
+
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+_PNG_COLOUR_OF = {1: 0, 2: 4, 3: 2, 4: 6}
+
+
+def png_image_rows(shapes, offsets, depth=8, colour=None, plte=None, trns=None):
+    """The host rows encode_png_batch takes.  shapes: (H, W) or (H, W, C) per
+    image; offsets: where each image's pixels start in the data tensor, in
+    bytes; depth and colour: one value or one per image - colour None takes the
+    colour type from C (1 grey, 2 grey + alpha, 3 RGB, 4 RGBA; (H, W) is grey);
+    plte / trns: None, or per image None or (offset in the data tensor, entries
+    / length).  -> numpy uint64 (images, PNG_WORDS)."""
+    n = len(shapes)
+
+    def per_image(v):
+        return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+    depths, colours = per_image(depth), per_image(colour)
+    pl, tr = per_image(plte) if plte is not None else [None] * n, \
+        per_image(trns) if trns is not None else [None] * n
+    assert len(offsets) == n and len(depths) == n and len(colours) == n
+    rows = np.zeros((n, binding.PNG_WORDS), dtype=np.uint64)
+    for k, shp in enumerate(shapes):
+        h, w = int(shp[0]), int(shp[1])
+        c = int(shp[2]) if len(shp) > 2 else 1
+        col = _PNG_COLOUR_OF[c] if colours[k] is None else int(colours[k])
+        if _PNG_CHANNELS.get(col) != c:
+            raise ValueError(f"image {k}: colour type {col} has not {c} channels")
+        rb = (w * c * int(depths[k]) + 7) // 8
+        rows[k, 0], rows[k, 1] = int(offsets[k]), h * rb
+        rows[k, 2] = w | h << 32
+        rows[k, 3] = int(depths[k]) | col << 8
+        if pl[k] is not None:
+            rows[k, 6] = int(pl[k][0]) | int(pl[k][1]) << 48
+        if tr[k] is not None:
+            rows[k, 7] = int(tr[k][0]) | int(tr[k][1]) << 48
+    return rows
 
 
 def _stream_ptr(stream):

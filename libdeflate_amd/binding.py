@@ -46,6 +46,8 @@ TAR_EOF, TAR_HAS_L, TAR_HAS_PAX = 1, 2, 4
 # the PNG reader: a per-file result (the ZIP and tar readers' value), u64 per
 # index row, the one flag of a decode
 PNG_UNSUPPORTED, PNG_WORDS, PNG_LE16 = 18, 8, 1
+# the PNG writer: the filter mode beyond the five types, the words of its result
+PNG_FILTER_ADAPTIVE, PNGW_RESULT_WORDS = 5, 4
 # the ZIP writer: the two flags, the words of its result
 ZIP_STORE, ZIP_FORCE_ZIP64, ZIPW_RESULT_WORDS = 1, 2, 4
 # the writer of concatenated gzip members: the words of its result, the longest
@@ -108,6 +110,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_targz_compress_batch",
     "libdeflate_amd_png_index_batch", "libdeflate_amd_png_out_sizes",
     "libdeflate_amd_png_decode_batch",
+    "libdeflate_amd_png_encode_bound", "libdeflate_amd_png_encode_batch",
 ]
 
 _lib = None
@@ -243,6 +246,11 @@ def load():
     sig("libdeflate_amd_png_out_sizes", c_int, P, SZ, SZ, P, SZ, P, P)
     sig("libdeflate_amd_png_decode_batch", c_int, P, P, SZ, P, SZ, SZ, P, P, SZ, SZ, c_uint32,
         P, P, P)
+    # PNG files written: the bound (host arithmetic), and pixel arrays of a
+    # device buffer -> files (the image rows on the host)
+    sig("libdeflate_amd_png_encode_bound", SZ, P, SZ, P)
+    sig("libdeflate_amd_png_encode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P, c_uint32,
+        c_uint32, P)
     # a ZIP archive written: the exact bound (host arithmetic), and named ranges
     # of a device buffer -> archive (names, offsets and sizes on the host)
     sig("libdeflate_amd_zip_compress_bound", SZ, SZ, P, P, c_uint32)

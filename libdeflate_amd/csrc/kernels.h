@@ -530,6 +530,36 @@ extern "C" __global__ void
 lda_png_final_kernel(uint64_t n_sel, const uint64_t *c_meta, const int32_t *gather,
 		     const int32_t *decode, const int32_t *unfilter, int32_t *results);
 
+/* png_write_kernels.hip: PNG files written into device memory
+ * (host_png_write.hip, png_write_plan.h): the scanlines filtered into the
+ * scratch, 4, 16 or 64 lanes per row; behind the checksum and compress
+ * batches the files sized and placed, a wave per image; the pieces are copied
+ * by lda_zipw_copy_kernel */
+extern "C" __global__ void
+lda_pngw_filter4_kernel(uint64_t n, uint64_t n_items, uint32_t filter, const uint64_t *work,
+			const uint64_t *icols, const uint8_t *in, uint8_t *scan);
+extern "C" __global__ void
+lda_pngw_filter16_kernel(uint64_t n, uint64_t n_items, uint32_t filter, const uint64_t *work,
+			 const uint64_t *icols, const uint8_t *in, uint8_t *scan);
+extern "C" __global__ void
+lda_pngw_filter64_kernel(uint64_t n, uint64_t n_items, uint32_t filter, const uint64_t *work,
+			 const uint64_t *icols, const uint8_t *in, uint8_t *scan);
+extern "C" __global__ void
+lda_pngw_image_kernel(uint64_t n, uint64_t np, uint32_t crc_head, const uint64_t *icols,
+		      const uint64_t *pcols, const uint64_t *out_n, const uint32_t *adlers,
+		      const uint32_t *crcs, uint64_t *csize, uint32_t *adler, uint32_t *crc,
+		      uint64_t *sizes);
+extern "C" __global__ void
+lda_pngw_place_kernel(uint64_t n, uint64_t np, int level, uint64_t out_avail,
+		      const uint64_t *icols, const uint64_t *pcols, const uint64_t *out_n,
+		      const uint64_t *csize, const uint32_t *adler, const uint32_t *crc,
+		      const uint64_t *offsets, const uint64_t *block_sums, const uint8_t *in,
+		      uint8_t *out, uint64_t *cp_src, uint64_t *cp_dst, uint64_t *cp_len,
+		      uint64_t *index);
+extern "C" __global__ void
+lda_pngw_final_kernel(uint64_t n, uint64_t pixels_total, uint64_t out_avail,
+		      const uint64_t *total_at, uint64_t *result);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
