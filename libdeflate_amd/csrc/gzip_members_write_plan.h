@@ -7,11 +7,12 @@
  * (gzip_members_write_kernels.hip) read.  Free of HIP:
  * tools/test_gzip_members_write_plan.cpp runs it on the CPU.
  *
- * The pieces are the ZIP writer's (zip_write_plan.h: zipw_cut_pieces(), the
- * segment rule of large_plan.h, slots of zipw_slot(), the launch groups small /
- * whole / per segment size), so every record meets the kernel, the seg_info and
- * the size bound that libdeflate_gzip_compress() on its bytes would give it.
- * Two things differ.  Nothing is ever stored in place of the compressor's
+ * The pieces are the writers' shared ones (write_pieces_plan.h:
+ * zipw_cut_pieces(), the segment rule of large_plan.h, slots of zipw_slot(), the
+ * launch groups small / whole / per segment size), so every record meets the
+ * kernel, the seg_info and the size bound that libdeflate_gzip_compress() on its
+ * bytes would give it.  Two things differ from the ZIP writer's use of them.
+ * Nothing is ever stored in place of the compressor's
  * stream: level 0 goes through the compress kernel like every other level (its
  * stored blocks are the stream), and the slot of
  * libdeflate_deflate_compress_bound() always holds it.  And a record of 0
@@ -21,7 +22,12 @@
 #ifndef LDA_GZIP_MEMBERS_WRITE_PLAN_H
 #define LDA_GZIP_MEMBERS_WRITE_PLAN_H
 
-#include "zip_write_plan.h"
+#include <stdint.h>
+#include <stdio.h>
+#include <string>
+#include <vector>
+
+#include "write_pieces_plan.h"
 
 namespace lda {
 

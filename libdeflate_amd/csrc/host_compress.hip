@@ -395,7 +395,8 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 	return LIBDEFLATE_AMD_OK;
 }
 
-/* host_objects.h: what the ZIP writer launches its pieces through */
+/* host_objects.h: what the writers' piece pipeline (host_write_pieces.hip) launches
+ * its pieces through */
 int lda::compress_deflate_pieces(struct libdeflate_compressor *c, size_t n, const void *d_in,
 				 const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
 				 void *d_out, const uint64_t *d_out_offsets,

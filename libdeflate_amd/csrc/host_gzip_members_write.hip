@@ -3,27 +3,21 @@
  * members in device memory (include/libdeflate_amd.h:
  * libdeflate_amd_gzip_members_compress_batch).
  *
- * The ZIP writer's pipeline (host_zip_write.hip) with a simpler container:
  * gzip_members_write_plan.h checks the host arrays and cuts the records into
- * the ZIP writer's pieces; its columns and the names go up through the
- * object's pinned block in ONE copy; ONE CRC-32 batch runs over the pieces,
- * the compress batches of every launch group run into slots in the object's
- * scratch (compress_deflate_pieces()), and the kernels of
- * gzip_members_write_kernels.hip size the members, place header, name and
- * footer and - through the ZIP writer's copy kernel - the pieces.  Nothing
- * comes back, and the device is waited for only where the pinned block is
- * still on its way up from the previous call on the same object (and where
- * scratch grows).  The scratch and the pinned block are the ZIP writer's
- * (c->zipw, c->zipw_up): [record columns][piece columns][seg_info][names]
- * (what goes up), [out_n][cp_src cp_dst cp_len][sizes][offsets][block sums]
- * [csize][crc][crcs][slots].
+ * pieces; its columns and the names go up, ONE CRC-32 batch runs over the
+ * pieces, the pieces are compressed into slots (the shared piece pipeline,
+ * host_write_pieces.hip), and the kernels of gzip_members_write_kernels.hip
+ * size the members and place header, name and footer.
+ * c->zipw: [record columns][piece columns][seg_info][names] (what goes up),
+ * [out_n][cp_src cp_dst cp_len][sizes][offsets][block sums][slots][csize][crc]
+ * [crcs].
  */
 #include <string.h>
 #include <algorithm>
 #include <string>
 #include <vector>
 
-#include "host_objects.h"
+#include "host_write_pieces.h"
 #include "kernels.h"
 #include "gzip_members_write_plan.h"
 
@@ -46,16 +40,9 @@ libdeflate_amd_gzip_members_compress_bound(struct libdeflate_compressor *c, size
 	return (size_t)gzmw_bound(n_records, name_offsets, in_nbytes);
 }
 
-struct GzmwScratch {
-	/* what goes up */
-	uint64_t *ecols, *pcols;
-	uint32_t *seg;
-	uint8_t *names;
-	size_t up_bytes;
-	/* what the kernels leave */
-	uint64_t *out_n, *cp_src, *cp_dst, *cp_len, *sizes, *offs, *bsum, *csize;
+struct GzmwScratch : PiecesScratch {
+	uint64_t *ecols, *csize;
 	uint32_t *crc, *crcs;
-	uint8_t *slots;
 	size_t bytes;
 };
 
@@ -63,33 +50,14 @@ static GzmwScratch gzmw_scratch(void *base, const gzmw_plan &p)
 {
 	GzmwScratch s;
 	Carve c(base);
-	const size_t n = (size_t)p.n, np = (size_t)p.np;
 
-	s.ecols = c.take<uint64_t>(GZMW_ECOLS * n);
-	s.pcols = c.take<uint64_t>(ZIPW_PCOLS * np);
-	s.seg = c.take<uint32_t>(np);
-	s.names = c.take<uint8_t>((size_t)p.names_bytes);
-	s.up_bytes = c.at;
-	s.out_n = c.take<uint64_t>(np);
-	s.cp_src = c.take<uint64_t>(np);
-	s.cp_dst = c.take<uint64_t>(np);
-	s.cp_len = c.take<uint64_t>(np);
-	s.sizes = c.take<uint64_t>(n);
-	s.offs = c.take<uint64_t>(n);
-	s.bsum = c.take<uint64_t>(scan_blocks(n) + 1);
-	s.csize = c.take<uint64_t>(n);
-	s.crc = c.take<uint32_t>(n);
-	s.crcs = c.take<uint32_t>(np);
-	s.slots = c.take<uint8_t>((size_t)p.slots_bytes, 256);
+	s.ecols = c.take<uint64_t>(GZMW_ECOLS * (size_t)p.n);
+	pieces_carve(c, p, (size_t)p.n, (size_t)p.names_bytes, s);
+	s.csize = c.take<uint64_t>((size_t)p.n);
+	s.crc = c.take<uint32_t>((size_t)p.n);
+	s.crcs = c.take<uint32_t>((size_t)p.np);
 	s.bytes = c.at + 16;
 	return s;
-}
-
-/* pieces per compress launch of a group: segments as the segmented
- * single-buffer path slices them, whole records in one call */
-static size_t gzmw_per_launch(const zipw_group &g)
-{
-	return g.S ? (size_t)lda_large_per_slice(g.S) : (size_t)(g.hi - g.lo);
 }
 
 static int gzmw_enqueue(struct libdeflate_compressor *c, const gzmw_plan &p, const uint8_t *names,
@@ -101,52 +69,27 @@ static int gzmw_enqueue(struct libdeflate_compressor *c, const gzmw_plan &p, con
 		return LIBDEFLATE_AMD_NO_DEVICE;
 	const size_t n = (size_t)p.n, np = (size_t)p.np;
 	const GzmwScratch sz = gzmw_scratch(NULL, p);
+	const std::vector<zipw_launch> launches = zipw_launches(p);
+	uint8_t *ws, *h;
 
-	LDA_OK_TRY(c->zipw_up.begin());
-	/* all of the call's scratch before anything is queued: growing frees
-	 * memory (and waits for the device) */
-	size_t kernels = 0;
-	for (const zipw_group &g : p.groups)
-		kernels = std::max(kernels, compress_pieces_scratch(
-			c, std::min(gzmw_per_launch(g), (size_t)(g.hi - g.lo)), (size_t)g.max_in,
-			g.S != 0));
-	uint8_t *ws = (uint8_t *)c->zipw.reserve(sz.bytes);
-	uint8_t *h = (uint8_t *)c->zipw_up.pinned(sz.up_bytes);
-	if (!ws || !h || (kernels && !c->scratch.reserve(kernels)))
-		return LIBDEFLATE_AMD_OOM;
+	LDA_OK_TRY(pieces_reserve(c, launches, sz.bytes, sz.up_bytes, &ws, &h));
 	const GzmwScratch s = gzmw_scratch(ws, p), hs = gzmw_scratch(h, p);
 	if (sz.up_bytes) {
 		memcpy(hs.ecols, p.ecols.data(), p.ecols.size() * 8);
-		memcpy(hs.pcols, p.pcols.data(), p.pcols.size() * 8);
-		memcpy(hs.seg, p.seg_info.data(), p.seg_info.size() * 4);
 		if (p.names_bytes)
-			memcpy(hs.names, names, (size_t)p.names_bytes);
-		LDA_OK_TRY(c->zipw_up.send(ws, sz.up_bytes, st));
+			memcpy(hs.behind, names, (size_t)p.names_bytes);
 	}
-	const uint64_t *ecol[GZMW_ECOLS], *pcol[ZIPW_PCOLS];
+	LDA_OK_TRY(pieces_upload(c, hs, p, ws, st));
+	const uint64_t *ecol[GZMW_ECOLS], *const *pcol = s.pcol;
 	for (size_t a = 0; a < GZMW_ECOLS; a++)
 		ecol[a] = s.ecols + a * n;
-	for (size_t a = 0; a < ZIPW_PCOLS; a++)
-		pcol[a] = s.pcols + a * np;
 
 	int rc = libdeflate_amd_crc32_batch(np, d_in, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N], NULL,
 					    s.crcs, st);
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
-	for (const zipw_group &g : p.groups) {
-		const size_t per = gzmw_per_launch(g);
-		for (size_t lo = (size_t)g.lo; lo < g.hi; lo += per) {
-			const size_t nk = std::min(per, (size_t)g.hi - lo);
-			rc = compress_deflate_pieces(c, nk, d_in, pcol[ZIPW_P_IN_OFF] + lo,
-						     pcol[ZIPW_P_IN_N] + lo, s.slots,
-						     pcol[ZIPW_P_SLOT_OFF] + lo,
-						     pcol[ZIPW_P_SLOT_AV] + lo, s.out_n + lo, st,
-						     g.S ? s.seg + lo : NULL, (size_t)g.max_in);
-			if (rc != LIBDEFLATE_AMD_OK)
-				return rc;
-		}
-	}
-	const unsigned wave_grid = (unsigned)std::max((size_t)1, std::min((n + 3) / 4, (size_t)ctx->num_cus * 16));
+	LDA_OK_TRY(pieces_compress(c, s, launches, d_in, st));
+	const unsigned wave_grid = pieces_wave_grid(ctx, n);
 	if (n)
 		hipLaunchKernelGGL(lda_gzmw_member_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
 				   ecol[GZMW_E_FIRST], ecol[GZMW_E_COUNT], ecol[GZMW_E_NAME_LEN],
@@ -159,18 +102,12 @@ static int gzmw_enqueue(struct libdeflate_compressor *c, const gzmw_plan &p, con
 		hipLaunchKernelGGL(lda_gzmw_place_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
 				   c->level, mtime, out_avail, ecol[GZMW_E_FIRST], ecol[GZMW_E_COUNT],
 				   ecol[GZMW_E_NAME_OFF], ecol[GZMW_E_NAME_LEN], ecol[GZMW_E_USIZE],
-				   ecol[GZMW_E_UOFF], (const uint8_t *)s.names, pcol[ZIPW_P_PC_OFF],
+				   ecol[GZMW_E_UOFF], (const uint8_t *)s.behind, pcol[ZIPW_P_PC_OFF],
 				   pcol[ZIPW_P_PC_N], pcol[ZIPW_P_SLOT_OFF], (const uint64_t *)s.out_n,
 				   (const uint64_t *)s.csize, (const uint32_t *)s.crc,
 				   (const uint64_t *)s.offs, (const uint64_t *)s.bsum, d_out, s.cp_src,
 				   s.cp_dst, s.cp_len, d_index);
-	if (np) {
-		const size_t grid = std::min(np, (size_t)ctx->num_cus * 8);
-		hipLaunchKernelGGL(lda_zipw_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
-				   (uint64_t)np, total_at, out_avail, (uint64_t)0,
-				   (const uint64_t *)s.cp_src, (const uint64_t *)s.cp_dst,
-				   (const uint64_t *)s.cp_len, d_in, (const uint8_t *)s.slots, d_out);
-	}
+	pieces_copy(ctx, s, np, total_at, out_avail, 0, d_in, d_out, st);
 	hipLaunchKernelGGL(lda_gzmw_final_kernel, dim3(1), dim3(64), 0, st, (uint64_t)n,
 			   p.usize_total, out_avail, total_at, d_result, d_index);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -203,15 +140,8 @@ libdeflate_amd_gzip_members_compress_batch(struct libdeflate_compressor *c, size
 		DeviceGuard on(c->device);
 		if (!on.ok() || !device_ctx())
 			return LIBDEFLATE_AMD_NO_DEVICE;
-		const EnvCfg &env = env_cfg();
-		zipw_params pr;
-		pr.level = c->level;
-		pr.store = false;	/* level 0 too: its stored blocks are the compress kernel's */
-		pr.no_segments = env.no_segments;
-		pr.env_seg = env.seg_bytes;
-		pr.D = compress_prime_window();
-		pr.tile = lda_deflate_tile();
-		pr.small_max = c->level <= 9 && !env.no_small ? lda_deflate_small_max() : 0;
+		/* (level 0 too: its stored blocks are the compress kernel's) */
+		const zipw_params pr = pieces_params(c, false);
 		gzmw_plan p;
 		gzmw_plan_build(pr, n_records, name_offsets, in_offsets, in_nbytes, p);
 		return gzmw_enqueue(c, p,

@@ -78,10 +78,11 @@ struct libdeflate_compressor {
 	/* one stream from one device buffer (libdeflate_amd_compress_large_batch):
 	 * descriptor rows, seg_info, per-piece sums, scan offsets, segment slots */
 	lda::DevBuf large;
-	/* a ZIP archive, a file of gzip members or PNG files written on the device
-	 * (host_zip_write.hip, host_gzip_members_write.hip, host_png_write.hip):
-	 * the plan's columns and the names, per-piece and per-entry results, the
-	 * slots - and the PNG writer's filtered scanlines -; the columns on their
+	/* a ZIP archive, a file of gzip members or PNG files written on the device:
+	 * the common regions of host_write_pieces.hip (the piece columns, per-piece
+	 * and per-entry results, the slots), each writer's own columns in front and
+	 * its results behind them - the PNG writer's filtered scanlines last -; the
+	 * tar writer's rows and archive (host_tar_write.hip); the columns on their
 	 * way up */
 	lda::DevBuf zipw;
 	lda::Upload zipw_up;
@@ -110,9 +111,8 @@ int fanout(Obj *o, size_t n, const size_t *weight,
 	   const std::function<Obj *(const struct libdeflate_options *)> &alloc,
 	   const std::function<int(Obj *, size_t, size_t)> &body);
 
-/* host_compress.hip, for the ZIP, gzip-members and PNG writers (host_zip_write.hip,
- * host_gzip_members_write.hip, host_png_write.hip): one compress
- * batch of raw DEFLATE as the batch entry points launch it - seg_info NULL or
+/* host_compress.hip, for the writers' piece pipeline (host_write_pieces.hip): one
+ * compress batch of raw DEFLATE as the batch entry points launch it - seg_info NULL or
  * one word per chunk (large_plan.h), max_in the size bound of the chunks - the
  * kernels' scratch such a launch reserves in the object (reserve the largest
  * before the first of several is queued: growing frees memory), and the bytes

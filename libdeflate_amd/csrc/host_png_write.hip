@@ -2,29 +2,25 @@
  * host_png_write.hip - C-ABI of writing PNG files in device memory
  * (include/libdeflate_amd.h: libdeflate_amd_png_encode_batch).
  *
- * The gzip-members writer's pipeline (host_gzip_members_write.hip) behind one
- * kernel of its own: png_write_plan.h checks the image rows, gives every image
- * a room for its filtered scanlines in the object's scratch and cuts the rooms
- * into the ZIP writer's pieces; its columns and the filter kernel's work list
- * go up through the object's pinned block in ONE copy; the filter kernel
+ * png_write_plan.h checks the image rows, gives every image a room for its
+ * filtered scanlines in the object's scratch and cuts the rooms into pieces;
+ * its columns and the filter kernel's work list go up; the filter kernel
  * (png_write_kernels.hip) fills the rooms from the pixels in d_in, one launch
- * per group class; ONE Adler-32 batch runs over the pieces, the compress
- * batches of every launch group run into slots (compress_deflate_pieces()),
- * ONE CRC-32 batch runs over the COMPRESSED pieces in their slots - an IDAT
- * chunk's CRC covers compressed bytes -, and the kernels of
- * png_write_kernels.hip size the files, place their fixed parts and - through
- * the ZIP writer's copy kernel - the pieces.  Nothing comes back.  The scratch
- * and the pinned block are the ZIP writer's (c->zipw, c->zipw_up): [image
- * columns][piece columns][seg_info][work list] (what goes up), [out_n][cp_src
- * cp_dst cp_len][sizes][offsets][block sums][csize][adler crc][adlers crcs]
- * [slots][scanlines].
+ * per group class; ONE Adler-32 batch runs over the pieces, the pieces are
+ * compressed from the rooms into slots (the shared piece pipeline,
+ * host_write_pieces.hip), ONE CRC-32 batch runs over the COMPRESSED pieces in
+ * their slots - an IDAT chunk's CRC covers compressed bytes -, and the kernels
+ * of png_write_kernels.hip size the files and place their fixed parts.
+ * c->zipw: [image columns][piece columns][seg_info][work list] (what goes up),
+ * [out_n][cp_src cp_dst cp_len][sizes][offsets][block sums][slots][csize]
+ * [adler crc][adlers crcs][scanlines].
  */
 #include <string.h>
 #include <algorithm>
 #include <string>
 #include <vector>
 
-#include "host_objects.h"
+#include "host_write_pieces.h"
 #include "kernels.h"
 #include "png_write_plan.h"
 
@@ -50,16 +46,10 @@ libdeflate_amd_png_encode_bound(struct libdeflate_compressor *c, size_t n_images
 	return (size_t)pngw_bound(n_images, images, c->level);
 }
 
-struct PngwScratch {
-	/* what goes up */
-	uint64_t *icols, *pcols;
-	uint32_t *seg;
-	uint64_t *work;
-	size_t up_bytes;
-	/* what the kernels leave */
-	uint64_t *out_n, *cp_src, *cp_dst, *cp_len, *sizes, *offs, *bsum, *csize;
+struct PngwScratch : PiecesScratch {
+	uint64_t *icols, *csize;
 	uint32_t *adler, *crc, *adlers, *crcs;
-	uint8_t *slots, *scan;
+	uint8_t *scan;
 	size_t bytes;
 };
 
@@ -70,33 +60,15 @@ static PngwScratch pngw_scratch(void *base, const pngw_plan &p)
 	const size_t n = (size_t)p.n, np = (size_t)p.np;
 
 	s.icols = c.take<uint64_t>(PNGW_ICOLS * n);
-	s.pcols = c.take<uint64_t>(ZIPW_PCOLS * np);
-	s.seg = c.take<uint32_t>(np);
-	s.work = c.take<uint64_t>(p.work.size());
-	s.up_bytes = c.at;
-	s.out_n = c.take<uint64_t>(np);
-	s.cp_src = c.take<uint64_t>(np);
-	s.cp_dst = c.take<uint64_t>(np);
-	s.cp_len = c.take<uint64_t>(np);
-	s.sizes = c.take<uint64_t>(n);
-	s.offs = c.take<uint64_t>(n);
-	s.bsum = c.take<uint64_t>(scan_blocks(n) + 1);
+	pieces_carve(c, p, n, p.work.size() * 8, s);
 	s.csize = c.take<uint64_t>(n);
 	s.adler = c.take<uint32_t>(n);
 	s.crc = c.take<uint32_t>(n);
 	s.adlers = c.take<uint32_t>(np);
 	s.crcs = c.take<uint32_t>(np);
-	s.slots = c.take<uint8_t>((size_t)p.slots_bytes, 256);
 	s.scan = c.take<uint8_t>((size_t)p.scan_bytes + 64, 256);
 	s.bytes = c.at + 16;
 	return s;
-}
-
-/* pieces per compress launch of a group: segments as the segmented
- * single-buffer path slices them, whole images in one call */
-static size_t pngw_per_launch(const zipw_group &g)
-{
-	return g.S ? (size_t)lda_large_per_slice(g.S) : (size_t)(g.hi - g.lo);
 }
 
 static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, const uint8_t *d_in,
@@ -108,30 +80,17 @@ static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, con
 		return LIBDEFLATE_AMD_NO_DEVICE;
 	const size_t n = (size_t)p.n, np = (size_t)p.np;
 	const PngwScratch sz = pngw_scratch(NULL, p);
+	const std::vector<zipw_launch> launches = zipw_launches(p);
+	uint8_t *ws, *h;
 
-	LDA_OK_TRY(c->zipw_up.begin());
-	/* all of the call's scratch before anything is queued: growing frees
-	 * memory (and waits for the device) */
-	size_t kernels = 0;
-	for (const zipw_group &g : p.groups)
-		kernels = std::max(kernels, compress_pieces_scratch(
-			c, std::min(pngw_per_launch(g), (size_t)(g.hi - g.lo)), (size_t)g.max_in,
-			g.S != 0));
-	uint8_t *ws = (uint8_t *)c->zipw.reserve(sz.bytes);
-	uint8_t *h = (uint8_t *)c->zipw_up.pinned(sz.up_bytes);
-	if (!ws || !h || (kernels && !c->scratch.reserve(kernels)))
-		return LIBDEFLATE_AMD_OOM;
+	LDA_OK_TRY(pieces_reserve(c, launches, sz.bytes, sz.up_bytes, &ws, &h));
 	const PngwScratch s = pngw_scratch(ws, p), hs = pngw_scratch(h, p);
 	if (sz.up_bytes) {
 		memcpy(hs.icols, p.icols.data(), p.icols.size() * 8);
-		memcpy(hs.pcols, p.pcols.data(), p.pcols.size() * 8);
-		memcpy(hs.seg, p.seg_info.data(), p.seg_info.size() * 4);
-		memcpy(hs.work, p.work.data(), p.work.size() * 8);
-		LDA_OK_TRY(c->zipw_up.send(ws, sz.up_bytes, st));
+		memcpy(hs.behind, p.work.data(), p.work.size() * 8);
 	}
-	const uint64_t *pcol[ZIPW_PCOLS];
-	for (size_t a = 0; a < ZIPW_PCOLS; a++)
-		pcol[a] = s.pcols + a * np;
+	LDA_OK_TRY(pieces_upload(c, hs, p, ws, st));
+	const uint64_t *const *pcol = s.pcol, *work = (const uint64_t *)s.behind;
 
 	for (unsigned cls = 0; cls < PNGW_CLASSES && (stages & PNGW_STAGE_FILTER); cls++) {
 		const size_t items = (size_t)(p.items[cls + 1] - p.items[cls]);
@@ -142,7 +101,7 @@ static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, con
 				   cls == 1 ? lda_pngw_filter16_kernel : lda_pngw_filter64_kernel,
 				   dim3((unsigned)grid), dim3(256), 0, st, (uint64_t)n, (uint64_t)items,
 				   (uint32_t)filter,
-				   (const uint64_t *)s.work + PNGW_WORK_WORDS * p.items[cls],
+				   work + PNGW_WORK_WORDS * p.items[cls],
 				   (const uint64_t *)s.icols, d_in, s.scan);
 	}
 	int rc = LIBDEFLATE_AMD_OK;
@@ -151,21 +110,10 @@ static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, con
 						  NULL, s.adlers, st);
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
-	for (const zipw_group &g : p.groups) {
-		if (!(stages & PNGW_STAGE_COMPRESS))
-			break;
-		const size_t per = pngw_per_launch(g);
-		for (size_t lo = (size_t)g.lo; lo < g.hi; lo += per) {
-			const size_t nk = std::min(per, (size_t)g.hi - lo);
-			rc = compress_deflate_pieces(c, nk, s.scan, pcol[ZIPW_P_IN_OFF] + lo,
-						     pcol[ZIPW_P_IN_N] + lo, s.slots,
-						     pcol[ZIPW_P_SLOT_OFF] + lo,
-						     pcol[ZIPW_P_SLOT_AV] + lo, s.out_n + lo, st,
-						     g.S ? s.seg + lo : NULL, (size_t)g.max_in);
-			if (rc != LIBDEFLATE_AMD_OK)
-				return rc;
-		}
-	}
+	if (stages & PNGW_STAGE_COMPRESS)
+		rc = pieces_compress(c, s, launches, s.scan, st);
+	if (rc != LIBDEFLATE_AMD_OK)
+		return rc;
 	if (stages & PNGW_STAGE_COMPRESS)
 		rc = libdeflate_amd_crc32_batch(np, s.slots, pcol[ZIPW_P_SLOT_OFF], s.out_n, NULL, s.crcs,
 						st);
@@ -175,7 +123,7 @@ static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, con
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 		return LIBDEFLATE_AMD_OK;
 	}
-	const unsigned wave_grid = (unsigned)std::max((size_t)1, std::min((n + 3) / 4, (size_t)ctx->num_cus * 16));
+	const unsigned wave_grid = pieces_wave_grid(ctx, n);
 	if (n)
 		hipLaunchKernelGGL(lda_pngw_image_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
 				   (uint64_t)np, pngw_idat_head_crc(c->level), (const uint64_t *)s.icols,
@@ -192,13 +140,7 @@ static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, con
 				   (const uint32_t *)s.crc, (const uint64_t *)s.offs,
 				   (const uint64_t *)s.bsum, d_in, d_out, s.cp_src, s.cp_dst, s.cp_len,
 				   d_index);
-	if (np) {
-		const size_t grid = std::min(np, (size_t)ctx->num_cus * 8);
-		hipLaunchKernelGGL(lda_zipw_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
-				   (uint64_t)np, total_at, out_avail, (uint64_t)0,
-				   (const uint64_t *)s.cp_src, (const uint64_t *)s.cp_dst,
-				   (const uint64_t *)s.cp_len, d_in, (const uint8_t *)s.slots, d_out);
-	}
+	pieces_copy(ctx, s, np, total_at, out_avail, 0, d_in, d_out, st);
 	hipLaunchKernelGGL(lda_pngw_final_kernel, dim3(1), dim3(64), 0, st, (uint64_t)n,
 			   p.pixels_total, out_avail, total_at, d_result);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -223,15 +165,8 @@ static int pngw_call(const char *what, struct libdeflate_compressor *c, size_t n
 		DeviceGuard on(c->device);
 		if (!on.ok() || !device_ctx())
 			return LIBDEFLATE_AMD_NO_DEVICE;
-		const EnvCfg &env = env_cfg();
-		zipw_params pr;
-		pr.level = c->level;
-		pr.store = false;	/* level 0 too: its stored blocks are the compress kernel's */
-		pr.no_segments = env.no_segments;
-		pr.env_seg = env.seg_bytes;
-		pr.D = compress_prime_window();
-		pr.tile = lda_deflate_tile();
-		pr.small_max = c->level <= 9 && !env.no_small ? lda_deflate_small_max() : 0;
+		/* (level 0 too: its stored blocks are the compress kernel's) */
+		const zipw_params pr = pieces_params(c, false);
 		pngw_plan p;
 		pngw_plan_build(pr, n_images, images, flags, p);
 		return pngw_enqueue(c, p, (const uint8_t *)d_in, (uint8_t *)d_out, out_avail, d_result,

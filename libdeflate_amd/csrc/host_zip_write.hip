@@ -3,25 +3,20 @@
  * (include/libdeflate_amd.h: libdeflate_amd_zip_compress_batch).
  *
  * zip_write_plan.h checks the host arrays, decides ZIP64 and cuts the entries
- * into pieces; its columns and the names go up through a pinned block in ONE
- * copy (Upload, host_common.h), as the descriptors of
- * libdeflate_amd_zip_read_batch do.  ONE CRC-32
- * batch runs over the pieces, the compress batches of every launch group run
- * into slots in the object's scratch (compress_deflate_pieces(): the launches
- * of the batch entry points, sliced like the segmented single-buffer path),
- * and the kernels of zip_write_kernels.hip decide deflate or stored per entry
- * and place headers, data, directory and end records.  Nothing comes back, and
- * the device is waited for only where the pinned block is still on its way up
- * from the previous call on the same object (and where scratch grows).
+ * into pieces; its columns and the names go up, ONE CRC-32 batch runs over the
+ * pieces, the pieces are compressed into slots (the shared piece pipeline,
+ * host_write_pieces.hip), and the kernels of zip_write_kernels.hip decide
+ * deflate or stored per entry and place headers, data, directory and end
+ * records.
  * c->zipw: [entry columns][piece columns][seg_info][names] (what goes up),
- * [out_n][cp_src cp_dst cp_len][sizes][offsets][block sums][e_info][crcs][slots].
+ * [out_n][cp_src cp_dst cp_len][sizes][offsets][block sums][slots][e_info][crcs].
  */
 #include <string.h>
 #include <algorithm>
 #include <string>
 #include <vector>
 
-#include "host_objects.h"
+#include "host_write_pieces.h"
 #include "kernels.h"
 #include "zip_write_plan.h"
 
@@ -44,16 +39,9 @@ libdeflate_amd_zip_compress_bound(size_t n_entries, const uint64_t *name_offsets
 	return (size_t)zipw_bound(n_entries, name_offsets, in_nbytes, flags, NULL, NULL, NULL);
 }
 
-struct ZipwScratch {
-	/* what goes up */
-	uint64_t *ecols, *pcols;
-	uint32_t *seg;
-	uint8_t *names;
-	size_t up_bytes;
-	/* what the kernels leave */
-	uint64_t *out_n, *cp_src, *cp_dst, *cp_len, *sizes, *offs, *bsum, *e_info;
+struct ZipwScratch : PiecesScratch {
+	uint64_t *ecols, *e_info;
 	uint32_t *crcs;
-	uint8_t *slots;
 	size_t bytes;
 };
 
@@ -61,33 +49,13 @@ static ZipwScratch zipw_scratch(void *base, const zipw_plan &p, size_t names_byt
 {
 	ZipwScratch s;
 	Carve c(base);
-	const size_t n = (size_t)p.n, np = (size_t)p.np;
 
-	s.ecols = c.take<uint64_t>(ZIPW_ECOLS * n);
-	s.pcols = c.take<uint64_t>(ZIPW_PCOLS * np);
-	s.seg = c.take<uint32_t>(np);
-	s.names = c.take<uint8_t>(names_bytes);
-	s.up_bytes = c.at;
-	s.out_n = c.take<uint64_t>(np);
-	s.cp_src = c.take<uint64_t>(np);
-	s.cp_dst = c.take<uint64_t>(np);
-	s.cp_len = c.take<uint64_t>(np);
-	s.sizes = c.take<uint64_t>(n);
-	s.offs = c.take<uint64_t>(n);
-	s.bsum = c.take<uint64_t>(scan_blocks(n) + 1);
-	s.e_info = c.take<uint64_t>(n);
-	s.crcs = c.take<uint32_t>(np);
-	s.slots = c.take<uint8_t>((size_t)p.slots_bytes, 256);
+	s.ecols = c.take<uint64_t>(ZIPW_ECOLS * (size_t)p.n);
+	pieces_carve(c, p, (size_t)p.n, names_bytes, s);
+	s.e_info = c.take<uint64_t>((size_t)p.n);
+	s.crcs = c.take<uint32_t>((size_t)p.np);
 	s.bytes = c.at + 16;
 	return s;
-}
-
-/* pieces per compress launch of a group: segments as the segmented
- * single-buffer path slices them, whole entries in one call (which slices
- * itself where its token lists need it) */
-static size_t zipw_per_launch(const zipw_group &g)
-{
-	return g.S ? (size_t)lda_large_per_slice(g.S) : (size_t)(g.hi - g.lo);
 }
 
 static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, const uint8_t *names,
@@ -100,52 +68,27 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 	const size_t n = (size_t)p.n, np = (size_t)p.np;
 	const uint64_t tail = p.cd_size + p.end_bytes;
 	const ZipwScratch sz = zipw_scratch(NULL, p, names_bytes);
+	const std::vector<zipw_launch> launches = zipw_launches(p);
+	uint8_t *ws, *h;
 
-	LDA_OK_TRY(c->zipw_up.begin());
-	/* all of the call's scratch before anything is queued: growing frees
-	 * memory (and waits for the device) */
-	size_t kernels = 0;
-	for (const zipw_group &g : p.groups)
-		kernels = std::max(kernels, compress_pieces_scratch(
-			c, std::min(zipw_per_launch(g), (size_t)(g.hi - g.lo)), (size_t)g.max_in,
-			g.S != 0));
-	uint8_t *ws = (uint8_t *)c->zipw.reserve(sz.bytes);
-	uint8_t *h = (uint8_t *)c->zipw_up.pinned(sz.up_bytes);
-	if (!ws || !h || (kernels && !c->scratch.reserve(kernels)))
-		return LIBDEFLATE_AMD_OOM;
+	LDA_OK_TRY(pieces_reserve(c, launches, sz.bytes, sz.up_bytes, &ws, &h));
 	const ZipwScratch s = zipw_scratch(ws, p, names_bytes), hs = zipw_scratch(h, p, names_bytes);
 	if (sz.up_bytes) {
 		memcpy(hs.ecols, p.ecols.data(), p.ecols.size() * 8);
-		memcpy(hs.pcols, p.pcols.data(), p.pcols.size() * 8);
-		memcpy(hs.seg, p.seg_info.data(), p.seg_info.size() * 4);
-		memcpy(hs.names, names, names_bytes);
-		LDA_OK_TRY(c->zipw_up.send(ws, sz.up_bytes, st));
+		memcpy(hs.behind, names, names_bytes);
 	}
-	const uint64_t *ecol[ZIPW_ECOLS], *pcol[ZIPW_PCOLS];
+	LDA_OK_TRY(pieces_upload(c, hs, p, ws, st));
+	const uint64_t *ecol[ZIPW_ECOLS], *const *pcol = s.pcol;
 	for (size_t a = 0; a < ZIPW_ECOLS; a++)
 		ecol[a] = s.ecols + a * n;
-	for (size_t a = 0; a < ZIPW_PCOLS; a++)
-		pcol[a] = s.pcols + a * np;
 	const bool compressed = !p.groups.empty();
 
 	int rc = libdeflate_amd_crc32_batch(np, d_in, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N], NULL,
 					    s.crcs, st);
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
-	for (const zipw_group &g : p.groups) {
-		const size_t per = zipw_per_launch(g);
-		for (size_t lo = (size_t)g.lo; lo < g.hi; lo += per) {
-			const size_t nk = std::min(per, (size_t)g.hi - lo);
-			rc = compress_deflate_pieces(c, nk, d_in, pcol[ZIPW_P_IN_OFF] + lo,
-						     pcol[ZIPW_P_IN_N] + lo, s.slots,
-						     pcol[ZIPW_P_SLOT_OFF] + lo,
-						     pcol[ZIPW_P_SLOT_AV] + lo, s.out_n + lo, st,
-						     g.S ? s.seg + lo : NULL, (size_t)g.max_in);
-			if (rc != LIBDEFLATE_AMD_OK)
-				return rc;
-		}
-	}
-	const unsigned wave_grid = (unsigned)std::max((size_t)1, std::min((n + 3) / 4, (size_t)ctx->num_cus * 16));
+	LDA_OK_TRY(pieces_compress(c, s, launches, d_in, st));
+	const unsigned wave_grid = pieces_wave_grid(ctx, n);
 	if (n)
 		hipLaunchKernelGGL(lda_zipw_entry_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
 				   ecol[ZIPW_E_FIRST], ecol[ZIPW_E_COUNT], ecol[ZIPW_E_NAME_LEN],
@@ -159,18 +102,12 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 				   (uint32_t)p.zip64, dos_datetime, out_avail, tail, ecol[ZIPW_E_FIRST],
 				   ecol[ZIPW_E_COUNT], ecol[ZIPW_E_NAME_OFF], ecol[ZIPW_E_NAME_LEN],
 				   ecol[ZIPW_E_CEN], ecol[ZIPW_E_USIZE], ecol[ZIPW_E_UOFF],
-				   (const uint8_t *)s.names, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
+				   (const uint8_t *)s.behind, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
 				   pcol[ZIPW_P_SLOT_OFF], (const uint64_t *)s.out_n,
 				   (const uint64_t *)s.e_info, (const uint64_t *)s.offs,
 				   (const uint64_t *)s.bsum, d_out, s.cp_src, s.cp_dst, s.cp_len,
 				   d_index);
-	if (np) {
-		const size_t grid = std::min(np, (size_t)ctx->num_cus * 8);
-		hipLaunchKernelGGL(lda_zipw_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st,
-				   (uint64_t)np, total_at, out_avail, tail,
-				   (const uint64_t *)s.cp_src, (const uint64_t *)s.cp_dst,
-				   (const uint64_t *)s.cp_len, d_in, (const uint8_t *)s.slots, d_out);
-	}
+	pieces_copy(ctx, s, np, total_at, out_avail, tail, d_in, d_out, st);
 	hipLaunchKernelGGL(lda_zipw_final_kernel, dim3(1), dim3(1024), 0, st, (uint64_t)n,
 			   (uint32_t)p.zip64, out_avail, p.cd_size, tail, ecol[ZIPW_E_USIZE],
 			   (const uint64_t *)s.e_info, total_at, d_out,
@@ -204,15 +141,7 @@ libdeflate_amd_zip_compress_batch(struct libdeflate_compressor *c, size_t n_entr
 		DeviceGuard on(c->device);
 		if (!on.ok() || !device_ctx())
 			return LIBDEFLATE_AMD_NO_DEVICE;
-		const EnvCfg &env = env_cfg();
-		zipw_params pr;
-		pr.level = c->level;
-		pr.store = c->level == 0 || (flags & LIBDEFLATE_AMD_ZIP_STORE);
-		pr.no_segments = env.no_segments;
-		pr.env_seg = env.seg_bytes;
-		pr.D = compress_prime_window();
-		pr.tile = lda_deflate_tile();
-		pr.small_max = c->level <= 9 && !env.no_small ? lda_deflate_small_max() : 0;
+		const zipw_params pr = pieces_params(c, c->level == 0 || (flags & LIBDEFLATE_AMD_ZIP_STORE));
 		zipw_plan p;
 		const uint8_t *nm = n_entries ? (const uint8_t *)names + name_offsets[0] : NULL;
 		zipw_plan_build(pr, n_entries, (const uint8_t *)names, name_offsets, in_offsets,

@@ -3,7 +3,7 @@
  * (host_png_write.hip): the refusals, the bound, and the plan over many images
  * - every image's room for its filtered scanlines in the object's scratch,
  * those rooms cut into the pieces the compress, Adler-32 and CRC-32 batches run
- * on (zip_write_plan.h: zipw_cut_pieces(), as it is, store false), the fixed
+ * on (write_pieces_plan.h: zipw_cut_pieces(), store false), the fixed
  * part of every file, the per-image columns the kernels of
  * png_write_kernels.hip read and the filter kernel's work list.  Free of HIP:
  * tools/test_png_write_plan.cpp runs it on the CPU.
@@ -17,7 +17,7 @@
 #define LDA_PNG_WRITE_PLAN_H
 
 #include "png_plan.h"
-#include "zip_write_plan.h"
+#include "write_pieces_plan.h"
 
 namespace lda {
 

@@ -48,6 +48,7 @@ Which step touches which field of the object (csrc/host_objects.h):
     c-dict                    compress-dict   no        c->scratch
     c-zip                     zip-write       no        c->zipw, c->zipw_up, c->scratch
     c-gzm                     gzm-write       no        c->zipw, c->zipw_up, c->scratch
+    c-png                     png-write       no        c->zipw, c->zipw_up, c->scratch
     c-tar                     tar-write       no        c->zipw, c->zipw_up
     c-targz                   tar-write       no        c->zipw, c->zipw_up, c->large, c->scratch
     c-large                   compress-large  no        c->large, c->scratch
@@ -67,11 +68,14 @@ import numpy as np
 from tests import bgzf_files, bgzf_walk, datagen
 from tests import deflate_synth as S
 from tests import gzip_members_files as gf
+from tests import png_files as pf
 from tests import prefix_expect, sizes_expect
 from tests import tar_files as tf
 from tests import tar_write_cases as tw
 from tests import zip_files as zf
 from tests import zip_large_files as zl
+from tools.models import png_model as pm
+from tools.models import png_write as pw
 from tools.models import tar_walk, zip_walk
 
 SUCCESS, BAD_DATA, SHORT_OUTPUT, INSUFFICIENT_SPACE = 0, 1, 2, 3
@@ -1294,6 +1298,86 @@ class CGzm(_Entries):
         return got
 
 
+_png_streams = {}
+
+
+def _png_zlib(level, raws):
+    """a fresh object's own libdeflate_zlib_compress() of every image's
+    scanlines, the streams the CPU model assembles the files around (as
+    tests/test_png_write_gpu.py takes them); once per level"""
+    from libdeflate_amd import api
+    if level not in _png_streams:
+        c = api.Compressor(level)
+        _png_streams[level] = [c.compress("zlib", raw) for raw in raws]
+        c.close()
+    return _png_streams[level]
+
+
+class CPng(CStep):
+    """encode_png_batch: byte for byte the files of the CPU model
+    (tools/models/png_write.py) around the object's own zlib streams of the
+    model's filtered scanlines, with its result words and index rows"""
+    family, fields = "png-write", "c->zipw, c->zipw_up, c->scratch"
+
+    def __init__(self, name, images):
+        """images: (width, height, depth, colour, pixels); in one buffer at
+        offsets of their own, with other bytes between them"""
+        self.name, self.images = name, images
+        buf, self.rows = bytearray(b"\xEE" * 3), []
+        for k, (w, h, d, c, px) in enumerate(images):
+            self.rows.append([len(buf), len(px), w | h << 32, d | c << 8, 0, 0, 0, 0])
+            buf += px + b"\xEE" * (1 + 5 * k % 16)
+        self.buf = bytes(buf)
+        self.raws = [pw.image_scanlines(r, self.buf)[0] for r in self.rows]
+        self.expected = self.raws       # what a CPU inflate of every IDAT has to give back
+
+    def validate(self):
+        assert [pw.geometry(r)[:4] for r in self.rows] == \
+            [(1, 1, 8, 0), (7, 5, 8, 2), (33, 17, 16, 6), (43690, 3, 8, 0)]
+        # one call with a whole-entry group and a segmented one: the last
+        # image is the first size above the segment rule's edge
+        assert [len(raw) for raw in self.raws] == [2, 110, 4505, 131073]
+        assert pw.bound(self.rows) > 0
+        # the model's scanlines unfilter to the pixels, and its files around
+        # zlib's streams are files the reader's model decodes to them
+        files = pw.encode(self.rows, self.buf, [zlib.compress(raw) for raw in self.raws])[0]
+        for (w, h, d, c, px), row, raw, f in zip(self.images, self.rows, self.raws, files):
+            rb, unit = pw.geometry(row)[4:]
+            assert pm.unfilter(raw, h, rb, unit) == (True, px), self.name
+            assert pm.read(f)[2:] == (SUCCESS, px), self.name
+
+    def prepare(self, torch, obj=None):
+        h = Handle()
+        h.d_in = _stage(torch, h, self.buf)
+        h.level = obj.level
+        h.bound = obj.png_encode_bound(self.rows)
+        h.out = Guarded(torch, h.bound)
+        h.res = Guarded(torch, 4, torch.int64, UNSET)
+        h.idx = Guarded(torch, 8 * len(self.rows), torch.int64, -1)
+        return h
+
+    def enqueue(self, obj, h, stream):
+        obj.encode_png_batch(self.rows, h.d_in, h.out.t, h.res.t, h.idx.t, stream=stream,
+                             in_avail=len(self.buf), out_avail=h.bound)
+
+    def check(self, h):
+        words = [int(x) for x in h.res.host(self.name)]
+        host = h.out.host(self.name)
+        assert words[0] == SUCCESS and 0 < words[1] <= h.bound, (self.name, words)
+        got = host[:words[1]].tobytes()
+        assert (host[words[1]:] == CANARY).all(), (self.name, "bytes written behind the files")
+        rows = h.idx.host(self.name).view(np.uint64).reshape(-1, 8).tolist()
+        # a CPU inflate of every IDAT payload: the model's filtered scanlines
+        for k, (r, raw) in enumerate(zip(rows, self.raws)):
+            assert 0 < r[5] and r[4] + 8 + r[5] <= len(got), (self.name, k, r)
+            assert _inflate("zlib", got[r[4] + 8:r[4] + 8 + r[5]]) == raw, (self.name, k, "round trip")
+        files, want_words, want_rows = pw.encode(self.rows, self.buf, _png_zlib(h.level, self.raws))
+        assert words == want_words, (self.name, words, want_words)
+        assert got == b"".join(files), (self.name, "files differ from the model's")
+        assert rows == want_rows, (self.name, "index rows")
+        return got
+
+
 class CTar(_Entries):
     """write_tar_batch: byte for byte tarfile's archive"""
     family, fields = "tar-write", "c->zipw, c->zipw_up"
@@ -1508,6 +1592,9 @@ def compressor_steps():
     gnames = [None, b"a", b"", "w/漢字.warc".encode("utf-8"), b"b", None, b"big.bin", b"noise"]
     add(CGzm("c-gzm", gnames, _entries(0x2B1, (0, 1, 31, 32, 4096, 4097, 131073)) +
              [datagen.random_chunk(7000, 7)]))
+    add(CPng("c-png", [(w, h, d, c, build(w, h, d, c, 0x9C + w)) for w, h, d, c, build in
+                       ((1, 1, 8, 0, pf.pixels_random), (7, 5, 8, 2, pf.pixels_random),
+                        (33, 17, 16, 6, pf.pixels_smooth), (43690, 3, 8, 0, pf.pixels_smooth))]))
     tnames = ["a", "dir/file01.txt", "d" * 101, "é€" * 60, "g" * 600, "dir/file05.txt", "e6", "e7"]
     tsizes = (0, 1, 511, 512, 513, 65536, 65537, 17)
     tdatas = [tw.payload(k, s) for k, s in enumerate(tsizes)]

@@ -9,8 +9,8 @@ from tests import object_steps as O
 # the call families the issue names; a catalogue that lost one would hide it
 D_FAMILIES = {"batch", "batch-dict", "prefix", "sizes", "packed", "zip", "zip-large", "tar", "bgzf",
               "gzip-members", "stream", "seek", "host", "refused"}
-C_FAMILIES = {"compress", "compress-dict", "zip-write", "gzm-write", "tar-write", "compress-large",
-              "bgzf-write", "host"}
+C_FAMILIES = {"compress", "compress-dict", "zip-write", "gzm-write", "png-write", "tar-write",
+              "compress-large", "bgzf-write", "host"}
 
 
 @pytest.fixture(scope="module")
@@ -76,6 +76,9 @@ class _Bounds:
 
     def gzip_members_compress_bound(self, sizes, names=None):
         return sum(sizes) + 10000
+
+    def png_encode_bound(self, images):
+        return O.pw.bound(images)
 
     def tar_write_size(self, names, sizes):
         return len(O.tw.tarfile_bytes(names, [bytes(n) for n in sizes]))

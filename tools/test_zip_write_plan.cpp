@@ -4,7 +4,8 @@
  * bound and the ZIP64 decision, the refusals, and the plan's columns against a
  * plain model - pieces that tile their entry, primes that never reach in
  * front of it, slots that never overlap, launch groups that cover every piece
- * once.  Stand-alone: tests/test_zip_write_plan.py builds it with the host
+ * once, and the list of compress launches (csrc/write_pieces_plan.h) over those
+ * groups.  Stand-alone: tests/test_zip_write_plan.py builds it with the host
  * compiler under the address and undefined-behaviour sanitizers and runs it.
  */
 #include <stdio.h>
@@ -36,6 +37,35 @@ static uint64_t model_slot(uint64_t len)
 {
 	uint64_t b = len + 5 * ((len + 4999) / 5000 ? (len + 4999) / 5000 : 1) + 32;
 	return (b + 15) & ~(uint64_t)15;
+}
+
+/* the launch list: every piece of every group exactly once, in piece order, no
+ * launch across two groups, a whole-entry group in one launch, a segmented
+ * group in launches of lda_large_per_slice(S) pieces but for the last */
+static void check_launches(const zipw_pieces &p)
+{
+	const std::vector<zipw_launch> ls = zipw_launches(p);
+	size_t at = 0;
+	for (const zipw_group &g : p.groups) {
+		/* the model: 32 MiB of segments a launch, one at least */
+		const uint64_t per = !g.S ? g.hi - g.lo : 32 * MiB / g.S ? 32 * MiB / g.S : 1;
+		const uint64_t want = (g.hi - g.lo + per - 1) / per;
+		CHECK(g.S ? per == lda_large_per_slice(g.S) : want == 1);
+		for (uint64_t i = 0; i < want; i++, at++) {
+			CHECK(at < ls.size());
+			if (at >= ls.size())
+				return;
+			const zipw_launch &l = ls[at];
+			CHECK(l.lo == g.lo + i * per);
+			CHECK(l.count == (i + 1 < want ? per : g.hi - g.lo - i * per) && l.count >= 1);
+			CHECK(l.lo + l.count <= g.hi);
+			CHECK(l.max_in == g.max_in && l.segmented == (g.S != 0));
+		}
+		CHECK(ls[at - 1].lo + ls[at - 1].count == g.hi);
+	}
+	CHECK(at == ls.size());
+	if (p.groups.empty())
+		CHECK(ls.empty());
 }
 
 static void check_plan(const zipw_params &pr, const std::vector<std::string> &names,
@@ -114,6 +144,7 @@ static void check_plan(const zipw_params &pr, const std::vector<std::string> &na
 		slot_at += P(ZIPW_P_SLOT_AV, j);
 	}
 	CHECK(p.slots_bytes == slot_at);
+	check_launches(p);
 	/* the launch groups: every piece once, of one kind each */
 	if (pr.store) {
 		CHECK(p.groups.empty() && p.slots_bytes == 0);
@@ -194,6 +225,36 @@ static void plans(void)
 	}
 	/* an entry just below 4 GiB: 65 536 segments whose offsets pass 2^32 */
 	check_plan(pr, { "big", "tail" }, { 5000000000ull, 1 }, { 0xFFFFFFFFull, 9 }, 0);
+	/* segmented groups of exactly one launch's pieces, one more, and twice as
+	 * many: 512 segments of 64 KiB a launch, and 1600 of 20 000 bytes */
+	for (uint64_t env_seg : { (uint64_t)0, (uint64_t)20000 }) {
+		pr.env_seg = env_seg;
+		const uint64_t S = env_seg ? env_seg : 65536, per = 32 * MiB / S;
+		for (uint64_t pieces : { per, per + 1, 2 * per }) {
+			check_plan(pr, { "seg", "small" }, { 64, 3 }, { pieces * S, 50 }, 0);
+			check_plan(pr, { "seg" }, { 0 }, { (pieces - 1) * S + 1 }, 0);
+			zipw_plan p;
+			const uint64_t noff[2] = { 0, 1 }, off = 0, size = pieces * S;
+			zipw_plan_build(pr, 1, (const uint8_t *)"s", noff, &off, &size, 0, p);
+			const std::vector<zipw_launch> ls = zipw_launches(p);
+			CHECK(p.groups.size() == 1 && p.np == pieces && ls.size() == (pieces + per - 1) / per);
+			CHECK(ls.size() && ls[0].count == per && ls.back().count == (pieces % per ? pieces % per : per));
+		}
+	}
+	pr.env_seg = 0;
+	/* a store plan has pieces and no groups: nothing is launched */
+	{
+		zipw_params st = pr;
+		st.store = true;
+		zipw_plan p;
+		const uint64_t noff[3] = { 0, 1, 2 }, off[2] = { 0, 9 }, size[2] = { 9, 40 * MiB };
+		zipw_plan_build(st, 2, (const uint8_t *)"ab", noff, off, size, ZIPW_STORE, p);
+		CHECK(p.np == 1 + 640 && p.groups.empty() && zipw_launches(p).empty());
+		check_plan(st, { "a", "b" }, { 0, 9 }, { 9, 40 * MiB }, ZIPW_STORE);
+		/* n == 0 */
+		zipw_plan_build(pr, 0, NULL, noff, NULL, NULL, 0, p);
+		CHECK(p.np == 0 && p.groups.empty() && zipw_launches(p).empty());
+	}
 }
 
 static void bounds_and_refusals(void)
