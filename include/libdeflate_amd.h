@@ -293,6 +293,18 @@ libdeflate_amd_compress_batch_bounded(struct libdeflate_compressor *compressor,
 				      void *stream);
 
 /*
+ * How the last batch call on this compressor was scheduled (diagnostics; tests
+ * use it to see which schedule ran): [0] 1 = the two-kernel path, [1] 1 = its
+ * last chunks (the tail) ran on the compressor's own stream beside the others
+ * (the head) on the caller's, joined again before the call's work ends on the
+ * caller's stream (LDA_COMPRESS_OVERLAP=0: never); [2] chunks of the head,
+ * [3] of the tail, summed over the call's launches.
+ */
+LIBDEFLATEAPI void
+libdeflate_amd_compress_last_schedule(const struct libdeflate_compressor *compressor,
+				      uint32_t out[4]);
+
+/*
  * Decompress: d_results[i] receives the enum libdeflate_result of chunk i.
  * d_actual_in / d_actual_out may be NULL; a NULL d_actual_out has the
  * reference's meaning (the stream must fill d_out_avail[i] exactly, else

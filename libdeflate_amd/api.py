@@ -373,6 +373,11 @@ class Compressor:
                 out_nbytes.data_ptr(), int(max_chunk), _stream_ptr(stream)),
                 "compress_batch_bounded")
 
+    def last_schedule(self):
+        """libdeflate_amd_compress_last_schedule: how the last batch call on
+        this object was scheduled -> dict(split, overlapped, head, tail)."""
+        return binding.compress_last_schedule(self._h)
+
     def compress_dict(self, fmt, dictionary, data, out_avail=None):
         """libdeflate_amd_compress_dict: one host buffer with a preset
         dictionary ("deflate" or "zlib").  Returns the compressed bytes, or

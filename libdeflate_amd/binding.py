@@ -79,7 +79,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_device_ready", "libdeflate_amd_last_error",
     "libdeflate_amd_reload_env",
     "libdeflate_amd_compress_batch", "libdeflate_amd_decompress_batch",
-    "libdeflate_amd_compress_batch_bounded",
+    "libdeflate_amd_compress_batch_bounded", "libdeflate_amd_compress_last_schedule",
     "libdeflate_amd_crc32_batch", "libdeflate_amd_adler32_batch",
     "libdeflate_amd_compress_batch_host",
     "libdeflate_amd_decompress_batch_host",
@@ -172,6 +172,7 @@ def load():
         P, P, P)
     sig("libdeflate_amd_compress_batch_bounded", c_int, P, c_int, SZ, P, P, P, P, P,
         P, P, SZ, P)
+    sig("libdeflate_amd_compress_last_schedule", None, P, POINTER(c_uint32))
     sig("libdeflate_amd_decompress_batch", c_int, P, c_int, SZ, P, P, P, P, P,
         P, P, P, P, P)
     sig("libdeflate_amd_compress_batch_host", c_int, P, c_int, SZ, P, P, P, P,
@@ -309,6 +310,15 @@ def stream_stats():
             "repairs", "chunks_decoded", "bytes", "us_in", "us_find", "us_count",
             "us_decode", "us_sum", "us_out", "windows", "host_chunks")
     return dict(zip(keys, [int(v) for v in out]))
+
+
+def compress_last_schedule(compressor):
+    """libdeflate_amd_compress_last_schedule of a compressor handle: how its
+    last batch call was scheduled (see include/libdeflate_amd.h)."""
+    out = (c_uint32 * 4)()
+    load().libdeflate_amd_compress_last_schedule(compressor, out)
+    return {"split": int(out[0]), "overlapped": int(out[1]), "head": int(out[2]),
+            "tail": int(out[3])}
 
 
 def last_error():

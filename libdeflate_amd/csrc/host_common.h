@@ -109,6 +109,8 @@ struct EnvCfg {
 	bool bgzf_serial = false;	/* LDA_BGZF_SERIAL: the BGZF reader finds the members by the serial walk */
 	bool tar_serial = false;	/* LDA_TAR_SERIAL: the tar reader finds the records by the serial walk */
 	bool fanout_oversub = false;	/* LDA_FANOUT_OVERSUB: more shards than visible devices (a test aid: several shards share a GPU) */
+	bool compress_overlap = true;	/* LDA_COMPRESS_OVERLAP: 0 = the split path's kernels in series on the caller's stream */
+	int compress_tail_rounds = 0;	/* LDA_COMPRESS_TAIL_ROUNDS: buffers per CU of a slice's tail (0 = compress_plan.h's) */
 };
 const EnvCfg &env_cfg();
 
@@ -185,6 +187,21 @@ struct StreamPair {
 	 * has nothing in flight.  (The blocking calls that do take a stream wait
 	 * for it with an event instead: decompress_large_body().) */
 	bool enter();
+	void release();
+};
+
+/*
+ * The stream of a compressor that the tail of a split compress launch runs on
+ * beside its head on the caller's stream (compress_batch_impl()), and the two
+ * events that order them: `in` on the caller's stream, which the tail waits
+ * for, `tail` behind the tail, which the caller's stream waits for.  Made on
+ * first use; where that fails once, the object keeps the serial schedule.
+ */
+struct SideStream {
+	hipStream_t side = nullptr;
+	hipEvent_t in = nullptr, tail = nullptr;
+	bool failed = false;
+	bool ensure();
 	void release();
 };
 

@@ -17,6 +17,7 @@
 #include "host_objects.h"
 #include "kernels.h"
 #include "large_plan.h"
+#include "compress_plan.h"
 
 using namespace lda;
 
@@ -108,6 +109,7 @@ libdeflate_free_compressor(struct libdeflate_compressor *c)
 	c->zipw.release();
 	c->zipw_up.release();
 	c->streams.release();
+	c->side.release();	/* (idle: freeing the scratch has waited for the device) */
 	free_func_t f = c->free_func;
 	c->~libdeflate_compressor();
 	f(c);
@@ -165,84 +167,42 @@ static dict_shape shape_dict(int level, size_t dict_nbytes)
 }
 
 /*
- * The split path's scratch (kernels.h, LDA_BLK_*) is at most this much per
- * launch: 4 B of token list per byte of the size bound plus the block
- * descriptors, so 4096 buffers of 64 KiB (1.08 GiB) are one launch.  A batch
- * that needs more runs as consecutive slices of buffers on the same stream; a
- * bound whose single buffer needs more keeps the fused kernel.
+ * The plan of a batch call (compress_plan.h) for this compressor on its device.
+ * The LZ77 launch's tail: a persistent grid that hands buffers out from a
+ * counter ends spread over one buffer's time, about half a buffer of idle CU
+ * at the end of every launch (estimated 0.18 ms of the bench batch's 5.81, 3 %;
+ * measured: 0.14 ms x 256 CUs of entropy work run inside it, the step ends
+ * 0.09 ms earlier - DESIGN 3.3, profiles/r15_overlap.md).  The split path therefore runs a slice as a head on the
+ * caller's stream and a tail of R buffers per CU on the compressor's own:
+ *
+ *   caller's:  memset, checksums - in - K_head - E_head ------- wait tail - F
+ *   side:                     wait in - K_tail - E_tail - tail
+ *
+ * K_tail's workgroups take the CUs K_head's leave, E_head's the CUs K_tail's
+ * leave; stream order and the two events are the only hand-overs.  The entropy
+ * stage as a whole cannot be hidden: LZ77 needs 5.81 x 256 CU-ms and the
+ * entropy stage 0.42 x 256 CU-ms, they cannot share a CU (157 of 160 KiB of
+ * LDS against 4 x 20 KiB), so only the tail is there to win.  `overlap` false:
+ * the serial schedule (LDA_COMPRESS_OVERLAP=0, or no side stream).
  */
-#define LDA_SPLIT_SCRATCH ((size_t)1280 << 20)
-/* buffers per CU from which a call takes the split path (see plan_batch());
- * a tuning build may set another (make VARIANT=... EXTRA=-DLDA_SPLIT_MIN_PER_CU=1) */
-#ifndef LDA_SPLIT_MIN_PER_CU
-#define LDA_SPLIT_MIN_PER_CU 4
-#endif
-
-/*
- * The kernels' scratch of one compress_batch_impl() call: [per-workgroup
- * state: u64 x lda_deflate_seq_words() x grid][chunk counters: four u32 per
- * slice (the LZ77 stage's, the fused kernel's behind it, the count of buffers
- * left to that one, the entropy kernel's)][sums: u32 x n], then the dictionary block (see
- * lda_dict_prep_kernel()) or, on the split path, one slice's token lists and
- * block descriptors.  The same sum sizes the reservations the host-pointer
- * entry points make up front.
- */
-struct batch_plan {
-	bool small, split;
-	size_t grid, per_slice, nslices;
-	uint32_t tok_stride, blk_stride;	/* u32 entries / descriptors per buffer */
-	size_t cnt_at, sums_at, tok_at, blk_at, dict_at, total;
-};
-
 static batch_plan plan_batch(const struct libdeflate_compressor *c, size_t n,
-			     size_t max_in, bool seg, bool dict)
+			     size_t max_in, bool seg, bool dict, bool overlap = true)
 {
-	batch_plan p = {};
-	/* buffers of at most 4 KiB (filesystem blocks): the 256-thread kernel,
-	 * several workgroups per CU (deflate_small.hip); levels 10-12 keep the
-	 * big one (their parse wants its LDS); a dictionary needs the ring of
-	 * the big kernel */
-	p.small = max_in <= lda_deflate_small_max() && c->level <= 9 && !seg && !dict &&
-		  !env_cfg().no_small;
-	/* levels 0-9 of the big kernel split the block end off into the entropy
-	 * kernel (deflate_entropy.hip) wherever the host knows a size bound to
-	 * size the token lists by, and the call has buffers enough to fill the
-	 * CUs several times over: the entropy kernel's work per buffer (0.11 ms
-	 * for 64 KiB at level 6: 0.42 ms per 4096 of the bench mix, four to a
-	 * CU; 0.19 before round 9) is what the split saves only where other
-	 * buffers' block ends run beside it - with one buffer per CU it is a tail
-	 * the fused kernel does not have (4096 x 64 KiB: 7.16 -> 6.57 ms in
-	 * round 7, 6.23 in round 9).  A 16 MiB single-buffer call (256
-	 * segments) forced onto the split path measured 1.24 -> 1.49 ms in round
-	 * 7; in round 9 fused and split are 1.26 - 1.39 and 1.29 - 1.40 ms, inside
-	 * each other's spread, so the threshold stays */
-	const size_t tile = lda_deflate_tile();
-	const size_t tok_stride = align_up(max_in, 16);
-	const size_t blk_stride = std::max<size_t>(1, (tok_stride + tile - 1) / tile);
-	const size_t per_buf = tok_stride * 4 + blk_stride * LDA_BLK_WORDS * 4 + 4;
-	const size_t num_cus = (size_t)device_ctx()->num_cus;
-	p.split = !p.small && c->level <= 9 && !dict && max_in != SIZE_MAX &&
-		  n >= LDA_SPLIT_MIN_PER_CU * num_cus &&
-		  per_buf <= LDA_SPLIT_SCRATCH && tok_stride <= 0xFFFFFFF0u;
-	p.per_slice = p.split ? std::min(n, LDA_SPLIT_SCRATCH / per_buf) : n;
-	p.per_slice = std::max<size_t>(p.per_slice, 1);
-	p.nslices = (n + p.per_slice - 1) / p.per_slice;
-	const size_t grid_max = num_cus * (p.small ? lda_deflate_small_wgs() : 1);
-	p.grid = std::min(p.per_slice, grid_max);
-	p.cnt_at = p.grid * lda_deflate_seq_words() * 8;
-	p.sums_at = p.cnt_at + 16 * p.nslices;
-	p.dict_at = p.tok_at = align_up(p.sums_at + n * 4, 64);
-	p.total = p.sums_at + n * 4;
-	if (dict)
-		p.total = p.dict_at + LDA_DICT_BLK_HDR + dict_window();
-	if (p.split) {
-		p.tok_stride = (uint32_t)tok_stride;
-		p.blk_stride = (uint32_t)blk_stride;
-		p.blk_at = align_up(p.tok_at + p.per_slice * tok_stride * 4, 64);
-		p.total = p.blk_at + (LDA_BLK_HDR_WORDS(p.per_slice) +
-				      p.per_slice * blk_stride * LDA_BLK_WORDS) * 4;
-	}
-	return p;
+	static_assert(LDA_PLAN_BLK_WORDS == LDA_BLK_WORDS && LDA_PLAN_BLK_LIST(17) == LDA_BLK_LIST(17) &&
+		      LDA_PLAN_BLK_HDR_WORDS(17) == LDA_BLK_HDR_WORDS(17), "compress_plan.h, kernels.h");
+	const EnvCfg &env = env_cfg();
+	compress_plan_env e;
+	e.num_cus = (size_t)device_ctx()->num_cus;
+	e.small_max = lda_deflate_small_max();
+	e.small_wgs = lda_deflate_small_wgs();
+	e.no_small = env.no_small;
+	e.tile = lda_deflate_tile();
+	e.seq_words = lda_deflate_seq_words();
+	e.dict_bytes = LDA_DICT_BLK_HDR + dict_window();
+	e.tail_rounds = !overlap || !env.compress_overlap || c->side.failed ? 0 :
+			env.compress_tail_rounds ? (size_t)env.compress_tail_rounds :
+			LDA_COMPRESS_TAIL_ROUNDS;
+	return plan_batch(e, n, max_in, c->level, seg, dict);
 }
 
 static int
@@ -275,13 +235,21 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
 	const bool dict = d_dict && dict_nbytes;
-	const batch_plan pl = plan_batch(c, n, max_in_nbytes, d_seg_info != NULL, dict);
+	batch_plan pl = plan_batch(c, n, max_in_nbytes, d_seg_info != NULL, dict);
+	/* no side stream (once: SideStream::failed): the serial schedule */
+	if (pl.overlap && !c->side.ensure())
+		pl = plan_batch(c, n, max_in_nbytes, d_seg_info != NULL, dict, false);
 	const bool small = pl.small;
+	c->last_schedule[0] = pl.split;
+	c->last_schedule[1] = 0;
+	c->last_schedule[2] = (uint32_t)std::min<size_t>(n, 0xFFFFFFFFu);
+	c->last_schedule[3] = 0;
 	uint8_t *scr = (uint8_t *)c->scratch.reserve(pl.total);
 	if (!scr)
 		return LIBDEFLATE_AMD_OOM;
 	uint32_t *next_chunk = (uint32_t *)(scr + pl.cnt_at);
-	LDA_HIP_TRY(hipMemsetAsync(next_chunk, 0, 16 * pl.nslices, st),
+	/* (the tail's counters lie behind the head's: cnt2_at) */
+	LDA_HIP_TRY(hipMemsetAsync(next_chunk, 0, (pl.overlap ? 32 : 16) * pl.nslices, st),
 		    LIBDEFLATE_AMD_NO_DEVICE);
 	uint8_t *blk = NULL;
 	if (dict) {
@@ -360,39 +328,103 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 	 * descriptors, the entropy kernel writes the streams, and the fused
 	 * kernel compresses the buffers larger than the bound (the bound is a
 	 * promise the host cannot check; what such a buffer gets does not depend
-	 * on which path its batch took).  Stream order is the only hand-over. */
-	uint32_t *tok = (uint32_t *)(scr + pl.tok_at), *bd = (uint32_t *)(scr + pl.blk_at);
+	 * on which path its batch took).  Stream order is the only hand-over:
+	 * within a part on its stream, and through the two events between the
+	 * head on the caller's stream and the tail on the object's (plan_batch()).
+	 * A part is a batch of its own to the kernels: its rows of the caller's
+	 * arrays, its token lists, block descriptors, counters and workgroup
+	 * state.  The slices stay in series, they share the scratch. */
+	uint32_t *tok = (uint32_t *)(scr + pl.tok_at);
+	struct part {
+		size_t lo, n;
+		uint32_t *tok, *bd;
+		/* its counters of this slice; the fused kernel's, the count of buffers
+		 * listed for that one and the entropy kernel's lie nslices, 2 nslices
+		 * and 3 nslices words behind the LZ77 stage's */
+		uint32_t *cnt;
+		uint64_t *seq;
+		size_t grid_max;
+	};
+	auto lz77_entropy = [&](const part &q, hipStream_t on) -> int {
+		const uint32_t *sk = sums ? sums + q.lo : NULL;
+		const uint32_t *gk = d_seg_info ? d_seg_info + q.lo : NULL;
+		hipLaunchKernelGGL(lda_deflate_batch_kernel, dim3((unsigned)std::min(q.n, q.grid_max)),
+				   dim3(LDA_DEFLATE_THREADS), lds, on, (uint64_t)q.n, format,
+				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
+				   d_in_offsets + q.lo, d_in_nbytes + q.lo, (uint8_t *)d_out,
+				   d_out_offsets + q.lo, d_out_avail + q.lo, d_out_nbytes + q.lo, sk,
+				   q.seq, gk, q.cnt, (const uint8_t *)NULL,
+				   q.tok, q.bd, pl.tok_stride, pl.blk_stride, q.cnt + 2 * pl.nslices);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		hipLaunchKernelGGL(lda_deflate_entropy_kernel, dim3((unsigned)q.n),
+				   dim3(LDA_DEFLATE_ENTROPY_THREADS), lda_deflate_entropy_lds_bytes(),
+				   on, (uint64_t)q.n, format, c->level, (const uint8_t *)d_in,
+				   d_in_offsets + q.lo, d_in_nbytes + q.lo, (uint8_t *)d_out,
+				   d_out_offsets + q.lo, d_out_avail + q.lo, d_out_nbytes + q.lo, sk, gk,
+				   (const uint32_t *)q.tok, (const uint32_t *)q.bd, pl.tok_stride,
+				   pl.blk_stride, q.cnt + 3 * pl.nslices);
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		return LIBDEFLATE_AMD_OK;
+	};
+	/* (on the caller's stream for both parts: one launch after the other, so
+	 * they share the head's workgroup state) */
+	auto fused = [&](const part &q) -> int {
+		const uint32_t *sk = sums ? sums + q.lo : NULL;
+		const uint32_t *gk = d_seg_info ? d_seg_info + q.lo : NULL;
+		hipLaunchKernelGGL(lda_deflate_fused_kernel, dim3((unsigned)std::min(q.n, pl.grid)),
+				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)q.n, format,
+				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
+				   d_in_offsets + q.lo, d_in_nbytes + q.lo, (uint8_t *)d_out,
+				   d_out_offsets + q.lo, d_out_avail + q.lo, d_out_nbytes + q.lo, sk,
+				   (uint64_t *)scr, gk, q.cnt + pl.nslices,
+				   (const uint8_t *)NULL, (const uint32_t *)q.bd,
+				   (const uint32_t *)(q.cnt + 2 * pl.nslices));
+		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		return LIBDEFLATE_AMD_OK;
+	};
+	size_t heads = 0, tails = 0;
 	for (size_t k = 0; k < pl.nslices; k++) {
 		const size_t lo = k * pl.per_slice, nk = std::min(pl.per_slice, n - lo);
-		const uint32_t *sk = sums ? sums + lo : NULL;
-		const uint32_t *gk = d_seg_info ? d_seg_info + lo : NULL;
-		hipLaunchKernelGGL(lda_deflate_batch_kernel, dim3((unsigned)std::min(nk, pl.grid)),
-				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)nk, format,
-				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
-				   d_in_offsets + lo, d_in_nbytes + lo, (uint8_t *)d_out,
-				   d_out_offsets + lo, d_out_avail + lo, d_out_nbytes + lo, sk,
-				   (uint64_t *)scr, gk, next_chunk + k, (const uint8_t *)NULL,
-				   tok, bd, pl.tok_stride, pl.blk_stride, next_chunk + 2 * pl.nslices + k);
-		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-		hipLaunchKernelGGL(lda_deflate_entropy_kernel, dim3((unsigned)nk),
-				   dim3(LDA_DEFLATE_ENTROPY_THREADS), lda_deflate_entropy_lds_bytes(),
-				   st, (uint64_t)nk, format, c->level, (const uint8_t *)d_in,
-				   d_in_offsets + lo, d_in_nbytes + lo, (uint8_t *)d_out,
-				   d_out_offsets + lo, d_out_avail + lo, d_out_nbytes + lo, sk, gk,
-				   (const uint32_t *)tok, (const uint32_t *)bd, pl.tok_stride,
-				   pl.blk_stride, next_chunk + 3 * pl.nslices + k);
-		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-		hipLaunchKernelGGL(lda_deflate_fused_kernel, dim3((unsigned)std::min(nk, pl.grid)),
-				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)nk, format,
-				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
-				   d_in_offsets + lo, d_in_nbytes + lo, (uint8_t *)d_out,
-				   d_out_offsets + lo, d_out_avail + lo, d_out_nbytes + lo, sk,
-				   (uint64_t *)scr, gk, next_chunk + pl.nslices + k,
-				   (const uint8_t *)NULL, (const uint32_t *)bd,
-				   (const uint32_t *)(next_chunk + 2 * pl.nslices + k));
-		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+		const size_t tail_n = plan_tail_of(nk, (size_t)ctx->num_cus, pl.tail_rounds);
+		const size_t head_n = nk - tail_n;
+		const part head = { lo, head_n, tok, (uint32_t *)(scr + pl.blk_at), next_chunk + k,
+				    (uint64_t *)scr, pl.grid };
+		const part tail = { lo + head_n, tail_n, tok + head_n * (size_t)pl.tok_stride,
+				    (uint32_t *)(scr + pl.blk2_at),
+				    (uint32_t *)(scr + pl.cnt2_at) + k,
+				    (uint64_t *)(scr + pl.seq2_at), pl.grid2 };
+		heads += head_n;
+		tails += tail_n;
+		if (tail_n) {
+			LDA_HIP_TRY(hipEventRecord(c->side.in, st), LIBDEFLATE_AMD_NO_DEVICE);
+			LDA_HIP_TRY(hipStreamWaitEvent(c->side.side, c->side.in, 0),
+				    LIBDEFLATE_AMD_NO_DEVICE);
+		}
+		LDA_OK_TRY(lz77_entropy(head, st));
+		if (tail_n) {
+			/* whatever happens to the tail's launches, the caller's stream
+			 * waits for what the side stream was given */
+			const int rc = lz77_entropy(tail, c->side.side);
+			LDA_HIP_TRY(hipEventRecord(c->side.tail, c->side.side), LIBDEFLATE_AMD_NO_DEVICE);
+			LDA_HIP_TRY(hipStreamWaitEvent(st, c->side.tail, 0), LIBDEFLATE_AMD_NO_DEVICE);
+			LDA_OK_TRY(rc);
+		}
+		LDA_OK_TRY(fused(head));
+		if (tail_n)
+			LDA_OK_TRY(fused(tail));
 	}
+	c->last_schedule[1] = tails != 0;
+	c->last_schedule[2] = (uint32_t)std::min<size_t>(heads, 0xFFFFFFFFu);
+	c->last_schedule[3] = (uint32_t)std::min<size_t>(tails, 0xFFFFFFFFu);
 	return LIBDEFLATE_AMD_OK;
+}
+
+/* include/libdeflate_amd.h */
+extern "C" LIBDEFLATEAPI void
+libdeflate_amd_compress_last_schedule(const struct libdeflate_compressor *c, uint32_t out[4])
+{
+	for (int i = 0; i < 4; i++)
+		out[i] = c ? c->last_schedule[i] : 0;
 }
 
 /* host_objects.h: what the writers' piece pipeline (host_write_pieces.hip) launches

@@ -103,6 +103,13 @@ static EnvCfg read_env()
 	c.no_selfcheck = getenv("LDA_NO_SELFCHECK") != nullptr;
 	c.bgzf_serial = getenv("LDA_BGZF_SERIAL") != nullptr;
 	c.tar_serial = getenv("LDA_TAR_SERIAL") != nullptr;
+	if (const char *e = getenv("LDA_COMPRESS_OVERLAP"))
+		c.compress_overlap = atoi(e) != 0;
+	if (const char *e = getenv("LDA_COMPRESS_TAIL_ROUNDS")) {
+		int v = atoi(e);
+		if (v >= 1 && v <= 16)
+			c.compress_tail_rounds = v;
+	}
 	return c;
 }
 
@@ -238,6 +245,35 @@ void StreamPair::release()
 		(void)hipEventDestroy(mark2);
 	copy = comp = nullptr;
 	mark = mark2 = nullptr;
+}
+
+bool SideStream::ensure()
+{
+	if (side && in && tail)
+		return true;
+	if (failed)
+		return false;
+	if ((!side && hipStreamCreateWithFlags(&side, hipStreamNonBlocking) != hipSuccess) ||
+	    (!in && hipEventCreateWithFlags(&in, hipEventDisableTiming) != hipSuccess) ||
+	    (!tail && hipEventCreateWithFlags(&tail, hipEventDisableTiming) != hipSuccess)) {
+		(void)hipGetLastError();	/* the caller goes on without it */
+		release();
+		failed = true;
+		return false;
+	}
+	return true;
+}
+
+void SideStream::release()
+{
+	if (side)
+		(void)hipStreamDestroy(side);
+	if (in)
+		(void)hipEventDestroy(in);
+	if (tail)
+		(void)hipEventDestroy(tail);
+	side = nullptr;
+	in = tail = nullptr;
 }
 
 int run_slices(const char *what, const StreamPair &sp, size_t ns,

@@ -89,6 +89,9 @@ struct libdeflate_compressor {
 	lda::PinnedPair pinned;	/* host-pointer entry points */
 	lda::PinnedBuf meta;	/* host-pointer entry points: per-chunk read-backs */
 	lda::StreamPair streams;	/* host-pointer entry points: transfers / kernels */
+	lda::SideStream side;	/* the split path's tail beside its head (compress_batch_impl()) */
+	/* what the last batch call did (libdeflate_amd_compress_last_schedule) */
+	uint32_t last_schedule[4] = { 0, 0, 0, 0 };
 };
 
 namespace lda {
