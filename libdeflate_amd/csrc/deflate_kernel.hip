@@ -19,16 +19,19 @@
  *   head[]  most recent position per hash bucket; head3[] for 3-byte matches
  *   M[]     per-position best (length, distance) of the current tile
  *
- * and advances in TILES of 4096 positions (each stage is a function below;
- * deflate_batch_body() is the schedule: two tiles are in flight - the final
+ * and advances in TILES of 4096 positions (deflate_batch_body() is the
+ * schedule, the stages it calls stand in front of it - "the stages of a
+ * buffer / of a tile / phase X / of a block end" - and the functions named
+ * below do their work: two tiles are in flight - the final
  * parse, the token emission and the split statistics of tile k run in the
  * same phase ("phase X") as the shallow search and the first parse of tile
  * k + 1 and the chain insertion of tile k + 2, handing over through LDS
  * counters and flags; see the comment at the tile loop and DESIGN.md 3.3):
  *
  *   S0  input up to the end of the tile after the next (it joins the chains
- *       while the next one is searched);
- *   S1+S2  chain insertion WITHOUT a sort (insert_tile): a masked LDS
+ *       while the next one is searched): stage_s0();
+ *   S1+S2  chain insertion WITHOUT a sort (insert_tile, from
+ *       px_insert_chains() and px_insert3()): a masked LDS
  *       exchange per position; conflicting lanes of one LDS atomic are
  *       served in lane order, so 64 consecutive positions per instruction
  *       get what a serial insertion loop would have returned.  One wave, two
@@ -1960,19 +1963,330 @@ split_stats(lds_t *L, u32 walkpos, u32 block_start, bool fit_split, u32 lane)
 			L->vars[V_WPOS_PRE] - block_start >= 5000 ? 2 : 1;
 }
 
-#ifdef LDA_DEBUG_SPLIT	/* per-tile trace of the block-split inputs of buffer 0 (debug builds) */
-static __device__ u32 lda_dbg[2048];
-extern "C" __attribute__((visibility("default"))) void libdeflate_amd_debug_read(u32 *out)
+/* ---------------- the stages of a buffer ---------------- */
+
+/*
+ * deflate_batch_body() below is the schedule; the stages it calls are here.
+ * A stage takes what it reads by value and hands changed state back as its
+ * result, so the loop-carried locals (loaded, walkpos, ml_cur / ml_nxt,
+ * mx_pending, tail_*, carryv, block_start) stay plain registers of the body,
+ * which alone says in which order the stages run.  What is still written out
+ * in the body (the buffer's description, the search policy, the tile
+ * geometry, round B, the min-cost parse loop, the two parses of phase X, the
+ * block-end decision, the retro token move) compiled to other code in every
+ * form tried as a function: profiles/deflate_body_stages.md.
+ */
+
+/* Buffers are handed out dynamically (one global counter): their cost
+ * depends on their content, and a fixed stride gives every workgroup
+ * the same kind of buffer whenever the batch is periodic. */
+static __device__ __forceinline__ u64 claim_buffer(lds_t *L, u32 *next_chunk, u32 tid)
 {
-	(void)hipDeviceSynchronize();
-	(void)hipMemcpyFromSymbol(out, HIP_SYMBOL(lda_dbg), sizeof(lda_dbg));
+	__syncthreads();
+	if (tid == 0)
+		L->vars[V_TMP0] = atomicAdd(next_chunk, 1u);
+	__syncthreads();
+	/* (workgroup-uniform values read back from LDS are made scalar: what
+	 * derives from them - descriptors, addresses, loop bounds - then lives
+	 * in SGPRs instead of vector registers) */
+	return bcast_first(L->vars[V_TMP0]);
 }
-#define DBG(tile, k, v) do { if ((tile) < 250) lda_dbg[8 * (tile) + (k)] = (v); } while (0)
+
+/* ---- per-buffer init ---- */
+static __device__ __forceinline__ void buffer_lds_init(lds_t *L, u32 tid)
+{
+	for (u32 i = tid; i < (1u << HASH_BITS) / 2; i += NT)
+		((u32 *)L->head)[i] = 0x80008000u;
+	for (u32 i = tid; i < (1u << HASH3_BITS) / 2; i += NT)
+		((u32 *)L->head3)[i] = 0x80008000u;
+	for (u32 i = tid; i < 320; i += NT)
+		L->freq[i] = 0;
+	if (tid < 10)
+		L->obs[0][tid] = 0;
+	if (tid < TILE / 64 + 1)
+		L->rdy[tid] = 0;
+	for (u32 i = tid; i < STG_WORDS + 8; i += NT)
+		stg_of(L)[i] = 0;
+	if (tid < 8)
+		L->M[tid] = 0;
+	if (tid == 0) {
+		L->vars[V_NSEQ] = 0;
+		L->vars[V_ENTRY] = 0;
+		L->vars[V_PFLAG] = 0;
+	}
+}
+
+/* ---------------- the stages of a tile ---------------- */
+
+/* what the searches of an iteration may reach and what its parse walks */
+struct tile_window {
+	u32 lo_cur, lo_nxt;	/* the oldest position a match of tile cur / nxt may start at */
+	s32 limit;		/* positions of tile cur that the parse walks */
+};
+
+static __device__ __forceinline__ struct tile_window
+tile_window_of(u32 t, u32 tend, u32 tn, u32 lo_min, bool last_tile)
+{
+	struct tile_window w;
+#ifdef LDA_SMALL
+	w.lo_cur = 0, w.lo_nxt = 0;	/* the whole buffer is resident */
+	(void)lo_min;	/* (no dictionary here) */
 #else
-#define DBG(tile, k, v) do { } while (0)
+	const s32 lo_s = (s32)(t + 2 * TILE + LOOKAHEAD) - (s32)RING;
+	w.lo_cur = lo_s > (s32)lo_min ? (u32)lo_s : lo_min;
+	const s32 lo_n = (s32)(tn + 2 * TILE + LOOKAHEAD) - (s32)RING;
+	w.lo_nxt = lo_n > (s32)lo_min ? (u32)lo_n : lo_min;
 #endif
+	w.limit = last_tile ? (s32)(tend - t) : (s32)TILE - 2;
+	return w;
+}
+
+/* ---- tile cur: its shallow results into M[] ----
+ * (with a round B ahead - wl_copies - build_worklist() moves the results
+ * and its first barrier is this stage's) */
+static __device__ __forceinline__ void
+cur_results_to_m(lds_t *L, const AS3 u32 *MX, u32 *fsave, bool mx_pending, bool wl_copies,
+		 u32 carryv, u32 walkpos, u32 tid)
+{
+	if (mx_pending && !wl_copies)
+		for (u32 i = tid; i < TILE; i += NT)
+			L->M[4 + i] = MX[4 + i];
+	if (tid < 4) {
+		L->M[tid] = carryv;
+		L->M[TILE + 4 + tid] = 0;
+	}
+	/* the block as it is before this tile's tokens: if the tile
+	 * turns out to be of different content, the block ends in
+	 * front of it (see "block end?") */
+	for (u32 i = tid; i < 320; i += NT)
+		fsave[i] = L->freq[i];
+	if (tid == 0) {
+		L->vars[V_NSEQ_PRE] = L->vars[V_NSEQ];
+		L->vars[V_WPOS_PRE] = walkpos;
+	}
+	if (!wl_copies)
+		__syncthreads();
+}
+
+/* ---- S0: input up to the end of tile it + 1 (+ LOOKAHEAD): what
+ * the shallow search of tile nxt reads and what the insertion
+ * of tile it + 1 hashes.  The 16 bytes per thread that were requested ahead
+ * (s0_pre, s0_p, s0_v) are stored; the hand-over counters of phase X restart ---- */
+struct s0_state {
+	u32 loaded;	/* input bytes present in the ring */
+	u32 ml_nxt;	/* minimum match length of tile nxt */
+};
+
+static __device__ __forceinline__ struct s0_state
+stage_s0(lds_t *L, AS3 u32 *MX, const u8 *inp, bool aligned_in, bool s0_pre, u32 s0_p, uint4 s0_v,
+	 u32 want, u32 loaded, u32 ml_nxt, bool cur_real, bool nxt_real, u32 tail_n, u32 it, u32 tid)
+{
+	if (s0_pre) {
+		*(uint4 *)&L->in[s0_p & RMASK] = s0_v;
+		if ((s0_p & RMASK) < 32)
+			*(uint4 *)&L->in[RING + (s0_p & RMASK)] = s0_v;
+	}
+	if (aligned_in) {	/* (more than one unit per thread: first tile only) */
+		if ((loaded & ~15u) + NT * 16 < want)
+			stage_input(L, inp, (loaded & ~15u) + NT * 16, want, true, tid);
+	} else {
+		stage_input(L, inp, loaded, want, false, tid);
+	}
+	loaded = want > loaded ? want : loaded;
+	if (tid == 0) {
+		L->vars[V_CTR] = 0;
+		L->vars[V_CTR2] = 0;
+		L->vars[V_CTR3] = 0;
+		L->vars[V_STDONE] = 0;
+		L->vars[V_EMDONE] = 0;
+		L->vars[V_TAILDONE] = 0;
+		L->vars[V_CTR4] = 0;
+		L->vars[V_ST2DONE] = 0;
+	}
+	/* what the first parse of tile nxt reads around its search
+	 * results: the entries its predecessor's walk deferred, and
+	 * no matches past the end */
+	if (tid < 4 && nxt_real) {
+		AS3 u32 *const Mo = cur_real ? MX : (AS3 u32 *)L->M;
+		/* (behind a deferred generation of round B the
+		 * entries may still change: wave 0 copies them after
+		 * its final parse) */
+		if (!tail_n)
+			Mo[tid] = cur_real ? L->M[TILE + tid] : 0;
+		Mo[TILE + 4 + tid] = 0;
+	}
+	/* (the minimum match length of tile nxt was estimated a
+	 * tile ahead, beside phase X) */
+	if (nxt_real && it)
+		ml_nxt = bcast_first(L->vars[V_MINLEN]);
+	__syncthreads();
+	const struct s0_state r = { loaded, ml_nxt };
+	return r;
+}
+
+/* ---------------- phase X: what each wave does ---------------- */
+
+/* the chain insertion of tile it + 1 (the last wave): one wave's serial
+ * instruction stream, the longest item of this phase -
+ * it gets the issue slots of its SIMD first */
+static __device__ __forceinline__ void
+px_insert_chains(lds_t *L, bool have_ins, u32 tnend, u32 n, u32 lane)
+{
+	__builtin_amdgcn_s_setprio(3);
+	if (have_ins)
+		insert_tile(L, tnend, tnend + TILE < n ? tnend + TILE : n,
+			    n, lane);
+	__builtin_amdgcn_s_setprio(0);
+}
+
+/* the 3-byte table of tile it + 1 (the last wave but one) */
+static __device__ __forceinline__ void
+px_insert3(lds_t *L, u16 *c3ins, u32 tnend, u32 n, u32 lane)
+{
+	insert_tile3(L, c3ins, tnend,
+		     tnend + TILE < n ? tnend + TILE : n, n, lane);
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+}
+
+/* the minimum match length of the tile after nxt (the last wave but one) */
+static __device__ __forceinline__ void
+px_minlen_ahead(lds_t *L, u32 tnend, u32 n, u32 dict_len, u32 loaded, u32 depth, bool use3, u32 lane)
+{
+	const u32 nd = wave_distinct_bytes(L, tnend,
+		loaded - tnend < TILE ? loaded - tnend : TILE, lane);
+	if (lane == 0)
+		L->vars[V_MINLEN] = min_len_policy(nd, n - dict_len, depth, use3);
+}
+
+/* ---- round B's last generation, deferred (waves 1 ..
+ * RB_TAIL_WAVES; wave 0 stays free to start the final
+ * parse the moment its steps are there: with a batch of
+ * its own it measured 0.6 % slower): beside the shallow
+ * search of tile nxt.  Phase X has staged the input of
+ * the tile after nxt and inserts it meanwhile, over the
+ * oldest tile of the window round B had: these items
+ * search with the window of tile nxt ---- */
+static __device__ __forceinline__ void
+px_round_b_tail(lds_t *L, u32 t, u32 n, u32 lo_nxt, u32 ml_cur, u32 depth, u32 nice,
+		u32 mode, s32 limit, u32 tail_n, u32 tail_e, u32 tail_gen, u32 lane, u32 wave)
+{
+	__builtin_amdgcn_s_setprio(2);
+	if (64 * (wave - 1) < tail_n) {
+		u32 nx;
+		(void)rb_batch(L, t, n, lo_nxt, ml_cur, rb_trim_depth(depth), nice,
+			       tail_e, tail_e != 0, tail_gen, lane, &nx);
+	}
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+	if (lane == 0)
+		atomicAdd((u32 *)&L->vars[V_TAILDONE], 1u);
+	/* (all of them share the steps: a tail of one batch
+	 * would leave one wave with the whole tile's - measured
+	 * 6 % slower than no deferral at all) */
+	wait_lds_eq(L, V_TAILDONE, RB_TAIL_WAVES);
+	stage_steps_cur_claimed(L, limit, mode, nice, lane);
+	__builtin_amdgcn_s_setprio(0);
+}
+
+/* ---- S3 round A: tile nxt (every wave, as it gets free) ---- */
+static __device__ __forceinline__ void
+px_round_a(lds_t *L, AS3 u32 *Mo, u16 *c3nxt, bool optm, u32 tn, u32 tnend, u32 n,
+	   u32 lo_nxt, u32 ml_nxt, u32 depth, u32 nice, u32 ra_depth, u32 ra_class,
+	   u32 dlim3, u32 it, u32 tid, u32 wave)
+{
+	if (optm) {
+		/* the min-cost parse prices every position: all of
+		 * them are searched to the full depth */
+		if (wave < NWAVES - 2)
+			search_items(L, Mo, tn, n, lo_nxt, ml_nxt, depth, nice,
+				     NULL, TILE, NWAVES - 2, tid);
+	} else {
+		round_a(L, Mo, c3nxt, tn, tnend, n, lo_nxt, ml_nxt, ra_depth,
+			ra_class, nice, dlim3, it + 1, tid);
+	}
+}
+
+/* the tokens of tile cur are emitted as soon as its parse is through */
+static __device__ __forceinline__ void px_wait_final_parse(lds_t *L, u32 it)
+{
+	while (*(volatile AS3 u32 *)&L->vars[V_PFLAG] != it)
+		__builtin_amdgcn_s_sleep(4);
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+/* block split observations of tile cur, by the last wave
+ * once every group is emitted (wave 0 is still walking
+ * the next tile's first parse) */
+static __device__ __forceinline__ void px_split_stats(lds_t *L, u32 block_start, u32 lane)
+{
+	wait_lds_eq(L, V_EMDONE, TILE / 64);
+	split_stats(L, bcast_first(L->vars[V_WALKPOS_LO]), block_start, false, lane);
+}
+
+/* ---------------- the stages of a block end ---------------- */
+
+/* SPLIT: the block's descriptor (LDA_BLK_*) for the entropy
+ * kernel; the tokens stay where they are, the next block's
+ * start behind this one's in the buffer's list */
+static __device__ __forceinline__ void
+write_block_desc(lds_t *L, u32 *d, const u32 *fsave, bool retro, u32 blk_tok0, u32 nseq,
+		 u32 bstart, u32 bend, u32 flags, u32 tid)
+{
+	for (u32 i = tid; i < 320; i += NT) {
+		const u32 f = L->freq[i], fp = retro ? fsave[i] : f;
+		d[LDA_BLK_FREQ + i] = fp;
+		L->freq[i] = f - fp;
+	}
+	if (tid == 0) {
+		d[LDA_BLK_TOK0] = blk_tok0;
+		d[LDA_BLK_NTOK] = nseq - blk_tok0;
+		d[LDA_BLK_START] = bstart;
+		d[LDA_BLK_END] = bend;
+		d[LDA_BLK_FLAGS] = flags;
+	}
+}
+
+/* a block that ends in front of the last tile: the histogram as it was before
+ * the tile is the block's, the tile's share is kept for the next block */
+static __device__ __forceinline__ void retro_histogram(lds_t *L, u32 *fsave, u32 tid)
+{
+	for (u32 i = tid; i < 320; i += NT) {
+		u32 f = L->freq[i], fp = fsave[i];
+		fsave[320 + i] = f - fp;
+		L->freq[i] = fp;
+	}
+	__syncthreads();
+}
+
+/* the block-end tables and the bit staging area are MX's LDS:
+ * the next tile's search results wait in HBM meanwhile */
+static __device__ __forceinline__ void mx_save(lds_t *L, u32 *msave, u32 tid)
+{
+	const AS3 u32 *MXs = (const AS3 u32 *)L->nxtB;
+	for (u32 i = tid; i < TILE; i += NT)
+		msave[4 + i] = MXs[4 + i];
+}
+
+static __device__ __forceinline__ void mx_restore(lds_t *L, const u32 *msave, u32 tid)
+{
+	for (u32 i = tid; i < TILE; i += NT)
+		L->M[4 + i] = msave[4 + i];
+}
 
 /* ---------------- the kernel ---------------- */
+
+#define DEFLATE_KERNEL_PARAMS                                                  \
+	u64 n_chunks, int format, int level, u32 depth, u32 nice, u32 mode,    \
+	const u8 *__restrict__ in_base, const u64 *__restrict__ in_offsets,    \
+	const u64 *__restrict__ in_nbytes, u8 *__restrict__ out_base,          \
+	const u64 *__restrict__ out_offsets,                                   \
+	const u64 *__restrict__ out_avail_arr, u64 *__restrict__ out_nbytes,   \
+	const u32 *__restrict__ sums, u64 *__restrict__ seq_scratch,           \
+	const u32 *__restrict__ seg_info, u32 *__restrict__ next_chunk,       \
+	const u8 *__restrict__ dict_pre
+#define DEFLATE_KERNEL_ARGS                                                    \
+	lds_raw, n_chunks, format, level, depth, nice, mode, in_base,          \
+	in_offsets, in_nbytes, out_base, out_offsets, out_avail_arr,           \
+	out_nbytes, sums, seq_scratch, seg_info, next_chunk, dict_pre
 
 /*
  * The body is compiled three times: OPT = false for levels 0-9 (the min-cost
@@ -1988,20 +2302,7 @@ extern "C" __attribute__((visibility("default"))) void libdeflate_amd_debug_read
  * blk_buf set: only the *fused_cnt buffers so listed.
  */
 template <bool OPT, bool SPLIT = false> static __device__ __forceinline__ void
-deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
-		   u32 nice, u32 mode,
-		   const u8 *__restrict__ in_base,
-		   const u64 *__restrict__ in_offsets,
-		   const u64 *__restrict__ in_nbytes,
-		   u8 *__restrict__ out_base,
-		   const u64 *__restrict__ out_offsets,
-		   const u64 *__restrict__ out_avail_arr,
-		   u64 *__restrict__ out_nbytes,
-		   const u32 *__restrict__ sums,
-		   u64 *__restrict__ seq_scratch,
-		   const u32 *__restrict__ seg_info,
-		   u32 *__restrict__ next_chunk,
-		   const u8 *__restrict__ dict_pre,
+deflate_batch_body(u8 *lds_raw, DEFLATE_KERNEL_PARAMS,
 		   u32 *__restrict__ tok_buf = NULL, u32 *__restrict__ blk_buf = NULL,
 		   u32 tok_stride = 0, u32 blk_stride = 0, u32 *__restrict__ fused_cnt = NULL)
 {
@@ -2032,22 +2333,12 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		length_code(i + 3, &sl, &xb, &xv);
 		L->lslot[i] = (u8)sl;
 	}
-	/* Buffers are handed out dynamically (one global counter): their cost
-	 * depends on their content, and a fixed stride gives every workgroup
-	 * the same kind of buffer whenever the batch is periodic. */
 	/* the fused kernel behind a split launch: only the buffers its LZ77 stage
 	 * listed (larger than the bound, LDA_BLK_FUSED) - usually none */
 	const u32 *__restrict__ only = !SPLIT && blk_buf ? blk_buf + LDA_BLK_LIST(n_chunks) : NULL;
 	const u64 n_todo = only ? bcast_first(*fused_cnt) : n_chunks;
 	for (;;) {
-		__syncthreads();
-		if (tid == 0)
-			L->vars[V_TMP0] = atomicAdd(next_chunk, 1u);
-		__syncthreads();
-		/* (workgroup-uniform values read back from LDS are made scalar: what
-		 * derives from them - descriptors, addresses, loop bounds - then lives
-		 * in SGPRs instead of vector registers) */
-		const u64 i_todo = bcast_first(L->vars[V_TMP0]);
+		const u64 i_todo = claim_buffer(L, next_chunk, tid);
 		if (i_todo >= n_todo)
 			break;
 		const u64 c = only ? bcast_first(only[i_todo]) : i_todo;
@@ -2118,25 +2409,7 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		/* ---- per-buffer init ---- */
 		__syncthreads();
 		PROF_START();
-		for (u32 i = tid; i < (1u << HASH_BITS) / 2; i += NT)
-			((u32 *)L->head)[i] = 0x80008000u;
-		for (u32 i = tid; i < (1u << HASH3_BITS) / 2; i += NT)
-			((u32 *)L->head3)[i] = 0x80008000u;
-		for (u32 i = tid; i < 320; i += NT)
-			L->freq[i] = 0;
-		if (tid < 10)
-			L->obs[0][tid] = 0;
-		if (tid < TILE / 64 + 1)
-			L->rdy[tid] = 0;
-		for (u32 i = tid; i < STG_WORDS + 8; i += NT)
-			stg_of(L)[i] = 0;
-		if (tid < 8)
-			L->M[tid] = 0;
-		if (tid == 0) {
-			L->vars[V_NSEQ] = 0;
-			L->vars[V_ENTRY] = 0;
-			L->vars[V_PFLAG] = 0;
-		}
+		buffer_lds_init(L, tid);
 		os.sg = (u64)(0 - ((uintptr_t)os.out & 15));
 		os.bits = 0;
 		__syncthreads();
@@ -2246,44 +2519,15 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 				walkpos = tend;
 			} else {
 				AS3 u32 *const MX = (AS3 u32 *)L->nxtB;
-#ifdef LDA_SMALL
-				const u32 lo_cur = 0, lo_nxt = 0;	/* the whole buffer is resident */
-				(void)lo_min;	/* (no dictionary here) */
-#else
-				const s32 lo_s = (s32)(t + 2 * TILE + LOOKAHEAD) - (s32)RING;
-				const u32 lo_cur = lo_s > (s32)lo_min ? (u32)lo_s : lo_min;
-				const s32 lo_n = (s32)(tn + 2 * TILE + LOOKAHEAD) - (s32)RING;
-				const u32 lo_nxt = lo_n > (s32)lo_min ? (u32)lo_n : lo_min;
-#endif
+				const struct tile_window w = tile_window_of(t, tend, tn, lo_min, last_tile);
 				u16 *c3nxt = c3g + (it & 1) * (TILE + 8);
 				u16 *c3ins = c3g + ((it + 1) & 1) * (TILE + 8);
-				const s32 limit = last_tile ? (s32)(tend - t) : (s32)TILE - 2;
 
-				/* (with a round B ahead, build_worklist() moves the results
-				 * and its first barrier is this block's) */
 				const bool wl_copies = cur_real && !optm && rounds && mx_pending;
 				if (cur_real) {
-					/* ---- tile cur: its shallow results into M[] ---- */
-					if (mx_pending && !wl_copies)
-						for (u32 i = tid; i < TILE; i += NT)
-							L->M[4 + i] = MX[4 + i];
-					if (tid < 4) {
-						L->M[tid] = carryv;
-						L->M[TILE + 4 + tid] = 0;
-					}
+					cur_results_to_m(L, MX, fsave, mx_pending, wl_copies, carryv, walkpos, tid);
 					mx_pending = false;
 					ml_cur = ml_nxt;
-					/* the block as it is before this tile's tokens: if the tile
-					 * turns out to be of different content, the block ends in
-					 * front of it (see "block end?") */
-					for (u32 i = tid; i < 320; i += NT)
-						fsave[i] = L->freq[i];
-					if (tid == 0) {
-						L->vars[V_NSEQ_PRE] = L->vars[V_NSEQ];
-						L->vars[V_WPOS_PRE] = walkpos;
-					}
-					if (!wl_copies)
-						__syncthreads();
 					PROF_MARK(6);
 				}
 				/* the input of the tile that S0 stages below is requested now:
@@ -2307,7 +2551,7 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 						PROF_MARK(39);
 						if (wc) {
 							AS3 u32 *tl = (AS3 u32 *)L->nxtB;
-							search_queue(L, t, n, lo_cur, ml_cur, depth, nice,
+							search_queue(L, t, n, w.lo_cur, ml_cur, depth, nice,
 								     (AS3 u32 *)L->nxtB, (AS3 u32 *)L->nxtA, wc, tid,
 								     nxt_real, &tail_n, &tail_gen, &tl);
 							/* a deferred last generation: its items leave the
@@ -2330,7 +2574,7 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 					 * which round B's last barrier has released, counters, and
 					 * of MX only entries behind the lists - and ends with one) */
 					if (!tail_n)
-						stage_steps(L, limit, mode, nice, tid);
+						stage_steps(L, w.limit, mode, nice, tid);
 				}
 				if (cur_real && optm) {
 					/* levels 10-12 (mode 3): min-cost parse, see opt_parse_wave().
@@ -2354,13 +2598,8 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 						 * the lazy parse (stage 0, final) */
 						const u32 fit = opt_build_costs(L, tid, false, true, t, tend - t, bsave);
 						opt_stage = fit ? 0 : 1;
-						if (tid == 0) {
+						if (tid == 0)
 							L->vars[V_FIT] = fit;
-							if (c == 0) {
-								DBG(tile, 6, 100 + fit);
-								DBG(tile, 7, L->vars[V_TMP3]);
-							}
-						}
 					}
 					for (;;) {
 						/* opaque again: see the top of the tile loop */
@@ -2374,26 +2613,26 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 							s32 lo = (s32)(OPT_SEG * wave), hi = lo + OPT_SEG;
 							if (wave == 0 && ent < 0)
 								lo = ent;
-							if (hi > limit)
-								hi = limit;
+							if (hi > w.limit)
+								hi = w.limit;
 							s32 e = hi + OPT_WARM;
 							if (e > pend)
 								e = pend;
 							if (lo < hi)
 								opt_parse_wave(L, L->nxtA, t, lo, hi, e, lane);
 							__syncthreads();
-							for (s32 i = (s32)tid + (ent < 0 ? ent : 0); i < limit; i += NT) {
+							for (s32 i = (s32)tid + (ent < 0 ? ent : 0); i < w.limit; i += NT) {
 								u32 c = L->nxtA[i + 4], m = L->M[i + 4];
 								L->M[i + 4] = c >= 3 ? c | (m & 0xFFFF0000u) : 0;
 							}
 							__syncthreads();
 						}
-						stage_steps(L, limit, s4mode, nice, tid);
+						stage_steps(L, w.limit, s4mode, nice, tid);
 						if (tid == 0)
 							L->vars[V_CTR2] = 0;
 						__syncthreads();
 						if (wave == 0)
-							parse_and_base(L, tokg, t, limit, s4mode, nice, lane);
+							parse_and_base(L, tokg, t, w.limit, s4mode, nice, lane);
 						__syncthreads();
 						PROF_MARK(12);
 						emit_groups(L, tokg, t, lane);
@@ -2416,51 +2655,11 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 					}
 				}
 
-				/* ---- S0: input up to the end of tile it + 1 (+ LOOKAHEAD): what
-				 * the shallow search of tile nxt reads and what the insertion
-				 * of tile it + 1 hashes ---- */
-				{
-					const u32 want = s0_want;
-					if (s0_pre) {
-						*(uint4 *)&L->in[s0_p & RMASK] = s0_v;
-						if ((s0_p & RMASK) < 32)
-							*(uint4 *)&L->in[RING + (s0_p & RMASK)] = s0_v;
-					}
-					if (aligned_in) {	/* (more than one unit per thread: first tile only) */
-						if ((loaded & ~15u) + NT * 16 < want)
-							stage_input(L, inp, (loaded & ~15u) + NT * 16, want, true, tid);
-					} else {
-						stage_input(L, inp, loaded, want, false, tid);
-					}
-					loaded = want > loaded ? want : loaded;
-					if (tid == 0) {
-						L->vars[V_CTR] = 0;
-						L->vars[V_CTR2] = 0;
-						L->vars[V_CTR3] = 0;
-						L->vars[V_STDONE] = 0;
-						L->vars[V_EMDONE] = 0;
-						L->vars[V_TAILDONE] = 0;
-						L->vars[V_CTR4] = 0;
-						L->vars[V_ST2DONE] = 0;
-					}
-					/* what the first parse of tile nxt reads around its search
-					 * results: the entries its predecessor's walk deferred, and
-					 * no matches past the end */
-					if (tid < 4 && nxt_real) {
-						AS3 u32 *const Mo = cur_real ? MX : (AS3 u32 *)L->M;
-						/* (behind a deferred generation of round B the
-						 * entries may still change: wave 0 copies them after
-						 * its final parse) */
-						if (!tail_n)
-							Mo[tid] = cur_real ? L->M[TILE + tid] : 0;
-						Mo[TILE + 4 + tid] = 0;
-					}
-					/* (the minimum match length of tile nxt was estimated a
-					 * tile ahead, beside phase X) */
-					if (nxt_real && it)
-						ml_nxt = bcast_first(L->vars[V_MINLEN]);
-					__syncthreads();
-				}
+				/* ---- S0: the input of tile it + 1, the counters of phase X ---- */
+				const struct s0_state s0 = stage_s0(L, MX, inp, aligned_in, s0_pre, s0_p, s0_v,
+					s0_want, loaded, ml_nxt, cur_real, nxt_real, tail_n, it, tid);
+				loaded = s0.loaded;
+				ml_nxt = s0.ml_nxt;
 				PROF_MARK(1);
 				if (it == 0) {
 					/* the first tile joins the chains up front */
@@ -2489,30 +2688,15 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 					PROF_WDECL;
 					PROF_W0();
 					if (wave == NWAVES - 1) {
-						/* the chain insertion of tile it + 1: one wave's serial
-						 * instruction stream, the longest item of this phase -
-						 * it gets the issue slots of its SIMD first */
-						__builtin_amdgcn_s_setprio(3);
-						if (have_ins)
-							insert_tile(L, tnend, tnend + TILE < n ? tnend + TILE : n,
-								    n, lane);
-						__builtin_amdgcn_s_setprio(0);
+						px_insert_chains(L, have_ins, tnend, n, lane);
 						PROF_W(24);
 					} else if (wave == NWAVES - 2) {
 						__builtin_amdgcn_s_setprio(2);
-						if (have_ins && use3) {
-							insert_tile3(L, c3ins, tnend,
-								     tnend + TILE < n ? tnend + TILE : n, n, lane);
-							__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-						}
+						if (have_ins && use3)
+							px_insert3(L, c3ins, tnend, n, lane);
 						__builtin_amdgcn_s_setprio(0);
-						/* the minimum match length of the tile after nxt */
-						if (have_ins && tnend >= dict_len) {
-							const u32 nd = wave_distinct_bytes(L, tnend,
-								loaded - tnend < TILE ? loaded - tnend : TILE, lane);
-							if (lane == 0)
-								L->vars[V_MINLEN] = min_len_policy(nd, n - dict_len, depth, use3);
-						}
+						if (have_ins && tnend >= dict_len)
+							px_minlen_ahead(L, tnend, n, dict_len, loaded, depth, use3, lane);
 						PROF_W(25);
 					} else if (wave == 0 && do_p2) {
 						/* ---- S4: the final parse of tile cur ----
@@ -2522,7 +2706,7 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 						if (tail_n)	/* its steps follow round B's last generation */
 							wait_lds_eq(L, V_ST2DONE, TILE / 64);
 						__builtin_amdgcn_s_setprio(3);
-						parse_and_base(L, tokg, t, limit, mode, nice, lane);
+						parse_and_base(L, tokg, t, w.limit, mode, nice, lane);
 						__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
 						if (lane == 0)
 							*(volatile AS3 u32 *)&L->vars[V_PFLAG] = it;
@@ -2533,43 +2717,14 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 							Mo[lane] = L->M[TILE + lane];
 						PROF_W(26);
 					} else if (RB_DEFER && tail_n && wave <= RB_TAIL_WAVES) {
-						/* ---- round B's last generation, deferred (waves 1 ..
-						 * RB_TAIL_WAVES; wave 0 stays free to start the final
-						 * parse the moment its steps are there: with a batch of
-						 * its own it measured 0.6 % slower): beside the shallow
-						 * search of tile nxt.  Phase X has staged the input of
-						 * the tile after nxt and inserts it meanwhile, over the
-						 * oldest tile of the window round B had: these items
-						 * search with the window of tile nxt ---- */
-						__builtin_amdgcn_s_setprio(2);
-						if (64 * (wave - 1) < tail_n) {
-							u32 nx;
-							(void)rb_batch(L, t, n, lo_nxt, ml_cur, rb_trim_depth(depth), nice,
-								       tail_e, tail_e != 0, tail_gen, lane, &nx);
-						}
-						__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-						if (lane == 0)
-							atomicAdd((u32 *)&L->vars[V_TAILDONE], 1u);
-						/* (all of them share the steps: a tail of one batch
-						 * would leave one wave with the whole tile's - measured
-						 * 6 % slower than no deferral at all) */
-						wait_lds_eq(L, V_TAILDONE, RB_TAIL_WAVES);
-						stage_steps_cur_claimed(L, limit, mode, nice, lane);
-						__builtin_amdgcn_s_setprio(0);
+						/* round B's last generation, deferred */
+						px_round_b_tail(L, t, n, w.lo_nxt, ml_cur, depth, nice, mode, w.limit,
+								tail_n, tail_e, tail_gen, lane, wave);
 					}
 					/* ---- S3 round A: tile nxt ---- */
-					if (nxt_real) {
-						if (optm) {
-							/* the min-cost parse prices every position: all of
-							 * them are searched to the full depth */
-							if (wave < NWAVES - 2)
-								search_items(L, Mo, tn, n, lo_nxt, ml_nxt, depth, nice,
-									     NULL, TILE, NWAVES - 2, tid);
-						} else {
-							round_a(L, Mo, c3nxt, tn, tnend, n, lo_nxt, ml_nxt, ra_depth,
-								ra_class, nice, dlim3, it + 1, tid);
-						}
-					}
+					if (nxt_real)
+						px_round_a(L, Mo, c3nxt, optm, tn, tnend, n, w.lo_nxt, ml_nxt, depth,
+							   nice, ra_depth, ra_class, dlim3, it, tid, wave);
 					if (wave == 1)
 						PROF_W(27);
 					if (nxt_real && rounds) {
@@ -2594,23 +2749,15 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 							PROF_W(34);
 					}
 					if (do_p2) {
-						/* ---- the tokens of tile cur, as soon as its parse is
-						 * through ---- */
-						while (*(volatile AS3 u32 *)&L->vars[V_PFLAG] != it)
-							__builtin_amdgcn_s_sleep(4);
-						__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+						/* ---- the tokens of tile cur ---- */
+						px_wait_final_parse(L, it);
 						if (wave == 1)
 							PROF_W(28);
 						emit_groups(L, tokg, t, lane);
 						if (wave == 1)
 							PROF_W(29);
-						/* block split observations of tile cur, by the last wave
-						 * once every group is emitted (wave 0 is still walking
-						 * the next tile's first parse) */
-						if (wave == NWAVES - 1 && splits && !last_tile) {
-							wait_lds_eq(L, V_EMDONE, TILE / 64);
-							split_stats(L, bcast_first(L->vars[V_WALKPOS_LO]), block_start, false, lane);
-						}
+						if (wave == NWAVES - 1 && splits && !last_tile)
+							px_split_stats(L, block_start, lane);
 					}
 					__syncthreads();
 					if (wave == 1)
@@ -2625,7 +2772,7 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 								u32 p = tn + i, b3 = 0;
 								if (p + 3 <= n && Mo[4 + i] == 0) {
 									u32 bd = find_len3(L, p, ld32(L->in, p),
-											   c3nxt[4 + i], p - lo_nxt,
+											   c3nxt[4 + i], p - w.lo_nxt,
 											   dlim3, &b3);
 									if (bd)
 										Mo[4 + i] = 3 | (bd << 16);
@@ -2705,22 +2852,9 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 			const u32 nseq = retro ? bcast_first(L->vars[V_NSEQ_PRE]) : nseq_all;
 			const u32 is_final = last_tile && seg_last ? 1 : 0;
 			if (SPLIT) {
-				/* the block's descriptor (LDA_BLK_*) for the entropy
-				 * kernel; the tokens stay where they are, the next block's
-				 * start behind this one's in the buffer's list */
-				u32 *d = blk_desc + (size_t)nblocks * LDA_BLK_WORDS;
-				for (u32 i = tid; i < 320; i += NT) {
-					const u32 f = L->freq[i], fp = retro ? fsave[i] : f;
-					d[LDA_BLK_FREQ + i] = fp;
-					L->freq[i] = f - fp;
-				}
-				if (tid == 0) {
-					d[LDA_BLK_TOK0] = blk_tok0;
-					d[LDA_BLK_NTOK] = nseq - blk_tok0;
-					d[LDA_BLK_START] = bstart;
-					d[LDA_BLK_END] = bend;
-					d[LDA_BLK_FLAGS] = is_final | (stored_only ? LDA_BLK_STORED : 0);
-				}
+				write_block_desc(L, blk_desc + (size_t)nblocks * LDA_BLK_WORDS, fsave, retro,
+						 blk_tok0, nseq, bstart, bend,
+						 is_final | (stored_only ? LDA_BLK_STORED : 0), tid);
 				nblocks++;
 				blk_tok0 = nseq;
 				/* (as after a written block: see below) */
@@ -2729,23 +2863,12 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 				__syncthreads();
 				continue;
 			}
-			if (retro) {
-				for (u32 i = tid; i < 320; i += NT) {
-					u32 f = L->freq[i], fp = fsave[i];
-					fsave[320 + i] = f - fp;
-					L->freq[i] = fp;
-				}
-				__syncthreads();
-			}
+			if (retro)
+				retro_histogram(L, fsave, tid);
 
 			/* ---- S5, S6: the block is written (block_emit()) ---- */
-			/* the block-end tables and the bit staging area are MX's LDS:
-			 * the next tile's search results wait in HBM meanwhile */
-			if (!stored_only && mx_pending) {
-				const AS3 u32 *MXs = (const AS3 u32 *)L->nxtB;
-				for (u32 i = tid; i < TILE; i += NT)
-					msave[4 + i] = MXs[4 + i];
-			}
+			if (!stored_only && mx_pending)
+				mx_save(L, msave, tid);
 			PROF_MARK(10);
 			if (!block_emit(L, &os, tokg, nseq, inp, bstart, blen, is_final, stored_only,
 					ftr_bytes, &tog, tid, lane, wave)) {
@@ -2784,8 +2907,7 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 			 * re-evaluated as "no match" after a block end */
 			carryv = 0;
 			if (mx_pending) {
-				for (u32 i = tid; i < TILE; i += NT)
-					L->M[4 + i] = msave[4 + i];
+				mx_restore(L, msave, tid);
 				mx_pending = false;
 			}
 			block_start = bend;
@@ -2808,21 +2930,6 @@ deflate_batch_body(u8 *lds_raw, u64 n_chunks, int format, int level, u32 depth,
 		}
 	}
 }
-
-/* host helper: dynamic LDS size the kernel needs */
-#define DEFLATE_KERNEL_PARAMS                                                  \
-	u64 n_chunks, int format, int level, u32 depth, u32 nice, u32 mode,    \
-	const u8 *__restrict__ in_base, const u64 *__restrict__ in_offsets,    \
-	const u64 *__restrict__ in_nbytes, u8 *__restrict__ out_base,          \
-	const u64 *__restrict__ out_offsets,                                   \
-	const u64 *__restrict__ out_avail_arr, u64 *__restrict__ out_nbytes,   \
-	const u32 *__restrict__ sums, u64 *__restrict__ seq_scratch,           \
-	const u32 *__restrict__ seg_info, u32 *__restrict__ next_chunk,       \
-	const u8 *__restrict__ dict_pre
-#define DEFLATE_KERNEL_ARGS                                                    \
-	lds_raw, n_chunks, format, level, depth, nice, mode, in_base,          \
-	in_offsets, in_nbytes, out_base, out_offsets, out_avail_arr,           \
-	out_nbytes, sums, seq_scratch, seg_info, next_chunk, dict_pre
 
 #ifdef LDA_SMALL
 /* buffers of at most RING bytes, 256 threads, SMALL_WGS workgroups per CU

@@ -155,10 +155,6 @@ opt_build_costs(lds_t *L, u32 tid, bool try_flat, bool check_fit, u32 t, u32 tn,
 	__syncthreads();
 	if (tv2 > (u32)(2 * 0.6f * 65536.0f))
 		return 2;
-#ifdef LDA_DEBUG_SPLIT
-	if (tid == 0)
-		L->vars[V_TMP3] = 100 * e_blk / (e_own ? e_own : 1);
-#endif
 	return OPT_FIT_DEN * e_blk <= OPT_FIT_NUM * e_own ? 0 : 2 * e_blk <= 5 * e_own ? 1 : 2;
 }
 
