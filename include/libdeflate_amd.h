@@ -1616,9 +1616,9 @@ libdeflate_amd_png_out_sizes(const uint64_t *index, size_t entries, size_t n_sel
  *
  * Not covered: Adam7; the CRCs of IDAT, PLTE and ancillary chunks - only the
  * IHDR's is checked; the zlib stream's Adler-32 vouches for the pixel bytes,
- * and nothing vouches for a palette; transforms other than LE16 (palette
- * expansion, tRNS, gamma, depth scaling: the row hands the caller PLTE and
- * tRNS, so one gather on the device expands them); APNG frames (the default
+ * and nothing vouches for a palette; gamma (palette expansion, tRNS, depth
+ * scaling and channel conversion are libdeflate_amd_png_decode_pixels_batch,
+ * below); APNG frames (the default
  * image alone is decoded); images of 2^32 raw bytes and more; routing a few
  * huge images to the many-wave decoder, as libdeflate_amd_zip_read_large does
  * for ZIP (every image is one wave's work here); a host-pointer form.
@@ -1631,6 +1631,75 @@ libdeflate_amd_png_decode_batch(struct libdeflate_decompressor *decompressor,
 				void *d_out, size_t out_avail, size_t out_align,
 				unsigned flags, uint64_t *out_offsets,
 				int32_t *d_results, void *stream);
+
+/*
+ * Decode a selection to ONE pixel format: what libdeflate_amd_png_decode_batch
+ * does, and then every image expanded to the channels and sample depth of
+ * `format`, whatever its file stores (png_set_expand, png_set_gray_to_rgb and
+ * png_set_scale_16 of libpng; mode=RGB of torchvision.io.decode_png).
+ * format: LIBDEFLATE_AMD_PNG_GRAY, _GRAY_ALPHA, _RGB or _RGBA (the channels),
+ * alone for 8-bit samples or with LIBDEFLATE_AMD_PNG_OUT16 for 16-bit ones.
+ * Selection r takes height * width * channels * (1 or 2) bytes at d_out +
+ * out_offsets[r], rounded up to out_align: interleaved pixels, no row padding;
+ * a zero row takes none.  16-bit samples are big-endian, little-endian with
+ * LIBDEFLATE_AMD_PNG_LE16 in flags.  Per pixel, in this order:
+ *  1. the samples at the file's depth; depths 1, 2, 4 unpacked
+ *     most-significant-bit first, the spare low bits of a row's last byte
+ *     ignored;
+ *  2. colour type 3: index i becomes R, G, B of PLTE entry i with alpha tRNS[i]
+ *     for i < min(tRNS length, entries) and 255 otherwise, 8-bit RGBA; an index
+ *     at or above `entries` makes the selection LIBDEFLATE_BAD_DATA;
+ *  3. the colour key: colour type 0 with a tRNS of exactly 2 bytes - alpha 0
+ *     where the sample equals the key's low `depth` bits; colour type 2 with a
+ *     tRNS of exactly 6 bytes - alpha 0 where all three samples equal the key
+ *     (16-bit big-endian words, their low byte at depth 8); opaque otherwise.
+ *     A tRNS of another length, or of colour types 4 and 6, is ignored;
+ *  4. the depth, every channel alike: 1, 2, 4 -> 8 by bit replication (v *
+ *     0xFF, 0x55, 0x11); 8 -> 16 is v * 257; 16 -> 8 is (v * 255 + 32895) >> 16,
+ *     round to nearest (libpng's png_set_scale_16);
+ *  5. the channels: grey -> RGB by replication; RGB -> grey is (19595 R +
+ *     38470 G + 7471 B + 32768) >> 16; alpha is dropped without compositing
+ *     where the format has none, and is the file's, the palette's, the key's
+ *     or opaque where it has one.
+ * An image that already is the format is unfiltered straight into its room; the
+ * others go through scratch of the decompressor object and one more kernel.
+ *
+ * libdeflate_amd_png_pixels_out_sizes is the host arithmetic of the rooms, as
+ * libdeflate_amd_png_out_sizes.  Sizes are u64: a 1-bit image below 2^32 raw
+ * bytes converts to far more than 2^32.
+ *
+ * d_results[r]: the first verdict of libdeflate_amd_png_decode_batch that
+ * applies, then LIBDEFLATE_BAD_DATA for a palette index out of range, then
+ * LIBDEFLATE_SUCCESS.  Nothing is written outside the selections' rooms; a
+ * failed selection's room is undefined.  Only enqueues; nothing is read back.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work: everything
+ * libdeflate_amd_png_decode_batch refuses (an interlaced row among it), a
+ * format whose low four bits are not 1 .. 4 or with other bits than OUT16, a
+ * selection that needs more than out_avail.
+ *
+ * Not covered: gamma and sBIT, compositing against bKGD, Adam7, APNG, a
+ * host-pointer form.
+ */
+#define LIBDEFLATE_AMD_PNG_GRAY        1	/* format = channels ... */
+#define LIBDEFLATE_AMD_PNG_GRAY_ALPHA  2
+#define LIBDEFLATE_AMD_PNG_RGB         3
+#define LIBDEFLATE_AMD_PNG_RGBA        4
+#define LIBDEFLATE_AMD_PNG_OUT16       0x10	/* ... | this: 16-bit samples, else 8-bit */
+
+LIBDEFLATEAPI int
+libdeflate_amd_png_pixels_out_sizes(const uint64_t *index, size_t entries, size_t n_sel,
+				    const uint64_t *sel, unsigned format, size_t out_align,
+				    uint64_t *out_offsets, uint64_t *total_ret);
+
+LIBDEFLATEAPI int
+libdeflate_amd_png_decode_pixels_batch(struct libdeflate_decompressor *decompressor,
+				       const void *d_in, size_t in_nbytes,
+				       const uint64_t *index, size_t entries,
+				       size_t n_sel, const uint64_t *sel, unsigned format,
+				       void *d_out, size_t out_avail, size_t out_align,
+				       unsigned flags, uint64_t *out_offsets,
+				       int32_t *d_results, void *stream);
 
 /*
  * ---- ZIP archives written on the device ----

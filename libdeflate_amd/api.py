@@ -698,6 +698,29 @@ class Decompressor:
             _stream_ptr(stream)), "png_decode_batch")
         return offs
 
+    def decode_png_pixels_batch(self, data, index, sel, out, results, fmt, out_align=1, flags=0,
+                                stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_png_decode_pixels_batch: decode_png_batch, and every
+        image expanded to ONE pixel format whatever its file stores: fmt is
+        binding.PNG_GRAY, PNG_GRAY_ALPHA, PNG_RGB or PNG_RGBA, alone (uint8
+        samples) or with PNG_OUT16 (16-bit, big-endian unless flags has
+        PNG_LE16).  Palette and tRNS are applied, depths scaled, grey
+        replicated or RGB weighted to grey, alpha dropped where fmt has none.
+        Selection r is height x width x channels interleaved at out[offsets[r]];
+        png_pixels_shapes(index, fmt) gives the shapes and the dtype.  Returns
+        the numpy uint64 offsets (len(sel) + 1).  Only enqueues."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+        s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+        offs = np.zeros(len(s) + 1, dtype=np.uint64)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_png_decode_pixels_batch(
+            self._h, data.data_ptr() if n else None, n, idx.ctypes.data_as(c_void_p), len(idx),
+            len(s), s.ctypes.data_as(c_void_p), int(fmt), out.data_ptr() if avail else None,
+            avail, int(out_align), int(flags), offs.ctypes.data_as(c_void_p),
+            results.data_ptr(), _stream_ptr(stream)), "png_decode_pixels_batch")
+        return offs
+
     def read_targz(self, data, out, max_records, spacing=1 << 20, max_points=1024,
                    in_nbytes=None, out_avail=None, stream=None):
         """A .tar.gz in the CUDA tensor `data`: decompress_large_index("gzip")
@@ -1120,6 +1143,36 @@ def png_shapes(index):
     idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
     return [(int(r[2] >> 32), int(r[2] & 0xFFFFFFFF), int(r[3] >> 32), int(r[3] & 0xFF),
              int(r[3] >> 8 & 0xFF)) for r in idx.tolist()]
+
+
+def png_pixels_out_sizes(index, sel, fmt, out_align=1):
+    """libdeflate_amd_png_pixels_out_sizes: where decode_png_pixels_batch puts
+    the images `sel` of the host index rows `index` in the format fmt ->
+    (numpy uint64 offsets, len(sel) + 1, total bytes).  An image takes height *
+    width * channels * (1 or 2) bytes rounded up to out_align, a zero row none.
+    No device is touched."""
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+    s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+    offs = np.zeros(len(s) + 1, dtype=np.uint64)
+    total = ctypes.c_uint64(0)
+    check(binding.load().libdeflate_amd_png_pixels_out_sizes(
+        idx.ctypes.data_as(c_void_p), len(idx), len(s), s.ctypes.data_as(c_void_p), int(fmt),
+        int(out_align), offs.ctypes.data_as(c_void_p), ctypes.byref(total)),
+        "png_pixels_out_sizes")
+    return offs, total.value
+
+
+def png_pixels_shapes(index, fmt):
+    """([(height, width, channels) per host index row, zeros for a refused
+    file], the numpy dtype) of what decode_png_pixels_batch writes in the
+    format fmt (uint16 wants PNG_LE16 in the call's flags)."""
+    ch = int(fmt) & 0xF
+    if not 1 <= ch <= 4 or int(fmt) & ~(0xF | binding.PNG_OUT16):
+        raise ValueError("png_pixels_shapes: format 0x%x" % int(fmt))
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+    shapes = [(int(r[2] >> 32), int(r[2] & 0xFFFFFFFF), ch) if any(r[2:]) else (0, 0, 0)
+              for r in idx.tolist()]
+    return shapes, np.dtype(np.uint16 if int(fmt) & binding.PNG_OUT16 else np.uint8)
 
 
 _PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}

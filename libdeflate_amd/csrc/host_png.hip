@@ -162,7 +162,7 @@ static int png_decode(struct libdeflate_decompressor *d, const uint8_t *d_in, si
 		hipLaunchKernelGGL(lda_png_unfilter_kernel, dim3(unfilter_grid(ctx, n_sel)), dim3(256),
 				   0, st, (uint64_t)n_sel, col[PNG_COL_RAW_OFF], col[PNG_COL_RAW_N],
 				   col[PNG_COL_OUT_OFF], col[PNG_COL_GEOM], col[PNG_COL_META],
-				   (const uint8_t *)g_area, out, g_unf);
+				   (const uint8_t *)g_area, out, out, g_unf);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
 	hipLaunchKernelGGL(lda_png_final_kernel, dim3((unsigned)((n_sel + 255) / 256)), dim3(256), 0,

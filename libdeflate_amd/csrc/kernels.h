@@ -515,6 +515,7 @@ lda_tarw_pack_kernel(uint64_t n, uint64_t end, uint64_t total, uint64_t mtime,
 #define LDA_PNG_UNSUPPORTED 18		/* LIBDEFLATE_AMD_PNG_UNSUPPORTED */
 #define LDA_PNG_WORDS 8
 #define LDA_PNG_META_LE16 0x100		/* meta: LIBDEFLATE_AMD_PNG_LE16 << 8, 16-bit images */
+#define LDA_PNG_META_ALT 0x200		/* meta: the unfilter writes at alt_base + c_out_off */
 extern "C" __global__ void
 lda_png_index_kernel(uint64_t n_files, const uint8_t *in, const uint64_t *in_off,
 		     const uint64_t *in_n, uint64_t *rows, int32_t *results);
@@ -525,10 +526,29 @@ lda_png_gather_kernel(uint64_t n_sel, const uint64_t *c_idat, const uint64_t *c_
 extern "C" __global__ void
 lda_png_unfilter_kernel(uint64_t n_sel, const uint64_t *c_raw_off, const uint64_t *c_raw_n,
 			const uint64_t *c_out_off, const uint64_t *c_geom, const uint64_t *c_meta,
-			const uint8_t *ws, uint8_t *out_base, int32_t *flags);
+			const uint8_t *ws, uint8_t *out_base, uint8_t *alt_base, int32_t *flags);
 extern "C" __global__ void
 lda_png_final_kernel(uint64_t n_sel, const uint64_t *c_meta, const int32_t *gather,
 		     const int32_t *decode, const int32_t *unfilter, int32_t *results);
+
+/* png_pixels_kernels.hip: the selections of a PNG decode that are not yet the
+ * target pixel format converted from the scratch into their rooms
+ * (host_png_pixels.hip): tiles of LDA_PNGX_TILE pixels, the grid strides over
+ * them; the verdicts merged.  The x_* columns are png_pixels_plan.h's of the
+ * converted selections, c_src is PNG_COL_OUT_OFF of all selections */
+#define LDA_PNGX_TILE 4096		/* pixels: 256 threads x 16 */
+#define LDA_PNGX_OUT16 0x10		/* LIBDEFLATE_AMD_PNG_OUT16 */
+#define LDA_PNGX_KIND_KEY 0x10000	/* kind: the tRNS is a colour key */
+extern "C" __global__ void
+lda_pngx_convert_kernel(uint64_t n_conv, uint64_t n_tiles, uint32_t format, uint32_t le16,
+			const uint64_t *x_tile_end, const uint64_t *x_sel, const uint64_t *c_src,
+			const uint64_t *x_dst, const uint64_t *x_shape, const uint64_t *x_kind,
+			const uint64_t *x_plte, const uint64_t *x_trns, const uint8_t *in,
+			const uint8_t *ws, uint8_t *out_base, int32_t *flags);
+extern "C" __global__ void
+lda_pngx_final_kernel(uint64_t n_sel, const uint64_t *c_meta, const int32_t *gather,
+		      const int32_t *decode, const int32_t *unfilter, const int32_t *convert,
+		      int32_t *results);
 
 /* png_write_kernels.hip: PNG files written into device memory
  * (host_png_write.hip, png_write_plan.h): the scanlines filtered into the

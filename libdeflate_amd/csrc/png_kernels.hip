@@ -366,14 +366,15 @@ unfilter_image(const u8 *__restrict__ raw, u8 *__restrict__ out, u32 height, u32
  * above 4.  meta bit 8 (LDA_PNG_META_LE16): the 16-bit samples are swapped in
  * place in a last pass over the selection, behind stores_visible() - the
  * filters run on the bytes in PNG order, and so does the read of the upper row
- * at a band's start.
+ * at a band's start.  meta bit 9 (LDA_PNG_META_ALT): c_out_off counts from
+ * alt_base, not from out_base (host_png_pixels.hip: the scratch).
  */
 extern "C" __global__ void __launch_bounds__(256)
 lda_png_unfilter_kernel(uint64_t n_sel, const uint64_t *__restrict__ c_raw_off,
 			const uint64_t *__restrict__ c_raw_n, const uint64_t *__restrict__ c_out_off,
 			const uint64_t *__restrict__ c_geom, const uint64_t *__restrict__ c_meta,
 			const uint8_t *__restrict__ ws, uint8_t *__restrict__ out_base,
-			int32_t *__restrict__ flags)
+			uint8_t *__restrict__ alt_base, int32_t *__restrict__ flags)
 {
 	const u32 lane = lane_id();
 	const u64 waves = (u64)gridDim.x * 4;
@@ -383,7 +384,7 @@ lda_png_unfilter_kernel(uint64_t n_sel, const uint64_t *__restrict__ c_raw_off,
 		const u32 height = (u32)geom, rowbytes = (u32)(geom >> 32);
 		const u32 bpp = (u32)meta & 0xFF;
 		const u8 *raw = ws + c_raw_off[r];
-		u8 *out = out_base + c_out_off[r];
+		u8 *out = (meta & LDA_PNG_META_ALT ? alt_base : out_base) + c_out_off[r];
 		bool bad = false;
 
 		if (c_raw_n[r] == 0) {	/* a zero row */
