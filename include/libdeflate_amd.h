@@ -1614,7 +1614,8 @@ libdeflate_amd_png_out_sizes(const uint64_t *index, size_t entries, size_t n_sel
  * lie inside in_nbytes or whose fields are not a valid IHDR, a selection that
  * needs more than out_avail.
  *
- * Not covered: Adam7; the CRCs of IDAT, PLTE and ancillary chunks - only the
+ * Not covered: Adam7 here - the _ex calls below read it, and this call keeps
+ * its verdicts; the CRCs of IDAT, PLTE and ancillary chunks - only the
  * IHDR's is checked; the zlib stream's Adler-32 vouches for the pixel bytes,
  * and nothing vouches for a palette; gamma (palette expansion, tRNS, depth
  * scaling and channel conversion are libdeflate_amd_png_decode_pixels_batch,
@@ -1678,8 +1679,9 @@ libdeflate_amd_png_decode_batch(struct libdeflate_decompressor *decompressor,
  * format whose low four bits are not 1 .. 4 or with other bits than OUT16, a
  * selection that needs more than out_avail.
  *
- * Not covered: gamma and sBIT, compositing against bKGD, Adam7, APNG, a
- * host-pointer form.
+ * Not covered: gamma and sBIT, compositing against bKGD, APNG, a host-pointer
+ * form; Adam7 here - the _ex calls below read it, and this call keeps its
+ * verdicts.
  */
 #define LIBDEFLATE_AMD_PNG_GRAY        1	/* format = channels ... */
 #define LIBDEFLATE_AMD_PNG_GRAY_ALPHA  2
@@ -1700,6 +1702,68 @@ libdeflate_amd_png_decode_pixels_batch(struct libdeflate_decompressor *decompres
 				       void *d_out, size_t out_avail, size_t out_align,
 				       unsigned flags, uint64_t *out_offsets,
 				       int32_t *d_results, void *stream);
+
+/*
+ * Adam7-interlaced files: the three calls above with a flag that lets
+ * interlace 1 through.  They are new entry points, and the calls above keep
+ * their verdicts: without LIBDEFLATE_AMD_PNG_ADAM7 every result, row, offset
+ * and byte of these calls is that of the older call.
+ *
+ * libdeflate_amd_png_index_batch_ex: flags 0 gives exactly the rows and
+ * verdicts of libdeflate_amd_png_index_batch.  With LIBDEFLATE_AMD_PNG_ADAM7 an
+ * interlace-1 file that passes every other rule is LIBDEFLATE_SUCCESS with a
+ * full row, bit 16 of whose word 3 is set; it is
+ * LIBDEFLATE_AMD_PNG_UNSUPPORTED where height * (1 + rowbytes) or raw7 is 2^32
+ * or more - raw7 the bytes its zlib stream inflates to: for each of the seven
+ * passes (PNG 8.2) of w_p x h_p pixels, none of them 0, h_p * (1 + ceil(w_p *
+ * channels * depth / 8)).  LIBDEFLATE_BAD_DATA still comes first.  Any other
+ * flag bit is LIBDEFLATE_AMD_BAD_ARG.
+ *
+ * libdeflate_amd_png_out_sizes_ex: host arithmetic only.  format 0 gives the
+ * rooms of libdeflate_amd_png_out_sizes, any other value (a format of
+ * libdeflate_amd_png_decode_pixels_batch) those of
+ * libdeflate_amd_png_pixels_out_sizes.  flags: 0 or LIBDEFLATE_AMD_PNG_ADAM7;
+ * an interlaced row is refused without it ("interlaced") and takes the room of
+ * its non-interlaced twin with it.
+ *
+ * libdeflate_amd_png_decode_batch_ex: flags are LIBDEFLATE_AMD_PNG_LE16 |
+ * LIBDEFLATE_AMD_PNG_ADAM7.  format 0 gives the layout and the verdict order
+ * of libdeflate_amd_png_decode_batch, any other value those of
+ * libdeflate_amd_png_decode_pixels_batch.  Interlaced and plain rows, zero rows
+ * and duplicates mix freely in one selection; an interlaced image's bytes are
+ * those of its non-interlaced twin.  An interlaced selection's d_results[r] is
+ * the first of: LIBDEFLATE_AMD_PNG_UNSUPPORTED for a zero row; the gather's
+ * LIBDEFLATE_BAD_DATA; the zlib decoder's own result against the exact fill of
+ * raw7 bytes; LIBDEFLATE_BAD_DATA for a filter-type byte above 4 in any pass;
+ * with a pixel format, LIBDEFLATE_BAD_DATA for a palette index out of range;
+ * LIBDEFLATE_SUCCESS.  Nothing is written outside the selections' rooms,
+ * whatever the file holds.  LIBDEFLATE_AMD_BAD_ARG before any device work:
+ * what the older calls refuse, an interlaced row without the flag among it.
+ * Only enqueues; scratch belongs to the decompressor object.  A selection
+ * without an interlaced row queues what the older call queues.
+ */
+#define LIBDEFLATE_AMD_PNG_ADAM7            2	/* flag: interlace 1 is read */
+
+LIBDEFLATEAPI int
+libdeflate_amd_png_index_batch_ex(struct libdeflate_decompressor *decompressor,
+				  size_t n_files, const void *d_in,
+				  const uint64_t *d_in_offsets, const uint64_t *d_in_nbytes,
+				  unsigned flags, uint64_t *d_index, int32_t *d_results,
+				  void *stream);
+
+LIBDEFLATEAPI int
+libdeflate_amd_png_out_sizes_ex(const uint64_t *index, size_t entries, size_t n_sel,
+				const uint64_t *sel, unsigned format, size_t out_align,
+				unsigned flags, uint64_t *out_offsets, uint64_t *total_ret);
+
+LIBDEFLATEAPI int
+libdeflate_amd_png_decode_batch_ex(struct libdeflate_decompressor *decompressor,
+				   const void *d_in, size_t in_nbytes,
+				   const uint64_t *index, size_t entries,
+				   size_t n_sel, const uint64_t *sel, unsigned format,
+				   void *d_out, size_t out_avail, size_t out_align,
+				   unsigned flags, uint64_t *out_offsets,
+				   int32_t *d_results, void *stream);
 
 /*
  * ---- ZIP archives written on the device ----

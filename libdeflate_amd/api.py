@@ -721,6 +721,40 @@ class Decompressor:
             results.data_ptr(), _stream_ptr(stream)), "png_decode_pixels_batch")
         return offs
 
+    def index_png_batch_ex(self, data, in_offsets, in_nbytes, index, results, flags=0,
+                           stream=None):
+        """libdeflate_amd_png_index_batch_ex: index_png_batch with flags.  0:
+        its rows and results exactly; binding.PNG_ADAM7: an Adam7-interlaced
+        file that passes every other rule is a full row (bit 16 of word 3 set)
+        and result 0, PNG_UNSUPPORTED only where the image or the bytes its
+        stream inflates to reach 2^32.  Only enqueues."""
+        n = in_offsets.numel()
+        check(self._lib.libdeflate_amd_png_index_batch_ex(
+            self._h, n, data.data_ptr(), in_offsets.data_ptr(), in_nbytes.data_ptr(), int(flags),
+            index.data_ptr(), results.data_ptr(), _stream_ptr(stream)), "png_index_batch_ex")
+
+    def decode_png_batch_ex(self, data, index, sel, out, results, fmt=0, out_align=1, flags=0,
+                            stream=None, in_nbytes=None, out_avail=None):
+        """libdeflate_amd_png_decode_batch_ex: fmt 0 is decode_png_batch's
+        layout (height rows of rowbytes bytes as PNG stores them), any other
+        fmt decode_png_pixels_batch's; flags: binding.PNG_LE16 |
+        binding.PNG_ADAM7.  With PNG_ADAM7 the selection may hold interlaced
+        rows of index_png_batch_ex among plain ones, zero rows and duplicates;
+        an interlaced image's bytes are those of its non-interlaced twin.
+        Returns the numpy uint64 offsets (len(sel) + 1); png_shapes(index) or
+        png_pixels_shapes(index, fmt) gives the shapes.  Only enqueues."""
+        idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+        s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+        offs = np.zeros(len(s) + 1, dtype=np.uint64)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        check(self._lib.libdeflate_amd_png_decode_batch_ex(
+            self._h, data.data_ptr() if n else None, n, idx.ctypes.data_as(c_void_p), len(idx),
+            len(s), s.ctypes.data_as(c_void_p), int(fmt), out.data_ptr() if avail else None,
+            avail, int(out_align), int(flags), offs.ctypes.data_as(c_void_p),
+            results.data_ptr(), _stream_ptr(stream)), "png_decode_batch_ex")
+        return offs
+
     def read_targz(self, data, out, max_records, spacing=1 << 20, max_points=1024,
                    in_nbytes=None, out_avail=None, stream=None):
         """A .tar.gz in the CUDA tensor `data`: decompress_large_index("gzip")
@@ -1131,6 +1165,24 @@ def png_out_sizes(index, sel, out_align=1):
     check(binding.load().libdeflate_amd_png_out_sizes(
         idx.ctypes.data_as(c_void_p), len(idx), len(s), s.ctypes.data_as(c_void_p),
         int(out_align), offs.ctypes.data_as(c_void_p), ctypes.byref(total)), "png_out_sizes")
+    return offs, total.value
+
+
+def png_out_sizes_ex(index, sel, fmt=0, out_align=1, flags=0):
+    """libdeflate_amd_png_out_sizes_ex: where decode_png_batch_ex puts the
+    images `sel` of the host index rows `index` -> (numpy uint64 offsets,
+    len(sel) + 1, total bytes): png_out_sizes for fmt 0, png_pixels_out_sizes
+    for any other.  An interlaced row is taken only with binding.PNG_ADAM7 in
+    flags, and takes the room of its non-interlaced twin.  No device is
+    touched."""
+    idx = np.ascontiguousarray(index, dtype=np.uint64).reshape(-1, binding.PNG_WORDS)
+    s = np.ascontiguousarray(sel, dtype=np.uint64).reshape(-1)
+    offs = np.zeros(len(s) + 1, dtype=np.uint64)
+    total = ctypes.c_uint64(0)
+    check(binding.load().libdeflate_amd_png_out_sizes_ex(
+        idx.ctypes.data_as(c_void_p), len(idx), len(s), s.ctypes.data_as(c_void_p), int(fmt),
+        int(out_align), int(flags), offs.ctypes.data_as(c_void_p), ctypes.byref(total)),
+        "png_out_sizes_ex")
     return offs, total.value
 
 

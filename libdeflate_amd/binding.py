@@ -46,6 +46,8 @@ TAR_EOF, TAR_HAS_L, TAR_HAS_PAX = 1, 2, 4
 # the PNG reader: a per-file result (the ZIP and tar readers' value), u64 per
 # index row, the one flag of a decode
 PNG_UNSUPPORTED, PNG_WORDS, PNG_LE16 = 18, 8, 1
+# the flag of the _ex calls that lets Adam7-interlaced files through
+PNG_ADAM7 = 2
 # the pixel format of decode_png_pixels_batch: the channels, alone (8-bit
 # samples) or with PNG_OUT16
 PNG_GRAY, PNG_GRAY_ALPHA, PNG_RGB, PNG_RGBA, PNG_OUT16 = 1, 2, 3, 4, 0x10
@@ -115,6 +117,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_png_decode_batch",
     "libdeflate_amd_png_pixels_out_sizes", "libdeflate_amd_png_decode_pixels_batch",
     "libdeflate_amd_png_encode_bound", "libdeflate_amd_png_encode_batch",
+    "libdeflate_amd_png_index_batch_ex", "libdeflate_amd_png_out_sizes_ex",
+    "libdeflate_amd_png_decode_batch_ex",
 ]
 
 _lib = None
@@ -254,6 +258,12 @@ def load():
     # the same to one pixel format (format behind sel)
     sig("libdeflate_amd_png_pixels_out_sizes", c_int, P, SZ, SZ, P, c_uint32, SZ, P, P)
     sig("libdeflate_amd_png_decode_pixels_batch", c_int, P, P, SZ, P, SZ, SZ, P, c_uint32, P, SZ,
+        SZ, c_uint32, P, P, P)
+    # the same three with Adam7: flags behind the sizes of the index call,
+    # format behind sel and flags behind out_align in the other two
+    sig("libdeflate_amd_png_index_batch_ex", c_int, P, SZ, P, P, P, c_uint32, P, P, P)
+    sig("libdeflate_amd_png_out_sizes_ex", c_int, P, SZ, SZ, P, c_uint32, SZ, c_uint32, P, P)
+    sig("libdeflate_amd_png_decode_batch_ex", c_int, P, P, SZ, P, SZ, SZ, P, c_uint32, P, SZ,
         SZ, c_uint32, P, P, P)
     # PNG files written: the bound (host arithmetic), and pixel arrays of a
     # device buffer -> files (the image rows on the host)

@@ -56,8 +56,8 @@ libdeflate_amd_png_index_batch(struct libdeflate_decompressor *d, size_t n_files
 	if (!on.ok() || !device_ctx())
 		return LIBDEFLATE_AMD_NO_DEVICE;
 	hipLaunchKernelGGL(lda_png_index_kernel, dim3((unsigned)((n_files + 255) / 256)), dim3(256), 0,
-			   (hipStream_t)stream, (uint64_t)n_files, (const uint8_t *)d_in, d_in_offsets,
-			   d_in_nbytes, d_index, d_results);
+			   (hipStream_t)stream, (uint64_t)n_files, (uint32_t)0, (const uint8_t *)d_in,
+			   d_in_offsets, d_in_nbytes, d_index, d_results);
 	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	return LIBDEFLATE_AMD_OK;
 }

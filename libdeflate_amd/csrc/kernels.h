@@ -516,8 +516,9 @@ lda_tarw_pack_kernel(uint64_t n, uint64_t end, uint64_t total, uint64_t mtime,
 #define LDA_PNG_WORDS 8
 #define LDA_PNG_META_LE16 0x100		/* meta: LIBDEFLATE_AMD_PNG_LE16 << 8, 16-bit images */
 #define LDA_PNG_META_ALT 0x200		/* meta: the unfilter writes at alt_base + c_out_off */
+#define LDA_PNG_ADAM7 2			/* LIBDEFLATE_AMD_PNG_ADAM7: the index takes interlace 1 */
 extern "C" __global__ void
-lda_png_index_kernel(uint64_t n_files, const uint8_t *in, const uint64_t *in_off,
+lda_png_index_kernel(uint64_t n_files, uint32_t flags, const uint8_t *in, const uint64_t *in_off,
 		     const uint64_t *in_n, uint64_t *rows, int32_t *results);
 extern "C" __global__ void
 lda_png_gather_kernel(uint64_t n_sel, const uint64_t *c_idat, const uint64_t *c_end,
@@ -549,6 +550,23 @@ extern "C" __global__ void
 lda_pngx_final_kernel(uint64_t n_sel, const uint64_t *c_meta, const int32_t *gather,
 		      const int32_t *decode, const int32_t *unfilter, const int32_t *convert,
 		      int32_t *results);
+
+/* png_adam7_kernels.hip: Adam7-interlaced selections of a PNG decode
+ * (host_png_adam7.hip): the pass images the unfilter left in the scratch woven
+ * into the finished images, tiles of LDA_PNG7_TILE 16-byte pieces, the grid
+ * strides over them; the verdicts merged over every selection's units.  The
+ * d_* columns are png_adam7_plan.h's of the interlaced selections (d_pass:
+ * seven words a selection), c_units its PNG7_COL_UNITS */
+#define LDA_PNG7_TILE 1024		/* pieces: 256 threads x 4 */
+#define LDA_PNG7_KIND_ALT 0x100		/* kind: d_dst counts from the scratch */
+extern "C" __global__ void
+lda_png7_deinterlace_kernel(uint64_t n_il, uint64_t n_tiles, const uint64_t *d_tile_end,
+			    const uint64_t *d_pass, const uint64_t *d_shape, const uint64_t *d_kind,
+			    const uint64_t *d_dst, uint8_t *ws, uint8_t *out_base);
+extern "C" __global__ void
+lda_png7_final_kernel(uint64_t n_sel, const uint64_t *c_meta, const uint64_t *c_units,
+		      const int32_t *gather, const int32_t *decode, const int32_t *unit_flags,
+		      const int32_t *convert, int32_t *results);
 
 /* png_write_kernels.hip: PNG files written into device memory
  * (host_png_write.hip, png_write_plan.h): the scanlines filtered into the

@@ -64,13 +64,33 @@ static __device__ __forceinline__ bool png_depth_ok(u32 depth, u32 colour)
 	return false;
 }
 
+/* the bytes an Adam7 stream of this image inflates to: the seven passes'
+ * rows with their filter bytes (png_adam7_plan.h).  A pass is no larger than
+ * the image, whose height * (1 + rowbytes) the caller has found below 2^32 */
+static __device__ __forceinline__ u64 png_raw7(u32 width, u32 height, u32 bits)
+{
+	/* x0, y0 and the binary logarithms of dx, dy of the passes (PNG 8.2) */
+	constexpr u32 X0[7] = { 0, 4, 0, 2, 0, 1, 0 }, Y0[7] = { 0, 0, 4, 0, 2, 0, 1 };
+	constexpr u32 LX[7] = { 3, 3, 2, 2, 1, 1, 0 }, LY[7] = { 3, 3, 3, 2, 2, 1, 1 };
+	u64 sum = 0;
+#pragma unroll
+	for (u32 p = 0; p < 7; p++) {
+		const u64 w = width > X0[p] ? ((u64)width - X0[p] + (1u << LX[p]) - 1) >> LX[p] : 0;
+		const u64 h = height > Y0[p] ? ((u64)height - Y0[p] + (1u << LY[p]) - 1) >> LY[p] : 0;
+		if (w && h)
+			sum += h * (1 + ((w * bits + 7) >> 3));
+	}
+	return sum;
+}
+
 /*
  * One lane per file: the serial walk over the chunks.  Every step advances 12
  * bytes at least and stays inside the file's length, so the loop ends on any
- * input.
+ * input.  flags: 0, or LDA_PNG_ADAM7 - an interlaced file is then indexed like
+ * any other, its row's interlace byte 1 (libdeflate_amd_png_index_batch_ex).
  */
 extern "C" __global__ void __launch_bounds__(256)
-lda_png_index_kernel(uint64_t n_files, const uint8_t *__restrict__ in,
+lda_png_index_kernel(uint64_t n_files, uint32_t flags, const uint8_t *__restrict__ in,
 		     const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ in_n,
 		     uint64_t *__restrict__ rows, int32_t *__restrict__ results)
 {
@@ -154,7 +174,10 @@ lda_png_index_kernel(uint64_t n_files, const uint8_t *__restrict__ in,
 	}
 	if (state == 0 || (colour == 3 && !plte))
 		return;
-	if (interlace || unknown || rowbytes + 1 > 0xFFFFFFFFull / height) {
+	bool large = rowbytes + 1 > 0xFFFFFFFFull / height;
+	if (interlace && (flags & LDA_PNG_ADAM7) && !large)
+		large = png_raw7(width, height, bits) > 0xFFFFFFFFull;
+	if ((interlace && !(flags & LDA_PNG_ADAM7)) || unknown || large) {
 		results[k] = LDA_PNG_UNSUPPORTED;
 		return;
 	}
