@@ -2255,6 +2255,105 @@ libdeflate_amd_gzip_members_peek_batch(struct libdeflate_decompressor *decompres
 				       size_t max_members, size_t head_nbytes, void *d_heads,
 				       uint64_t *d_head_nbytes, int32_t *d_results, void *stream);
 
+/*
+ * Byte-shuffled deflate chunks: the chunked arrays of HDF5 and NetCDF-4
+ * (filters shuffle, then deflate) and of Zarr (numcodecs.Shuffle, then Zlib or
+ * GZip).  A chunk is one ordinary zlib, gzip or raw DEFLATE stream whose content
+ * is the chunk's bytes transposed.  A chunk of n raw bytes and element size es
+ * has ne = n / es elements and left = n % es bytes behind them:
+ *
+ *     shuffled[j * ne + k]  = raw[k * es + j]      0 <= j < es, 0 <= k < ne
+ *     shuffled[es * ne + t] = raw[es * ne + t]     0 <= t < left
+ *
+ * (H5Z_FILTER_SHUFFLE; the identity when es == 1 or ne <= 1).  Raw bytes 0..9
+ * with es 4 are shuffled 0 4 1 5 2 6 3 7 8 9.
+ *
+ * A chunk is described by a row of LIBDEFLATE_AMD_SHUF_WORDS uint64_t on the
+ * HOST:
+ *   [0] the offset of the stored chunk in the compressed buffer
+ *   [1] its stored size
+ *   [2] the offset of the chunk's raw bytes in the raw buffer (its room)
+ *   [3] the chunk's raw size: exact, and below 2^32
+ *   [4] the element size, 1 .. LIBDEFLATE_AMD_SHUF_ELEM_MAX
+ *   [5] a mask: LIBDEFLATE_AMD_SHUF_NO_DEFLATE - the stored bytes are the
+ *       shuffled bytes themselves (HDF5's filter mask of a chunk on which the
+ *       optional deflate filter was skipped) -, LIBDEFLATE_AMD_SHUF_NO_SHUFFLE -
+ *       the shuffle was skipped.  Any other bit is refused.
+ *
+ * The reader.  format is LIBDEFLATE_AMD_DEFLATE, _ZLIB or _GZIP.  The call only
+ * enqueues on `stream`; the rows go up through the object's pinned block and
+ * the scratch is the object's (object and stream rules:
+ * libdeflate_amd_decompress_batch).  d_results[i] is what
+ * libdeflate_<format>_decompress_ex reports for the chunk with out_nbytes_avail
+ * = word 3 and a NULL actual_out: LIBDEFLATE_SUCCESS only if the stream fills
+ * the raw size exactly, else SHORT_OUTPUT, INSUFFICIENT_SPACE or BAD_DATA.  A
+ * NO_DEFLATE row succeeds if and only if word 1 equals word 3; otherwise it is
+ * BAD_DATA and its room is not written.  A failed chunk's room is undefined; no
+ * byte outside the rooms is ever written; a failed chunk never affects its
+ * neighbours.  The rooms must not overlap each other or d_in (not checked).
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with the row and the reason
+ * in libdeflate_amd_last_error(): a NULL object or pointer (d_in with
+ * in_nbytes == 0 and d_out with out_avail == 0 may be NULL), an unknown format,
+ * n_chunks above 2^28, an element size of 0 or above 256, unknown mask bits, a
+ * raw size of 2^32 or more, a stored range outside in_nbytes, a room outside
+ * out_avail.  n_chunks == 0 does nothing and returns 0.
+ *
+ * Cost: the deflated rows whose transform is not the identity are decoded into
+ * scratch and transposed by one memory-bound kernel over all chunks (tiles of
+ * elements, so many small chunks and one huge chunk are the same work); the
+ * others are decoded straight into d_out, in a decompress batch of their own.
+ * A batch that is identity throughout queues what
+ * libdeflate_amd_decompress_batch queues, plus one small kernel.
+ *
+ * The writer.  Rows use words 2 to 5 (the raw bytes in d_in); words 0 and 1 are
+ * ignored and only LIBDEFLATE_AMD_SHUF_NO_SHUFFLE is allowed in the mask: a
+ * reader's row is a valid writer's row.  Stream k - header, DEFLATE stream,
+ * footer - is byte for byte what libdeflate_<format>_compress() of this build
+ * returns for the shuffled chunk at the object's level, and stands behind
+ * stream k - 1, from offset 0 of d_out.  Chunks of many MiB are compressed as
+ * primed segments like libdeflate_amd_compress_large_batch's.  d_result
+ * (LIBDEFLATE_AMD_SHUFW_RESULT_WORDS uint64_t, device): [0] 0 or
+ * LIBDEFLATE_INSUFFICIENT_SPACE - then nothing is written -, [1] the bytes
+ * written in all, [2] the raw bytes in all, [3] the chunks.  d_index (device, may
+ * be NULL) receives the reader's rows: word 0 the stream's offset in d_out,
+ * word 1 its size, words 2 to 5 the input's; d_out and these rows can go
+ * straight to the reader.  libdeflate_amd_shuffle_compress_bound is the sum of
+ * libdeflate_<format>_compress_bound(raw size), room enough for out_avail; 0
+ * for rows the call refuses.  LIBDEFLATE_AMD_BAD_ARG mirrors the reader's
+ * (in_avail in the place of out_avail; d_out and d_result must not be NULL).
+ * The call only enqueues; conventions are libdeflate_amd_png_encode_batch's.
+ *
+ * Not covered: the Fletcher-32, N-bit, scale-offset and szip filters;
+ * bitshuffle, delta and blosc; parsing a file's own metadata (the caller maps
+ * its chunk index onto the rows: INTEGRATION.md); element sizes above 256;
+ * chunks of 2^32 bytes or more; routing huge chunks to the many-wave decoder
+ * (a chunk is decoded by one wave); store-if-larger in the writer (no chunk is
+ * written with NO_DEFLATE); host-pointer forms.
+ */
+#define LIBDEFLATE_AMD_SHUF_WORDS 6
+#define LIBDEFLATE_AMD_SHUF_ELEM_MAX 256
+#define LIBDEFLATE_AMD_SHUF_NO_DEFLATE 1
+#define LIBDEFLATE_AMD_SHUF_NO_SHUFFLE 2
+#define LIBDEFLATE_AMD_SHUFW_RESULT_WORDS 4
+
+LIBDEFLATEAPI int
+libdeflate_amd_shuffle_decompress_batch(struct libdeflate_decompressor *decompressor, int format,
+					size_t n_chunks, const uint64_t *chunks /* host rows */,
+					const void *d_in, size_t in_nbytes, void *d_out,
+					size_t out_avail, int32_t *d_results, void *stream);
+
+LIBDEFLATEAPI size_t
+libdeflate_amd_shuffle_compress_bound(struct libdeflate_compressor *compressor, int format,
+				      size_t n_chunks, const uint64_t *chunks);
+
+LIBDEFLATEAPI int
+libdeflate_amd_shuffle_compress_batch(struct libdeflate_compressor *compressor, int format,
+				      size_t n_chunks, const uint64_t *chunks /* host rows */,
+				      const void *d_in, size_t in_avail, void *d_out,
+				      size_t out_avail, uint64_t *d_result,
+				      uint64_t *d_index /* may be NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

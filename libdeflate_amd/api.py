@@ -268,6 +268,39 @@ class Compressor:
             result.data_ptr(), index.data_ptr() if index is not None else None, int(filter),
             int(flags), _stream_ptr(stream)), "png_encode_batch")
 
+    def shuffle_compress_bound(self, fmt, rows):
+        """libdeflate_amd_shuffle_compress_bound: room enough for the streams
+        compress_shuffle_batch writes for these rows (shuffle_rows()).  No
+        device is touched; ValueError for rows the call would refuse."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.SHUF_WORDS)
+        size = self._lib.libdeflate_amd_shuffle_compress_bound(
+            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p))
+        if len(r) and not size:
+            raise ValueError("shuffle_compress_bound: a row the compress call refuses")
+        return size
+
+    def compress_shuffle_batch(self, fmt, rows, data, out, result, index=None, stream=None,
+                               in_avail=None, out_avail=None):
+        """libdeflate_amd_shuffle_compress_batch: every chunk of `data` (uint8
+        CUDA tensor; rows: shuffle_rows(), words 2 to 5) byte-shuffled and
+        compressed into one stream of `fmt`, the streams back to back from
+        out[0].  result: int64 CUDA tensor of SHUFW_RESULT_WORDS - [0] 0 or
+        INSUFFICIENT_SPACE, [1] the streams' bytes, [2] the raw bytes, [3] the
+        chunks; index: None or an int64 CUDA tensor of chunks x SHUF_WORDS, the
+        rows decompress_shuffle_batch takes for `out`.  Returns the rows as
+        passed (numpy uint64).  Only enqueues on `stream`."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.SHUF_WORDS)
+        assert result.numel() >= binding.SHUFW_RESULT_WORDS
+        assert index is None or index.numel() >= binding.SHUF_WORDS * len(r)
+        avail = data.numel() if in_avail is None else int(in_avail)
+        check(self._lib.libdeflate_amd_shuffle_compress_batch(
+            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if avail else None, avail, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
+            "shuffle_compress_batch")
+        return r
+
     def tar_write_size(self, names, sizes):
         """libdeflate_amd_tar_write_size: the exact size of the tar archive
         write_tar_batch writes for entries of these names (str or bytes, or
@@ -906,6 +939,25 @@ class Decompressor:
             actual_out.data_ptr() if actual_out is not None else None,
             _stream_ptr(stream)), "decompress_batch")
 
+    def decompress_shuffle_batch(self, fmt, rows, data, out, results, stream=None,
+                                 in_nbytes=None, out_avail=None):
+        """libdeflate_amd_shuffle_decompress_batch: byte-shuffled deflate chunks
+        (HDF5, NetCDF-4, Zarr) of `data` decoded and unshuffled into their rooms
+        of `out`.  rows: host rows of SHUF_WORDS u64 (shuffle_rows(), or the
+        index compress_shuffle_batch wrote); data, out: uint8 CUDA tensors;
+        results: int32 CUDA tensor, one enum libdeflate_result per chunk.
+        Returns the rows as passed (numpy uint64).  Only enqueues."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.SHUF_WORDS)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        assert results.numel() >= len(r)
+        check(self._lib.libdeflate_amd_shuffle_decompress_batch(
+            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
+            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
+            "shuffle_decompress_batch")
+        return r
+
     def decompress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
                               out_offsets, out_avail, results, actual_in=None,
                               actual_out=None, stream=None):
@@ -1261,6 +1313,30 @@ def png_image_rows(shapes, offsets, depth=8, colour=None, plte=None, trns=None):
             rows[k, 6] = int(pl[k][0]) | int(pl[k][1]) << 48
         if tr[k] is not None:
             rows[k, 7] = int(tr[k][0]) | int(tr[k][1]) << 48
+    return rows
+
+
+def shuffle_rows(raw_offsets, raw_sizes, itemsize, stored_offsets=None, stored_sizes=None,
+                 mask=0):
+    """The host rows of the shuffle calls.  raw_offsets / raw_sizes: where each
+    chunk's raw bytes lie (the writer's input, the reader's rooms), in bytes;
+    itemsize: the element size (numpy's dtype.itemsize), one value or one per
+    chunk; stored_offsets / stored_sizes: the stored chunks in the compressed
+    buffer (the reader; None: zeros, which the writer ignores); mask: 0 or
+    SHUF_NO_DEFLATE | SHUF_NO_SHUFFLE, one value or one per chunk.
+    -> numpy uint64 (chunks, SHUF_WORDS)."""
+    n = len(raw_offsets)
+
+    def per_chunk(v):
+        return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+    rows = np.zeros((n, binding.SHUF_WORDS), dtype=np.uint64)
+    cols = (per_chunk(0 if stored_offsets is None else stored_offsets),
+            per_chunk(0 if stored_sizes is None else stored_sizes),
+            raw_offsets, raw_sizes, per_chunk(itemsize), per_chunk(mask))
+    for w, col in enumerate(cols):
+        assert len(col) == n
+        for k in range(n):
+            rows[k, w] = int(col[k])
     return rows
 
 

@@ -64,6 +64,10 @@ SEEK_WINDOW, SEEK_WORDS = 32768, 4
 SIZE_LIMIT_MAX = 0xFFFFFFFF
 # the prefix decompress: the per-stream result of a stream cut at its limit
 PREFIX = 19
+# byte-shuffled deflate chunks: u64 per row, the largest element size, the two
+# mask bits, the words of the writer's result
+SHUF_WORDS, SHUF_ELEM_MAX, SHUF_NO_DEFLATE, SHUF_NO_SHUFFLE = 6, 256, 1, 2
+SHUFW_RESULT_WORDS = 4
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -119,6 +123,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_png_encode_bound", "libdeflate_amd_png_encode_batch",
     "libdeflate_amd_png_index_batch_ex", "libdeflate_amd_png_out_sizes_ex",
     "libdeflate_amd_png_decode_batch_ex",
+    "libdeflate_amd_shuffle_decompress_batch", "libdeflate_amd_shuffle_compress_bound",
+    "libdeflate_amd_shuffle_compress_batch",
 ]
 
 _lib = None
@@ -265,6 +271,11 @@ def load():
     sig("libdeflate_amd_png_out_sizes_ex", c_int, P, SZ, SZ, P, c_uint32, SZ, c_uint32, P, P)
     sig("libdeflate_amd_png_decode_batch_ex", c_int, P, P, SZ, P, SZ, SZ, P, c_uint32, P, SZ,
         SZ, c_uint32, P, P, P)
+    # byte-shuffled deflate chunks (HDF5, NetCDF-4, Zarr): host rows of
+    # SHUF_WORDS u64, streams in a device buffer -> raw bytes and back
+    sig("libdeflate_amd_shuffle_decompress_batch", c_int, P, c_int, SZ, P, P, SZ, P, SZ, P, P)
+    sig("libdeflate_amd_shuffle_compress_bound", SZ, P, c_int, SZ, P)
+    sig("libdeflate_amd_shuffle_compress_batch", c_int, P, c_int, SZ, P, P, SZ, P, SZ, P, P, P)
     # PNG files written: the bound (host arithmetic), and pixel arrays of a
     # device buffer -> files (the image rows on the host)
     sig("libdeflate_amd_png_encode_bound", SZ, P, SZ, P)

@@ -598,6 +598,43 @@ extern "C" __global__ void
 lda_pngw_final_kernel(uint64_t n, uint64_t pixels_total, uint64_t out_avail,
 		      const uint64_t *total_at, uint64_t *result);
 
+/* shuffle_kernels.hip: byte-shuffled deflate chunks (HDF5, NetCDF-4, Zarr;
+ * host_shuffle.hip, host_shuffle_write.hip): the byte transpose over many ragged
+ * chunks and its inverse, tiles of consecutive elements of one chunk, the grid
+ * strides over them; the reader's verdicts merged; the writer's streams sized
+ * and placed, a wave per chunk, their pieces copied by lda_zipw_copy_kernel.
+ * The u_* columns are shuffle_plan.h's SHUF_UCOLS.  Copies of the header's and
+ * the plan's constants (static_assert in host_shuffle.hip) */
+#define LDA_SHUF_TILE 4096		/* elements of a tile, es 1, 2, 4, 8: 256 threads x 16 */
+#define LDA_SHUF_GEN_BYTES 16384	/* any other es: a tile is (this / es) & ~15 elements */
+#define LDA_SHUF_SRC_ALT ((uint64_t)1 << 63)	/* u_src counts from the second base */
+#define LDA_SHUF_VERD_OWN ((uint64_t)1 << 63)	/* verd: the row's own verdict in the low bits */
+extern "C" __global__ void
+lda_unshuffle_kernel(uint64_t n_u, uint64_t n_tiles, const uint64_t *u_tile_end,
+		     const uint64_t *u_src, const uint64_t *u_dst, const uint64_t *u_geom,
+		     const uint8_t *ws, const uint8_t *alt, uint8_t *out);
+extern "C" __global__ void
+lda_shuf_final_kernel(uint64_t n, const uint64_t *verd, const int32_t *decode, int32_t *results);
+extern "C" __global__ void
+lda_shuffle_kernel(uint64_t n_u, uint64_t n_tiles, const uint64_t *u_tile_end,
+		   const uint64_t *u_src, const uint64_t *u_dst, const uint64_t *u_geom,
+		   const uint8_t *in, uint8_t *rooms);
+extern "C" __global__ void
+lda_shufw_chunk_kernel(uint64_t n, int format, const uint64_t *first, const uint64_t *count,
+		       const uint64_t *usize, const uint64_t *pc_off, const uint64_t *pc_n,
+		       const uint64_t *out_n, const uint32_t *sums, uint64_t *csize, uint32_t *sum,
+		       uint64_t *sizes);
+extern "C" __global__ void
+lda_shufw_place_kernel(uint64_t n, int format, int level, uint64_t out_avail,
+		       const uint64_t *ecols, const uint64_t *pc_off, const uint64_t *pc_n,
+		       const uint64_t *slot_off, const uint64_t *out_n, const uint64_t *csize,
+		       const uint32_t *sum, const uint64_t *offsets, const uint64_t *block_sums,
+		       uint8_t *out, uint64_t *cp_src, uint64_t *cp_dst, uint64_t *cp_len,
+		       uint64_t *index);
+extern "C" __global__ void
+lda_shufw_final_kernel(uint64_t n, uint64_t raw_total, uint64_t out_avail,
+		       const uint64_t *total_at, uint64_t *result);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
