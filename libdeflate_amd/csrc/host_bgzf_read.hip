@@ -17,8 +17,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "host_finder.h"
-#include "host_objects.h"
+#include "host_read_plan.h"
 
 using namespace lda;
 
@@ -288,28 +287,21 @@ static int read_ranges(struct libdeflate_decompressor *d, const uint8_t *d_in,
 
 	/* device: [descriptors, transposed][first][trims][ain][results][range
 	 * results are the caller's][slots] */
-	Carve sizes(NULL);
 	uint64_t *g_desc = NULL, *g_first = NULL, *g_trims = NULL, *g_ain = NULL;
 	int32_t *g_res = NULL;
 	uint8_t *g_slots = NULL;
-	size_t up_bytes = 0;
-	auto lay = [&](Carve *cv) {
-		g_desc = cv->take<uint64_t>(4 * N);
-		g_first = cv->take<uint64_t>(n_ranges + 1, 8);
-		g_trims = cv->take<uint64_t>(3 * T, 8);
-		up_bytes = cv->at;
-		g_ain = cv->take<uint64_t>(N);
-		g_res = cv->take<int32_t>(N);
-		g_slots = cv->take<uint8_t>(T * BR_SLOT + 16, 256);
-	};
-	lay(&sizes);
-	LDA_OK_TRY(d->bgzf_up.begin());
-	uint8_t *ws = (uint8_t *)d->bgzf.reserve(sizes.at);
-	uint64_t *h = (uint64_t *)d->bgzf_up.pinned(up_bytes);
-	if (!ws || !h)
-		return LIBDEFLATE_AMD_OOM;
-	Carve real(ws);
-	lay(&real);
+	ReadStage s;
+	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+		g_desc = cv.take<uint64_t>(4 * N);
+		g_first = cv.take<uint64_t>(n_ranges + 1, 8);
+		g_trims = cv.take<uint64_t>(3 * T, 8);
+		const ReadUp up = { g_desc, cv.at };
+		g_ain = cv.take<uint64_t>(N);
+		g_res = cv.take<int32_t>(N);
+		g_slots = cv.take<uint8_t>(T * BR_SLOT + 16, 256);
+		return up;
+	}, s, 0));	/* (the slots end in the slack) */
+	uint64_t *h = (uint64_t *)s.h;
 	/* an edge member's slot as an offset from d_out: the batch has one output
 	 * base, and base + offset is computed modulo 2^64 on both sides */
 	for (size_t t = 0; t < T; t++)
@@ -321,7 +313,7 @@ static int read_ranges(struct libdeflate_decompressor *d, const uint8_t *d_in,
 	memcpy(h + 4 * N, first.data(), (n_ranges + 1) * 8);
 	if (T)
 		memcpy(h + 4 * N + n_ranges + 1, trims.data(), 3 * T * 8);
-	LDA_OK_TRY(d->bgzf_up.send(ws, up_bytes, st));
+	LDA_OK_TRY(read_send(d, s, st));
 	if (N) {
 		int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_GZIP, N, d_in, g_desc, g_desc + N,
 						     d_out, g_desc + 2 * N, g_desc + 3 * N, g_res, g_ain,
@@ -330,9 +322,7 @@ static int read_ranges(struct libdeflate_decompressor *d, const uint8_t *d_in,
 			return rc;
 	}
 	if (T) {
-		DeviceCtx *ctx = device_ctx();
-		const size_t grid = std::min(T, (size_t)ctx->num_cus * 8);
-		hipLaunchKernelGGL(lda_bgzf_trim_kernel, dim3((unsigned)grid), dim3(256), 0, st,
+		hipLaunchKernelGGL(lda_bgzf_trim_kernel, dim3(tile_grid(device_ctx(), T)), dim3(256), 0, st,
 				   (uint64_t)T, (const uint64_t *)g_trims, (const uint8_t *)g_slots,
 				   d_out);
 	}

@@ -89,9 +89,9 @@ static int gzmw_enqueue(struct libdeflate_compressor *c, const gzmw_plan &p, con
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
 	LDA_OK_TRY(pieces_compress(c, s, launches, d_in, st));
-	const unsigned wave_grid = pieces_wave_grid(ctx, n);
+	const unsigned grid = wave_grid(ctx, n);
 	if (n)
-		hipLaunchKernelGGL(lda_gzmw_member_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_gzmw_member_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   ecol[GZMW_E_FIRST], ecol[GZMW_E_COUNT], ecol[GZMW_E_NAME_LEN],
 				   ecol[GZMW_E_USIZE], pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
 				   (const uint64_t *)s.out_n, (const uint32_t *)s.crcs, s.csize, s.crc,
@@ -99,7 +99,7 @@ static int gzmw_enqueue(struct libdeflate_compressor *c, const gzmw_plan &p, con
 	/* (of no records, the total alone: a file of 0 bytes) */
 	const uint64_t *total_at = s.bsum + scan_enqueue(st, n, s.sizes, s.offs, s.bsum);
 	if (n)
-		hipLaunchKernelGGL(lda_gzmw_place_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_gzmw_place_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   c->level, mtime, out_avail, ecol[GZMW_E_FIRST], ecol[GZMW_E_COUNT],
 				   ecol[GZMW_E_NAME_OFF], ecol[GZMW_E_NAME_LEN], ecol[GZMW_E_USIZE],
 				   ecol[GZMW_E_UOFF], (const uint8_t *)s.behind, pcol[ZIPW_P_PC_OFF],

@@ -123,9 +123,9 @@ static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, con
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 		return LIBDEFLATE_AMD_OK;
 	}
-	const unsigned wave_grid = pieces_wave_grid(ctx, n);
+	const unsigned grid = wave_grid(ctx, n);
 	if (n)
-		hipLaunchKernelGGL(lda_pngw_image_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_pngw_image_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   (uint64_t)np, pngw_idat_head_crc(c->level), (const uint64_t *)s.icols,
 				   (const uint64_t *)s.pcols, (const uint64_t *)s.out_n,
 				   (const uint32_t *)s.adlers, (const uint32_t *)s.crcs, s.csize, s.adler,
@@ -133,7 +133,7 @@ static int pngw_enqueue(struct libdeflate_compressor *c, const pngw_plan &p, con
 	/* (of no images, the total alone: 0 bytes) */
 	const uint64_t *total_at = s.bsum + scan_enqueue(st, n, s.sizes, s.offs, s.bsum);
 	if (n)
-		hipLaunchKernelGGL(lda_pngw_place_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_pngw_place_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   (uint64_t)np, c->level, out_avail, (const uint64_t *)s.icols,
 				   (const uint64_t *)s.pcols, (const uint64_t *)s.out_n,
 				   (const uint64_t *)s.csize, (const uint32_t *)s.adler,

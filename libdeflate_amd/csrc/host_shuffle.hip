@@ -20,8 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "host_objects.h"
-#include "kernels.h"
+#include "host_read_plan.h"
 #include "shuffle_plan.h"
 
 using namespace lda;
@@ -48,23 +47,16 @@ static int shuf_decode(struct libdeflate_decompressor *d, int format, const shuf
 	uint8_t *g_area = NULL;
 	uint64_t *g_cols = NULL;
 	int32_t *g_decode = NULL;
-	const size_t up_words = p.cols.size(), up_bytes = up_words * sizeof(uint64_t);
-	auto lay = [&](Carve *cv) {
-		g_area = cv->take<uint8_t>((size_t)p.scratch + 16, 256);
-		g_cols = cv->take<uint64_t>(up_words);
-		g_decode = cv->take<int32_t>(n_dec + 1);
-	};
-	Carve sizes(NULL);
-	lay(&sizes);
-	LDA_OK_TRY(d->bgzf_up.begin());
-	uint8_t *ws = (uint8_t *)d->bgzf.reserve(sizes.at + 16);
-	void *h = d->bgzf_up.pinned(up_bytes);
-	if (!ws || !h)
-		return LIBDEFLATE_AMD_OOM;
-	Carve real(ws);
-	lay(&real);
-	memcpy(h, p.cols.data(), up_bytes);
-	LDA_OK_TRY(d->bgzf_up.send(g_cols, up_bytes, st));
+	ReadStage s;
+	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+		g_area = cv.take<uint8_t>((size_t)p.scratch + 16, 256);
+		g_cols = cv.take<uint64_t>(p.cols.size());
+		g_decode = cv.take<int32_t>(n_dec + 1);
+		return ReadUp{ g_cols, p.cols.size() * sizeof(uint64_t) };
+	}, s));
+	memcpy(s.h, p.cols.data(), s.up.bytes);
+	LDA_OK_TRY(read_send(d, s, st));
+	uint8_t *ws = s.ws;
 	const uint64_t *dcol[SHUF_DCOLS], *ucol[SHUF_UCOLS];
 	for (size_t a = 0; a < SHUF_DCOLS; a++)
 		dcol[a] = g_cols + a * n_dec;
@@ -88,11 +80,9 @@ static int shuf_decode(struct libdeflate_decompressor *d, int format, const shuf
 			return rc;
 	}
 	if (p.tiles && (stages & SHUF_STAGE_UNSHUFFLE)) {
-		/* the workgroups stride over the tiles: eight to a CU fill its wave slots */
-		const unsigned grid = (unsigned)std::min(p.tiles, (uint64_t)ctx->num_cus * 8);
-		hipLaunchKernelGGL(lda_unshuffle_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n_u,
-				   p.tiles, ucol[SHUF_U_TILE_END], ucol[SHUF_U_SRC], ucol[SHUF_U_DST],
-				   ucol[SHUF_U_GEOM], (const uint8_t *)g_area, in, out);
+		hipLaunchKernelGGL(lda_unshuffle_kernel, dim3(tile_grid(ctx, p.tiles)), dim3(256), 0, st,
+				   (uint64_t)n_u, p.tiles, ucol[SHUF_U_TILE_END], ucol[SHUF_U_SRC],
+				   ucol[SHUF_U_DST], ucol[SHUF_U_GEOM], (const uint8_t *)g_area, in, out);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
 	hipLaunchKernelGGL(lda_shuf_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
@@ -111,19 +101,12 @@ static int shuf_call(const char *what, struct libdeflate_decompressor *d, int fo
 		set_error("%s: NULL argument", what);
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
-	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
-		std::string err;
-		if (!shuf_check(format, n_chunks, chunks, true, in_nbytes, out_avail, -1, err)) {
-			set_error("%s: %s", what, err.c_str());
-			return LIBDEFLATE_AMD_BAD_ARG;
-		}
-		if (n_chunks == 0)
-			return LIBDEFLATE_AMD_OK;
-		DeviceGuard on(d->device);
-		if (!on.ok() || !device_ctx())
-			return LIBDEFLATE_AMD_NO_DEVICE;
-		shuf_read_plan p;
+	return read_call<shuf_read_plan>(what, d, n_chunks, [&](shuf_read_plan &p, std::string &err) {
+		if (!shuf_check(format, n_chunks, chunks, true, in_nbytes, out_avail, -1, err))
+			return false;
 		shuf_read_plan_build(n_chunks, chunks, p);
+		return true;
+	}, [&](const shuf_read_plan &p) {
 		return shuf_decode(d, format, p, (const uint8_t *)d_in, (uint8_t *)d_out, d_results,
 				   stages, (hipStream_t)stream);
 	});

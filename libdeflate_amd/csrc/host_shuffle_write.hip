@@ -89,10 +89,8 @@ static int shufw_enqueue(struct libdeflate_compressor *c, int format, const shuf
 		ucol[a] = s.ecols + SHUFW_ECOLS * n + a * n_u;
 
 	if (p.tiles && (stages & SHUFW_STAGE_SHUFFLE)) {
-		/* the workgroups stride over the tiles: eight to a CU fill its wave slots */
-		const unsigned grid = (unsigned)std::min(p.tiles, (uint64_t)ctx->num_cus * 8);
-		hipLaunchKernelGGL(lda_shuffle_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n_u,
-				   p.tiles, ucol[SHUF_U_TILE_END], ucol[SHUF_U_SRC], ucol[SHUF_U_DST],
+		hipLaunchKernelGGL(lda_shuffle_kernel, dim3(tile_grid(ctx, p.tiles)), dim3(256), 0, st,
+				   (uint64_t)n_u, p.tiles, ucol[SHUF_U_TILE_END], ucol[SHUF_U_SRC], ucol[SHUF_U_DST],
 				   ucol[SHUF_U_GEOM], d_in, s.rooms);
 	}
 	int rc = LIBDEFLATE_AMD_OK;
@@ -110,16 +108,16 @@ static int shufw_enqueue(struct libdeflate_compressor *c, int format, const shuf
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 		return LIBDEFLATE_AMD_OK;
 	}
-	const unsigned wave_grid = pieces_wave_grid(ctx, n);
+	const unsigned grid = wave_grid(ctx, n);
 	if (n)
-		hipLaunchKernelGGL(lda_shufw_chunk_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_shufw_chunk_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   format, ecol[SHUFW_E_FIRST], ecol[SHUFW_E_COUNT], ecol[SHUFW_E_USIZE],
 				   pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N], (const uint64_t *)s.out_n,
 				   (const uint32_t *)s.sums, s.csize, s.sum, s.sizes);
 	/* (of no chunks, the total alone: 0 bytes) */
 	const uint64_t *total_at = s.bsum + scan_enqueue(st, n, s.sizes, s.offs, s.bsum);
 	if (n)
-		hipLaunchKernelGGL(lda_shufw_place_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_shufw_place_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   format, c->level, out_avail, (const uint64_t *)s.ecols,
 				   pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N], pcol[ZIPW_P_SLOT_OFF],
 				   (const uint64_t *)s.out_n, (const uint64_t *)s.csize,

@@ -22,8 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "host_finder.h"
-#include "host_objects.h"
+#include "host_read_plan.h"
 #include "tar_plan.h"
 
 using namespace lda;
@@ -80,15 +79,6 @@ static TarScratch tar_scratch(void *base, size_t nb, size_t M)
 	return s;
 }
 
-static bool align_ok(const char *what, size_t out_align)
-{
-	if (!out_align || out_align > 256 || (out_align & (out_align - 1))) {
-		set_error("%s: out_align %zu is not a power of two in 1 .. 256", what, out_align);
-		return false;
-	}
-	return true;
-}
-
 /* what the two device-only calls check before they touch a device */
 static bool tar_args_ok(const char *what, const struct libdeflate_decompressor *d,
 			const void *d_in, size_t n, size_t max_records, size_t out_align,
@@ -100,14 +90,7 @@ static bool tar_args_ok(const char *what, const struct libdeflate_decompressor *
 	}
 	return finder_args_ok(what, d, d_in, n, "%s: max_records %zu (1 .. 2^28)", max_records, 1,
 			      d_result) &&
-	       align_ok(what, out_align);
-}
-
-/* the copy's grid from a bound on its tiles: eight workgroups of four waves
- * fill a CU, and the grid strides over what is beyond */
-static unsigned copy_grid(const DeviceCtx *ctx, uint64_t tiles_bound)
-{
-	return (unsigned)std::max((uint64_t)1, std::min(tiles_bound, (uint64_t)ctx->num_cus * 8));
+	       read_align_ok(what, out_align);
 }
 
 static int tar_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, size_t n, size_t M,
@@ -225,19 +208,17 @@ static int tar_read(struct libdeflate_decompressor *d, const uint8_t *d_in, size
 	DeviceCtx *ctx = device_ctx();
 	/* device: [the plan's columns][the tile count][the results] */
 	const size_t col_bytes = cols.size() * sizeof(uint64_t);
-	const size_t up_bytes = col_bytes + n_sel * sizeof(int32_t);
-
-	LDA_OK_TRY(d->bgzf_up.begin());
-	uint8_t *ws = (uint8_t *)d->bgzf.reserve(up_bytes + 16);
-	uint8_t *h = (uint8_t *)d->bgzf_up.pinned(up_bytes);
-	if (!ws || !h)
-		return LIBDEFLATE_AMD_OOM;
-	memcpy(h, cols.data(), col_bytes);
-	memcpy(h + col_bytes, results.data(), n_sel * sizeof(int32_t));
-	LDA_OK_TRY(d->bgzf_up.send(ws, up_bytes, st));
-	const uint64_t *g = (const uint64_t *)ws;
+	ReadStage s;
+	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+		uint8_t *up = cv.take<uint8_t>(col_bytes + n_sel * sizeof(int32_t));
+		return ReadUp{ up, cv.at };
+	}, s));
+	memcpy(s.h, cols.data(), col_bytes);
+	memcpy(s.h + col_bytes, results.data(), n_sel * sizeof(int32_t));
+	LDA_OK_TRY(read_send(d, s, st));
+	const uint64_t *g = (const uint64_t *)s.ws;
 	const uint64_t tiles = cols[TAR_COLS * n_sel];
-	LDA_HIP_TRY(hipMemcpyAsync(d_results, ws + col_bytes, n_sel * sizeof(int32_t),
+	LDA_HIP_TRY(hipMemcpyAsync(d_results, s.ws + col_bytes, n_sel * sizeof(int32_t),
 				   hipMemcpyDeviceToDevice, st),
 		    LIBDEFLATE_AMD_NO_DEVICE);
 	if (tiles) {	/* (then d_out is not NULL) */
@@ -250,20 +231,6 @@ static int tar_read(struct libdeflate_decompressor *d, const uint8_t *d_in, size
 	return LIBDEFLATE_AMD_OK;
 }
 
-static bool sel_args_ok(const char *what, const uint64_t *index, size_t entries, size_t n_sel,
-			const uint64_t *sel)
-{
-	if ((!index && entries) || (n_sel && !sel)) {
-		set_error("%s: NULL argument", what);
-		return false;
-	}
-	if (entries > LDA_FINDER_MAX_RECORDS || n_sel > LDA_FINDER_MAX_RECORDS) {
-		set_error("%s: entries %zu, n_sel %zu (at most 2^28)", what, entries, n_sel);
-		return false;
-	}
-	return true;
-}
-
 extern "C" LIBDEFLATEAPI int
 libdeflate_amd_tar_read_batch(struct libdeflate_decompressor *d, const void *d_in,
 			      size_t in_nbytes, const uint64_t *index, size_t entries, size_t n_sel,
@@ -271,33 +238,18 @@ libdeflate_amd_tar_read_batch(struct libdeflate_decompressor *d, const void *d_i
 			      uint64_t *out_offsets, int32_t *d_results, void *stream)
 {
 	const char *what = "tar_read_batch";
-	if (!d || (!d_in && in_nbytes) || (!d_out && out_avail) || (n_sel && !d_results)) {
-		set_error("%s: NULL argument", what);
+	if (!read_args_ok(what, d, d_in, in_nbytes, index, entries, n_sel, sel, d_out, out_avail,
+			  out_align, d_results))
 		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	if (!sel_args_ok(what, index, entries, n_sel, sel))
-		return LIBDEFLATE_AMD_BAD_ARG;
-	if (in_nbytes > LDA_FINDER_MAX_FILE) {
-		set_error("%s: in_nbytes %zu above 2^36", what, in_nbytes);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	if (!align_ok(what, out_align))
-		return LIBDEFLATE_AMD_BAD_ARG;
-	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
+	struct Plan {
 		std::vector<uint64_t> cols;
 		std::vector<int32_t> results;
-		std::string err;
-		if (!tar_plan_read(index, entries, n_sel, sel, in_nbytes, out_avail, out_align - 1,
-				   cols, results, out_offsets, NULL, err)) {
-			set_error("%s: %s", what, err.c_str());
-			return LIBDEFLATE_AMD_BAD_ARG;
-		}
-		if (n_sel == 0)
-			return LIBDEFLATE_AMD_OK;
-		DeviceGuard on(d->device);
-		if (!on.ok() || !device_ctx())
-			return LIBDEFLATE_AMD_NO_DEVICE;
-		return tar_read(d, (const uint8_t *)d_in, n_sel, cols, results, (uint8_t *)d_out,
+	};
+	return read_call<Plan>(what, d, n_sel, [&](Plan &p, std::string &err) {
+		return tar_plan_read(index, entries, n_sel, sel, in_nbytes, out_avail, out_align - 1,
+				     p.cols, p.results, out_offsets, NULL, err);
+	}, [&](const Plan &p) {
+		return tar_read(d, (const uint8_t *)d_in, n_sel, p.cols, p.results, (uint8_t *)d_out,
 				d_results, (hipStream_t)stream);
 	});
 }
@@ -307,21 +259,18 @@ libdeflate_amd_tar_ranges(const uint64_t *index, size_t entries, size_t n_sel, c
 			  uint64_t *ranges, uint64_t *total_ret)
 {
 	const char *what = "tar_ranges";
-	if (!sel_args_ok(what, index, entries, n_sel, sel))
+	if (!read_sel_args_ok(what, index, entries, n_sel, sel))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	if (n_sel && !ranges) {
 		set_error("%s: NULL argument", what);
 		return LIBDEFLATE_AMD_BAD_ARG;
 	}
-	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
-		std::string err;
+	return read_plan_call(what, [&](std::string &err) {
 		uint64_t total = 0;
-		if (!tar_plan_ranges(index, entries, n_sel, sel, ranges, &total, err)) {
-			set_error("%s: %s", what, err.c_str());
-			return LIBDEFLATE_AMD_BAD_ARG;
-		}
+		if (!tar_plan_ranges(index, entries, n_sel, sel, ranges, &total, err))
+			return false;
 		if (total_ret)
 			*total_ret = total;
-		return LIBDEFLATE_AMD_OK;
+		return true;
 	});
 }

@@ -8,7 +8,7 @@
 #ifndef LDA_HOST_WRITE_PIECES_H
 #define LDA_HOST_WRITE_PIECES_H
 
-#include "host_objects.h"
+#include "host_read_plan.h"	/* the grids: wave_grid(), tile_grid() */
 #include "write_pieces_plan.h"
 
 namespace lda {
@@ -47,9 +47,6 @@ int pieces_upload(struct libdeflate_compressor *c, const PiecesScratch &hs, cons
 /* every launch of the list: the pieces, read at src + their offsets, into their slots */
 int pieces_compress(struct libdeflate_compressor *c, const PiecesScratch &s,
 		    const std::vector<zipw_launch> &launches, const uint8_t *src, hipStream_t st);
-
-/* 256-thread workgroups of the kernels that give every entry a wave */
-unsigned pieces_wave_grid(const DeviceCtx *ctx, size_t n);
 
 /* lda_zipw_copy_kernel over the np pieces the writer's place kernel has listed;
  * tail: bytes the writer puts behind the pieces' total (the ZIP directory) */

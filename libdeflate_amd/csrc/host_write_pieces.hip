@@ -94,19 +94,13 @@ int lda::pieces_compress(struct libdeflate_compressor *c, const PiecesScratch &s
 	return LIBDEFLATE_AMD_OK;
 }
 
-unsigned lda::pieces_wave_grid(const DeviceCtx *ctx, size_t n)
-{
-	return (unsigned)std::max((size_t)1, std::min((n + 3) / 4, (size_t)ctx->num_cus * 16));
-}
-
 void lda::pieces_copy(const DeviceCtx *ctx, const PiecesScratch &s, size_t np, const uint64_t *total_at,
 		      uint64_t out_avail, uint64_t tail, const uint8_t *d_in, uint8_t *d_out,
 		      hipStream_t st)
 {
 	if (!np)
 		return;
-	const size_t grid = std::min(np, (size_t)ctx->num_cus * 8);
-	hipLaunchKernelGGL(lda_zipw_copy_kernel, dim3((unsigned)grid), dim3(256), 0, st, (uint64_t)np,
+	hipLaunchKernelGGL(lda_zipw_copy_kernel, dim3(tile_grid(ctx, np)), dim3(256), 0, st, (uint64_t)np,
 			   total_at, out_avail, tail, (const uint64_t *)s.cp_src,
 			   (const uint64_t *)s.cp_dst, (const uint64_t *)s.cp_len, d_in,
 			   (const uint8_t *)s.slots, d_out);

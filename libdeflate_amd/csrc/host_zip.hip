@@ -25,7 +25,7 @@
 #include <string>
 #include <vector>
 
-#include "host_zip_args.h"
+#include "host_read_plan.h"
 #include "zip_plan.h"
 
 using namespace lda;
@@ -93,7 +93,7 @@ static bool zip_args_ok(const char *what, const struct libdeflate_decompressor *
 	}
 	return finder_args_ok(what, d, d_in, n, "%s: max_entries %zu (1 .. 2^28)", max_entries, 1,
 			      d_result) &&
-	       zip_align_ok(what, out_align);
+	       read_align_ok(what, out_align);
 }
 
 static int zip_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, size_t n, size_t M,
@@ -156,7 +156,7 @@ static int zip_enqueue(struct libdeflate_decompressor *d, const uint8_t *d_in, s
 						     NULL, st);
 		if (rc != LIBDEFLATE_AMD_OK)
 			return rc;
-		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(zip_copy_grid(ctx, M)), dim3(256), 0, st,
+		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, M)), dim3(256), 0, st,
 				   (uint64_t)M, (const uint64_t *)s.cp_src,
 				   (const uint64_t *)s.out_off, (const uint64_t *)s.cp_len, d_in, out);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
@@ -212,53 +212,50 @@ libdeflate_amd_zip_index_batch(struct libdeflate_decompressor *d, const void *d_
 
 /* ---- a selection of entries, index rows on the host ---- */
 
+int lda::zip_read_entries(struct libdeflate_decompressor *d, size_t n, const uint64_t *const *col,
+			  int32_t *g_res, uint64_t *g_ain, uint32_t *g_crc, const uint8_t *in,
+			  uint8_t *out, hipStream_t st, size_t n_pieces, const uint64_t *pc_src,
+			  const uint64_t *pc_dst, const uint64_t *pc_len)
+{
+	DeviceCtx *ctx = device_ctx();
+	LDA_OK_TRY(libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_DEFLATE, n, in, col[ZIP_COL_IN_OFF],
+						   col[ZIP_COL_IN_N], out, col[ZIP_COL_OUT_OFF],
+						   col[ZIP_COL_OUT_AV], g_res, g_ain, NULL, st));
+	hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, n)), dim3(256), 0, st, (uint64_t)n,
+			   col[ZIP_COL_CP_SRC], col[ZIP_COL_OUT_OFF], col[ZIP_COL_CP_LEN], in, out);
+	if (n_pieces)
+		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, n_pieces)), dim3(256), 0, st,
+				   (uint64_t)n_pieces, pc_src, pc_dst, pc_len, in, out);
+	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+	return libdeflate_amd_crc32_batch(n, out, col[ZIP_COL_OUT_OFF], col[ZIP_COL_CRC_N], NULL, g_crc,
+					  st);
+}
+
 static int zip_read(struct libdeflate_decompressor *d, const uint8_t *d_in, size_t n_sel,
 		    const std::vector<uint64_t> &cols, uint8_t *d_out, int32_t *d_results,
 		    hipStream_t st)
 {
-	DeviceCtx *ctx = device_ctx();
 	/* device: [the plan's columns][ain][batch results][crcs] */
 	uint64_t *g_cols = NULL, *g_ain = NULL;
 	int32_t *g_res = NULL;
 	uint32_t *g_crc = NULL;
-	size_t up_bytes = 0;
-	auto lay = [&](Carve *cv) {
-		g_cols = cv->take<uint64_t>(ZIP_COLS * n_sel);
-		up_bytes = cv->at;
-		g_ain = cv->take<uint64_t>(n_sel);
-		g_res = cv->take<int32_t>(n_sel);
-		g_crc = cv->take<uint32_t>(n_sel);
-	};
-	Carve sizes(NULL);
-	lay(&sizes);
-	LDA_OK_TRY(d->bgzf_up.begin());
-	uint8_t *ws = (uint8_t *)d->bgzf.reserve(sizes.at + 16);
-	void *h = d->bgzf_up.pinned(up_bytes);
-	if (!ws || !h)
-		return LIBDEFLATE_AMD_OOM;
-	Carve real(ws);
-	lay(&real);
-	memcpy(h, cols.data(), up_bytes);
-	LDA_OK_TRY(d->bgzf_up.send(ws, up_bytes, st));
+	ReadStage s;
+	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+		g_cols = cv.take<uint64_t>(ZIP_COLS * n_sel);
+		const ReadUp up = { g_cols, cv.at };
+		g_ain = cv.take<uint64_t>(n_sel);
+		g_res = cv.take<int32_t>(n_sel);
+		g_crc = cv.take<uint32_t>(n_sel);
+		return up;
+	}, s));
+	memcpy(s.h, cols.data(), s.up.bytes);
+	LDA_OK_TRY(read_send(d, s, st));
 	const uint64_t *col[ZIP_COLS];
 	for (size_t a = 0; a < ZIP_COLS; a++)
 		col[a] = g_cols + a * n_sel;
 	/* (a NULL d_out has out_avail 0: nothing is written, nothing is read) */
-	uint8_t *out = d_out ? d_out : ws;
-	int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_DEFLATE, n_sel, d_in,
-					     col[ZIP_COL_IN_OFF], col[ZIP_COL_IN_N], out,
-					     col[ZIP_COL_OUT_OFF], col[ZIP_COL_OUT_AV], g_res, g_ain, NULL,
-					     st);
-	if (rc != LIBDEFLATE_AMD_OK)
-		return rc;
-	hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(zip_copy_grid(ctx, n_sel)), dim3(256), 0, st,
-			   (uint64_t)n_sel, col[ZIP_COL_CP_SRC], col[ZIP_COL_OUT_OFF],
-			   col[ZIP_COL_CP_LEN], d_in, out);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	rc = libdeflate_amd_crc32_batch(n_sel, out, col[ZIP_COL_OUT_OFF], col[ZIP_COL_CRC_N], NULL,
-					g_crc, st);
-	if (rc != LIBDEFLATE_AMD_OK)
-		return rc;
+	uint8_t *out = d_out ? d_out : s.ws;
+	LDA_OK_TRY(zip_read_entries(d, n_sel, col, g_res, g_ain, g_crc, d_in, out, st));
 	hipLaunchKernelGGL(lda_zip_rfinal_kernel, dim3((unsigned)((n_sel + 255) / 256)), dim3(256),
 			   0, st, (uint64_t)n_sel, col[ZIP_COL_META], col[ZIP_COL_IN_N],
 			   (const int32_t *)g_res, (const uint64_t *)g_ain, (const uint32_t *)g_crc,
@@ -274,22 +271,14 @@ libdeflate_amd_zip_read_batch(struct libdeflate_decompressor *d, const void *d_i
 			      uint64_t *out_offsets, int32_t *d_results, void *stream)
 {
 	const char *what = "zip_read_batch";
-	if (!zip_read_args_ok(what, d, d_in, in_nbytes, index, entries, n_sel, sel, d_out, out_avail,
-			      out_align, d_results))
+	if (!read_args_ok(what, d, d_in, in_nbytes, index, entries, n_sel, sel, d_out, out_avail,
+			  out_align, d_results))
 		return LIBDEFLATE_AMD_BAD_ARG;
-	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
-		std::vector<uint64_t> cols;
-		std::string err;
-		if (!zip_plan_read(index, entries, n_sel, sel, in_nbytes, out_avail, out_align - 1,
-				   cols, out_offsets, NULL, err)) {
-			set_error("%s: %s", what, err.c_str());
-			return LIBDEFLATE_AMD_BAD_ARG;
-		}
-		if (n_sel == 0)
-			return LIBDEFLATE_AMD_OK;
-		DeviceGuard on(d->device);
-		if (!on.ok() || !device_ctx())
-			return LIBDEFLATE_AMD_NO_DEVICE;
+	typedef std::vector<uint64_t> Cols;
+	return read_call<Cols>(what, d, n_sel, [&](Cols &cols, std::string &err) {
+		return zip_plan_read(index, entries, n_sel, sel, in_nbytes, out_avail, out_align - 1,
+				     cols, out_offsets, NULL, err);
+	}, [&](const Cols &cols) {
 		return zip_read(d, (const uint8_t *)d_in, n_sel, cols, (uint8_t *)d_out, d_results,
 				(hipStream_t)stream);
 	});

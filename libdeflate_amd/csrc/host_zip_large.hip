@@ -29,7 +29,7 @@
 #include <string>
 #include <vector>
 
-#include "host_zip_args.h"
+#include "host_read_plan.h"
 #include "zip_large_plan.h"
 
 using namespace lda;
@@ -49,28 +49,21 @@ static int zip_read_large(struct libdeflate_decompressor *d, const uint8_t *d_in
 	uint64_t *g_cols = NULL, *g_own = NULL, *g_pcs = NULL, *g_ain = NULL;
 	int32_t *g_res = NULL;
 	uint32_t *g_crc = NULL, *g_pcrc = NULL;
-	size_t up_bytes = 0;
-	auto lay = [&](Carve *cv) {
-		g_cols = cv->take<uint64_t>(ZIP_COLS * n_sel, 8);
-		g_own = cv->take<uint64_t>(ZIPL_COLS * L, 8);
-		g_pcs = cv->take<uint64_t>(ZIPP_COLS * P, 8);
-		up_bytes = cv->at;
-		g_ain = cv->take<uint64_t>(n_sel);
-		g_res = cv->take<int32_t>(n_sel);
-		g_crc = cv->take<uint32_t>(n_sel);
-		g_pcrc = cv->take<uint32_t>(P);
-	};
-	Carve sizes(NULL);
-	lay(&sizes);
-	LDA_OK_TRY(d->bgzf_up.begin());
-	uint8_t *ws = (uint8_t *)d->bgzf.reserve(sizes.at + 16);
-	uint8_t *h = (uint8_t *)d->bgzf_up.pinned(up_bytes);
-	if (!ws || !h)
-		return LIBDEFLATE_AMD_OOM;
-	Carve real(ws);
-	lay(&real);
+	ReadStage s;
+	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+		g_cols = cv.take<uint64_t>(ZIP_COLS * n_sel, 8);
+		g_own = cv.take<uint64_t>(ZIPL_COLS * L, 8);
+		g_pcs = cv.take<uint64_t>(ZIPP_COLS * P, 8);
+		const ReadUp up = { g_cols, cv.at };
+		g_ain = cv.take<uint64_t>(n_sel);
+		g_res = cv.take<int32_t>(n_sel);
+		g_crc = cv.take<uint32_t>(n_sel);
+		g_pcrc = cv.take<uint32_t>(P);
+		return up;
+	}, s));
+	uint8_t *h = s.h;
 	/* (a NULL d_out has out_avail 0: nothing is written, nothing is read) */
-	uint8_t *out = d_out ? d_out : ws;
+	uint8_t *out = d_out ? d_out : s.ws;
 
 	/* the many-wave entries, one after another, each filling the device */
 	uint64_t *own[ZIPL_COLS];
@@ -96,7 +89,7 @@ static int zip_read_large(struct libdeflate_decompressor *d, const uint8_t *d_in
 		memcpy(h + b_cols, p.own.data(), b_own);
 	if (P)
 		memcpy(h + b_cols + b_own, p.pieces.data(), sizeof(uint64_t) * ZIPP_COLS * P);
-	LDA_OK_TRY(d->bgzf_up.send(ws, up_bytes, st));
+	LDA_OK_TRY(read_send(d, s, st));
 	const uint64_t *col[ZIP_COLS], *lc[ZIPL_COLS], *pc[ZIPP_COLS];
 	for (size_t a = 0; a < ZIP_COLS; a++)
 		col[a] = g_cols + a * n_sel;
@@ -105,27 +98,12 @@ static int zip_read_large(struct libdeflate_decompressor *d, const uint8_t *d_in
 	for (size_t a = 0; a < ZIPP_COLS; a++)
 		pc[a] = g_pcs + a * P;
 
-	int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_DEFLATE, n_sel, d_in,
-						 col[ZIP_COL_IN_OFF], col[ZIP_COL_IN_N], out,
-						 col[ZIP_COL_OUT_OFF], col[ZIP_COL_OUT_AV], g_res, g_ain, NULL,
-						 st);
-	if (rc != LIBDEFLATE_AMD_OK)
-		return rc;
-	hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(zip_copy_grid(ctx, n_sel)), dim3(256), 0, st,
-			   (uint64_t)n_sel, col[ZIP_COL_CP_SRC], col[ZIP_COL_OUT_OFF],
-			   col[ZIP_COL_CP_LEN], d_in, out);
+	/* the sibling's batch, the pieces' copy behind the entries' */
+	LDA_OK_TRY(zip_read_entries(d, n_sel, col, g_res, g_ain, g_crc, d_in, out, st, P,
+				    pc[ZIPP_COL_SRC], pc[ZIPP_COL_DST], pc[ZIPP_COL_CP]));
 	if (P)
-		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(zip_copy_grid(ctx, P)), dim3(256), 0, st,
-				   (uint64_t)P, pc[ZIPP_COL_SRC], pc[ZIPP_COL_DST], pc[ZIPP_COL_CP], d_in,
-				   out);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	rc = libdeflate_amd_crc32_batch(n_sel, out, col[ZIP_COL_OUT_OFF], col[ZIP_COL_CRC_N], NULL,
-					g_crc, st);
-	if (rc == LIBDEFLATE_AMD_OK && P)
-		rc = libdeflate_amd_crc32_batch(P, out, pc[ZIPP_COL_DST], pc[ZIPP_COL_LEN], NULL, g_pcrc,
-						st);
-	if (rc != LIBDEFLATE_AMD_OK)
-		return rc;
+		LDA_OK_TRY(libdeflate_amd_crc32_batch(P, out, pc[ZIPP_COL_DST], pc[ZIPP_COL_LEN], NULL,
+						      g_pcrc, st));
 	/* the two final kernels never write the same row: the runs are the rows
 	 * without the mark that lda_zip_lfinal_kernel looks for */
 	for (size_t k = 0; k + 1 < p.runs.size(); k += 2) {
@@ -136,9 +114,8 @@ static int zip_read_large(struct libdeflate_decompressor *d, const uint8_t *d_in
 				   (const uint32_t *)g_crc + r0, d_results + r0);
 	}
 	if (L)
-		hipLaunchKernelGGL(lda_zip_lfinal_kernel,
-				   dim3((unsigned)std::min((L + 3) / 4, (size_t)ctx->num_cus * 8)),
-				   dim3(256), 0, st, (uint64_t)L, (uint64_t)n_sel, (uint64_t)P,
+		hipLaunchKernelGGL(lda_zip_lfinal_kernel, dim3(tile_grid(ctx, (L + 3) / 4)), dim3(256), 0,
+				   st, (uint64_t)L, (uint64_t)n_sel, (uint64_t)P,
 				   lc[ZIPL_COL_SEL], lc[ZIPL_COL_FLAGS], lc[ZIPL_COL_IN_N],
 				   lc[ZIPL_COL_USIZE], lc[ZIPL_COL_FIRST], lc[ZIPL_COL_COUNT],
 				   lc[ZIPL_COL_RES], lc[ZIPL_COL_AIN], col[ZIP_COL_META],
@@ -156,25 +133,16 @@ libdeflate_amd_zip_read_large(struct libdeflate_decompressor *d, const void *d_i
 			      void *stream)
 {
 	const char *what = "zip_read_large";
-	if (!zip_read_args_ok(what, d, d_in, in_nbytes, index, entries, n_sel, sel, d_out, out_avail,
-			      out_align, d_results))
+	if (!read_args_ok(what, d, d_in, in_nbytes, index, entries, n_sel, sel, d_out, out_avail,
+			  out_align, d_results))
 		return LIBDEFLATE_AMD_BAD_ARG;
 	if (!large_min)
 		large_min = env_cfg().zip_large_min;
-	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
-		ZipLargePlan plan;
-		std::string err;
-		if (!zip_plan_read_large(index, entries, n_sel, sel, in_nbytes, out_avail,
-					 out_align - 1, large_min, LIBDEFLATE_AMD_ZIP_PIECE, plan,
-					 out_offsets, NULL, err)) {
-			set_error("%s: %s", what, err.c_str());
-			return LIBDEFLATE_AMD_BAD_ARG;
-		}
-		if (n_sel == 0)
-			return LIBDEFLATE_AMD_OK;
-		DeviceGuard on(d->device);
-		if (!on.ok() || !device_ctx())
-			return LIBDEFLATE_AMD_NO_DEVICE;
+	return read_call<ZipLargePlan>(what, d, n_sel, [&](ZipLargePlan &plan, std::string &err) {
+		return zip_plan_read_large(index, entries, n_sel, sel, in_nbytes, out_avail,
+					   out_align - 1, large_min, LIBDEFLATE_AMD_ZIP_PIECE, plan,
+					   out_offsets, NULL, err);
+	}, [&](ZipLargePlan &plan) {
 		return zip_read_large(d, (const uint8_t *)d_in, n_sel, plan, (uint8_t *)d_out,
 				      d_results, (hipStream_t)stream);
 	});

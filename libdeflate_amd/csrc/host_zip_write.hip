@@ -88,9 +88,9 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 	if (rc != LIBDEFLATE_AMD_OK)
 		return rc;
 	LDA_OK_TRY(pieces_compress(c, s, launches, d_in, st));
-	const unsigned wave_grid = pieces_wave_grid(ctx, n);
+	const unsigned grid = wave_grid(ctx, n);
 	if (n)
-		hipLaunchKernelGGL(lda_zipw_entry_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_zipw_entry_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   ecol[ZIPW_E_FIRST], ecol[ZIPW_E_COUNT], ecol[ZIPW_E_NAME_LEN],
 				   ecol[ZIPW_E_USIZE], pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
 				   (const uint64_t *)(compressed ? s.out_n : NULL),
@@ -98,7 +98,7 @@ static int zipw_enqueue(struct libdeflate_compressor *c, const zipw_plan &p, con
 	/* (of no entries, the total alone: cd_off 0) */
 	const uint64_t *total_at = s.bsum + scan_enqueue(st, n, s.sizes, s.offs, s.bsum);
 	if (n)
-		hipLaunchKernelGGL(lda_zipw_place_kernel, dim3(wave_grid), dim3(256), 0, st, (uint64_t)n,
+		hipLaunchKernelGGL(lda_zipw_place_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
 				   (uint32_t)p.zip64, dos_datetime, out_avail, tail, ecol[ZIPW_E_FIRST],
 				   ecol[ZIPW_E_COUNT], ecol[ZIPW_E_NAME_OFF], ecol[ZIPW_E_NAME_LEN],
 				   ecol[ZIPW_E_CEN], ecol[ZIPW_E_USIZE], ecol[ZIPW_E_UOFF],

@@ -44,6 +44,13 @@ Which step touches which field of the object (csrc/host_objects.h):
     batch-host, ex-host       host            yes       d->tokens, d->scratch, pinned slices
     refused-*                 refused         no        - (the call returns before any device work)
 
+    (reader_steps(): the readers that joined the shared host pipeline later)
+    png, png-zero             png             no        d->bgzf, d->bgzf_up, d->tokens
+    png-pixels                png-pixels      no        d->bgzf, d->bgzf_up, d->tokens
+    png-ex, png-ex-raw        png-adam7       no        d->bgzf, d->bgzf_up, d->tokens
+    shuffle                   shuffle         no        d->bgzf, d->bgzf_up, d->tokens
+    refused-png*, -shuffle    refused         no        -
+
     c-batch-large/-small      compress        no        c->scratch
     c-dict                    compress-dict   no        c->scratch
     c-zip                     zip-write       no        c->zipw, c->zipw_up, c->scratch
@@ -68,14 +75,18 @@ import numpy as np
 from tests import bgzf_files, bgzf_walk, datagen
 from tests import deflate_synth as S
 from tests import gzip_members_files as gf
+from tests import png_adam7_files as p7
 from tests import png_files as pf
-from tests import prefix_expect, sizes_expect
+from tests import prefix_expect, shuffle_chunks, sizes_expect
 from tests import tar_files as tf
 from tests import tar_write_cases as tw
 from tests import zip_files as zf
 from tests import zip_large_files as zl
+from tools.models import png_adam7 as p7m
 from tools.models import png_model as pm
+from tools.models import png_pixels_model as px
 from tools.models import png_write as pw
+from tools.models import shuffle_model as sm
 from tools.models import tar_walk, zip_walk
 
 SUCCESS, BAD_DATA, SHORT_OUTPUT, INSUFFICIENT_SPACE = 0, 1, 2, 3
@@ -1103,6 +1114,202 @@ def decompressor_steps(oracle):
     add(Refused("refused-tar-row", tread, "read_tar_batch", sel=[8]))
     add(Refused("refused-zip-large-row", zlarge, "read_zip_large", sel=[len(zlarge.rows)]))
     _steps["d"] = st
+    return st
+
+
+# ===================================== the PNG decodes and the shuffled chunks
+
+UNSUPPORTED = 18
+
+
+class PngDecode(_Selection):
+    """decode_png_batch / decode_png_pixels_batch / decode_png_batch_ex through
+    host rows that come from the models' index, not from an index call.  The
+    plain calls' rows are indexed without PNG_ADAM7: an interlaced file is a
+    zero row to them, UNSUPPORTED and without a room"""
+    fields = "d->bgzf, d->bgzf_up, d->tokens"
+    free_failed = False
+    ALIGN = 16
+
+    def __init__(self, name, family, call, files, sel, fmt=0, flags=0):
+        self.name, self.family, self.call, self.files, self.sel = name, family, call, files, list(sel)
+        self.fmt, self.flags = fmt, flags
+        self.data, at = _pack([f.data for f in files])
+        self.rows = [p7m.index(self.data, o, len(f.data), flags & p7m.ADAM7)[1]
+                     for o, f in zip(at, files)]
+        self.kw = {"out_align": self.ALIGN, "flags": flags}
+        if call != "decode_png_batch":
+            self.kw["fmt"] = fmt
+        self.offs = p7m.out_sizes(self.rows, self.sel, fmt, self.ALIGN)
+        got = [p7m.decode(self.data, self.rows[k], flags, fmt) for k in self.sel]
+        self.results, self.plain = [r for r, _ in got], [b for _, b in got]
+        self.expected = (self.offs, self.results, self.plain)
+
+    def validate(self):
+        """against the pixels the files were built from, through the model of
+        the call's own layout"""
+        for k, r, b in zip(self.sel, self.results, self.plain):
+            f, row = self.files[k], self.rows[k]
+            if pm.is_zero(row):
+                assert (r, b) == (UNSUPPORTED, None), (self.name, k)
+                continue
+            assert r == SUCCESS, (self.name, k, r)
+            if not self.fmt:
+                le = self.flags & pm.LE16 and f.depth == 16
+                assert b == (pm.swap16(f.pixels) if le else f.pixels), (self.name, k)
+            else:
+                plte, trns = px.chunks_of(self.data, row)
+                want = px.convert(f.pixels, f.width, f.height, f.depth, f.colour, self.fmt, plte,
+                                  trns, self.flags & pm.LE16)
+                assert want == (SUCCESS, b), (self.name, k)
+            if not p7m.is_interlaced(row):     # the older models say the same
+                older = px.decode(self.data, row, self.fmt, self.flags & pm.LE16) if self.fmt else \
+                    pm.decode(self.data, row, self.flags & pm.LE16)
+                assert older == (r, b), (self.name, k)
+
+
+class ShuffleRead(Step):
+    """decompress_shuffle_batch: the stored chunks at odd offsets with junk
+    between them, the rooms at odd offsets with gaps between them"""
+    family, fields = "shuffle", "d->bgzf, d->bgzf_up, d->tokens"
+
+    def __init__(self, name, fmt, chunks):
+        """chunks: (element size, raw bytes, mask)"""
+        self.name, self.fmt, self.chunks = name, fmt, chunks
+        buf, rows, at = bytearray(), [], 0
+        for k, (es, n, mask) in enumerate(chunks):
+            raw = shuffle_chunks.raw_bytes(es, n)
+            stored = sm.stored(raw, es, mask, lambda b: _deflate(fmt, b))
+            buf += bytes([0x78, 0x9C, k][:1 + k % 3])
+            at += k % 4
+            rows.append([len(buf), len(stored), at, n, es, mask])
+            buf += stored
+            at += n
+        self.data, self.rows, self.total = bytes(buf), rows, at
+        self.expected = [(r[2], shuffle_chunks.raw_bytes(r[4], r[3])) for r in rows]
+
+    def validate(self):
+        """zlib and the model's inverse transform give the rooms' bytes"""
+        for r, (off, raw) in zip(self.rows, self.expected):
+            body = self.data[r[0]:r[0] + r[1]]
+            if not r[5] & sm.NO_DEFLATE:
+                body = _inflate(self.fmt, body)
+            if not sm.identity(r[3], r[4], r[5]):
+                body = sm.unshuffle(body, r[4])
+            assert bytes(body) == raw and len(raw) == r[3], (self.name, r)
+
+    def prepare(self, torch, obj=None):
+        h = Handle()
+        h.d_in = _stage(torch, h, self.data, b"\x78\x9c" * 5)
+        h.out = Guarded(torch, self.total)
+        h.per = Guarded(torch, len(self.rows), torch.int32, UNSET)
+        return h
+
+    def enqueue(self, obj, h, stream):
+        obj.decompress_shuffle_batch(self.fmt, self.rows, h.d_in, h.out.t, h.per.t, stream=stream,
+                                     in_nbytes=len(self.data), out_avail=self.total)
+
+    def check(self, h):
+        assert not h.per.host(self.name).any(), (self.name, h.per.host(self.name))
+        _same(h.out.host(self.name), _image(self.total, self.expected), self.name)
+
+
+class RefusedReader(Refused):
+    """Refused for the PNG decodes (an unknown flag bit) and the shuffle read
+    (an element size of 0)"""
+
+    def __init__(self, name, base, **kw):
+        self.name, self.base, self.kw = name, base, kw
+        self.expected = "RuntimeError"
+
+    def validate(self):
+        if isinstance(self.base, ShuffleRead):
+            assert sm.row_why(self.rows()[self.kw["row"]], True, len(self.base.data),
+                              self.base.total) == "element size"
+        else:
+            assert self.kw["flags"] & ~(pm.LE16 | p7m.ADAM7)
+
+    def rows(self):
+        rows = [list(r) for r in self.base.rows]
+        rows[self.kw["row"]][4] = 0
+        return rows
+
+    def enqueue(self, obj, h, stream):
+        b = self.base
+        h.error = None
+        try:
+            if isinstance(b, ShuffleRead):
+                obj.decompress_shuffle_batch(b.fmt, self.rows(), h.d_in, h.out.t, h.per.t,
+                                             stream=stream, in_nbytes=len(b.data), out_avail=b.total)
+            else:
+                getattr(obj, b.call)(h.d_in, b.rows, b.sel, h.out.t, h.per.t, stream=stream,
+                                     in_nbytes=len(b.data), out_avail=b.offs[-1],
+                                     **{**b.kw, **self.kw})
+        except RuntimeError as e:
+            h.error = str(e)
+
+    def check(self, h):
+        call = "shuffle_decompress_batch" if isinstance(self.base, ShuffleRead) else \
+            {"decode_png_batch": "png_decode_batch", "decode_png_pixels_batch": "png_decode_pixels_batch",
+             "decode_png_batch_ex": "png_decode_batch_ex"}[self.base.call]
+        assert h.error is not None and call in h.error, (self.name, h.error)
+        assert (h.out.host(self.name) == CANARY).all(), (self.name, "d_out was written")
+        assert (h.per.host(self.name) == UNSET).all(), (self.name, "d_results was written")
+
+
+def png_files():
+    """seven files of at most 64 x 64: a palette with tRNS, 16-bit RGBA, one
+    pixel wide, interlaced and three pixels wide (passes 2, 4 and 6 absent), the
+    largest, 8-bit RGBA (what the pixel format of the steps is), interlaced
+    16-bit grey"""
+    return [pf.make(33, 17, depth=4, colour=3, trns=bytes(range(0, 160, 10)), seed=0x91),
+            pf.make(20, 9, depth=16, colour=6, seed=0x92),
+            pf.make(1, 40, depth=8, colour=2, seed=0x93),
+            p7.make7(3, 5, depth=8, colour=2, seed=0x94),
+            pf.make(64, 64, depth=8, colour=2, seed=0x95),
+            pf.make(7, 5, depth=8, colour=6, seed=0x96),
+            p7.make7(19, 10, depth=16, colour=0, seed=0x97)]
+
+
+def shuffle_shapes():
+    """(element size, raw bytes, mask): a full tile and a part of one, bytes
+    behind the last element, element sizes that do not divide the tile (3,
+    255), every class of the reader's plan"""
+    return [(4, 4 * 4096 + 4 * 17, 0), (8, 2059, 0), (3, 3001, 0), (2, 1000, sm.NO_SHUFFLE),
+            (4, 2048, sm.NO_DEFLATE), (1, 500, 0), (5, 0, 0), (255, 255 * 20 + 7, 0),
+            (16, 700, sm.NO_DEFLATE | sm.NO_SHUFFLE)]
+
+
+def reader_steps():
+    """name -> Step of the PNG decodes and the shuffle read; a catalogue of its
+    own, so that the seeded shuffles of the older one draw what they always
+    drew.  Built once per process"""
+    if "r" in _steps:
+        return _steps["r"]
+    st = {}
+
+    def add(s):
+        assert s.name not in st
+        st[s.name] = s
+    files = png_files()
+    png = PngDecode("png", "png", "decode_png_batch", files, [4, 0, 2, 3, 1, 5, 0], flags=pm.LE16)
+    add(png)
+    add(PngDecode("png-zero", "png", "decode_png_batch", files, [3, 6]))
+    pixels = PngDecode("png-pixels", "png-pixels", "decode_png_pixels_batch", files,
+                       [0, 5, 1, 4, 6, 2, 5], fmt=px.RGBA)
+    add(pixels)
+    ex = PngDecode("png-ex", "png-adam7", "decode_png_batch_ex", files, [3, 0, 6, 1, 3, 5, 2],
+                   fmt=px.RGBA, flags=p7m.ADAM7)
+    add(ex)
+    add(PngDecode("png-ex-raw", "png-adam7", "decode_png_batch_ex", files, [6, 2, 3, 1],
+                  flags=p7m.ADAM7 | pm.LE16))
+    shuf = ShuffleRead("shuffle", "zlib", shuffle_shapes())
+    add(shuf)
+    add(RefusedReader("refused-png", png, flags=0x80))
+    add(RefusedReader("refused-png-pixels", pixels, flags=0x80))
+    add(RefusedReader("refused-png-ex", ex, flags=0x80 | p7m.ADAM7))
+    add(RefusedReader("refused-shuffle", shuf, row=2))
+    _steps["r"] = st
     return st
 
 

@@ -61,6 +61,13 @@ def steps(oracle):
     return O.decompressor_steps(oracle)
 
 
+@pytest.fixture(scope="module")
+def rsteps(steps):
+    """the older catalogue and the PNG and shuffle readers' beside it (the
+    seeded shuffles draw from `steps` alone, as they always have)"""
+    return {**steps, **O.reader_steps()}
+
+
 @pytest.fixture(params=["current", "side"])
 def stream(request, torch):
     """the current stream, and a side stream as tests/test_seek_gpu.py::
@@ -119,14 +126,20 @@ def both(obj, seq, stream, label, fresh=None):
 
 # ---------------------------------------------------------------- decompressor
 
-def test_five_readers_share_one_scratch(dec, steps, stream):
+def test_five_readers_share_one_scratch(dec, rsteps, stream):
     """D1: ZIP, tar, BGZF, gzip members through d->bgzf and d->bgzf_up, the
     false-candidate and overflow files between the good ones, then the ranged
-    and selected reads through the four indices in reverse order"""
-    names = ["zip", "zip-false", "tar", "zip-overflow", "bgzf", "tar-overflow", "gzm", "bgzf-walk",
-             "zip-defect", "tar-pax", "gzm-false",
-             "bgzf-read", "tar-read", "zip-read", "zip-large", "gzm-peek"]
-    both(dec, [steps[n] for n in names], stream, "D1")
+    and selected reads through the four indices in reverse order; the PNG
+    decodes and the shuffle read, which stage their plans through the same
+    pipeline on the host, between them - the first in front of every step that
+    grows d->bgzf (a fresh object: "zip" is the first to reserve more than a
+    few KiB, "bgzf" and "zip-large" grow it again), the others behind"""
+    names = ["png", "zip", "shuffle", "zip-false", "tar", "png-pixels", "zip-overflow", "bgzf",
+             "png-ex", "tar-overflow", "gzm", "bgzf-walk", "png-zero", "zip-defect", "tar-pax",
+             "gzm-false", "shuffle",
+             "bgzf-read", "png-ex-raw", "tar-read", "png", "zip-read", "png-ex", "zip-large",
+             "png-pixels", "gzm-peek", "shuffle"]
+    both(dec, [rsteps[n] for n in names], stream, "D1")
 
 
 @pytest.mark.parametrize("mode", ["1", "0"])
@@ -157,15 +170,21 @@ def test_scratch_grows_under_queued_work(dec, steps, stream):
     run_sequence(dec, [steps[n] for n in names], stream, True, label="D4")
 
 
-def test_failing_and_refused_calls_leave_the_object_whole(dec, steps, stream):
+def test_failing_and_refused_calls_leave_the_object_whole(dec, rsteps, stream):
     """D5: refusals before any device work, defect archives and short-output
-    batches between good steps on a busy stream; then one more good sequence"""
+    batches between good steps on a busy stream; then one more good sequence.
+    The PNG decodes' and the shuffle read's refusals stand between good calls
+    of the same kind: the refusal path is the readers' shared one, and it
+    leaves d->bgzf_up as it found it"""
     names = ["zip", "refused-zip-space", "tar", "refused-tar-row", "batch-short", "refused-zip-input",
+             "png", "refused-png", "png-pixels", "refused-png-pixels", "png",
              "zip-defect", "batch2", "refused-tar-space", "tar-defect", "zip-read-defect",
+             "png-ex", "refused-png-ex", "png-ex-raw", "shuffle", "refused-shuffle", "shuffle",
              "refused-zip-large-row", "bgzf", "zip-space", "refused-zip-row", "refused-tar-input",
              "gzm", "batch-synth"]
-    both(dec, [steps[n] for n in names], stream, "D5")
-    both(dec, [steps[n] for n in ("zip", "tar", "bgzf", "gzm", "batch2", "tar-read", "zip-read")],
+    both(dec, [rsteps[n] for n in names], stream, "D5")
+    both(dec, [rsteps[n] for n in ("zip", "tar", "bgzf", "gzm", "batch2", "tar-read", "zip-read",
+                                    "png", "shuffle")],
          stream, "D5 after")
 
 

@@ -119,3 +119,75 @@ def test_every_device_output_check_fails_on_outputs_that_nothing_wrote(dsteps, m
             s.check(h)
         seen += 1
     assert seen == len(dsteps) - 5 + len(O.compressor_steps()) - 3
+
+
+# ------------------------------------------- the PNG decodes, the shuffle read
+
+R_FAMILIES = {"png", "png-pixels", "png-adam7", "shuffle", "refused"}
+
+
+@pytest.fixture(scope="module")
+def rsteps():
+    return O.reader_steps()
+
+
+def test_the_reader_steps_are_a_catalogue_of_their_own(dsteps, rsteps):
+    assert {s.family for s in rsteps.values()} == R_FAMILIES
+    assert not set(rsteps) & set(dsteps)    # (the seeded shuffles draw from dsteps alone)
+    for name, s in rsteps.items():
+        assert s.name == name and s.fields and s.expected is not None and not s.blocking, name
+        assert s.family in O.__doc__ and s.fields in O.__doc__, name
+    calls = {s.call for s in rsteps.values() if isinstance(s, O.PngDecode)}
+    assert calls == {"decode_png_batch", "decode_png_pixels_batch", "decode_png_batch_ex"}
+
+
+def test_reader_steps_expect_what_the_cpu_models_say(rsteps):
+    for s in rsteps.values():
+        s.validate()
+
+
+def test_the_reader_inputs_reach_every_stage(rsteps):
+    files = O.png_files()
+    assert len(files) == 7 and all(f.width <= 64 and f.height <= 64 for f in files)
+    rows = rsteps["png-ex"].rows
+    assert any(f.colour == 3 and r[6] and r[7] for f, r in zip(files, rows)), "no palette with tRNS"
+    assert any(f.depth == 16 for f in files) and any(f.width == 1 for f in files)
+    narrow = [f for f, r in zip(files, rows) if O.p7m.is_interlaced(r) and f.width < 8]
+    assert narrow and any((0, 0) in O.p7m.pass_sizes(f.width, f.height) for f in narrow)
+    # the plain calls: a zero row among the images; the pixel format: rooms the
+    # unfilter writes and rooms the convert writes; the _ex calls: interlaced
+    # and plain selections, with and without the convert behind them
+    assert {O.SUCCESS, O.UNSUPPORTED} == set(rsteps["png"].results)
+    assert set(rsteps["png-zero"].results) == {O.UNSUPPORTED} and rsteps["png-zero"].offs == [0, 0, 0]
+    for name in ("png-pixels", "png-ex"):
+        s = rsteps[name]
+        direct = {O.px.is_direct(files[k].depth, files[k].colour, s.fmt) for k in s.sel
+                  if not O.pm.is_zero(s.rows[k])}
+        assert direct == {True, False}, name
+    for name in ("png-ex", "png-ex-raw"):
+        s = rsteps[name]
+        assert {O.p7m.is_interlaced(s.rows[k]) for k in s.sel} == {True, False}, name
+        assert set(s.results) == {O.SUCCESS}, name
+    sh = rsteps["shuffle"]
+    assert 8 <= len(sh.rows) <= 10 and max(r[3] for r in sh.rows) <= 5 << 12
+    classes = {O.sm.classify(r) for r in sh.rows}
+    assert classes >= {O.sm.DECODE_DIRECT, O.sm.DECODE_UNSHUFFLE, O.sm.STORED_UNSHUFFLE,
+                       O.sm.STORED_COPY}, classes
+    assert any(r[5] == O.sm.NO_DEFLATE for r in sh.rows) and any(r[5] == O.sm.NO_SHUFFLE for r in sh.rows)
+    assert any(O.sm.GEN_BYTES % r[4] and not O.sm.identity(r[3], r[4], r[5]) for r in sh.rows)
+    assert any(O.sm.tiles(r[3], r[4]) > 1 for r in sh.rows)
+
+
+def test_every_reader_check_fails_on_outputs_that_nothing_wrote(rsteps, monkeypatch):
+    """as for the older catalogue: the right offsets, no exception from a
+    refused call, and tensors nothing wrote"""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(O, "DEVICE", "cpu")
+    for name, s in rsteps.items():
+        h = s.prepare(torch)
+        h.error = None
+        if hasattr(s, "offs"):
+            h.offs = np.array(s.offs, dtype=np.uint64)
+        with pytest.raises(AssertionError):
+            s.check(h)
