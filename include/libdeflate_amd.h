@@ -305,6 +305,16 @@ libdeflate_amd_compress_last_schedule(const struct libdeflate_compressor *compre
 				      uint32_t out[4]);
 
 /*
+ * The name of the compress kernel that call launched (diagnostics, as above):
+ * on the two-kernel path the LZ77 stage, which at levels 1-9 is the kernel
+ * built for the level ("lda_deflate_batch_kernel_l6") unless
+ * LDA_COMPRESS_SPECIALIZE=0 keeps the one that serves every level
+ * ("lda_deflate_batch_kernel").  A static string; "" before the first call.
+ */
+LIBDEFLATEAPI const char *
+libdeflate_amd_compress_last_kernel(const struct libdeflate_compressor *compressor);
+
+/*
  * Decompress: d_results[i] receives the enum libdeflate_result of chunk i.
  * d_actual_in / d_actual_out may be NULL; a NULL d_actual_out has the
  * reference's meaning (the stream must fill d_out_avail[i] exactly, else

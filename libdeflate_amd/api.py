@@ -411,6 +411,12 @@ class Compressor:
         this object was scheduled -> dict(split, overlapped, head, tail)."""
         return binding.compress_last_schedule(self._h)
 
+    def last_kernel(self):
+        """libdeflate_amd_compress_last_kernel: the name of the compress kernel
+        the last batch call on this object launched (on the split path the
+        LZ77 stage: the level's own instance or the generic kernel)."""
+        return binding.compress_last_kernel(self._h)
+
     def compress_dict(self, fmt, dictionary, data, out_avail=None):
         """libdeflate_amd_compress_dict: one host buffer with a preset
         dictionary ("deflate" or "zlib").  Returns the compressed bytes, or

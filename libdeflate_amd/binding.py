@@ -89,6 +89,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_reload_env",
     "libdeflate_amd_compress_batch", "libdeflate_amd_decompress_batch",
     "libdeflate_amd_compress_batch_bounded", "libdeflate_amd_compress_last_schedule",
+    "libdeflate_amd_compress_last_kernel",
     "libdeflate_amd_crc32_batch", "libdeflate_amd_adler32_batch",
     "libdeflate_amd_compress_batch_host",
     "libdeflate_amd_decompress_batch_host",
@@ -187,6 +188,7 @@ def load():
     sig("libdeflate_amd_compress_batch_bounded", c_int, P, c_int, SZ, P, P, P, P, P,
         P, P, SZ, P)
     sig("libdeflate_amd_compress_last_schedule", None, P, POINTER(c_uint32))
+    sig("libdeflate_amd_compress_last_kernel", c_char_p, P)
     sig("libdeflate_amd_decompress_batch", c_int, P, c_int, SZ, P, P, P, P, P,
         P, P, P, P, P)
     sig("libdeflate_amd_compress_batch_host", c_int, P, c_int, SZ, P, P, P, P,
@@ -348,6 +350,12 @@ def compress_last_schedule(compressor):
     load().libdeflate_amd_compress_last_schedule(compressor, out)
     return {"split": int(out[0]), "overlapped": int(out[1]), "head": int(out[2]),
             "tail": int(out[3])}
+
+
+def compress_last_kernel(compressor):
+    """libdeflate_amd_compress_last_kernel of a compressor handle: the name of
+    the compress kernel its last batch call launched."""
+    return load().libdeflate_amd_compress_last_kernel(compressor).decode()
 
 
 def last_error():

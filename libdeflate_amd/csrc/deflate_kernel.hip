@@ -75,6 +75,8 @@
  *
  * deflate_small.hip compiles this file a second time (LDA_SMALL: 256 threads,
  * a 4 KiB ring, tiles of 2048) for batches of buffers of at most 4096 bytes.
+ * deflate_l1.hip ... deflate_l9.hip compile it once each (LDA_LEVEL_INSTANCE)
+ * for the LZ77 stage of one level with that level's policy as constants.
  */
 #include <stddef.h>
 #include "device_common.h"
@@ -2300,13 +2302,45 @@ static __device__ __forceinline__ void mx_restore(lds_t *L, const u32 *msave, u3
  * marked LDA_BLK_FUSED and listed for the fused kernel, *fused_cnt of them);
  * blk_stride the descriptors per buffer (one per tile at most).  Fused with
  * blk_buf set: only the *fused_cnt buffers so listed.
+ *
+ * POLICY: policy_args (the kernels of this file) takes the level and its row
+ * of the table from the kernel arguments.  policy_level<> states them, and the
+ * body is then that level's alone: the kernel is bound by instruction issue,
+ * and what the arguments select at run time - which rounds exist, the depth
+ * classes, the walk's budget, the lazy rule's tests - costs instructions and
+ * scalar registers (spilled to vector lanes) in every hot loop.  The LZ77 stage
+ * is built once per level 1-9 that way (deflate_l1.hip ... deflate_l9.hip).
+ * The policy stays a type: its values reach the stage functions as constants
+ * only through inlining, never through memory.
  */
-template <bool OPT, bool SPLIT = false> static __device__ __forceinline__ void
+struct policy_args {
+	static constexpr bool fixed = false;
+	static constexpr int level = 0;
+	static constexpr u32 depth = 0, nice = 0, mode = 0;
+};
+
+template <int LEVEL, u32 DEPTH, u32 NICE, u32 MODE> struct policy_level {
+	static constexpr bool fixed = true;
+	static constexpr int level = LEVEL;
+	static constexpr u32 depth = DEPTH, nice = NICE, mode = MODE;
+};
+
+template <bool OPT, bool SPLIT = false, class POLICY = policy_args>
+static __device__ __forceinline__ void
 deflate_batch_body(u8 *lds_raw, DEFLATE_KERNEL_PARAMS,
 		   u32 *__restrict__ tok_buf = NULL, u32 *__restrict__ blk_buf = NULL,
 		   u32 tok_stride = 0, u32 blk_stride = 0, u32 *__restrict__ fused_cnt = NULL)
 {
 	static_assert(!(OPT && SPLIT), "levels 10-12 keep the fused block end");
+	static_assert(!POLICY::fixed || (SPLIT && POLICY::level >= 1 && POLICY::level <= 9 &&
+					 POLICY::mode <= 2), "instances: the LZ77 stage of levels 1-9");
+	if constexpr (POLICY::fixed) {
+		/* (the arguments are passed all the same and not read) */
+		level = POLICY::level;
+		depth = POLICY::depth;
+		nice = POLICY::nice;
+		mode = POLICY::mode;
+	}
 	lds_t *L = (lds_t *)(uintptr_t)0;
 	const u32 tid = threadIdx.x;
 	if ((u32)(uintptr_t)(__attribute__((address_space(3))) u8 *)lds_raw != 0)
@@ -2957,6 +2991,23 @@ extern "C" size_t lda_deflate_small_wgs(void)
 }
 
 LDA_PROF_DEFINE_READER(libdeflate_amd_profile_read_deflate_small)
+#elif defined(LDA_LEVEL_INSTANCE)
+/* the LZ77 stage of one level, 1-9 (deflate_l<N>.hip sets the level): the
+ * arguments of lda_deflate_batch_kernel, of which level, depth, nice and mode
+ * are not read - the level's row of deflate_levels.h is compiled in */
+#include "deflate_levels.h"
+#define LDA_CAT_(a, b) a##b
+#define LDA_CAT(a, b) LDA_CAT_(a, b)
+extern "C" __global__ void __launch_bounds__(NT)
+LDA_CAT(lda_deflate_batch_kernel_l, LDA_LEVEL_INSTANCE)(DEFLATE_KERNEL_PARAMS,
+	u32 *__restrict__ tok_buf, u32 *__restrict__ blk_buf, u32 tok_stride, u32 blk_stride,
+	u32 *__restrict__ fused_cnt)
+{
+	extern __shared__ __attribute__((aligned(16))) u8 lds_raw[];
+	typedef policy_level<LDA_LEVEL_INSTANCE, LDA_CAT(LDA_LEVEL_, LDA_LEVEL_INSTANCE)> policy;
+	deflate_batch_body<false, true, policy>(DEFLATE_KERNEL_ARGS, tok_buf, blk_buf, tok_stride,
+						blk_stride, fused_cnt);
+}
 #else
 /* levels 0-9, the LZ77 stage: block descriptors for lda_deflate_entropy_kernel */
 extern "C" __global__ void __launch_bounds__(NT)

@@ -110,6 +110,7 @@ struct EnvCfg {
 	bool tar_serial = false;	/* LDA_TAR_SERIAL: the tar reader finds the records by the serial walk */
 	bool fanout_oversub = false;	/* LDA_FANOUT_OVERSUB: more shards than visible devices (a test aid: several shards share a GPU) */
 	bool compress_overlap = true;	/* LDA_COMPRESS_OVERLAP: 0 = the split path's kernels in series on the caller's stream */
+	bool compress_specialize = true;	/* LDA_COMPRESS_SPECIALIZE: 0 = the split path's LZ77 stage is the generic kernel at every level */
 	int compress_tail_rounds = 0;	/* LDA_COMPRESS_TAIL_ROUNDS: buffers per CU of a slice's tail (0 = compress_plan.h's) */
 };
 const EnvCfg &env_cfg();

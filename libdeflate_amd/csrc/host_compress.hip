@@ -18,41 +18,47 @@
 #include "kernels.h"
 #include "large_plan.h"
 #include "compress_plan.h"
+#include "deflate_levels.h"
 
 using namespace lda;
 
-/*
- * level -> (search depth, nice length, parse mode), the policy table of
- * lib/deflate_compress.c:3927-3979.  Level 1 maps onto the same hash-chain
- * kernel with a 2-deep search (the reference's level 1 probes a 2-way
- * bucket, lib/ht_matchfinder.h:50-55).  Levels 10-12 (mode 3) choose the
- * tokens by a min-cost parse over the chain search's results instead of the
- * lazy rule (deflate_kernel.hip, "min-cost parse"); the reference's binary
- * tree match finder (lib/bt_matchfinder.h) has no counterpart.
- */
+/* level -> (search depth, nice length, parse mode): the rows of deflate_levels.h */
 struct level_cfg { uint32_t depth, nice, mode; };	/* mode: 0 greedy, 1 lazy, 2 lazy2, 3 min-cost */
 static const level_cfg k_levels[13] = {
-	{ 0, 0, 0 },		/* 0: stored */
-	{ 2, 32, 0 },		/* 1 */
-	{ 6, 10, 0 },		/* 2: greedy */
-	{ 12, 14, 0 },
-	{ 16, 30, 0 },
-	{ 16, 30, 1 },		/* 5: lazy */
-	{ 35, 65, 1 },
-	{ 100, 130, 1 },
-	{ 300, 258, 2 },	/* 8: lazy2 */
-	{ 600, 258, 2 },
-	/* 10-12: min-cost parse over every position's deepest match.  The chains
-	 * of a 64 KiB buffer are exhausted at ~600 steps (13 hash bits, 24 K
-	 * window: 600, 1000 and 2000 measured the same time and, to 0.02 %, the
-	 * same bytes - round 5's 600 / 1000 / 2000 were one level three times),
-	 * so the ladder is 150 / 300 / all of the chain: 38.4 / 45.6 / 53.0 ms
-	 * per 4096 x 64 KiB at 1.0062 / 1.0082 / 1.0074 x the reference's size
-	 * at the same level (the mix of tests/datagen.py; round 6) */
-	{ 150, 258, 3 },
-	{ 300, 258, 3 },
-	{ 2000, 258, 3 },
+	{ LDA_LEVEL_0 }, { LDA_LEVEL_1 }, { LDA_LEVEL_2 }, { LDA_LEVEL_3 }, { LDA_LEVEL_4 },
+	{ LDA_LEVEL_5 }, { LDA_LEVEL_6 }, { LDA_LEVEL_7 }, { LDA_LEVEL_8 }, { LDA_LEVEL_9 },
+	{ LDA_LEVEL_10 }, { LDA_LEVEL_11 }, { LDA_LEVEL_12 },
 };
+
+/*
+ * The LZ77 stage of the split path by level: the instance built for the level
+ * (deflate_l<N>.hip: the level's row above as constants), or the
+ * generic kernel, which reads the row from its arguments - level 0, a level
+ * whose instance measured no faster (none listed here), LDA_COMPRESS_SPECIALIZE=0,
+ * and the profiling build, whose phase counters are the generic kernel's.
+ */
+struct lz77_kernel { lda_lz77_kernel_t fn; const char *name; };
+#define LZ77_K(name) { name, #name }
+static const lz77_kernel k_lz77_generic = LZ77_K(lda_deflate_batch_kernel);
+static const lz77_kernel k_lz77_level[10] = {
+	LZ77_K(lda_deflate_batch_kernel),
+	LZ77_K(lda_deflate_batch_kernel_l1), LZ77_K(lda_deflate_batch_kernel_l2),
+	LZ77_K(lda_deflate_batch_kernel_l3), LZ77_K(lda_deflate_batch_kernel_l4),
+	LZ77_K(lda_deflate_batch_kernel_l5), LZ77_K(lda_deflate_batch_kernel_l6),
+	LZ77_K(lda_deflate_batch_kernel_l7), LZ77_K(lda_deflate_batch_kernel_l8),
+	LZ77_K(lda_deflate_batch_kernel_l9),
+};
+#undef LZ77_K
+
+static const lz77_kernel &lz77_kernel_of(int level)
+{
+#ifdef LDA_PROFILE
+	return k_lz77_generic;
+#else
+	return env_cfg().compress_specialize && level >= 1 && level <= 9 ?
+	       k_lz77_level[level] : k_lz77_generic;
+#endif
+}
 
 extern "C" LIBDEFLATEAPI struct libdeflate_compressor *
 libdeflate_alloc_compressor_ex(int level, const struct libdeflate_options *options)
@@ -244,6 +250,7 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 	c->last_schedule[1] = 0;
 	c->last_schedule[2] = (uint32_t)std::min<size_t>(n, 0xFFFFFFFFu);
 	c->last_schedule[3] = 0;
+	c->last_kernel = "";
 	uint8_t *scr = (uint8_t *)c->scratch.reserve(pl.total);
 	if (!scr)
 		return LIBDEFLATE_AMD_OOM;
@@ -298,10 +305,16 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 				(const void *)lda_deflate_fused_kernel,
 				hipFuncAttributeMaxDynamicSharedMemorySize,
 				(int)lda_deflate_lds_bytes()), LIBDEFLATE_AMD_NO_DEVICE);
+		for (int l = 1; l <= 9; l++)
+			LDA_HIP_TRY(hipFuncSetAttribute(
+					(const void *)k_lz77_level[l].fn,
+					hipFuncAttributeMaxDynamicSharedMemorySize,
+					(int)lda_deflate_lds_bytes()), LIBDEFLATE_AMD_NO_DEVICE);
 		ctx->deflate_attr_set.store(true, std::memory_order_release);
 	}
 	const level_cfg &lv = k_levels[c->level];
 	if (!pl.split && (small || lv.mode == 3)) {
+		c->last_kernel = small ? "lda_deflate_small_kernel" : "lda_deflate_opt_kernel";
 		hipLaunchKernelGGL(small ? lda_deflate_small_kernel : lda_deflate_opt_kernel,
 				   dim3((unsigned)pl.grid),
 				   dim3(small ? LDA_DEFLATE_SMALL_THREADS : LDA_DEFLATE_THREADS),
@@ -314,6 +327,7 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		return LIBDEFLATE_AMD_OK;
 	}
 	if (!pl.split) {
+		c->last_kernel = "lda_deflate_fused_kernel";
 		hipLaunchKernelGGL(lda_deflate_fused_kernel, dim3((unsigned)pl.grid),
 				   dim3(LDA_DEFLATE_THREADS), lds, st, (uint64_t)n, format,
 				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
@@ -345,10 +359,12 @@ compress_batch_impl(struct libdeflate_compressor *c, int format, size_t n,
 		uint64_t *seq;
 		size_t grid_max;
 	};
+	const lz77_kernel &lz77 = lz77_kernel_of(c->level);
+	c->last_kernel = lz77.name;
 	auto lz77_entropy = [&](const part &q, hipStream_t on) -> int {
 		const uint32_t *sk = sums ? sums + q.lo : NULL;
 		const uint32_t *gk = d_seg_info ? d_seg_info + q.lo : NULL;
-		hipLaunchKernelGGL(lda_deflate_batch_kernel, dim3((unsigned)std::min(q.n, q.grid_max)),
+		hipLaunchKernelGGL(lz77.fn, dim3((unsigned)std::min(q.n, q.grid_max)),
 				   dim3(LDA_DEFLATE_THREADS), lds, on, (uint64_t)q.n, format,
 				   c->level, lv.depth, lv.nice, lv.mode, (const uint8_t *)d_in,
 				   d_in_offsets + q.lo, d_in_nbytes + q.lo, (uint8_t *)d_out,
@@ -425,6 +441,13 @@ libdeflate_amd_compress_last_schedule(const struct libdeflate_compressor *c, uin
 {
 	for (int i = 0; i < 4; i++)
 		out[i] = c ? c->last_schedule[i] : 0;
+}
+
+/* include/libdeflate_amd.h */
+extern "C" LIBDEFLATEAPI const char *
+libdeflate_amd_compress_last_kernel(const struct libdeflate_compressor *c)
+{
+	return c ? c->last_kernel : "";
 }
 
 /* host_objects.h: what the writers' piece pipeline (host_write_pieces.hip) launches

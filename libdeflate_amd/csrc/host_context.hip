@@ -105,6 +105,8 @@ static EnvCfg read_env()
 	c.tar_serial = getenv("LDA_TAR_SERIAL") != nullptr;
 	if (const char *e = getenv("LDA_COMPRESS_OVERLAP"))
 		c.compress_overlap = atoi(e) != 0;
+	if (const char *e = getenv("LDA_COMPRESS_SPECIALIZE"))
+		c.compress_specialize = atoi(e) != 0;
 	if (const char *e = getenv("LDA_COMPRESS_TAIL_ROUNDS")) {
 		int v = atoi(e);
 		if (v >= 1 && v <= 16)

@@ -92,6 +92,8 @@ struct libdeflate_compressor {
 	lda::SideStream side;	/* the split path's tail beside its head (compress_batch_impl()) */
 	/* what the last batch call did (libdeflate_amd_compress_last_schedule) */
 	uint32_t last_schedule[4] = { 0, 0, 0, 0 };
+	/* and the compress kernel it launched (libdeflate_amd_compress_last_kernel) */
+	const char *last_kernel = "";
 };
 
 namespace lda {

@@ -128,6 +128,30 @@ lda_deflate_batch_kernel(uint64_t n_chunks, int format, int level,
 			 uint32_t *next_chunk, const uint8_t *dict_pre,
 			 uint32_t *tok_buf, uint32_t *blk_buf, uint32_t tok_stride,
 			 uint32_t blk_stride, uint32_t *fused_cnt);
+/* the same stage built for one level, 1-9, with that level's depth, nice length
+ * and mode as constants (deflate_l<N>.hip): the same arguments, of which level,
+ * depth, nice and mode are not read */
+typedef void (*lda_lz77_kernel_t)(uint64_t, int, int, uint32_t, uint32_t, uint32_t,
+				  const uint8_t *, const uint64_t *, const uint64_t *, uint8_t *,
+				  const uint64_t *, const uint64_t *, uint64_t *, const uint32_t *,
+				  uint64_t *, const uint32_t *, uint32_t *, const uint8_t *,
+				  uint32_t *, uint32_t *, uint32_t, uint32_t, uint32_t *);
+#define LDA_LZ77_INSTANCE(N)                                                   \
+	extern "C" __global__ void                                             \
+	lda_deflate_batch_kernel_l##N(uint64_t n_chunks, int format, int level, \
+		uint32_t depth, uint32_t nice, uint32_t mode,                  \
+		const uint8_t *in_base, const uint64_t *in_offsets,            \
+		const uint64_t *in_nbytes, uint8_t *out_base,                  \
+		const uint64_t *out_offsets, const uint64_t *out_avail,        \
+		uint64_t *out_nbytes, const uint32_t *sums,                    \
+		uint64_t *seq_scratch, const uint32_t *seg_info,               \
+		uint32_t *next_chunk, const uint8_t *dict_pre,                 \
+		uint32_t *tok_buf, uint32_t *blk_buf, uint32_t tok_stride,     \
+		uint32_t blk_stride, uint32_t *fused_cnt);
+LDA_LZ77_INSTANCE(1) LDA_LZ77_INSTANCE(2) LDA_LZ77_INSTANCE(3)
+LDA_LZ77_INSTANCE(4) LDA_LZ77_INSTANCE(5) LDA_LZ77_INSTANCE(6)
+LDA_LZ77_INSTANCE(7) LDA_LZ77_INSTANCE(8) LDA_LZ77_INSTANCE(9)
+#undef LDA_LZ77_INSTANCE
 /* the same body with the block end inside the tile loop (no bound: unbounded
  * batches, a preset dictionary; blk_buf NULL), or behind a split launch for
  * the buffers it marked LDA_BLK_FUSED (blk_buf of that launch) */

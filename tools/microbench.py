@@ -167,6 +167,12 @@ def bench_deflate(a, fmt="gzip", level=6):
     c_n = torch.zeros(n, dtype=torch.int64, device="cuda")
     f = lambda: c.compress_batch(fmt, data, offs, nb, comp, c_off, c_av, c_n, max_chunk=a.size)
     f(); torch.cuda.synchronize()
+    # which kernel that was: at levels 1-9 of the split path the level's own LZ77
+    # instance (lda_deflate_batch_kernel_l<N>) unless LDA_COMPRESS_SPECIALIZE=0
+    try:
+        print(f"kernel: {c.last_kernel()}")
+    except AttributeError:      # a build of the library from before the call existed
+        pass
     reader = ("libdeflate_amd_profile_read_deflate_small"
               if a.size <= 4096 and level <= 9 and not os.environ.get("LDA_NO_SMALL")
               else "libdeflate_amd_profile_read_deflate")

@@ -3,10 +3,15 @@
 # no trace domains in the same rocprofv3 command).
 # usage: tools/prof_pmc.sh <bench|small|opt|l1|l9|inflate64k|stream>   (run on the GPU box via gpurun)
 #   bench   bench.py's headline batch (4096 distinct 64 KiB chunks, gzip level 6:
-#           lda_deflate_batch_kernel + lda_deflate_entropy_kernel, lda_inflate_wave_kernel, CRC-32)
+#           lda_deflate_batch_kernel_l6 + lda_deflate_entropy_kernel, lda_inflate_wave_kernel, CRC-32)
 #   small   1 Mi/4 x 4 KiB zlib level 9 (lda_deflate_small_kernel), tools/microbench.py
 #   opt     4096 x 64 KiB level 12 (lda_deflate_opt_kernel), tools/microbench.py
-#   l1, l9  4096 x 64 KiB level 1 / 9 (lda_deflate_batch_kernel + lda_deflate_entropy_kernel), tools/microbench.py
+#   l1, l9  4096 x 64 KiB level 1 / 9 (lda_deflate_batch_kernel_l1 / _l9 + lda_deflate_entropy_kernel), tools/microbench.py
+# The LZ77 stage of levels 1-9 is the level's own instance; LDA_COMPRESS_SPECIALIZE=0
+# in the environment profiles lda_deflate_batch_kernel, the kernel of every level,
+# instead, and LDA_COMPRESS_OVERLAP=0 makes "per launch" mean per batch (one
+# launch of the stage per step instead of a head and a tail).  The rows are
+# keyed by the kernel names the profile holds, so they name what ran.
 #   inflate64k  65 536 gzip streams of 64 KiB (lda_inflate_wave_kernel), tools/microbench.py
 #   stream  one 16 MiB gzip stream through libdeflate_gzip_decompress (lda_stream_*)
 # writes gpurun_out/pmc_<what>.json: per kernel, counter -> value per launch
