@@ -2364,6 +2364,120 @@ libdeflate_amd_shuffle_compress_batch(struct libdeflate_compressor *compressor, 
 				      size_t out_avail, uint64_t *d_result,
 				      uint64_t *d_index /* may be NULL */, void *stream);
 
+/*
+ * Predictor-coded deflate strips and tiles: TIFF with Compression = 8 (Adobe
+ * deflate; 32946 is the same thing) - GeoTIFF, Cloud-Optimized GeoTIFF tiles,
+ * OME-TIFF planes, float rasters.  A *segment* is a strip or a tile: one zlib
+ * stream that decodes to coded_rows rows of coded_width pixels, each pixel spp
+ * samples of bps bytes, pixel-interleaved, samples little-endian.  The rows of
+ * a segment were coded by the file's Predictor (tag 317):
+ *
+ *   1  none.
+ *   2  horizontal differencing: every sample minus the sample of the same
+ *      channel one pixel to the left, modulo 2^(8 bps); the first pixel of a
+ *      row as it is.
+ *   3  floating point: the row's samples split into bps byte planes, the most
+ *      significant byte's plane first, then every byte of the row of planes
+ *      minus the byte spp places earlier (across the planes' boundaries).
+ *
+ * Undoing 2 is a prefix sum per row and channel; undoing 3 a prefix sum over
+ * the bytes of the whole coded row and a gather from the planes.
+ *
+ * A segment is described by a row of LIBDEFLATE_AMD_TIFF_WORDS uint64_t on the
+ * HOST:
+ *   [0] the offset of the stored segment in the compressed buffer
+ *   [1] its stored size
+ *   [2] the offset, in the raw buffer, of the segment's kept pixel (0, 0)
+ *   [3] the pitch in bytes between kept rows in the raw buffer
+ *   [4] coded_width | coded_rows << 32; both at least 1, and coded_width *
+ *       coded_rows * spp * bps below 2^32
+ *   [5] kept_width | kept_rows << 32; 1 <= kept <= coded.  The rectangle that
+ *       is written: an edge tile's padding is cropped, a strip is kept whole
+ *   [6] spp (bits 0-7, 1 .. LIBDEFLATE_AMD_TIFF_SPP_MAX) | bps << 8 (1, 2, 4,
+ *       8) | predictor << 16 (1, 2, 3; 3 needs bps 2, 4 or 8).  Any other bit
+ *       is refused
+ *   [7] reserved, must be 0
+ *
+ * The format is always zlib: TIFF prescribes it.
+ *
+ * The reader.  The call only enqueues on `stream`; object and stream rules are
+ * libdeflate_amd_shuffle_decompress_batch's.  d_results[i] is what
+ * libdeflate_zlib_decompress_ex reports for the stream with out_nbytes_avail =
+ * the coded size and a NULL actual_out: LIBDEFLATE_SUCCESS only if the stream
+ * fills the coded size exactly, else SHORT_OUTPUT, INSUFFICIENT_SPACE or
+ * BAD_DATA.  On success the kept rectangle holds the pixels: row r of it the
+ * kept_width * spp * bps bytes at word 2 + r * pitch.  The bytes of the pitch
+ * behind a kept row are never written, and nothing outside the kept rectangles
+ * is: neighbouring tiles interleave in one H x W x C image.  A failed segment
+ * leaves only its own rectangle undefined.  The rectangles must not overlap
+ * each other or d_in (not checked).
+ *
+ * The writer.  Rows use words 2 to 7, the raw pixels in d_in at that pitch: a
+ * reader's row is a valid writer's row.  The coded segment is the kept
+ * rectangle, padded on the right and at the bottom with zero samples up to the
+ * coded size, then predicted.  Stream k is byte for byte what
+ * libdeflate_zlib_compress() of this build returns for the predicted segment
+ * at the object's level, and stands behind stream k - 1, from offset 0 of
+ * d_out.  Segments of 128 KiB and more are compressed as primed segments like
+ * libdeflate_amd_compress_large_batch's.  d_result
+ * (LIBDEFLATE_AMD_TIFFW_RESULT_WORDS uint64_t, device): [0] 0 or
+ * LIBDEFLATE_INSUFFICIENT_SPACE - then nothing is written -, [1] the bytes
+ * written in all, [2] the kept rectangles' bytes in all, [3] the segments.
+ * d_index (device, may be NULL) receives the reader's rows: word 0 the
+ * stream's offset in d_out, word 1 its size, words 2 to 7 the input's.
+ * libdeflate_amd_tiff_encode_bound is the sum of
+ * libdeflate_zlib_compress_bound(coded size), room enough for out_avail; 0 for
+ * rows the call refuses.  The call only enqueues; conventions are
+ * libdeflate_amd_shuffle_compress_batch's.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with "row N:" and the reason
+ * in libdeflate_amd_last_error(): a NULL object or pointer (the reader's d_in
+ * with in_nbytes == 0 and d_out with out_avail == 0 may be NULL, the writer's
+ * d_in with in_avail == 0; its d_out and d_result must not be), n_segments
+ * above 2^28, a zero width or zero rows, kept above coded, spp 0 or above 16,
+ * bps not 1, 2, 4 or 8, a predictor not 1, 2 or 3, predictor 3 with bps 1,
+ * unknown bits in word 6, word 7 not 0, a coded size of 2^32 or more, a stored
+ * range outside in_nbytes, a kept rectangle whose last byte (word 2 +
+ * (kept_rows - 1) * pitch + the kept row's bytes) lies outside out_avail (the
+ * writer: in_avail), overflow included, a pitch below the kept row's bytes
+ * when kept_rows > 1; in the writer at level 0, a coded size above 0xFFFFFF00.
+ * n_segments == 0 does nothing and returns 0.
+ *
+ * Cost: a row that is direct - predictor 1, kept equal to coded, the pitch
+ * equal to the row's bytes or a single row - is decoded straight into d_out;
+ * every other row into scratch, and one memory-bound kernel over the kept rows
+ * of all segments undoes the predictor on the way to d_out (predictor 3: two
+ * kernels).  A batch that is direct throughout queues what
+ * libdeflate_amd_decompress_batch queues, plus one small kernel.
+ *
+ * Not covered: parsing the file on the device (libdeflate_amd/tiff.py walks
+ * the IFDs on the host and makes the rows: INTEGRATION.md); big-endian (MM)
+ * sample order; sample sizes that are not 1, 2, 4 or 8 bytes;
+ * PlanarConfiguration = 2 beyond what spp = 1 rows already give (planes as
+ * separate images); the LZW, JPEG, ZSTD and LERC compressions; uncompressed
+ * segments; routing huge strips to the many-wave decoder (a segment is decoded
+ * by one wave); writing the file's IFD on the device.
+ */
+#define LIBDEFLATE_AMD_TIFF_WORDS 8
+#define LIBDEFLATE_AMD_TIFF_SPP_MAX 16
+#define LIBDEFLATE_AMD_TIFFW_RESULT_WORDS 4
+
+LIBDEFLATEAPI int
+libdeflate_amd_tiff_decode_batch(struct libdeflate_decompressor *decompressor, size_t n_segments,
+				 const uint64_t *rows /* host rows */, const void *d_in,
+				 size_t in_nbytes, void *d_out, size_t out_avail,
+				 int32_t *d_results, void *stream);
+
+LIBDEFLATEAPI size_t
+libdeflate_amd_tiff_encode_bound(struct libdeflate_compressor *compressor, size_t n_segments,
+				 const uint64_t *rows);
+
+LIBDEFLATEAPI int
+libdeflate_amd_tiff_encode_batch(struct libdeflate_compressor *compressor, size_t n_segments,
+				 const uint64_t *rows /* host rows */, const void *d_in,
+				 size_t in_avail, void *d_out, size_t out_avail, uint64_t *d_result,
+				 uint64_t *d_index /* may be NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

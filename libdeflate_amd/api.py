@@ -301,6 +301,40 @@ class Compressor:
             "shuffle_compress_batch")
         return r
 
+    def tiff_encode_bound(self, rows):
+        """libdeflate_amd_tiff_encode_bound: room enough for the streams
+        encode_tiff_batch writes for these rows (tiff_rows()).  No device is
+        touched; ValueError for rows the call would refuse."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.TIFF_WORDS)
+        size = self._lib.libdeflate_amd_tiff_encode_bound(
+            self._h, len(r), r.ctypes.data_as(c_void_p))
+        if len(r) and not size:
+            raise ValueError("tiff_encode_bound: a row the encode call refuses")
+        return size
+
+    def encode_tiff_batch(self, rows, data, out, result, index=None, stream=None,
+                          in_avail=None, out_avail=None):
+        """libdeflate_amd_tiff_encode_batch: every segment (strip or tile) of
+        the pixels in `data` (uint8 CUDA tensor; rows: tiff_rows(), words 2 to
+        7) padded to its coded size, predicted and compressed into one zlib
+        stream, the streams back to back from out[0].  result: int64 CUDA
+        tensor of TIFFW_RESULT_WORDS - [0] 0 or INSUFFICIENT_SPACE, [1] the
+        streams' bytes, [2] the kept bytes, [3] the segments; index: None or
+        an int64 CUDA tensor of segments x TIFF_WORDS, the rows
+        decode_tiff_batch takes for `out`.  Returns the rows as passed (numpy
+        uint64).  Only enqueues on `stream`."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.TIFF_WORDS)
+        assert result.numel() >= binding.TIFFW_RESULT_WORDS
+        assert index is None or index.numel() >= binding.TIFF_WORDS * len(r)
+        avail = data.numel() if in_avail is None else int(in_avail)
+        check(self._lib.libdeflate_amd_tiff_encode_batch(
+            self._h, len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if avail else None, avail, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
+            "tiff_encode_batch")
+        return r
+
     def tar_write_size(self, names, sizes):
         """libdeflate_amd_tar_write_size: the exact size of the tar archive
         write_tar_batch writes for entries of these names (str or bytes, or
@@ -964,6 +998,26 @@ class Decompressor:
             "shuffle_decompress_batch")
         return r
 
+    def decode_tiff_batch(self, rows, data, out, results, stream=None, in_nbytes=None,
+                          out_avail=None):
+        """libdeflate_amd_tiff_decode_batch: the deflate strips or tiles of a
+        TIFF in `data` decoded, their predictor undone and their kept
+        rectangles written into `out` at the rows' offsets and pitch.  rows:
+        host rows of TIFF_WORDS u64 (tiff_rows(), libdeflate_amd.tiff.parse(),
+        or the index encode_tiff_batch wrote); data, out: uint8 CUDA tensors;
+        results: int32 CUDA tensor, one enum libdeflate_result per segment.
+        Returns the rows as passed (numpy uint64).  Only enqueues."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.TIFF_WORDS)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        assert results.numel() >= len(r)
+        check(self._lib.libdeflate_amd_tiff_decode_batch(
+            self._h, len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
+            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
+            "tiff_decode_batch")
+        return r
+
     def decompress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
                               out_offsets, out_avail, results, actual_in=None,
                               actual_out=None, stream=None):
@@ -1343,6 +1397,35 @@ def shuffle_rows(raw_offsets, raw_sizes, itemsize, stored_offsets=None, stored_s
         assert len(col) == n
         for k in range(n):
             rows[k, w] = int(col[k])
+    return rows
+
+
+def tiff_rows(raw_offsets, pitches, coded, kept, spp, bps, predictor, stored_offsets=None,
+              stored_sizes=None):
+    """The host rows of the TIFF calls, one per segment (strip or tile).
+    raw_offsets: where each segment's kept pixel (0, 0) lies in the raw
+    buffer; pitches: bytes between kept rows there; coded / kept: (width,
+    rows) of the coded segment and of the rectangle that is kept, one pair or
+    one per segment (kept None: the coded size); spp, bps, predictor: samples
+    per pixel, bytes per sample, 1 / 2 / 3, one value or one per segment;
+    stored_offsets / stored_sizes: the zlib streams in the compressed buffer
+    (the reader; None: zeros, which the writer ignores).
+    -> numpy uint64 (segments, TIFF_WORDS)."""
+    n = len(raw_offsets)
+
+    def per(v):
+        return list(v) if isinstance(v, (list, np.ndarray)) else [v] * n
+    so, sn = per(0 if stored_offsets is None else stored_offsets), \
+        per(0 if stored_sizes is None else stored_sizes)
+    pi, cd, sp, bp, pr = per(pitches), per(coded), per(spp), per(bps), per(predictor)
+    kp = cd if kept is None else per(kept)
+    rows = np.zeros((n, binding.TIFF_WORDS), dtype=np.uint64)
+    for k in range(n):
+        rows[k, 0], rows[k, 1], rows[k, 2], rows[k, 3] = int(so[k]), int(sn[k]), \
+            int(raw_offsets[k]), int(pi[k])
+        rows[k, 4] = int(cd[k][0]) | int(cd[k][1]) << 32
+        rows[k, 5] = int(kp[k][0]) | int(kp[k][1]) << 32
+        rows[k, 6] = int(sp[k]) | int(bp[k]) << 8 | int(pr[k]) << 16
     return rows
 
 

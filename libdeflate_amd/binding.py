@@ -68,6 +68,9 @@ PREFIX = 19
 # mask bits, the words of the writer's result
 SHUF_WORDS, SHUF_ELEM_MAX, SHUF_NO_DEFLATE, SHUF_NO_SHUFFLE = 6, 256, 1, 2
 SHUFW_RESULT_WORDS = 4
+# predictor-coded deflate strips and tiles (TIFF): u64 per row, the most
+# samples per pixel, the words of the writer's result
+TIFF_WORDS, TIFF_SPP_MAX, TIFFW_RESULT_WORDS = 8, 16, 4
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -126,6 +129,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_png_decode_batch_ex",
     "libdeflate_amd_shuffle_decompress_batch", "libdeflate_amd_shuffle_compress_bound",
     "libdeflate_amd_shuffle_compress_batch",
+    "libdeflate_amd_tiff_decode_batch", "libdeflate_amd_tiff_encode_bound",
+    "libdeflate_amd_tiff_encode_batch",
 ]
 
 _lib = None
@@ -278,6 +283,11 @@ def load():
     sig("libdeflate_amd_shuffle_decompress_batch", c_int, P, c_int, SZ, P, P, SZ, P, SZ, P, P)
     sig("libdeflate_amd_shuffle_compress_bound", SZ, P, c_int, SZ, P)
     sig("libdeflate_amd_shuffle_compress_batch", c_int, P, c_int, SZ, P, P, SZ, P, SZ, P, P, P)
+    # predictor-coded deflate strips and tiles (TIFF, GeoTIFF): host rows of
+    # TIFF_WORDS u64, zlib streams in a device buffer -> pixels and back
+    sig("libdeflate_amd_tiff_decode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P)
+    sig("libdeflate_amd_tiff_encode_bound", SZ, P, SZ, P)
+    sig("libdeflate_amd_tiff_encode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P, P)
     # PNG files written: the bound (host arithmetic), and pixel arrays of a
     # device buffer -> files (the image rows on the host)
     sig("libdeflate_amd_png_encode_bound", SZ, P, SZ, P)

@@ -659,6 +659,35 @@ extern "C" __global__ void
 lda_shufw_final_kernel(uint64_t n, uint64_t raw_total, uint64_t out_avail,
 		       const uint64_t *total_at, uint64_t *result);
 
+/* tiff_kernels.hip: predictor-coded deflate strips and tiles (TIFF, GeoTIFF;
+ * host_tiff.hip, host_tiff_write.hip): the per-row, per-channel prefix sums
+ * over the kept rows of many segments, groups of 4, 16 or 64 lanes a row, the
+ * grid strides over quads of lanes; the floating-point predictor's gather from
+ * the byte planes; the forward differences into the writer's rooms, tiles of
+ * LDA_TIFF_PTILE bytes; the writer's index rows.  The k_* and g_* columns are
+ * tiff_plan.h's TIFF_KCOLS and TIFF_GCOLS, ecols its TIFFW_ECOLS; the reader's
+ * verdicts and the writer's assembly are shuffle_kernels.hip's.  Copies of the
+ * header's and the plan's constants (static_assert in host_tiff.hip) */
+#define LDA_TIFF_WORDS 8
+#define LDA_TIFF_SPP_MAX 16
+#define LDA_TIFF_PTILE 4096		/* bytes of a room a workgroup predicts: 256 threads x 16 */
+#define LDA_TIFF_DST_WS ((uint64_t)1 << 63)	/* k_dst counts from the scratch: a scan in place */
+extern "C" __global__ void
+lda_tiff_unpredict_kernel(uint64_t n_k, uint64_t n_quads, const uint64_t *kcols, uint8_t *ws,
+			  uint8_t *out);
+extern "C" __global__ void
+lda_tiff_gather_kernel(uint64_t n_g, uint64_t n_tiles, const uint64_t *g_tile_end,
+		       const uint64_t *g_src, const uint64_t *g_dst, const uint64_t *g_dpitch,
+		       const uint64_t *g_geom, const uint64_t *g_plane, const uint8_t *ws,
+		       uint8_t *out);
+extern "C" __global__ void
+lda_tiff_predict_kernel(uint64_t n, uint64_t n_tiles, const uint64_t *ecols, const uint8_t *in,
+			uint8_t *rooms);
+extern "C" __global__ void
+lda_tiffw_index_kernel(uint64_t n, uint64_t out_avail, const uint64_t *ecols,
+		       const uint64_t *csize, const uint64_t *offsets, const uint64_t *block_sums,
+		       uint64_t *index);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
