@@ -2478,6 +2478,130 @@ libdeflate_amd_tiff_encode_batch(struct libdeflate_compressor *compressor, size_
 				 size_t in_avail, void *d_out, size_t out_avail, uint64_t *d_result,
 				 uint64_t *d_index /* may be NULL */, void *stream);
 
+/*
+ * OpenEXR chunks with the ZIP (16 scanlines a chunk) and ZIPS (1 scanline)
+ * compressions, scanline blocks and tiles: what the OpenEXR library writes by
+ * default.  A raw chunk holds `lines` lines of `width` pixels channel-planar:
+ * for every line in turn, for every channel in the file's chlist order, the
+ * line's samples of that channel, HALF (2 bytes) or FLOAT / UINT (4 bytes),
+ * little-endian; n = lines * width * (the sum of the sample sizes) bytes.  The
+ * file stores it coded, with h = (n + 1) / 2:
+ *
+ *   t[k] = raw[2k] (k < h), t[h + k] = raw[2k + 1]: the even bytes, then the odd
+ *   p[0] = t[0], p[i] = t[i] - t[i - 1] + 128 (mod 256)
+ *   data = the zlib stream of p - or, where that is not shorter than n, raw
+ *          itself: a reader tells the two apart by dataSize alone
+ *
+ * Undoing it is one byte-wise running sum over the whole chunk, an XOR of 0x80
+ * at the odd places, and the interleave of the two halves.
+ *
+ * A chunk is described by a row of LIBDEFLATE_AMD_EXR_WORDS uint64_t on the
+ * HOST:
+ *   [0] the offset of the chunk's data - the byte behind its dataSize field -
+ *       in the compressed buffer
+ *   [1] dataSize
+ *   [2] the offset, in the pixel buffer, of the chunk's line 0, pixel 0
+ *   [3] the pitch in bytes between lines in the pixel buffer
+ *   [4] width | lines << 32; both at least 1, and n below 2^32
+ *   [5] channels c (bits 0-7, 1 .. LIBDEFLATE_AMD_EXR_CHANNELS_MAX) | wide mask
+ *       << 8 (bit k set: channel k of the file has 4-byte samples, else 2) |
+ *       layout << 32 (LIBDEFLATE_AMD_EXR_LINES, _PIXELS).  Any other bit is
+ *       refused
+ *   [6] PIXELS: 4 bits per channel, the slot of the file's channel k in the
+ *       pixel; a permutation of 0 .. c - 1.  LINES: 0
+ *   [7] the length of the chunk's head in bytes: 0 (none), 8 (a scanline
+ *       chunk: y, dataSize) or 20 (a tile: tileX, tileY, levelX, levelY,
+ *       dataSize)
+ *   [8], [9] the head's int32 values in front of dataSize, the low half first
+ *       (length 8: one value, length 20: four).  The reader ignores them
+ *
+ * LINES is the file's own arrangement at a pitch: line y at word 2 + y *
+ * pitch holds the channels' planes one after another.  PIXELS interleaves:
+ * pixel x of line y stands at word 2 + y * pitch + x * px, px the sum of the
+ * sample sizes, and inside it the channels stand in slot order, each with its
+ * own size - so the file's A, B, G, R become an H x W x 4 RGBA tensor with
+ * slots 3, 2, 1, 0.  Samples are never converted: half stays half.  Lines of
+ * neighbouring chunks and tiles interleave in one image through offset and
+ * pitch; an edge tile's row has the tile's own width and lines.
+ *
+ * The reader.  The call only enqueues on `stream`; object, stream, scratch and
+ * pinned-block rules are libdeflate_amd_tiff_decode_batch's.  d_results[i]:
+ * dataSize == n: LIBDEFLATE_SUCCESS, the data is raw and is laid out; dataSize
+ * > n: LIBDEFLATE_BAD_DATA; else what libdeflate_zlib_decompress_ex reports
+ * for the stream with out_nbytes_avail = n and a NULL actual_out -
+ * LIBDEFLATE_SUCCESS only if the stream fills n exactly, else SHORT_OUTPUT,
+ * INSUFFICIENT_SPACE or BAD_DATA.  The bytes of the pitch behind a line are
+ * never written, and nothing outside the chunks' lines is.  A failed chunk
+ * leaves only its own lines undefined.  The chunks' lines must not overlap
+ * each other or d_in (not checked).
+ *
+ * The writer.  Rows use words 2 to 9, the pixels in d_in: a reader's row is a
+ * valid writer's row.  Every chunk's lines are gathered into the raw chunk and
+ * coded, and the coded bytes compressed to, byte for byte, what
+ * libdeflate_zlib_compress() of this build returns for them at the object's
+ * level (chunks of 128 KiB and more as primed segments like
+ * libdeflate_amd_compress_large_batch's).  Chunk k is written behind chunk k -
+ * 1, from offset 0 of d_out: the head's ints, int32 dataSize (a head of 0
+ * bytes: neither), then the data - the zlib stream if it is shorter than n,
+ * else the raw chunk with dataSize = n.  The choice is the format's and is not
+ * optional; at level 0 every chunk ends up raw.  d_result
+ * (LIBDEFLATE_AMD_EXRW_RESULT_WORDS uint64_t, device): [0] 0 or
+ * LIBDEFLATE_INSUFFICIENT_SPACE - then nothing is written -, [1] the bytes
+ * written in all, [2] the raw bytes in all, [3] the chunks.  d_index (device,
+ * may be NULL) receives the reader's rows: word 0 the offset of the data in
+ * d_out (the head starts word 7 bytes earlier), word 1 the chosen dataSize,
+ * words 2 to 9 the input's.  libdeflate_amd_exr_encode_bound is the sum of
+ * head + n, which no output exceeds; 0 for rows the call refuses.  The call
+ * only enqueues; conventions are libdeflate_amd_tiff_encode_batch's.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with "row N:" and the reason
+ * in libdeflate_amd_last_error(): a NULL object or pointer (as the TIFF calls),
+ * n_chunks above 2^28, unknown bits in word 5, c of 0 or above 16, a mask bit
+ * at or above c, a zero width or zero lines, word 6 not 0 for LINES or not a
+ * permutation for PIXELS, a head length that is not 0, 8 or 20, n of 2^32 or
+ * more, a stored range outside in_nbytes, a pitch below the line's bytes when
+ * lines > 1, a last byte (word 2 + (lines - 1) * pitch + the line's bytes)
+ * outside out_avail (the writer: in_avail), overflow included; in the writer
+ * at level 0, n above 0xFFFFFF00.  n_chunks == 0 does nothing and returns 0.
+ *
+ * Cost: a zlib chunk is inflated into scratch; three memory-bound launches
+ * over the bytes of all chunks (sums, carries, tiles) undo the coding - a row
+ * that is direct (LINES at a pitch equal to the line's bytes, or one line)
+ * straight into d_out, any other into a second room that the layout kernel
+ * reads.  A raw chunk is copied, or laid out straight from d_in.  A batch of
+ * direct raw rows queues one copy kernel and one small kernel.
+ *
+ * Not covered: the PXR24, PIZ, RLE, B44 and DWA compressions; multi-part and
+ * deep files; mip and rip levels; subsampled channels; half-to-float
+ * conversion; routing huge chunks to the many-wave decoder (a chunk is decoded
+ * by one wave); parsing the file on the device (libdeflate_amd/exr.py reads
+ * the header and the chunk heads on the host and makes the rows:
+ * INTEGRATION.md); host-pointer forms.  No file written by the OpenEXR library
+ * has been read yet: the format facts above are the specification this was
+ * built against.
+ */
+#define LIBDEFLATE_AMD_EXR_WORDS 10
+#define LIBDEFLATE_AMD_EXR_CHANNELS_MAX 16
+#define LIBDEFLATE_AMD_EXRW_RESULT_WORDS 4
+#define LIBDEFLATE_AMD_EXR_LINES 0
+#define LIBDEFLATE_AMD_EXR_PIXELS 1
+
+LIBDEFLATEAPI int
+libdeflate_amd_exr_decode_batch(struct libdeflate_decompressor *decompressor, size_t n_chunks,
+				const uint64_t *rows /* host rows */, const void *d_in,
+				size_t in_nbytes, void *d_out, size_t out_avail, int32_t *d_results,
+				void *stream);
+
+LIBDEFLATEAPI size_t
+libdeflate_amd_exr_encode_bound(struct libdeflate_compressor *compressor, size_t n_chunks,
+				const uint64_t *rows);
+
+LIBDEFLATEAPI int
+libdeflate_amd_exr_encode_batch(struct libdeflate_compressor *compressor, size_t n_chunks,
+				const uint64_t *rows /* host rows */, const void *d_in,
+				size_t in_avail, void *d_out, size_t out_avail, uint64_t *d_result,
+				uint64_t *d_index /* may be NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -335,6 +335,41 @@ class Compressor:
             "tiff_encode_batch")
         return r
 
+    def exr_encode_bound(self, rows):
+        """libdeflate_amd_exr_encode_bound: the sum of head + raw size over the
+        rows (exr_rows()), which nothing encode_exr_batch writes exceeds.  No
+        device is touched; ValueError for rows the call would refuse."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.EXR_WORDS)
+        size = self._lib.libdeflate_amd_exr_encode_bound(
+            self._h, len(r), r.ctypes.data_as(c_void_p))
+        if len(r) and not size:
+            raise ValueError("exr_encode_bound: a row the encode call refuses")
+        return size
+
+    def encode_exr_batch(self, rows, data, out, result, index=None, stream=None,
+                         in_avail=None, out_avail=None):
+        """libdeflate_amd_exr_encode_batch: every chunk (scanline block or
+        tile) of the pixels in `data` (uint8 CUDA tensor; rows: exr_rows(),
+        words 2 to 9) gathered, coded and compressed, and written as head,
+        dataSize and data - the zlib stream where it is shorter than the raw
+        chunk, else the raw chunk - back to back from out[0].  result: int64
+        CUDA tensor of EXRW_RESULT_WORDS - [0] 0 or INSUFFICIENT_SPACE, [1]
+        the bytes written, [2] the raw bytes, [3] the chunks; index: None or
+        an int64 CUDA tensor of chunks x EXR_WORDS, the rows decode_exr_batch
+        takes for `out`.  Returns the rows as passed (numpy uint64).  Only
+        enqueues on `stream`."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.EXR_WORDS)
+        assert result.numel() >= binding.EXRW_RESULT_WORDS
+        assert index is None or index.numel() >= binding.EXR_WORDS * len(r)
+        avail = data.numel() if in_avail is None else int(in_avail)
+        check(self._lib.libdeflate_amd_exr_encode_batch(
+            self._h, len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if avail else None, avail, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
+            "exr_encode_batch")
+        return r
+
     def tar_write_size(self, names, sizes):
         """libdeflate_amd_tar_write_size: the exact size of the tar archive
         write_tar_batch writes for entries of these names (str or bytes, or
@@ -1018,6 +1053,28 @@ class Decompressor:
             "tiff_decode_batch")
         return r
 
+    def decode_exr_batch(self, rows, data, out, results, stream=None, in_nbytes=None,
+                         out_avail=None):
+        """libdeflate_amd_exr_decode_batch: the ZIP / ZIPS chunks of an OpenEXR
+        file in `data` - zlib streams or raw, by their dataSize - decoded,
+        their coding undone and their lines written into `out` at the rows'
+        offsets and pitch, as the file's planes (LINES) or as interleaved
+        pixels (PIXELS).  rows: host rows of EXR_WORDS u64 (exr_rows(),
+        libdeflate_amd.exr.parse(), or the index encode_exr_batch wrote);
+        data, out: uint8 CUDA tensors; results: int32 CUDA tensor, one enum
+        libdeflate_result per chunk.  Returns the rows as passed (numpy
+        uint64).  Only enqueues."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.EXR_WORDS)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        assert results.numel() >= len(r)
+        check(self._lib.libdeflate_amd_exr_decode_batch(
+            self._h, len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
+            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
+            "exr_decode_batch")
+        return r
+
     def decompress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
                               out_offsets, out_avail, results, actual_in=None,
                               actual_out=None, stream=None):
@@ -1426,6 +1483,49 @@ def tiff_rows(raw_offsets, pitches, coded, kept, spp, bps, predictor, stored_off
         rows[k, 4] = int(cd[k][0]) | int(cd[k][1]) << 32
         rows[k, 5] = int(kp[k][0]) | int(kp[k][1]) << 32
         rows[k, 6] = int(sp[k]) | int(bp[k]) << 8 | int(pr[k]) << 16
+    return rows
+
+
+def exr_rows(pix_offsets, pitches, sizes, wide, layout=0, slots=None, data_offsets=None,
+             data_sizes=None, heads=None):
+    """The host rows of the OpenEXR calls, one per chunk (scanline block or
+    tile).  pix_offsets: where each chunk's line 0, pixel 0 lies in the pixel
+    buffer; pitches: bytes between lines there; sizes: (width, lines), one
+    pair or one per chunk; wide: per channel of the file, in its order, True
+    for 4-byte samples (FLOAT, UINT) and False for HALF - one list for all
+    chunks; layout: binding.EXR_LINES or EXR_PIXELS; slots: PIXELS only, the
+    place of the file's channel k in the pixel (None: the file's order);
+    data_offsets / data_sizes: the chunks' data in the compressed buffer (the
+    reader; None: zeros, which the writer ignores); heads: None (no head) or
+    per chunk a tuple of the int32 values in front of dataSize - (y,) or
+    (tileX, tileY, levelX, levelY).
+    -> numpy uint64 (chunks, EXR_WORDS)."""
+    n = len(pix_offsets)
+
+    def per(v):
+        return list(v) if isinstance(v, (list, np.ndarray)) else [v] * n
+    do, dn = per(0 if data_offsets is None else data_offsets), \
+        per(0 if data_sizes is None else data_sizes)
+    pi = per(pitches)
+    sz = [tuple(sizes)] * n if np.ndim(sizes) == 1 else [tuple(s) for s in sizes]
+    wide = [bool(w) for w in wide]
+    c = len(wide)
+    fmt = c | sum(1 << (8 + k) for k in range(c) if wide[k]) | int(layout) << 32
+    slot_word = 0
+    if int(layout) == binding.EXR_PIXELS:
+        for k, s in enumerate(range(c) if slots is None else slots):
+            slot_word |= int(s) << (4 * k)
+    rows = np.zeros((n, binding.EXR_WORDS), dtype=np.uint64)
+    for k in range(n):
+        rows[k, 0], rows[k, 1], rows[k, 2], rows[k, 3] = int(do[k]), int(dn[k]), \
+            int(pix_offsets[k]), int(pi[k])
+        rows[k, 4] = int(sz[k][0]) | int(sz[k][1]) << 32
+        rows[k, 5], rows[k, 6] = fmt, slot_word
+        head = () if heads is None else tuple(heads[k])
+        assert len(head) in (0, 1, 4), "a head of one or four ints, or none"
+        rows[k, 7] = 4 * len(head) + 4 if head else 0
+        v = [int(x) & 0xFFFFFFFF for x in head] + [0, 0, 0, 0]
+        rows[k, 8], rows[k, 9] = v[0] | v[1] << 32, v[2] | v[3] << 32
     return rows
 
 

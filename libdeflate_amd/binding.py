@@ -71,6 +71,10 @@ SHUFW_RESULT_WORDS = 4
 # predictor-coded deflate strips and tiles (TIFF): u64 per row, the most
 # samples per pixel, the words of the writer's result
 TIFF_WORDS, TIFF_SPP_MAX, TIFFW_RESULT_WORDS = 8, 16, 4
+# OpenEXR ZIP / ZIPS chunks: u64 per row, the most channels, the words of the
+# writer's result, the two layouts
+EXR_WORDS, EXR_CHANNELS_MAX, EXRW_RESULT_WORDS = 10, 16, 4
+EXR_LINES, EXR_PIXELS = 0, 1
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -131,6 +135,8 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_shuffle_compress_batch",
     "libdeflate_amd_tiff_decode_batch", "libdeflate_amd_tiff_encode_bound",
     "libdeflate_amd_tiff_encode_batch",
+    "libdeflate_amd_exr_decode_batch", "libdeflate_amd_exr_encode_bound",
+    "libdeflate_amd_exr_encode_batch",
 ]
 
 _lib = None
@@ -288,6 +294,11 @@ def load():
     sig("libdeflate_amd_tiff_decode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P)
     sig("libdeflate_amd_tiff_encode_bound", SZ, P, SZ, P)
     sig("libdeflate_amd_tiff_encode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P, P)
+    # OpenEXR ZIP / ZIPS chunks: host rows of EXR_WORDS u64, chunk data in a
+    # device buffer -> lines or interleaved pixels and back
+    sig("libdeflate_amd_exr_decode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P)
+    sig("libdeflate_amd_exr_encode_bound", SZ, P, SZ, P)
+    sig("libdeflate_amd_exr_encode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P, P)
     # PNG files written: the bound (host arithmetic), and pixel arrays of a
     # device buffer -> files (the image rows on the host)
     sig("libdeflate_amd_png_encode_bound", SZ, P, SZ, P)

@@ -688,6 +688,54 @@ lda_tiffw_index_kernel(uint64_t n, uint64_t out_avail, const uint64_t *ecols,
 		       const uint64_t *csize, const uint64_t *offsets, const uint64_t *block_sums,
 		       uint64_t *index);
 
+/* exr_kernels.hip: OpenEXR's ZIP and ZIPS chunks (host_exr.hip,
+ * host_exr_write.hip): the byte-wise running sum over a whole chunk and the
+ * interleave of its halves undone in three launches - stretch sums, their
+ * carries per chunk, the tiles -, a wave a tile of LDA_EXR_TILE raw bytes; the
+ * raw chunk laid out as lines at a pitch or as interleaved pixels, and
+ * gathered back, in tiles of LDA_EXR_LTILE items; the forward coding in tiles
+ * of LDA_EXR_CTILE bytes; the writer's choice between stream and raw and its
+ * placement.  ucols, lcols and ecols are exr_plan.h's EXR_UCOLS, EXR_LCOLS and
+ * EXRW_ECOLS; the reader's verdicts and the writer's sizes and result are
+ * shuffle_kernels.hip's.  Copies of the header's and the plan's constants
+ * (static_assert in host_exr.hip) */
+#define LDA_EXR_WORDS 10
+#define LDA_EXR_LAYOUT_LINES 0
+#define LDA_EXR_LANE 32			/* raw bytes a lane undoes */
+#define LDA_EXR_TILE 2048		/* raw bytes a wave undoes */
+#define LDA_EXR_WG_TILES 4		/* tiles of a workgroup of 256 */
+#define LDA_EXR_LTILE 256		/* items of a layout tile */
+#define LDA_EXR_CTILE 4096		/* bytes of a coded room a workgroup makes: 256 threads x 16 */
+#define LDA_EXRW_E_WORDS 5		/* the column of a row's word 2 in ecols */
+#define LDA_EXR_DST_OUT ((uint64_t)1 << 63)	/* u_dst counts from d_out, not from the raw area */
+#define LDA_EXR_RAW_IN ((uint64_t)1 << 63)	/* l_raw counts from d_in, not from the raw area */
+extern "C" __global__ void
+lda_exr_sums_kernel(uint64_t n_u, uint64_t n_tiles, const uint64_t *ucols, const uint8_t *coded,
+		    uint32_t *slots);
+extern "C" __global__ void
+lda_exr_carry_kernel(uint64_t n_u, const uint64_t *u_tile_end, uint32_t *slots);
+extern "C" __global__ void
+lda_exr_undo_kernel(uint64_t n_u, uint64_t n_tiles, const uint64_t *ucols, const uint8_t *coded,
+		    const uint32_t *slots, uint8_t *raw, uint8_t *out);
+extern "C" __global__ void
+lda_exr_layout_kernel(uint64_t n_l, uint64_t n_tiles, const uint64_t *lcols, const uint8_t *in,
+		      const uint8_t *raw, uint8_t *out);
+extern "C" __global__ void
+lda_exr_gather_kernel(uint64_t n_l, uint64_t n_tiles, const uint64_t *lcols, const uint8_t *in,
+		      uint8_t *raw);
+extern "C" __global__ void
+lda_exr_code_kernel(uint64_t n, uint64_t n_tiles, const uint64_t *ecols, const uint8_t *raw_area,
+		    uint8_t *coded_area);
+extern "C" __global__ void
+lda_exrw_choose_kernel(uint64_t n, const uint64_t *ecols, uint64_t *dsize, uint64_t *sizes);
+extern "C" __global__ void
+lda_exrw_place_kernel(uint64_t n, int level, uint64_t out_avail, const uint64_t *ecols,
+		      const uint64_t *pc_off, const uint64_t *pc_n, const uint64_t *slot_off,
+		      const uint64_t *out_n, const uint64_t *csize, const uint32_t *sum,
+		      const uint64_t *dsize, const uint64_t *offsets, const uint64_t *block_sums,
+		      uint8_t *out, uint64_t *cp_src, uint64_t *cp_dst, uint64_t *cp_len,
+		      uint64_t *index);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
