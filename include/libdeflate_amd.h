@@ -2602,6 +2602,129 @@ libdeflate_amd_exr_encode_batch(struct libdeflate_compressor *compressor, size_t
 				size_t in_avail, void *d_out, size_t out_avail, uint64_t *d_result,
 				uint64_t *d_index /* may be NULL */, void *stream);
 
+/*
+ * The pages of flat Parquet column chunks, GZIP-coded or uncompressed, turned
+ * into columns: what pandas.to_parquet(compression="gzip") and the warehouse
+ * exports write.  A column chunk is a sequence of pages, each behind a Thrift
+ * header that states its sizes: an optional dictionary page, then data pages.
+ * With the GZIP codec a compressed page is one gzip member (Arrow's reader
+ * takes zlib streams too: `format`).  A flat column has max_repetition_level
+ * 0; a nullable one has max_definition_level 1 and stores, per slot (row), a
+ * definition level 1 (a value follows) or 0 (null), and values for the valid
+ * slots only.
+ *
+ *   data page V1   body = [levels, if max_def 1: a 4-byte LE length, then that
+ *                  many bytes of hybrid stream of bit width 1][values]; the
+ *                  whole body is compressed
+ *   data page V2   body = [levels, definition_levels_byte_length bytes of
+ *                  hybrid stream, never compressed and with no length in
+ *                  front][values, compressed where is_compressed says so]
+ *   dictionary     body = entries x width bytes, PLAIN; compressed as a whole
+ *   values         PLAIN: the valid slots' values, width bytes each, back to
+ *                  back.  PLAIN_DICTIONARY / RLE_DICTIONARY: one byte w, the
+ *                  bit width, then a hybrid stream of bit width w of indices
+ *                  into the chunk's dictionary, one per valid slot
+ *
+ * The RLE / bit-packed hybrid stream.  A stream of bit width w that owes N
+ * values is a sequence of runs, each behind a ULEB128 header h.  h & 1 set: h
+ * >> 1 groups of 8 values, bit-packed LSB-first in (h >> 1) * w bytes; only
+ * the bytes that cover the values still owed must lie inside the stream.  h &
+ * 1 clear: h >> 1 copies of the value in the next ceil(w / 8) bytes,
+ * little-endian.  Values behind the Nth, and bytes behind the last run that is
+ * needed, are ignored.
+ *
+ * A page is described by a row of LIBDEFLATE_AMD_PARQUET_WORDS uint64_t on the
+ * HOST (libdeflate_amd/parquet.py makes them from a file's footer and page
+ * headers):
+ *   [0] the offset of the page body - the byte behind its Thrift header - in
+ *       d_in
+ *   [1] compressed_page_size
+ *   [2] uncompressed_page_size; both below 2^31
+ *   [3] kind (bits 0-3: LIBDEFLATE_AMD_PARQUET_DATA_V1 0, _DICT 2, _DATA_V2 3)
+ *       | encoding << 4 (0 PLAIN, 2 PLAIN_DICTIONARY, 8 RLE_DICTIONARY; a
+ *       dictionary page: 0) | body_is_compressed << 12 (V2: is_compressed)
+ *       | max_def << 13 (0 or 1; a dictionary page: 0) | (width - 1) << 16
+ *       (the value's bytes, 1 .. 256: INT32 and FLOAT 4, INT64 and DOUBLE 8,
+ *       INT96 12, FIXED_LEN_BYTE_ARRAY its length).  Any other bit is refused
+ *   [4] num_values (the slots, nulls included; a dictionary page: its entries;
+ *       below 2^31) | definition_levels_byte_length << 32 (a V2 data page
+ *       with max_def 1 only, else 0)
+ *   [5] a data page: the byte offset in d_out of the page's slot 0
+ *   [6] a data page with max_def 1: the byte offset in d_valid of slot 0's
+ *       validity byte
+ *   [7] a dictionary-coded data page: the index, in this call, of the row of
+ *       its dictionary page, which must come earlier and have the same width
+ *   A dictionary page ignores words 5 to 7, a PLAIN data page word 7, a page
+ *   with max_def 0 word 6.
+ *
+ * Output.  Slot r of a page holds its value at word 5 + r * width, or width
+ * zero bytes for a null; d_valid holds one byte per slot, 1 or 0 - a
+ * torch.bool tensor as it lies -, written only for rows with max_def 1.
+ * Nothing outside the pages' slots and validity bytes is written.  A failed
+ * page leaves only its own slots and validity bytes undefined.  The pages'
+ * slots must not overlap each other or d_in (not checked).  The call only
+ * enqueues on `stream`; object, stream, scratch and pinned-block rules are
+ * libdeflate_amd_tiff_decode_batch's.
+ *
+ * d_results[i], one enum libdeflate_result per row.  The *section* of a page
+ * is what the codec covers: the body of a V1 data page or a dictionary page,
+ * the values behind the levels of a V2 page (a V2 page's levels are never part
+ * of it).  A compressed section: what libdeflate_<format>_decompress_ex reports
+ * for it with out_nbytes_avail = the section's uncompressed size (word 2, less
+ * the level bytes of a V2 page) and a NULL actual_out - SUCCESS only if it
+ * fills that size exactly, else SHORT_OUTPUT, INSUFFICIENT_SPACE or BAD_DATA.
+ * Where that is SUCCESS, and for an uncompressed section:
+ *   a dictionary page: LIBDEFLATE_BAD_DATA where the section is shorter than
+ *   entries x width, else SUCCESS;
+ *   a data page whose dictionary page did not end in SUCCESS:
+ *   LIBDEFLATE_BAD_DATA;
+ *   any other data page: LIBDEFLATE_BAD_DATA for a run of 0 groups or 0 copies;
+ *   a run header of more than 5 bytes; a run that leaves its stream before N
+ *   is reached (a missing bit-width byte included); an index bit width w above
+ *   32; an RLE level above 1; a V1 level length prefix that leaves the page; an
+ *   index at or above the dictionary's entry count among the values owed; a
+ *   values section shorter than (the valid slots) x width; else SUCCESS.  A
+ *   dictionary-coded page without a valid slot needs no values section at all.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, with "row N:" and the reason
+ * in libdeflate_amd_last_error(): a NULL object or pointer (d_in, d_out with a
+ * size of 0 may be NULL; d_valid may be NULL while no row has max_def 1), a
+ * format other than DEFLATE, ZLIB and GZIP, n_pages above 2^28, unknown bits,
+ * kinds or encodings in word 3, a dictionary encoding or max_def on a
+ * dictionary page, a size or count of 2^31 or more, level bytes on a row that
+ * is not a V2 data page with max_def 1 or beyond either size, an uncompressed
+ * body with word 1 != word 2, a dictionary reference that is not an earlier
+ * dictionary row of the same width, a body outside in_nbytes, slots outside
+ * out_avail or validity bytes outside valid_avail (overflow included), d_valid
+ * NULL while a row has max_def 1.  n_pages == 0 does nothing and returns 0.
+ *
+ * Cost: compressed sections are inflated into scratch in one batch, a page by
+ * one wave; one wave per data page then walks its hybrid streams run by run
+ * (the only serial part, a step per run) and lists the runs in scratch - up to
+ * 16 bytes per slot of a page with levels or indices -; one memory-bound launch
+ * over the slots of all pages writes values and validity.
+ *
+ * Not covered: BYTE_ARRAY (strings) and BOOLEAN columns; nested and repeated
+ * columns (max_rep above 0, max_def above 1); the DELTA_* encodings and
+ * BYTE_STREAM_SPLIT; the Snappy, ZSTD, LZ4 and Brotli codecs; page CRCs;
+ * encryption; the page index and bloom filters; writing; host-pointer forms;
+ * routing pages so large that they want the many-wave decoder (a page is
+ * decoded by one wave); parsing the file on the device
+ * (libdeflate_amd/parquet.py reads the footer and the page headers on the host
+ * and makes the rows: INTEGRATION.md).
+ */
+#define LIBDEFLATE_AMD_PARQUET_WORDS 8
+#define LIBDEFLATE_AMD_PARQUET_DATA_V1 0
+#define LIBDEFLATE_AMD_PARQUET_DICT 2
+#define LIBDEFLATE_AMD_PARQUET_DATA_V2 3
+
+LIBDEFLATEAPI int
+libdeflate_amd_parquet_decode_batch(struct libdeflate_decompressor *decompressor, int format,
+				    size_t n_pages, const uint64_t *rows /* host rows */,
+				    const void *d_in, size_t in_nbytes, void *d_out, size_t out_avail,
+				    void *d_valid /* may be NULL */, size_t valid_avail,
+				    int32_t *d_results, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1075,6 +1075,33 @@ class Decompressor:
             "exr_decode_batch")
         return r
 
+    def parquet_decode_batch(self, fmt, rows, data, out, valid, results, stream=None,
+                             in_nbytes=None, out_avail=None, valid_avail=None):
+        """libdeflate_amd_parquet_decode_batch: the pages of flat Parquet column
+        chunks in `data` - gzip members (fmt "gzip"; "zlib" and "deflate" are
+        taken too) or uncompressed - decoded, their definition levels and
+        dictionary indices expanded and every slot written into `out` at the
+        rows' offsets, a null as zeros, with one validity byte per slot of a
+        nullable column in `valid`.  rows: host rows of PARQUET_WORDS u64
+        (parquet_rows(), or libdeflate_amd.parquet.pages()); data, out: uint8
+        CUDA tensors; valid: uint8 or bool CUDA tensor, or None while no row
+        has max_def 1; results: int32 CUDA tensor, one enum libdeflate_result
+        per page.  Returns the rows as passed (numpy uint64).  Only
+        enqueues."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.PARQUET_WORDS)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        v_avail = (0 if valid is None else valid.numel()) if valid_avail is None \
+            else int(valid_avail)
+        assert results.numel() >= len(r)
+        check(self._lib.libdeflate_amd_parquet_decode_batch(
+            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
+            valid.data_ptr() if valid is not None else None, v_avail,
+            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
+            "parquet_decode_batch")
+        return r
+
     def decompress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
                               out_offsets, out_avail, results, actual_in=None,
                               actual_out=None, stream=None):
@@ -1526,6 +1553,35 @@ def exr_rows(pix_offsets, pitches, sizes, wide, layout=0, slots=None, data_offse
         rows[k, 7] = 4 * len(head) + 4 if head else 0
         v = [int(x) & 0xFFFFFFFF for x in head] + [0, 0, 0, 0]
         rows[k, 8], rows[k, 9] = v[0] | v[1] << 32, v[2] | v[3] << 32
+    return rows
+
+
+def parquet_rows(offsets, csizes, usizes, kinds, counts, widths, encodings=0, compressed=True,
+                 max_def=0, def_lens=0, out_offsets=0, valid_offsets=0, dict_rows=0):
+    """The host rows of the Parquet call, one per page, in the call's order.
+    offsets, csizes, usizes: the page bodies in the compressed buffer and
+    their two sizes; kinds: binding.PARQUET_DATA_V1, _DICT or _DATA_V2;
+    counts: num_values (a dictionary page: its entries); widths: bytes of a
+    value; encodings: 0, 2 or 8; compressed: is the body (V2: the values
+    section) a stream; max_def: 0 or 1; def_lens: V2's
+    definition_levels_byte_length; out_offsets / valid_offsets: slot 0 in the
+    output and in the validity bytes; dict_rows: the row of a dictionary-coded
+    page's dictionary.  All but offsets: one value or one per page.
+    -> numpy uint64 (pages, PARQUET_WORDS)."""
+    n = len(offsets)
+
+    def per(v):
+        return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+    cs, us, kd, ct, wd, en, cp, md, dl, oo, vo, dr = (per(v) for v in (
+        csizes, usizes, kinds, counts, widths, encodings, compressed, max_def, def_lens,
+        out_offsets, valid_offsets, dict_rows))
+    rows = np.zeros((n, binding.PARQUET_WORDS), dtype=np.uint64)
+    for k in range(n):
+        rows[k, 0], rows[k, 1], rows[k, 2] = int(offsets[k]), int(cs[k]), int(us[k])
+        rows[k, 3] = int(kd[k]) | int(en[k]) << 4 | int(bool(cp[k])) << 12 | int(md[k]) << 13 | \
+            (int(wd[k]) - 1) << 16
+        rows[k, 4] = int(ct[k]) | int(dl[k]) << 32
+        rows[k, 5], rows[k, 6], rows[k, 7] = int(oo[k]), int(vo[k]), int(dr[k])
     return rows
 
 

@@ -75,6 +75,9 @@ TIFF_WORDS, TIFF_SPP_MAX, TIFFW_RESULT_WORDS = 8, 16, 4
 # writer's result, the two layouts
 EXR_WORDS, EXR_CHANNELS_MAX, EXRW_RESULT_WORDS = 10, 16, 4
 EXR_LINES, EXR_PIXELS = 0, 1
+# Parquet pages: u64 per row, the page kinds of a row's word 3
+PARQUET_WORDS = 8
+PARQUET_DATA_V1, PARQUET_DICT, PARQUET_DATA_V2 = 0, 2, 3
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -137,6 +140,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_tiff_encode_batch",
     "libdeflate_amd_exr_decode_batch", "libdeflate_amd_exr_encode_bound",
     "libdeflate_amd_exr_encode_batch",
+    "libdeflate_amd_parquet_decode_batch",
 ]
 
 _lib = None
@@ -299,6 +303,9 @@ def load():
     sig("libdeflate_amd_exr_decode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P)
     sig("libdeflate_amd_exr_encode_bound", SZ, P, SZ, P)
     sig("libdeflate_amd_exr_encode_batch", c_int, P, SZ, P, P, SZ, P, SZ, P, P, P)
+    # Parquet pages: host rows of PARQUET_WORDS u64, the file in a device
+    # buffer -> column slots and validity bytes
+    sig("libdeflate_amd_parquet_decode_batch", c_int, P, c_int, SZ, P, P, SZ, P, SZ, P, SZ, P, P)
     # PNG files written: the bound (host arithmetic), and pixel arrays of a
     # device buffer -> files (the image rows on the host)
     sig("libdeflate_amd_png_encode_bound", SZ, P, SZ, P)

@@ -736,6 +736,39 @@ lda_exrw_place_kernel(uint64_t n, int level, uint64_t out_avail, const uint64_t 
 		      uint8_t *out, uint64_t *cp_src, uint64_t *cp_dst, uint64_t *cp_len,
 		      uint64_t *index);
 
+/* parquet_kernels.hip: the pages of flat Parquet column chunks
+ * (host_parquet.hip): the runs of every data page's hybrid streams listed, a
+ * wave a page; the slots of all pages expanded in tiles of LDA_PQ_TILE; the
+ * verdicts merged.  ucols and vcols are parquet_plan.h's PQ_UCOLS and PQ_VCOLS;
+ * `runs` holds records of LDA_PQ_RUN_WORDS words, `info` LDA_PQ_INFO_WORDS
+ * words per data page.  Copies of the header's and the plan's constants
+ * (static_assert in host_parquet.hip) */
+#define LDA_PQ_TILE 1024		/* slots of an expand tile: 256 threads x 4 */
+#define LDA_PQ_LEVEL_PIECE 512		/* values of a piece of a bit-packed level run */
+#define LDA_PQ_RUN_WORDS 4
+#define LDA_PQ_INFO_WORDS 8
+#define LDA_PQ_DATA_V2 3
+#define LDA_PQ_PLAIN 0
+#define LDA_PQ_IN_PLACE ((uint64_t)1 << 63)	/* a section counts from d_in, not from the rooms */
+#define LDA_PQ_F_SKIP ((uint64_t)1 << 31)	/* u_fields: the page's dictionary is too short */
+#define LDA_PQ_V_IS_DICT ((uint64_t)1 << 63)	/* v_own: a dictionary page's own verdict */
+enum {
+	LDA_PQ_U_SLOT_END = 0, LDA_PQ_U_SEC, LDA_PQ_U_SEC_N, LDA_PQ_U_LEV, LDA_PQ_U_LEV_N,
+	LDA_PQ_U_FIELDS, LDA_PQ_U_COUNT, LDA_PQ_U_OUT, LDA_PQ_U_VALID, LDA_PQ_U_DICT,
+	LDA_PQ_U_DICT_N, LDA_PQ_U_LRUNS, LDA_PQ_U_LCAP, LDA_PQ_U_IRUNS, LDA_PQ_U_ICAP, LDA_PQ_UCOLS,
+	LDA_PQ_V_Z = 0, LDA_PQ_V_OWN, LDA_PQ_V_DICT
+};
+extern "C" __global__ void
+lda_pq_runs_kernel(uint64_t n_u, const uint64_t *ucols, const int32_t *decode, const uint8_t *in,
+		   const uint8_t *rooms, uint4 *runs, uint32_t *info);
+extern "C" __global__ void
+lda_pq_expand_kernel(uint64_t n_u, uint64_t n_tiles, const uint64_t *ucols, const uint8_t *in,
+		     const uint8_t *rooms, const uint4 *runs, uint32_t *info, uint8_t *out,
+		     uint8_t *valid);
+extern "C" __global__ void
+lda_pq_final_kernel(uint64_t n, const uint64_t *vcols, const int32_t *decode, const uint32_t *info,
+		    int32_t *results);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */
