@@ -10,6 +10,7 @@ compute.
 """
 import collections
 import ctypes
+import functools
 from ctypes import c_size_t, c_void_p
 
 import numpy as np
@@ -268,16 +269,38 @@ class Compressor:
             result.data_ptr(), index.data_ptr() if index is not None else None, int(filter),
             int(flags), _stream_ptr(stream)), "png_encode_batch")
 
+    def _chunk_bound(self, call, words, rows, refuses, *fmt):
+        """The body of the chunk codecs' *_bound wrappers: libdeflate_amd_<call>
+        (handle, [format,] rows) over rows of `words` u64."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, words)
+        size = getattr(self._lib, "libdeflate_amd_" + call)(
+            self._h, *fmt, len(r), r.ctypes.data_as(c_void_p))
+        if len(r) and not size:
+            raise ValueError(f"{call}: a row the {refuses} call refuses")
+        return size
+
+    def _chunk_encode(self, call, words, result_words, rows, data, out, result, index, stream,
+                      in_avail, out_avail, *fmt):
+        """The body of the chunk codecs' compress / encode wrappers:
+        libdeflate_amd_<call>(handle, [format,] rows, data, out, result, index,
+        stream).  An empty `data` goes as NULL."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, words)
+        assert result.numel() >= result_words
+        assert index is None or index.numel() >= words * len(r)
+        avail = data.numel() if in_avail is None else int(in_avail)
+        check(getattr(self._lib, "libdeflate_amd_" + call)(
+            self._h, *fmt, len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if avail else None, avail, out.data_ptr(),
+            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
+            index.data_ptr() if index is not None else None, _stream_ptr(stream)), call)
+        return r
+
     def shuffle_compress_bound(self, fmt, rows):
         """libdeflate_amd_shuffle_compress_bound: room enough for the streams
         compress_shuffle_batch writes for these rows (shuffle_rows()).  No
         device is touched; ValueError for rows the call would refuse."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.SHUF_WORDS)
-        size = self._lib.libdeflate_amd_shuffle_compress_bound(
-            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p))
-        if len(r) and not size:
-            raise ValueError("shuffle_compress_bound: a row the compress call refuses")
-        return size
+        return self._chunk_bound("shuffle_compress_bound", binding.SHUF_WORDS, rows, "compress",
+                                 FORMATS[fmt])
 
     def compress_shuffle_batch(self, fmt, rows, data, out, result, index=None, stream=None,
                                in_avail=None, out_avail=None):
@@ -289,28 +312,15 @@ class Compressor:
         chunks; index: None or an int64 CUDA tensor of chunks x SHUF_WORDS, the
         rows decompress_shuffle_batch takes for `out`.  Returns the rows as
         passed (numpy uint64).  Only enqueues on `stream`."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.SHUF_WORDS)
-        assert result.numel() >= binding.SHUFW_RESULT_WORDS
-        assert index is None or index.numel() >= binding.SHUF_WORDS * len(r)
-        avail = data.numel() if in_avail is None else int(in_avail)
-        check(self._lib.libdeflate_amd_shuffle_compress_batch(
-            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p),
-            data.data_ptr() if avail else None, avail, out.data_ptr(),
-            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
-            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
-            "shuffle_compress_batch")
-        return r
+        return self._chunk_encode("shuffle_compress_batch", binding.SHUF_WORDS,
+                                  binding.SHUFW_RESULT_WORDS, rows, data, out, result, index,
+                                  stream, in_avail, out_avail, FORMATS[fmt])
 
     def tiff_encode_bound(self, rows):
         """libdeflate_amd_tiff_encode_bound: room enough for the streams
         encode_tiff_batch writes for these rows (tiff_rows()).  No device is
         touched; ValueError for rows the call would refuse."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.TIFF_WORDS)
-        size = self._lib.libdeflate_amd_tiff_encode_bound(
-            self._h, len(r), r.ctypes.data_as(c_void_p))
-        if len(r) and not size:
-            raise ValueError("tiff_encode_bound: a row the encode call refuses")
-        return size
+        return self._chunk_bound("tiff_encode_bound", binding.TIFF_WORDS, rows, "encode")
 
     def encode_tiff_batch(self, rows, data, out, result, index=None, stream=None,
                           in_avail=None, out_avail=None):
@@ -323,28 +333,15 @@ class Compressor:
         an int64 CUDA tensor of segments x TIFF_WORDS, the rows
         decode_tiff_batch takes for `out`.  Returns the rows as passed (numpy
         uint64).  Only enqueues on `stream`."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.TIFF_WORDS)
-        assert result.numel() >= binding.TIFFW_RESULT_WORDS
-        assert index is None or index.numel() >= binding.TIFF_WORDS * len(r)
-        avail = data.numel() if in_avail is None else int(in_avail)
-        check(self._lib.libdeflate_amd_tiff_encode_batch(
-            self._h, len(r), r.ctypes.data_as(c_void_p),
-            data.data_ptr() if avail else None, avail, out.data_ptr(),
-            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
-            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
-            "tiff_encode_batch")
-        return r
+        return self._chunk_encode("tiff_encode_batch", binding.TIFF_WORDS,
+                                  binding.TIFFW_RESULT_WORDS, rows, data, out, result, index,
+                                  stream, in_avail, out_avail)
 
     def exr_encode_bound(self, rows):
         """libdeflate_amd_exr_encode_bound: the sum of head + raw size over the
         rows (exr_rows()), which nothing encode_exr_batch writes exceeds.  No
         device is touched; ValueError for rows the call would refuse."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.EXR_WORDS)
-        size = self._lib.libdeflate_amd_exr_encode_bound(
-            self._h, len(r), r.ctypes.data_as(c_void_p))
-        if len(r) and not size:
-            raise ValueError("exr_encode_bound: a row the encode call refuses")
-        return size
+        return self._chunk_bound("exr_encode_bound", binding.EXR_WORDS, rows, "encode")
 
     def encode_exr_batch(self, rows, data, out, result, index=None, stream=None,
                          in_avail=None, out_avail=None):
@@ -358,17 +355,9 @@ class Compressor:
         an int64 CUDA tensor of chunks x EXR_WORDS, the rows decode_exr_batch
         takes for `out`.  Returns the rows as passed (numpy uint64).  Only
         enqueues on `stream`."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.EXR_WORDS)
-        assert result.numel() >= binding.EXRW_RESULT_WORDS
-        assert index is None or index.numel() >= binding.EXR_WORDS * len(r)
-        avail = data.numel() if in_avail is None else int(in_avail)
-        check(self._lib.libdeflate_amd_exr_encode_batch(
-            self._h, len(r), r.ctypes.data_as(c_void_p),
-            data.data_ptr() if avail else None, avail, out.data_ptr(),
-            out.numel() if out_avail is None else int(out_avail), result.data_ptr(),
-            index.data_ptr() if index is not None else None, _stream_ptr(stream)),
-            "exr_encode_batch")
-        return r
+        return self._chunk_encode("exr_encode_batch", binding.EXR_WORDS,
+                                  binding.EXRW_RESULT_WORDS, rows, data, out, result, index,
+                                  stream, in_avail, out_avail)
 
     def tar_write_size(self, names, sizes):
         """libdeflate_amd_tar_write_size: the exact size of the tar archive
@@ -1014,6 +1003,22 @@ class Decompressor:
             actual_out.data_ptr() if actual_out is not None else None,
             _stream_ptr(stream)), "decompress_batch")
 
+    def _chunk_decode(self, call, words, rows, data, out, results, stream, in_nbytes, out_avail,
+                      fmt=None, more=()):
+        """The body of the chunk codecs' decompress / decode wrappers:
+        libdeflate_amd_<call>(handle, [format,] rows, data, out, [more,]
+        results, stream).  An empty `data` or `out` goes as NULL, and so does
+        `results` of no rows."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, words)
+        n = data.numel() if in_nbytes is None else int(in_nbytes)
+        avail = out.numel() if out_avail is None else int(out_avail)
+        assert results.numel() >= len(r)
+        check(getattr(self._lib, "libdeflate_amd_" + call)(
+            self._h, *(() if fmt is None else (fmt,)), len(r), r.ctypes.data_as(c_void_p),
+            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail, *more,
+            results.data_ptr() if len(r) else None, _stream_ptr(stream)), call)
+        return r
+
     def decompress_shuffle_batch(self, fmt, rows, data, out, results, stream=None,
                                  in_nbytes=None, out_avail=None):
         """libdeflate_amd_shuffle_decompress_batch: byte-shuffled deflate chunks
@@ -1022,16 +1027,8 @@ class Decompressor:
         index compress_shuffle_batch wrote); data, out: uint8 CUDA tensors;
         results: int32 CUDA tensor, one enum libdeflate_result per chunk.
         Returns the rows as passed (numpy uint64).  Only enqueues."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.SHUF_WORDS)
-        n = data.numel() if in_nbytes is None else int(in_nbytes)
-        avail = out.numel() if out_avail is None else int(out_avail)
-        assert results.numel() >= len(r)
-        check(self._lib.libdeflate_amd_shuffle_decompress_batch(
-            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p),
-            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
-            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
-            "shuffle_decompress_batch")
-        return r
+        return self._chunk_decode("shuffle_decompress_batch", binding.SHUF_WORDS, rows, data, out,
+                                  results, stream, in_nbytes, out_avail, fmt=FORMATS[fmt])
 
     def decode_tiff_batch(self, rows, data, out, results, stream=None, in_nbytes=None,
                           out_avail=None):
@@ -1042,16 +1039,8 @@ class Decompressor:
         or the index encode_tiff_batch wrote); data, out: uint8 CUDA tensors;
         results: int32 CUDA tensor, one enum libdeflate_result per segment.
         Returns the rows as passed (numpy uint64).  Only enqueues."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.TIFF_WORDS)
-        n = data.numel() if in_nbytes is None else int(in_nbytes)
-        avail = out.numel() if out_avail is None else int(out_avail)
-        assert results.numel() >= len(r)
-        check(self._lib.libdeflate_amd_tiff_decode_batch(
-            self._h, len(r), r.ctypes.data_as(c_void_p),
-            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
-            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
-            "tiff_decode_batch")
-        return r
+        return self._chunk_decode("tiff_decode_batch", binding.TIFF_WORDS, rows, data, out, results,
+                                  stream, in_nbytes, out_avail)
 
     def decode_exr_batch(self, rows, data, out, results, stream=None, in_nbytes=None,
                          out_avail=None):
@@ -1064,16 +1053,8 @@ class Decompressor:
         data, out: uint8 CUDA tensors; results: int32 CUDA tensor, one enum
         libdeflate_result per chunk.  Returns the rows as passed (numpy
         uint64).  Only enqueues."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.EXR_WORDS)
-        n = data.numel() if in_nbytes is None else int(in_nbytes)
-        avail = out.numel() if out_avail is None else int(out_avail)
-        assert results.numel() >= len(r)
-        check(self._lib.libdeflate_amd_exr_decode_batch(
-            self._h, len(r), r.ctypes.data_as(c_void_p),
-            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
-            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
-            "exr_decode_batch")
-        return r
+        return self._chunk_decode("exr_decode_batch", binding.EXR_WORDS, rows, data, out, results,
+                                  stream, in_nbytes, out_avail)
 
     def parquet_decode_batch(self, fmt, rows, data, out, valid, results, stream=None,
                              in_nbytes=None, out_avail=None, valid_avail=None):
@@ -1088,19 +1069,11 @@ class Decompressor:
         has max_def 1; results: int32 CUDA tensor, one enum libdeflate_result
         per page.  Returns the rows as passed (numpy uint64).  Only
         enqueues."""
-        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1, binding.PARQUET_WORDS)
-        n = data.numel() if in_nbytes is None else int(in_nbytes)
-        avail = out.numel() if out_avail is None else int(out_avail)
         v_avail = (0 if valid is None else valid.numel()) if valid_avail is None \
             else int(valid_avail)
-        assert results.numel() >= len(r)
-        check(self._lib.libdeflate_amd_parquet_decode_batch(
-            self._h, FORMATS[fmt], len(r), r.ctypes.data_as(c_void_p),
-            data.data_ptr() if n else None, n, out.data_ptr() if avail else None, avail,
-            valid.data_ptr() if valid is not None else None, v_avail,
-            results.data_ptr() if len(r) else None, _stream_ptr(stream)),
-            "parquet_decode_batch")
-        return r
+        return self._chunk_decode("parquet_decode_batch", binding.PARQUET_WORDS, rows, data, out,
+                                  results, stream, in_nbytes, out_avail, fmt=FORMATS[fmt],
+                                  more=(valid.data_ptr() if valid is not None else None, v_avail))
 
     def decompress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
                               out_offsets, out_avail, results, actual_in=None,
@@ -1460,6 +1433,13 @@ def png_image_rows(shapes, offsets, depth=8, colour=None, plte=None, trns=None):
     return rows
 
 
+def _per_row(v, n, pair=False):
+    """One value for all n rows, or a sequence of one per row.  pair: a tuple
+    is ONE value - a (width, rows) pair -, not a sequence of per-row values."""
+    return list(v) if isinstance(v, (list, np.ndarray) if pair else (list, tuple, np.ndarray)) \
+        else [v] * n
+
+
 def shuffle_rows(raw_offsets, raw_sizes, itemsize, stored_offsets=None, stored_sizes=None,
                  mask=0):
     """The host rows of the shuffle calls.  raw_offsets / raw_sizes: where each
@@ -1470,13 +1450,11 @@ def shuffle_rows(raw_offsets, raw_sizes, itemsize, stored_offsets=None, stored_s
     SHUF_NO_DEFLATE | SHUF_NO_SHUFFLE, one value or one per chunk.
     -> numpy uint64 (chunks, SHUF_WORDS)."""
     n = len(raw_offsets)
-
-    def per_chunk(v):
-        return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+    per = functools.partial(_per_row, n=n)
     rows = np.zeros((n, binding.SHUF_WORDS), dtype=np.uint64)
-    cols = (per_chunk(0 if stored_offsets is None else stored_offsets),
-            per_chunk(0 if stored_sizes is None else stored_sizes),
-            raw_offsets, raw_sizes, per_chunk(itemsize), per_chunk(mask))
+    cols = (per(0 if stored_offsets is None else stored_offsets),
+            per(0 if stored_sizes is None else stored_sizes),
+            raw_offsets, raw_sizes, per(itemsize), per(mask))
     for w, col in enumerate(cols):
         assert len(col) == n
         for k in range(n):
@@ -1496,9 +1474,7 @@ def tiff_rows(raw_offsets, pitches, coded, kept, spp, bps, predictor, stored_off
     (the reader; None: zeros, which the writer ignores).
     -> numpy uint64 (segments, TIFF_WORDS)."""
     n = len(raw_offsets)
-
-    def per(v):
-        return list(v) if isinstance(v, (list, np.ndarray)) else [v] * n
+    per = functools.partial(_per_row, n=n, pair=True)
     so, sn = per(0 if stored_offsets is None else stored_offsets), \
         per(0 if stored_sizes is None else stored_sizes)
     pi, cd, sp, bp, pr = per(pitches), per(coded), per(spp), per(bps), per(predictor)
@@ -1528,9 +1504,7 @@ def exr_rows(pix_offsets, pitches, sizes, wide, layout=0, slots=None, data_offse
     (tileX, tileY, levelX, levelY).
     -> numpy uint64 (chunks, EXR_WORDS)."""
     n = len(pix_offsets)
-
-    def per(v):
-        return list(v) if isinstance(v, (list, np.ndarray)) else [v] * n
+    per = functools.partial(_per_row, n=n, pair=True)
     do, dn = per(0 if data_offsets is None else data_offsets), \
         per(0 if data_sizes is None else data_sizes)
     pi = per(pitches)
@@ -1569,9 +1543,7 @@ def parquet_rows(offsets, csizes, usizes, kinds, counts, widths, encodings=0, co
     page's dictionary.  All but offsets: one value or one per page.
     -> numpy uint64 (pages, PARQUET_WORDS)."""
     n = len(offsets)
-
-    def per(v):
-        return list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+    per = functools.partial(_per_row, n=n)
     cs, us, kd, ct, wd, en, cp, md, dl, oo, vo, dr = (per(v) for v in (
         csizes, usizes, kinds, counts, widths, encodings, compressed, max_def, def_lens,
         out_offsets, valid_offsets, dict_rows))

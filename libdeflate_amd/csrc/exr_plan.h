@@ -53,7 +53,7 @@
 #include <string>
 #include <vector>
 
-#include "write_pieces_plan.h"
+#include "chunk_plan.h"
 
 namespace lda {
 
@@ -72,8 +72,6 @@ enum {
 	EXR_W_SLOTS, EXR_W_HEAD, EXR_W_H0, EXR_W_H1,
 	/* the row classes */
 	EXR_C_BAD = 0, EXR_C_RAW_DIRECT, EXR_C_RAW_LAYOUT, EXR_C_ZLIB,
-	/* the decode batch's columns, n_z words each */
-	EXR_D_IN_OFF = 0, EXR_D_IN_N, EXR_D_OUT_OFF, EXR_D_OUT_N, EXR_DCOLS,
 	/* the copy kernel's columns, n_copy words each */
 	EXR_P_SRC = 0, EXR_P_DST, EXR_P_LEN, EXR_PCOLS,
 	/* the undo kernels' columns, n_z words each */
@@ -92,9 +90,8 @@ enum {
 	EXR_L_DOFF0,		/* PIXELS: 8 bits per channel, where channel k stands in the pixel */
 	EXR_L_DOFF1,		/* channels 8 .. 15 */
 	EXR_LCOLS,
-	/* the writer's per-chunk columns, n words each: the first three are what
-	 * lda_shufw_chunk_kernel reads */
-	EXRW_E_FIRST = 0, EXRW_E_COUNT, EXRW_E_USIZE, EXRW_E_ROOM, EXRW_E_CTILE_END, EXRW_E_WORDS,
+	/* the writer's per-chunk columns, n words each, behind CHUNKW_E_USIZE */
+	EXRW_E_ROOM = CHUNKW_E_USIZE + 1, EXRW_E_CTILE_END, EXRW_E_WORDS,
 	EXRW_ECOLS = EXRW_E_WORDS + 8	/* words 2 .. 9 of the row */
 };
 #define EXR_MAX_CHUNKS ((uint64_t)1 << 28)
@@ -102,8 +99,6 @@ enum {
 #define EXR_RAW_IN ((uint64_t)1 << 63)	/* LDA_EXR_RAW_IN */
 #define EXR_VERD_OWN ((uint64_t)1 << 63)	/* LDA_SHUF_VERD_OWN */
 #define EXR_PIECE_MAX 0xFFFFFF00ull	/* as SHUF_PIECE_MAX */
-
-static inline uint64_t exr_align16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
 
 /* a row taken apart; sizes as 64-bit numbers */
 struct exr_chunk {
@@ -196,37 +191,18 @@ static inline bool
 exr_check(uint64_t n, const uint64_t *rows, bool reader, uint64_t stored_avail, uint64_t pix_avail,
 	  int level, std::string &err)
 {
-	char msg[200];
-
-	if (n > EXR_MAX_CHUNKS) {
-		snprintf(msg, sizeof(msg), "n_chunks %llu above 2^28", (unsigned long long)n);
-		err = msg;
-		return false;
-	}
-	for (uint64_t r = 0; r < n; r++) {
-		const char *why = exr_row_why(rows + EXR_WORDS * r, reader, stored_avail, pix_avail, level);
-		if (why) {
-			snprintf(msg, sizeof(msg), "row %llu: %s", (unsigned long long)r, why);
-			err = msg;
-			return false;
-		}
-	}
-	return true;
+	return chunk_check("n_chunks", n, EXR_MAX_CHUNKS, [&](uint64_t r) {
+		return exr_row_why(rows + EXR_WORDS * r, reader, stored_avail, pix_avail, level);
+	}, err);
 }
 
 /* the sum of head + n: no chunk is written longer than raw; 0 for rows the
  * writer refuses */
 static inline uint64_t exr_bound(uint64_t n, const uint64_t *rows)
 {
-	uint64_t sum = 0;
-	if (n > EXR_MAX_CHUNKS)
-		return 0;
-	for (uint64_t r = 0; r < n; r++) {
-		if (exr_row_why(rows + EXR_WORDS * r, false, 0, ~(uint64_t)0, -1))
-			return 0;
-		sum += rows[EXR_WORDS * r + EXR_W_HEAD] + exr_chunk_of(rows + EXR_WORDS * r).n;
-	}
-	return sum;
+	return chunk_bound(n, EXR_MAX_CHUNKS, [&](uint64_t r) {
+		return exr_row_why(rows + EXR_WORDS * r, false, 0, ~(uint64_t)0, -1);
+	}, [&](uint64_t r) { return rows[EXR_WORDS * r + EXR_W_HEAD] + exr_chunk_of(rows + EXR_WORDS * r).n; });
 }
 
 /* is the pixel side of the row the raw chunk itself, in one span? */
@@ -306,12 +282,6 @@ struct exr_layout_rows {
 		col[EXR_L_DOFF0].push_back(doff[0]);
 		col[EXR_L_DOFF1].push_back(doff[1]);
 	}
-	size_t rows() const { return col[0].size(); }
-	void append_to(std::vector<uint64_t> &cols) const
-	{
-		for (size_t a = 0; a < EXR_LCOLS; a++)
-			cols.insert(cols.end(), col[a].begin(), col[a].end());
-	}
 };
 
 struct exr_read_plan {
@@ -322,7 +292,7 @@ struct exr_read_plan {
 	uint64_t utiles;	/* the undo kernels' tiles; twice as many slots */
 	uint64_t coded_bytes;	/* the area of the rooms of p */
 	uint64_t raw_bytes;	/* the area of the rooms of raw */
-	/* what goes up: [EXR_DCOLS x n_z] at 0, [EXR_UCOLS x n_z] at u_at, [EXR_PCOLS
+	/* what goes up: [CHUNK_DCOLS x n_z] at 0, [EXR_UCOLS x n_z] at u_at, [EXR_PCOLS
 	 * x n_copy] at p_at, [EXR_LCOLS x n_l] at l_at, [n verdict words] at verd_at */
 	uint64_t u_at, p_at, l_at, verd_at;
 	std::vector<uint64_t> cols;
@@ -331,15 +301,20 @@ struct exr_read_plan {
 /* the rows have passed exr_check() */
 static inline void exr_read_plan_build(uint64_t n, const uint64_t *rows, exr_read_plan &p)
 {
-	std::vector<uint64_t> d[EXR_DCOLS], u[EXR_UCOLS], c[EXR_PCOLS], verd((size_t)n);
+	std::vector<uint64_t> u[EXR_UCOLS], c[EXR_PCOLS], verd((size_t)n);
+	chunk_rooms coded, raw;
 	exr_layout_rows l;
 
 	p.n = n;
-	p.utiles = p.coded_bytes = p.raw_bytes = 0;
+	p.n_z = p.utiles = 0;
+	std::vector<uint8_t> cls((size_t)n);
+	for (uint64_t r = 0; r < n; r++)
+		p.n_z += (cls[(size_t)r] = (uint8_t)exr_class(rows + EXR_WORDS * r)) == EXR_C_ZLIB;
+	chunk_decode_cols d(p.cols, p.n_z);
 	for (uint64_t r = 0; r < n; r++) {
 		const uint64_t *w = rows + EXR_WORDS * r;
 		const exr_chunk s = exr_chunk_of(w);
-		switch (exr_class(w)) {
+		switch (cls[(size_t)r]) {
 		case EXR_C_BAD:
 			verd[(size_t)r] = EXR_VERD_OWN | 1;	/* LIBDEFLATE_BAD_DATA */
 			break;
@@ -353,85 +328,62 @@ static inline void exr_read_plan_build(uint64_t n, const uint64_t *rows, exr_rea
 			verd[(size_t)r] = EXR_VERD_OWN | 0;
 			l.add(w, w[EXR_W_DATA_OFF] | EXR_RAW_IN);
 			break;
-		default:
-			verd[(size_t)r] = d[0].size();
-			d[EXR_D_IN_OFF].push_back(w[EXR_W_DATA_OFF]);
-			d[EXR_D_IN_N].push_back(w[EXR_W_DATA_N]);
-			d[EXR_D_OUT_OFF].push_back(p.coded_bytes);
-			d[EXR_D_OUT_N].push_back(s.n);
+		default: {
+			const uint64_t room = coded.take(s.n);
+			verd[(size_t)r] = d.add(false, w[EXR_W_DATA_OFF], w[EXR_W_DATA_N], room, s.n);
 			p.utiles += exr_tiles(s.n);
 			u[EXR_U_TILE_END].push_back(p.utiles);
-			u[EXR_U_SRC].push_back(p.coded_bytes);
+			u[EXR_U_SRC].push_back(room);
 			u[EXR_U_N].push_back(s.n);
 			if (exr_direct(w)) {
 				u[EXR_U_DST].push_back(w[EXR_W_PIX_OFF] | EXR_DST_OUT);
 			} else {
-				u[EXR_U_DST].push_back(p.raw_bytes);
-				l.add(w, p.raw_bytes);
-				p.raw_bytes += exr_align16(s.n);
+				u[EXR_U_DST].push_back(raw.take(s.n));
+				l.add(w, u[EXR_U_DST].back());
 			}
-			p.coded_bytes += exr_align16(s.n);
 			break;
 		}
+		}
 	}
-	p.n_z = d[0].size();
 	p.n_copy = c[0].size();
-	p.n_l = l.rows();
+	p.n_l = l.col[0].size();
 	p.ltiles = l.tiles;
-	p.cols.clear();
-	for (size_t a = 0; a < EXR_DCOLS; a++)
-		p.cols.insert(p.cols.end(), d[a].begin(), d[a].end());
-	p.u_at = p.cols.size();
-	for (size_t a = 0; a < EXR_UCOLS; a++)
-		p.cols.insert(p.cols.end(), u[a].begin(), u[a].end());
-	p.p_at = p.cols.size();
-	for (size_t a = 0; a < EXR_PCOLS; a++)
-		p.cols.insert(p.cols.end(), c[a].begin(), c[a].end());
-	p.l_at = p.cols.size();
-	l.append_to(p.cols);
-	p.verd_at = p.cols.size();
-	p.cols.insert(p.cols.end(), verd.begin(), verd.end());
+	p.coded_bytes = coded.bytes;
+	p.raw_bytes = raw.bytes;
+	p.u_at = chunk_append(p.cols, u, EXR_UCOLS);
+	p.p_at = chunk_append(p.cols, c, EXR_PCOLS);
+	p.l_at = chunk_append(p.cols, l.col, EXR_LCOLS);
+	p.verd_at = chunk_append(p.cols, &verd);
 }
 
-struct exr_write_plan : zipw_pieces {
-	uint64_t n, raw_total;	/* the chunks' raw bytes */
+struct exr_write_plan : chunk_write_plan {	/* rooms_bytes: of either area */
 	uint64_t ctiles;	/* the coding kernel's tiles */
 	uint64_t ltiles;	/* the gather kernel's */
-	uint64_t rooms_bytes;	/* of either area */
-	uint64_t l_at;		/* [EXRW_ECOLS x n] at 0, [EXR_LCOLS x n] at l_at */
-	std::vector<uint64_t> ecols;
+	uint64_t l_at;		/* ecols: [EXRW_ECOLS x n] at 0, [EXR_LCOLS x n] at l_at */
 };
 
 /* the rows have passed exr_check(); pr.store is false whatever the level */
 static inline void
 exr_write_plan_build(const zipw_params &pr, uint64_t n, const uint64_t *rows, exr_write_plan &p)
 {
-	std::vector<uint64_t> room((size_t)n), size((size_t)n);
+	chunk_write_rows e(p, n, EXRW_ECOLS);
 	exr_layout_rows l;
 
-	p.n = n;
-	p.raw_total = p.rooms_bytes = p.ctiles = 0;
-	p.ecols.assign((size_t)(EXRW_ECOLS * n), 0);
+	p.ctiles = 0;
 	for (uint64_t k = 0; k < n; k++) {
 		const uint64_t *w = rows + EXR_WORDS * k;
 		const exr_chunk s = exr_chunk_of(w);
-		room[(size_t)k] = p.rooms_bytes;
-		size[(size_t)k] = s.n;
+		const uint64_t room = e.add(s.n, s.n);
 		p.ctiles += (s.n + EXR_CTILE - 1) / EXR_CTILE;
-		p.ecols[(size_t)(EXRW_E_USIZE * n + k)] = s.n;
-		p.ecols[(size_t)(EXRW_E_ROOM * n + k)] = p.rooms_bytes;
+		p.ecols[(size_t)(EXRW_E_ROOM * n + k)] = room;
 		p.ecols[(size_t)(EXRW_E_CTILE_END * n + k)] = p.ctiles;
 		for (uint64_t a = 0; a < 8; a++)
 			p.ecols[(size_t)((EXRW_E_WORDS + a) * n + k)] = w[2 + a];
-		l.add(w, p.rooms_bytes);
-		p.rooms_bytes += exr_align16(s.n);
-		p.raw_total += s.n;
+		l.add(w, room);
 	}
 	p.ltiles = l.tiles;
-	p.l_at = p.ecols.size();
-	l.append_to(p.ecols);
-	zipw_cut_pieces(pr, n, room.data(), size.data(), p.ecols.data() + EXRW_E_FIRST * n,
-			p.ecols.data() + EXRW_E_COUNT * n, p);
+	e.cut(pr);
+	p.l_at = chunk_append(p.ecols, l.col, EXR_LCOLS);
 }
 
 } /* namespace lda */

@@ -49,37 +49,21 @@ static int exr_decode(struct libdeflate_decompressor *d, const exr_read_plan &p,
 	const size_t n = (size_t)p.n, n_z = (size_t)p.n_z, n_c = (size_t)p.n_copy, n_l = (size_t)p.n_l;
 	uint8_t *g_coded = NULL, *g_raw = NULL;
 	uint32_t *g_slots = NULL;
-	uint64_t *g_cols = NULL;
-	int32_t *g_decode = NULL;
-	ReadStage s;
-	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+	ChunkStage g;
+	LDA_OK_TRY(chunk_stage(d, p.cols, n_z, d_in, d_out, st, g, [&](Carve &cv) {
 		g_coded = cv.take<uint8_t>((size_t)p.coded_bytes + 16, 256);
 		g_raw = cv.take<uint8_t>((size_t)p.raw_bytes + 16, 256);
 		g_slots = cv.take<uint32_t>((size_t)(2 * p.utiles) + 1);
-		g_cols = cv.take<uint64_t>(p.cols.size());
-		g_decode = cv.take<int32_t>(n_z + 1);
-		return ReadUp{ g_cols, p.cols.size() * sizeof(uint64_t) };
-	}, s));
-	memcpy(s.h, p.cols.data(), s.up.bytes);
-	LDA_OK_TRY(read_send(d, s, st));
-	const uint64_t *dcol[EXR_DCOLS], *pcol[EXR_PCOLS];
-	for (size_t a = 0; a < EXR_DCOLS; a++)
-		dcol[a] = g_cols + a * n_z;
+	}));
+	const uint64_t *pcol[EXR_PCOLS];
 	for (size_t a = 0; a < EXR_PCOLS; a++)
-		pcol[a] = g_cols + p.p_at + a * n_c;
-	const uint64_t *ucols = g_cols + p.u_at, *lcols = g_cols + p.l_at;
-	/* (NULL d_in or d_out: in_nbytes or out_avail is 0, and no row passes the checks) */
-	const uint8_t *in = d_in ? d_in : s.ws;
-	uint8_t *out = d_out ? d_out : s.ws;
+		pcol[a] = g.cols + p.p_at + a * n_c;
+	const uint64_t *ucols = g.cols + p.u_at, *lcols = g.cols + p.l_at;
+	const uint8_t *in = g.in;
+	uint8_t *out = g.out;
 
-	if (n_z && (stages & EXR_STAGE_INFLATE)) {
-		int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_ZLIB, n_z, in,
-							 dcol[EXR_D_IN_OFF], dcol[EXR_D_IN_N], g_coded,
-							 dcol[EXR_D_OUT_OFF], dcol[EXR_D_OUT_N], g_decode,
-							 NULL, NULL, st);
-		if (rc != LIBDEFLATE_AMD_OK)
-			return rc;
-	}
+	if (stages & EXR_STAGE_INFLATE)
+		LDA_OK_TRY(chunk_inflate(d, LIBDEFLATE_AMD_ZLIB, g, n_z, g_coded, 0, st));
 	if (n_c && (stages & EXR_STAGE_UNDO))
 		hipLaunchKernelGGL(lda_zip_copy_kernel, dim3(copy_grid(ctx, n_c)), dim3(256), 0, st,
 				   (uint64_t)n_c, pcol[EXR_P_SRC], pcol[EXR_P_DST], pcol[EXR_P_LEN], in,
@@ -100,23 +84,15 @@ static int exr_decode(struct libdeflate_decompressor *d, const exr_read_plan &p,
 				   (uint64_t)n_l, p.ltiles, lcols, in, (const uint8_t *)g_raw, out);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
-	hipLaunchKernelGGL(lda_shuf_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-			   (uint64_t)n, (const uint64_t *)(g_cols + p.verd_at),
-			   (const int32_t *)g_decode, d_results);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	return LIBDEFLATE_AMD_OK;
+	return chunk_verdicts(g, n, p.verd_at, d_results, st);
 }
 
 static int exr_call(const char *what, struct libdeflate_decompressor *d, size_t n_chunks,
 		    const uint64_t *rows, const void *d_in, size_t in_nbytes, void *d_out,
 		    size_t out_avail, int32_t *d_results, unsigned stages, void *stream)
 {
-	if (!d || (n_chunks && (!rows || !d_results)) || (!d_in && in_nbytes) ||
-	    (!d_out && out_avail)) {
-		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	return read_call<exr_read_plan>(what, d, n_chunks, [&](exr_read_plan &p, std::string &err) {
+	return chunk_read_call<exr_read_plan>(what, d, n_chunks, rows, d_in, in_nbytes, d_out, out_avail,
+					      d_results, [&](exr_read_plan &p, std::string &err) {
 		if (!exr_check(n_chunks, rows, true, in_nbytes, out_avail, -1, err))
 			return false;
 		exr_read_plan_build(n_chunks, rows, p);

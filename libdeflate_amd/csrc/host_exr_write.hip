@@ -35,85 +35,42 @@ extern "C" LIBDEFLATEAPI size_t
 libdeflate_amd_exr_encode_bound(struct libdeflate_compressor *c, size_t n_chunks, const uint64_t *rows)
 {
 	(void)c;	/* (no level has another bound: a chunk is never written longer than raw) */
-	if (n_chunks && !rows) {
-		set_error("exr_encode_bound: NULL argument");
-		return 0;
-	}
-	return (size_t)exr_bound(n_chunks, rows);
+	return chunkw_bound_call("exr_encode_bound", n_chunks, rows, [&] { return exr_bound(n_chunks, rows); });
 }
 
-struct ExrwScratch : PiecesScratch {
-	uint64_t *ecols, *csize, *dsize;
-	uint32_t *sum, *sums;
-	uint8_t *raw, *coded;
-	size_t bytes;
-};
-
-static ExrwScratch exrw_scratch(void *base, const exr_write_plan &p)
-{
-	ExrwScratch s;
-	Carve c(base);
-	const size_t n = (size_t)p.n, np = (size_t)p.np;
-
-	s.ecols = c.take<uint64_t>(p.ecols.size());
-	pieces_carve(c, p, n, 0, s);
-	s.csize = c.take<uint64_t>(n);
-	s.dsize = c.take<uint64_t>(n);
-	s.sum = c.take<uint32_t>(n);
-	s.sums = c.take<uint32_t>(np);
-	s.raw = c.take<uint8_t>((size_t)p.rooms_bytes + 64, 256);
-	s.coded = c.take<uint8_t>((size_t)p.rooms_bytes + 64, 256);
-	s.bytes = c.at + 16;
-	return s;
-}
-
+/* (p.n is not 0: the call has returned for no chunks) */
 static int exrw_enqueue(struct libdeflate_compressor *c, const exr_write_plan &p, const uint8_t *d_in,
 			uint8_t *d_out, uint64_t out_avail, uint64_t *d_result, uint64_t *d_index,
 			hipStream_t st)
 {
 	DeviceCtx *ctx = device_ctx();
-	if (!ctx)
-		return LIBDEFLATE_AMD_NO_DEVICE;
-	const size_t n = (size_t)p.n, np = (size_t)p.np;
-	const ExrwScratch sz = exrw_scratch(NULL, p);
+	const size_t n = (size_t)p.n;
 	const std::vector<zipw_launch> launches = zipw_launches(p);
-	uint8_t *ws, *h;
+	ChunkwScratch s;	/* two areas: s.raw, and s.rooms the coded rooms */
 
-	LDA_OK_TRY(pieces_reserve(c, launches, sz.bytes, sz.up_bytes, &ws, &h));
-	const ExrwScratch s = exrw_scratch(ws, p), hs = exrw_scratch(h, p);
-	memcpy(hs.ecols, p.ecols.data(), p.ecols.size() * 8);
-	LDA_OK_TRY(pieces_upload(c, hs, p, ws, st));
-	const uint64_t *ecol[EXRW_ECOLS], *const *pcol = s.pcol;
-	for (size_t a = 0; a < EXRW_ECOLS; a++)
-		ecol[a] = s.ecols + a * n;
+	LDA_OK_TRY(chunkw_begin(c, p, launches, st, s, true));
+	const uint64_t *const *pcol = s.pcol;
 
 	hipLaunchKernelGGL(lda_exr_gather_kernel, dim3(tile_grid(ctx, p.ltiles)), dim3(256), 0, st,
 			   (uint64_t)n, p.ltiles, (const uint64_t *)(s.ecols + p.l_at), d_in, s.raw);
 	hipLaunchKernelGGL(lda_exr_code_kernel, dim3(tile_grid(ctx, p.ctiles)), dim3(256), 0, st,
-			   (uint64_t)n, p.ctiles, (const uint64_t *)s.ecols, (const uint8_t *)s.raw,
-			   s.coded);
-	LDA_OK_TRY(libdeflate_amd_adler32_batch(np, s.coded, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
-						NULL, s.sums, st));
-	LDA_OK_TRY(pieces_compress(c, s, launches, s.coded, st));
-	const unsigned grid = wave_grid(ctx, n);
-	hipLaunchKernelGGL(lda_shufw_chunk_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
-			   (int)LIBDEFLATE_AMD_ZLIB, ecol[EXRW_E_FIRST], ecol[EXRW_E_COUNT],
-			   ecol[EXRW_E_USIZE], pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
-			   (const uint64_t *)s.out_n, (const uint32_t *)s.sums, s.csize, s.sum, s.sizes);
+			   (uint64_t)n, p.ctiles, (const uint64_t *)s.ecols, (const uint8_t *)s.raw, s.rooms);
+	LDA_OK_TRY(chunkw_compress(c, LIBDEFLATE_AMD_ZLIB, p, s, launches, s.rooms, st));
+	chunkw_sizes(ctx, LIBDEFLATE_AMD_ZLIB, p, s, st);
+	/* between the sizes and their scan: a stream that is no shorter than its
+	 * raw chunk gives way to it */
 	hipLaunchKernelGGL(lda_exrw_choose_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
 			   (uint64_t)n, (const uint64_t *)s.ecols, s.dsize, s.sizes);
-	const uint64_t *total_at = s.bsum + scan_enqueue(st, n, s.sizes, s.offs, s.bsum);
-	hipLaunchKernelGGL(lda_exrw_place_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n, c->level,
-			   out_avail, (const uint64_t *)s.ecols, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
-			   pcol[ZIPW_P_SLOT_OFF], (const uint64_t *)s.out_n, (const uint64_t *)s.csize,
-			   (const uint32_t *)s.sum, (const uint64_t *)s.dsize, (const uint64_t *)s.offs,
-			   (const uint64_t *)s.bsum, d_out, s.cp_src, s.cp_dst, s.cp_len, d_index);
-	/* (a raw chunk's pieces are read from the raw area: the copy kernel's `in`) */
-	pieces_copy(ctx, s, np, total_at, out_avail, 0, s.raw, d_out, st);
-	hipLaunchKernelGGL(lda_shufw_final_kernel, dim3(1), dim3(64), 0, st, (uint64_t)n, p.raw_total,
-			   out_avail, total_at, d_result);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	return LIBDEFLATE_AMD_OK;
+	const uint64_t *total_at = chunkw_scan(p, s, st);
+	hipLaunchKernelGGL(lda_exrw_place_kernel, dim3(wave_grid(ctx, n)), dim3(256), 0, st, (uint64_t)n,
+			   c->level, out_avail, (const uint64_t *)s.ecols, pcol[ZIPW_P_PC_OFF],
+			   pcol[ZIPW_P_PC_N], pcol[ZIPW_P_SLOT_OFF], (const uint64_t *)s.out_n,
+			   (const uint64_t *)s.csize, (const uint32_t *)s.sum, (const uint64_t *)s.dsize,
+			   (const uint64_t *)s.offs, (const uint64_t *)s.bsum, d_out, s.cp_src, s.cp_dst,
+			   s.cp_len, d_index);
+	/* copy_src is the raw area, not d_in as in the shuffle and TIFF writers: a
+	 * raw chunk's pieces are the same ranges of it */
+	return chunkw_finish(ctx, p, s, total_at, out_avail, s.raw, d_out, d_result, st);
 }
 
 extern "C" LIBDEFLATEAPI int
@@ -121,27 +78,15 @@ libdeflate_amd_exr_encode_batch(struct libdeflate_compressor *c, size_t n_chunks
 				const void *d_in, size_t in_avail, void *d_out, size_t out_avail,
 				uint64_t *d_result, uint64_t *d_index, void *stream)
 {
-	const char *what = "exr_encode_batch";
-
-	if (!c || !d_out || !d_result || (!d_in && in_avail) || (n_chunks && !rows)) {
-		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
-		std::string err;
-		if (!exr_check(n_chunks, rows, false, 0, in_avail, c->level, err)) {
-			set_error("%s: %s", what, err.c_str());
-			return LIBDEFLATE_AMD_BAD_ARG;
-		}
-		if (n_chunks == 0)	/* nothing to do: d_result is not written either */
-			return LIBDEFLATE_AMD_OK;
-		DeviceGuard on(c->device);
-		if (!on.ok() || !device_ctx())
-			return LIBDEFLATE_AMD_NO_DEVICE;
-		/* (level 0 too: its stored blocks are longer than raw, so every chunk goes raw) */
-		const zipw_params pr = pieces_params(c, false);
-		exr_write_plan p;
+	/* empty_returns true: of no chunks nothing is queued, and d_result is not
+	 * written either.  (At level 0 the stored blocks are longer than raw, so
+	 * every chunk goes raw) */
+	return chunkw_call<exr_write_plan>("exr_encode_batch", c, n_chunks, rows, d_in, in_avail, d_out,
+					   d_result, true, [&](std::string &err) {
+		return exr_check(n_chunks, rows, false, 0, in_avail, c->level, err);
+	}, [&](const zipw_params &pr, exr_write_plan &p) {
 		exr_write_plan_build(pr, n_chunks, rows, p);
+	}, [&](const exr_write_plan &p) {
 		return exrw_enqueue(c, p, (const uint8_t *)d_in, (uint8_t *)d_out, out_avail, d_result,
 				    d_index, (hipStream_t)stream);
 	});

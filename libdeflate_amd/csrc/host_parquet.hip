@@ -47,34 +47,20 @@ static int pq_decode(struct libdeflate_decompressor *d, int format, const pq_pla
 	uint8_t *g_rooms = NULL;
 	uint4 *g_runs = NULL;
 	uint32_t *g_info = NULL;
-	uint64_t *g_cols = NULL;
-	int32_t *g_decode = NULL;
-	ReadStage s;
-	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+	ChunkStage g;
+	LDA_OK_TRY(chunk_stage(d, p.cols, n_z, d_in, d_out, st, g, [&](Carve &cv) {
 		g_rooms = cv.take<uint8_t>((size_t)p.room_bytes + 16, 256);
 		g_runs = cv.take<uint4>((size_t)p.run_records + 1);
 		g_info = cv.take<uint32_t>(PQ_INFO_WORDS * n_u + 1);
-		g_cols = cv.take<uint64_t>(p.cols.size());
-		g_decode = cv.take<int32_t>(n_z + 1);
-		return ReadUp{ g_cols, p.cols.size() * sizeof(uint64_t) };
-	}, s));
-	memcpy(s.h, p.cols.data(), s.up.bytes);
-	LDA_OK_TRY(read_send(d, s, st));
-	const uint64_t *dcol[PQ_DCOLS];
-	for (size_t a = 0; a < PQ_DCOLS; a++)
-		dcol[a] = g_cols + a * n_z;
-	const uint64_t *ucols = g_cols + p.u_at, *vcols = g_cols + p.v_at;
-	/* (NULL d_in, d_out or d_valid: its size is 0 or no row uses it) */
-	const uint8_t *in = d_in ? d_in : s.ws;
-	uint8_t *out = d_out ? d_out : s.ws, *valid = d_valid ? d_valid : s.ws;
+	}));
+	const uint64_t *ucols = g.cols + p.u_at, *vcols = g.cols + p.v_at;
+	const uint8_t *in = g.in;
+	/* (NULL d_valid: no row uses it) */
+	uint8_t *out = g.out, *valid = d_valid ? d_valid : g.ws;
+	const int32_t *g_decode = g.decode;
 
-	if (n_z && (stages & PQ_STAGE_INFLATE)) {
-		int rc = libdeflate_amd_decompress_batch(d, format, n_z, in, dcol[PQ_D_IN_OFF],
-							 dcol[PQ_D_IN_N], g_rooms, dcol[PQ_D_OUT_OFF],
-							 dcol[PQ_D_OUT_N], g_decode, NULL, NULL, st);
-		if (rc != LIBDEFLATE_AMD_OK)
-			return rc;
-	}
+	if (stages & PQ_STAGE_INFLATE)
+		LDA_OK_TRY(chunk_inflate(d, format, g, n_z, g_rooms, 0, st));
 	if (n_u && (stages & PQ_STAGE_RUNS))
 		hipLaunchKernelGGL(lda_pq_runs_kernel, dim3(wave_grid(ctx, n_u)), dim3(256), 0, st,
 				   (uint64_t)n_u, ucols, (const int32_t *)g_decode, in,
@@ -95,12 +81,8 @@ static int pq_call(const char *what, struct libdeflate_decompressor *d, int form
 		   size_t out_avail, void *d_valid, size_t valid_avail, int32_t *d_results,
 		   unsigned stages, void *stream)
 {
-	if (!d || (n_pages && (!rows || !d_results)) || (!d_in && in_nbytes) ||
-	    (!d_out && out_avail)) {
-		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	return read_call<pq_plan>(what, d, n_pages, [&](pq_plan &p, std::string &err) {
+	return chunk_read_call<pq_plan>(what, d, n_pages, rows, d_in, in_nbytes, d_out, out_avail, d_results,
+					[&](pq_plan &p, std::string &err) {
 		if (!pq_check(format, n_pages, rows, in_nbytes, out_avail, valid_avail, d_valid != NULL,
 			      err))
 			return false;

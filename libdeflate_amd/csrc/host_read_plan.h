@@ -1,12 +1,15 @@
 /*
  * host_read_plan.h - what the readers that take their plan from the host share:
- * the selections of the ZIP, tar and PNG readers, the BGZF ranged read and the
- * byte-shuffled chunks (host_zip.hip, host_zip_large.hip, host_tar.hip,
- * host_png*.hip, host_bgzf_read.hip, host_shuffle.hip).  The counterpart of
- * host_write_pieces.h: the refusals made before any device work, the envelope
- * of a call around its plan, the staging of the plan's columns through
- * d->bgzf and the pinned block of d->bgzf_up, and the grids of the kernels
- * that stride over entries, tiles or chunks - the writers' too.
+ * the selections of the ZIP, tar and PNG readers, the BGZF ranged read
+ * (host_zip.hip, host_zip_large.hip, host_tar.hip, host_png*.hip,
+ * host_bgzf_read.hip) and the chunk codecs - byte-shuffled chunks, TIFF
+ * segments, OpenEXR chunks, Parquet pages (host_shuffle.hip, host_tiff.hip,
+ * host_exr.hip, host_parquet.hip).  The counterpart of host_write_pieces.h:
+ * the refusals made before any device work, the envelope of a call around its
+ * plan, the staging of the plan's columns through d->bgzf and the pinned block
+ * of d->bgzf_up, the chunk codecs' inflate step and verdict launch, and the
+ * grids of the kernels that stride over entries, tiles or chunks - the
+ * writers' too.
  *
  * The object's rule lives in read_stage() alone: bgzf_up.begin() before
  * anything is reserved, and all of the call's scratch reserved before anything
@@ -15,9 +18,12 @@
 #ifndef LDA_HOST_READ_PLAN_H
 #define LDA_HOST_READ_PLAN_H
 
+#include <string.h>
 #include <algorithm>
 #include <string>
+#include <vector>
 
+#include "chunk_plan.h"
 #include "host_finder.h"
 #include "host_objects.h"
 
@@ -150,6 +156,93 @@ static inline int read_stage(struct libdeflate_decompressor *d, Lay lay, ReadSta
 static inline int read_send(struct libdeflate_decompressor *d, const ReadStage &s, hipStream_t st)
 {
 	return d->bgzf_up.send(s.up.dst, s.up.bytes, st);
+}
+
+/* ---- the chunk codecs: shuffle, TIFF, OpenEXR, Parquet (chunk_plan.h) ---- */
+
+/* read_call() behind the pointers such a call refuses */
+template <typename P, typename Plan, typename Run>
+static inline int
+chunk_read_call(const char *what, struct libdeflate_decompressor *d, size_t n, const uint64_t *rows,
+		const void *d_in, size_t in_nbytes, const void *d_out, size_t out_avail,
+		const int32_t *d_results, Plan plan, Run run)
+{
+	if (!d || (n && (!rows || !d_results)) || (!d_in && in_nbytes) || (!d_out && out_avail)) {
+		set_error("%s: NULL argument", what);
+		return LIBDEFLATE_AMD_BAD_ARG;
+	}
+	return read_call<P>(what, d, n, plan, run);
+}
+
+/* a plan's columns on the device */
+struct ChunkStage {
+	uint8_t *ws;				/* d->bgzf */
+	uint64_t *cols;
+	const uint64_t *dcol[CHUNK_DCOLS];	/* the decode batches' columns */
+	int32_t *decode;			/* and their results */
+	/* d_in and d_out; of a NULL one, whose size is 0 and which no row that
+	 * passed the checks touches, ws stands in */
+	const uint8_t *in;
+	uint8_t *out;
+};
+
+/* d->bgzf laid out as [what front(Carve &) takes: the format's rooms and work
+ * areas][the plan's columns][the decoder's results, n_dec + 1], and the columns
+ * on their way up through the pinned block in ONE copy */
+template <typename Front>
+static inline int
+chunk_stage(struct libdeflate_decompressor *d, const std::vector<uint64_t> &cols, size_t n_dec,
+	    const void *d_in, void *d_out, hipStream_t st, ChunkStage &g, Front front)
+{
+	ReadStage s;
+	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+		front(cv);
+		g.cols = cv.take<uint64_t>(cols.size());
+		g.decode = cv.take<int32_t>(n_dec + 1);
+		return ReadUp{ g.cols, cols.size() * sizeof(uint64_t) };
+	}, s));
+	memcpy(s.h, cols.data(), s.up.bytes);
+	LDA_OK_TRY(read_send(d, s, st));
+	for (size_t a = 0; a < CHUNK_DCOLS; a++)
+		g.dcol[a] = g.cols + a * n_dec;
+	g.ws = s.ws;
+	g.in = d_in ? (const uint8_t *)d_in : s.ws;
+	g.out = d_out ? (uint8_t *)d_out : s.ws;
+	return LIBDEFLATE_AMD_OK;
+}
+
+/* the scratch rows, which stand first in the columns, into `rooms`, the d_out
+ * rows behind them into d_out: one decompress batch per output base, each left
+ * out when it has no row */
+static inline int
+chunk_inflate(struct libdeflate_decompressor *d, int format, const ChunkStage &g, size_t n_ws,
+	      uint8_t *rooms, size_t n_out, hipStream_t st)
+{
+	for (int k = 0; k < 2; k++) {
+		const size_t lo = k ? n_ws : 0, cnt = k ? n_out : n_ws;
+		if (!cnt)
+			continue;
+		int rc = libdeflate_amd_decompress_batch(d, format, cnt, g.in, g.dcol[CHUNK_D_IN_OFF] + lo,
+							 g.dcol[CHUNK_D_IN_N] + lo, k ? g.out : rooms,
+							 g.dcol[CHUNK_D_OUT_OFF] + lo,
+							 g.dcol[CHUNK_D_OUT_N] + lo, g.decode + lo, NULL,
+							 NULL, st);
+		if (rc != LIBDEFLATE_AMD_OK)
+			return rc;
+	}
+	return LIBDEFLATE_AMD_OK;
+}
+
+/* the n verdict words at verd_at of the columns merged with the decoder's
+ * results into d_results; the call's last launch */
+static inline int chunk_verdicts(const ChunkStage &g, size_t n, uint64_t verd_at, int32_t *d_results,
+				 hipStream_t st)
+{
+	hipLaunchKernelGGL(lda_shuf_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+			   (uint64_t)n, (const uint64_t *)(g.cols + verd_at), (const int32_t *)g.decode,
+			   d_results);
+	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
+	return LIBDEFLATE_AMD_OK;
 }
 
 /* ---- the grids, 256 threads a workgroup ---- */

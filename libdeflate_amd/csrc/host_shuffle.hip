@@ -43,65 +43,33 @@ static int shuf_decode(struct libdeflate_decompressor *d, int format, const shuf
 		       hipStream_t st)
 {
 	DeviceCtx *ctx = device_ctx();
-	const size_t n = (size_t)p.n, n_dec = (size_t)(p.n_sd + p.n_id), n_u = (size_t)p.n_u;
+	const size_t n_u = (size_t)p.n_u;
 	uint8_t *g_area = NULL;
-	uint64_t *g_cols = NULL;
-	int32_t *g_decode = NULL;
-	ReadStage s;
-	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+	ChunkStage g;
+	LDA_OK_TRY(chunk_stage(d, p.cols, (size_t)(p.n_sd + p.n_id), d_in, d_out, st, g, [&](Carve &cv) {
 		g_area = cv.take<uint8_t>((size_t)p.scratch + 16, 256);
-		g_cols = cv.take<uint64_t>(p.cols.size());
-		g_decode = cv.take<int32_t>(n_dec + 1);
-		return ReadUp{ g_cols, p.cols.size() * sizeof(uint64_t) };
-	}, s));
-	memcpy(s.h, p.cols.data(), s.up.bytes);
-	LDA_OK_TRY(read_send(d, s, st));
-	uint8_t *ws = s.ws;
-	const uint64_t *dcol[SHUF_DCOLS], *ucol[SHUF_UCOLS];
-	for (size_t a = 0; a < SHUF_DCOLS; a++)
-		dcol[a] = g_cols + a * n_dec;
+	}));
+	const uint64_t *ucol[SHUF_UCOLS];
 	for (size_t a = 0; a < SHUF_UCOLS; a++)
-		ucol[a] = g_cols + p.u_at + a * n_u;
-	/* (NULL d_in or d_out: in_nbytes or out_avail is 0, and so is every row there) */
-	const uint8_t *in = d_in ? d_in : ws;
-	uint8_t *out = d_out ? d_out : ws;
+		ucol[a] = g.cols + p.u_at + a * n_u;
 
-	/* the scratch rows stand first in the columns, the d_out rows behind them */
-	for (int k = 0; k < 2 && (stages & SHUF_STAGE_INFLATE); k++) {
-		const size_t lo = k ? (size_t)p.n_sd : 0, cnt = (size_t)(k ? p.n_id : p.n_sd);
-		if (!cnt)
-			continue;
-		int rc = libdeflate_amd_decompress_batch(d, format, cnt, in, dcol[SHUF_D_IN_OFF] + lo,
-							 dcol[SHUF_D_IN_N] + lo, k ? out : g_area,
-							 dcol[SHUF_D_OUT_OFF] + lo,
-							 dcol[SHUF_D_OUT_N] + lo, g_decode + lo, NULL,
-							 NULL, st);
-		if (rc != LIBDEFLATE_AMD_OK)
-			return rc;
-	}
+	if (stages & SHUF_STAGE_INFLATE)
+		LDA_OK_TRY(chunk_inflate(d, format, g, (size_t)p.n_sd, g_area, (size_t)p.n_id, st));
 	if (p.tiles && (stages & SHUF_STAGE_UNSHUFFLE)) {
 		hipLaunchKernelGGL(lda_unshuffle_kernel, dim3(tile_grid(ctx, p.tiles)), dim3(256), 0, st,
 				   (uint64_t)n_u, p.tiles, ucol[SHUF_U_TILE_END], ucol[SHUF_U_SRC],
-				   ucol[SHUF_U_DST], ucol[SHUF_U_GEOM], (const uint8_t *)g_area, in, out);
+				   ucol[SHUF_U_DST], ucol[SHUF_U_GEOM], (const uint8_t *)g_area, g.in, g.out);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
-	hipLaunchKernelGGL(lda_shuf_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-			   (uint64_t)n, (const uint64_t *)(g_cols + p.verd_at),
-			   (const int32_t *)g_decode, d_results);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	return LIBDEFLATE_AMD_OK;
+	return chunk_verdicts(g, (size_t)p.n, p.verd_at, d_results, st);
 }
 
 static int shuf_call(const char *what, struct libdeflate_decompressor *d, int format, size_t n_chunks,
 		     const uint64_t *chunks, const void *d_in, size_t in_nbytes, void *d_out,
 		     size_t out_avail, int32_t *d_results, unsigned stages, void *stream)
 {
-	if (!d || (n_chunks && (!chunks || !d_results)) || (!d_in && in_nbytes) ||
-	    (!d_out && out_avail)) {
-		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	return read_call<shuf_read_plan>(what, d, n_chunks, [&](shuf_read_plan &p, std::string &err) {
+	return chunk_read_call<shuf_read_plan>(what, d, n_chunks, chunks, d_in, in_nbytes, d_out, out_avail,
+					       d_results, [&](shuf_read_plan &p, std::string &err) {
 		if (!shuf_check(format, n_chunks, chunks, true, in_nbytes, out_avail, -1, err))
 			return false;
 		shuf_read_plan_build(n_chunks, chunks, p);

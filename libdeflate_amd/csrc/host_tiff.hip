@@ -42,70 +42,41 @@ static int tiff_decode(struct libdeflate_decompressor *d, const tiff_read_plan &
 	DeviceCtx *ctx = device_ctx();
 	const size_t n = (size_t)p.n, n_k = (size_t)p.n_k, n_g = (size_t)p.n_g;
 	uint8_t *g_area = NULL;
-	uint64_t *g_cols = NULL;
-	int32_t *g_decode = NULL;
-	ReadStage s;
-	LDA_OK_TRY(read_stage(d, [&](Carve &cv) {
+	ChunkStage g;
+	LDA_OK_TRY(chunk_stage(d, p.cols, n, d_in, d_out, st, g, [&](Carve &cv) {
 		/* (128 to spare: the scan reads a row's tail as a whole piece of up to 64 bytes) */
 		g_area = cv.take<uint8_t>((size_t)p.scratch + 128, 256);
-		g_cols = cv.take<uint64_t>(p.cols.size());
-		g_decode = cv.take<int32_t>(n + 1);
-		return ReadUp{ g_cols, p.cols.size() * sizeof(uint64_t) };
-	}, s));
-	memcpy(s.h, p.cols.data(), s.up.bytes);
-	LDA_OK_TRY(read_send(d, s, st));
-	uint8_t *ws = s.ws;
-	const uint64_t *dcol[TIFF_DCOLS], *gcol[TIFF_GCOLS];
-	for (size_t a = 0; a < TIFF_DCOLS; a++)
-		dcol[a] = g_cols + a * n;
+	}));
+	const uint64_t *gcol[TIFF_GCOLS];
 	for (size_t a = 0; a < TIFF_GCOLS; a++)
-		gcol[a] = g_cols + p.g_at + a * n_g;
-	/* (NULL d_in: in_nbytes is 0, and so is every stored size) */
-	const uint8_t *in = d_in ? d_in : ws;
+		gcol[a] = g.cols + p.g_at + a * n_g;
 
-	/* the scratch rows stand first in the columns, the d_out rows behind them */
-	for (int k = 0; k < 2 && (stages & TIFF_STAGE_INFLATE); k++) {
-		const size_t lo = k ? (size_t)p.n_ws : 0, cnt = (size_t)(k ? p.n_direct : p.n_ws);
-		if (!cnt)
-			continue;
-		int rc = libdeflate_amd_decompress_batch(d, LIBDEFLATE_AMD_ZLIB, cnt, in,
-							 dcol[TIFF_D_IN_OFF] + lo, dcol[TIFF_D_IN_N] + lo,
-							 k ? d_out : g_area, dcol[TIFF_D_OUT_OFF] + lo,
-							 dcol[TIFF_D_OUT_N] + lo, g_decode + lo, NULL,
-							 NULL, st);
-		if (rc != LIBDEFLATE_AMD_OK)
-			return rc;
-	}
+	/* (every row has pixels inside out_avail: d_out is not NULL here, and g.out is d_out) */
+	if (stages & TIFF_STAGE_INFLATE)
+		LDA_OK_TRY(chunk_inflate(d, LIBDEFLATE_AMD_ZLIB, g, (size_t)p.n_ws, g_area,
+					 (size_t)p.n_direct, st));
 	if (p.quads && (stages & TIFF_STAGE_UNPREDICT)) {
 		hipLaunchKernelGGL(lda_tiff_unpredict_kernel, dim3(tile_grid(ctx, (p.quads + 63) / 64)),
 				   dim3(256), 0, st, (uint64_t)n_k, p.quads,
-				   (const uint64_t *)(g_cols + p.k_at), g_area, d_out);
+				   (const uint64_t *)(g.cols + p.k_at), g_area, g.out);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
 	if (p.gtiles && (stages & TIFF_STAGE_UNPREDICT)) {
 		hipLaunchKernelGGL(lda_tiff_gather_kernel, dim3(tile_grid(ctx, p.gtiles)),
 				   dim3(256), 0, st, (uint64_t)n_g, p.gtiles, gcol[TIFF_G_TILE_END],
 				   gcol[TIFF_G_SRC], gcol[TIFF_G_DST], gcol[TIFF_G_DPITCH],
-				   gcol[TIFF_G_GEOM], gcol[TIFF_G_PLANE], (const uint8_t *)g_area, d_out);
+				   gcol[TIFF_G_GEOM], gcol[TIFF_G_PLANE], (const uint8_t *)g_area, g.out);
 		LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
 	}
-	hipLaunchKernelGGL(lda_shuf_final_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-			   (uint64_t)n, (const uint64_t *)(g_cols + p.verd_at),
-			   (const int32_t *)g_decode, d_results);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	return LIBDEFLATE_AMD_OK;
+	return chunk_verdicts(g, n, p.verd_at, d_results, st);
 }
 
 static int tiff_call(const char *what, struct libdeflate_decompressor *d, size_t n_segments,
 		     const uint64_t *rows, const void *d_in, size_t in_nbytes, void *d_out,
 		     size_t out_avail, int32_t *d_results, unsigned stages, void *stream)
 {
-	if (!d || (n_segments && (!rows || !d_results)) || (!d_in && in_nbytes) ||
-	    (!d_out && out_avail)) {
-		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	return read_call<tiff_read_plan>(what, d, n_segments, [&](tiff_read_plan &p, std::string &err) {
+	return chunk_read_call<tiff_read_plan>(what, d, n_segments, rows, d_in, in_nbytes, d_out, out_avail,
+					       d_results, [&](tiff_read_plan &p, std::string &err) {
 		if (!tiff_check(n_segments, rows, true, in_nbytes, out_avail, -1, err))
 			return false;
 		tiff_read_plan_build(n_segments, rows, p);

@@ -32,92 +32,37 @@ libdeflate_amd_tiff_encode_bound(struct libdeflate_compressor *c, size_t n_segme
 				 const uint64_t *rows)
 {
 	(void)c;	/* (no level has another bound: libdeflate_zlib_compress_bound()) */
-	if (n_segments && !rows) {
-		set_error("tiff_encode_bound: NULL argument");
-		return 0;
-	}
-	return (size_t)tiff_bound(n_segments, rows);
+	return chunkw_bound_call("tiff_encode_bound", n_segments, rows,
+				 [&] { return tiff_bound(n_segments, rows); });
 }
 
-struct TiffwScratch : PiecesScratch {
-	uint64_t *ecols, *csize;
-	uint32_t *sum, *sums;
-	uint8_t *rooms;
-	size_t bytes;
-};
-
-static TiffwScratch tiffw_scratch(void *base, const tiff_write_plan &p)
-{
-	TiffwScratch s;
-	Carve c(base);
-	const size_t n = (size_t)p.n, np = (size_t)p.np;
-
-	s.ecols = c.take<uint64_t>(p.ecols.size());
-	pieces_carve(c, p, n, 0, s);
-	s.csize = c.take<uint64_t>(n);
-	s.sum = c.take<uint32_t>(n);
-	s.sums = c.take<uint32_t>(np);
-	s.rooms = c.take<uint8_t>((size_t)p.rooms_bytes + 64, 256);
-	s.bytes = c.at + 16;
-	return s;
-}
-
+/* (p.n is not 0: the call has returned for no segments) */
 static int tiffw_enqueue(struct libdeflate_compressor *c, const tiff_write_plan &p, const uint8_t *d_in,
 			 uint8_t *d_out, uint64_t out_avail, uint64_t *d_result, uint64_t *d_index,
 			 hipStream_t st)
 {
 	DeviceCtx *ctx = device_ctx();
-	if (!ctx)
-		return LIBDEFLATE_AMD_NO_DEVICE;
-	const size_t n = (size_t)p.n, np = (size_t)p.np;
-	const TiffwScratch sz = tiffw_scratch(NULL, p);
+	const size_t n = (size_t)p.n;
 	const std::vector<zipw_launch> launches = zipw_launches(p);
-	uint8_t *ws, *h;
+	ChunkwScratch s;
 
-	LDA_OK_TRY(pieces_reserve(c, launches, sz.bytes, sz.up_bytes, &ws, &h));
-	const TiffwScratch s = tiffw_scratch(ws, p), hs = tiffw_scratch(h, p);
-	if (sz.up_bytes && !p.ecols.empty())
-		memcpy(hs.ecols, p.ecols.data(), p.ecols.size() * 8);
-	LDA_OK_TRY(pieces_upload(c, hs, p, ws, st));
-	const uint64_t *ecol[TIFFW_ECOLS], *const *pcol = s.pcol;
-	for (size_t a = 0; a < TIFFW_ECOLS; a++)
-		ecol[a] = s.ecols + a * n;
-
+	LDA_OK_TRY(chunkw_begin(c, p, launches, st, s));
 	if (p.tiles)
 		hipLaunchKernelGGL(lda_tiff_predict_kernel, dim3(tile_grid(ctx, p.tiles)), dim3(256), 0, st,
 				   (uint64_t)n, p.tiles, (const uint64_t *)s.ecols, d_in, s.rooms);
-	LDA_OK_TRY(libdeflate_amd_adler32_batch(np, s.rooms, pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
-						NULL, s.sums, st));
-	LDA_OK_TRY(pieces_compress(c, s, launches, s.rooms, st));
-	const unsigned grid = wave_grid(ctx, n);
-	if (n)
-		hipLaunchKernelGGL(lda_shufw_chunk_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
-				   (int)LIBDEFLATE_AMD_ZLIB, ecol[TIFFW_E_FIRST], ecol[TIFFW_E_COUNT],
-				   ecol[TIFFW_E_USIZE], pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N],
-				   (const uint64_t *)s.out_n, (const uint32_t *)s.sums, s.csize, s.sum,
-				   s.sizes);
-	/* (of no segments, the total alone: 0 bytes) */
-	const uint64_t *total_at = s.bsum + scan_enqueue(st, n, s.sizes, s.offs, s.bsum);
-	if (n) {
-		/* (its index rows are the shuffle calls': ours come from lda_tiffw_index_kernel) */
-		hipLaunchKernelGGL(lda_shufw_place_kernel, dim3(grid), dim3(256), 0, st, (uint64_t)n,
-				   (int)LIBDEFLATE_AMD_ZLIB, c->level, out_avail, (const uint64_t *)s.ecols,
-				   pcol[ZIPW_P_PC_OFF], pcol[ZIPW_P_PC_N], pcol[ZIPW_P_SLOT_OFF],
-				   (const uint64_t *)s.out_n, (const uint64_t *)s.csize,
-				   (const uint32_t *)s.sum, (const uint64_t *)s.offs,
-				   (const uint64_t *)s.bsum, d_out, s.cp_src, s.cp_dst, s.cp_len,
-				   (uint64_t *)NULL);
-		if (d_index)
-			hipLaunchKernelGGL(lda_tiffw_index_kernel, dim3((unsigned)((n + 255) / 256)),
-					   dim3(256), 0, st, (uint64_t)n, out_avail,
-					   (const uint64_t *)s.ecols, (const uint64_t *)s.csize,
-					   (const uint64_t *)s.offs, (const uint64_t *)s.bsum, d_index);
-	}
-	pieces_copy(ctx, s, np, total_at, out_avail, 0, d_in, d_out, st);
-	hipLaunchKernelGGL(lda_shufw_final_kernel, dim3(1), dim3(64), 0, st, (uint64_t)n, p.raw_total,
-			   out_avail, total_at, d_result);
-	LDA_HIP_TRY(hipGetLastError(), LIBDEFLATE_AMD_NO_DEVICE);
-	return LIBDEFLATE_AMD_OK;
+	LDA_OK_TRY(chunkw_compress(c, LIBDEFLATE_AMD_ZLIB, p, s, launches, s.rooms, st));
+	chunkw_sizes(ctx, LIBDEFLATE_AMD_ZLIB, p, s, st);
+	const uint64_t *total_at = chunkw_scan(p, s, st);
+	/* d_index NULL: the place kernel's index rows are the shuffle calls'; ours
+	 * come from lda_tiffw_index_kernel */
+	chunkw_place(ctx, LIBDEFLATE_AMD_ZLIB, c->level, p, s, out_avail, d_out, NULL, st);
+	if (d_index)
+		hipLaunchKernelGGL(lda_tiffw_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+				   st, (uint64_t)n, out_avail, (const uint64_t *)s.ecols,
+				   (const uint64_t *)s.csize, (const uint64_t *)s.offs,
+				   (const uint64_t *)s.bsum, d_index);
+	/* (copy_src is d_in, as the shuffle writer's) */
+	return chunkw_finish(ctx, p, s, total_at, out_avail, d_in, d_out, d_result, st);
 }
 
 extern "C" LIBDEFLATEAPI int
@@ -125,27 +70,14 @@ libdeflate_amd_tiff_encode_batch(struct libdeflate_compressor *c, size_t n_segme
 				 const uint64_t *rows, const void *d_in, size_t in_avail, void *d_out,
 				 size_t out_avail, uint64_t *d_result, uint64_t *d_index, void *stream)
 {
-	const char *what = "tiff_encode_batch";
-
-	if (!c || !d_out || !d_result || (!d_in && in_avail) || (n_segments && !rows)) {
-		set_error("%s: NULL argument", what);
-		return LIBDEFLATE_AMD_BAD_ARG;
-	}
-	return no_unwind(what, (int)LIBDEFLATE_AMD_OOM, [&]() -> int {
-		std::string err;
-		if (!tiff_check(n_segments, rows, false, 0, in_avail, c->level, err)) {
-			set_error("%s: %s", what, err.c_str());
-			return LIBDEFLATE_AMD_BAD_ARG;
-		}
-		if (n_segments == 0)	/* nothing to do: d_result is not written either */
-			return LIBDEFLATE_AMD_OK;
-		DeviceGuard on(c->device);
-		if (!on.ok() || !device_ctx())
-			return LIBDEFLATE_AMD_NO_DEVICE;
-		/* (level 0 too: its stored blocks are the compress kernel's) */
-		const zipw_params pr = pieces_params(c, false);
-		tiff_write_plan p;
+	/* empty_returns true: of no segments nothing is queued, and d_result is not
+	 * written either */
+	return chunkw_call<tiff_write_plan>("tiff_encode_batch", c, n_segments, rows, d_in, in_avail, d_out,
+					    d_result, true, [&](std::string &err) {
+		return tiff_check(n_segments, rows, false, 0, in_avail, c->level, err);
+	}, [&](const zipw_params &pr, tiff_write_plan &p) {
 		tiff_write_plan_build(pr, n_segments, rows, p);
+	}, [&](const tiff_write_plan &p) {
 		return tiffw_enqueue(c, p, (const uint8_t *)d_in, (uint8_t *)d_out, out_avail, d_result,
 				     d_index, (hipStream_t)stream);
 	});

@@ -643,6 +643,9 @@ extern "C" __global__ void
 lda_shuffle_kernel(uint64_t n_u, uint64_t n_tiles, const uint64_t *u_tile_end,
 		   const uint64_t *u_src, const uint64_t *u_dst, const uint64_t *u_geom,
 		   const uint8_t *in, uint8_t *rooms);
+/* first, count, usize: columns 0 - 2 of every chunk writer's ecols, CHUNKW_E_FIRST, _COUNT and
+ * _USIZE of chunk_plan.h - what the comments in shuffle_kernels.hip and exr_kernels.hip still
+ * call SHUFW_E_FIRST, _COUNT, _USIZE and EXRW_E_USIZE */
 extern "C" __global__ void
 lda_shufw_chunk_kernel(uint64_t n, int format, const uint64_t *first, const uint64_t *count,
 		       const uint64_t *usize, const uint64_t *pc_off, const uint64_t *pc_n,

@@ -35,6 +35,8 @@
 #include <string>
 #include <vector>
 
+#include "chunk_plan.h"
+
 namespace lda {
 
 enum {
@@ -49,8 +51,6 @@ enum {
 	/* the kinds and encodings */
 	PQ_DATA_V1 = 0, PQ_DICT = 2, PQ_DATA_V2 = 3,
 	PQ_PLAIN = 0, PQ_PLAIN_DICTIONARY = 2, PQ_RLE_DICTIONARY = 8,
-	/* the decode batch's columns, n_z words each */
-	PQ_D_IN_OFF = 0, PQ_D_IN_N, PQ_D_OUT_OFF, PQ_D_OUT_N, PQ_DCOLS,
 	/* the data pages' columns, n_u words each */
 	PQ_U_SLOT_END = 0,	/* the slots of this page and all before it */
 	PQ_U_SEC,		/* the section: in the rooms, or PQ_IN_PLACE | its offset in d_in */
@@ -75,8 +75,6 @@ enum {
 #define PQ_F_SKIP ((uint64_t)1 << 31)		/* LDA_PQ_F_SKIP: the dictionary is too short for its entries */
 #define PQ_V_IS_DICT ((uint64_t)1 << 63)	/* LDA_PQ_V_IS_DICT */
 #define PQ_SIZE_MAX 0x7FFFFFFFull		/* Parquet's sizes and counts are int32 */
-
-static inline uint64_t pq_align16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
 
 /* a row taken apart */
 struct pq_page {
@@ -158,27 +156,13 @@ static inline bool
 pq_check(int format, uint64_t n, const uint64_t *rows, uint64_t in_nbytes, uint64_t out_avail,
 	 uint64_t valid_avail, bool have_valid, std::string &err)
 {
-	char msg[200];
-
 	if (format < 0 || format > 2) {
-		snprintf(msg, sizeof(msg), "format %d is not DEFLATE, ZLIB or GZIP", format);
-		err = msg;
+		err = "format " + std::to_string(format) + " is not DEFLATE, ZLIB or GZIP";
 		return false;
 	}
-	if (n > PQ_MAX_PAGES) {
-		snprintf(msg, sizeof(msg), "n_pages %llu above 2^28", (unsigned long long)n);
-		err = msg;
-		return false;
-	}
-	for (uint64_t r = 0; r < n; r++) {
-		const char *why = pq_row_why(rows, r, in_nbytes, out_avail, valid_avail, have_valid);
-		if (why) {
-			snprintf(msg, sizeof(msg), "row %llu: %s", (unsigned long long)r, why);
-			err = msg;
-			return false;
-		}
-	}
-	return true;
+	return chunk_check("n_pages", n, PQ_MAX_PAGES, [&](uint64_t r) {
+		return pq_row_why(rows, r, in_nbytes, out_avail, valid_avail, have_valid);
+	}, err);
 }
 
 /* the most records of the two run lists of a data page */
@@ -205,7 +189,7 @@ struct pq_plan {
 	uint64_t slots, tiles;	/* of all data pages */
 	uint64_t room_bytes;	/* the area of the rooms */
 	uint64_t run_records;	/* the run area */
-	/* what goes up: [PQ_DCOLS x n_z] at 0, [PQ_UCOLS x n_u] at u_at, [PQ_VCOLS x n]
+	/* what goes up: [CHUNK_DCOLS x n_z] at 0, [PQ_UCOLS x n_u] at u_at, [PQ_VCOLS x n]
 	 * at v_at */
 	uint64_t u_at, v_at;
 	std::vector<uint64_t> cols;
@@ -214,24 +198,24 @@ struct pq_plan {
 /* the rows have passed pq_check() */
 static inline void pq_plan_build(uint64_t n, const uint64_t *rows, pq_plan &p)
 {
-	std::vector<uint64_t> d[PQ_DCOLS], u[PQ_UCOLS], v[PQ_VCOLS];
+	std::vector<uint64_t> u[PQ_UCOLS], v[PQ_VCOLS];
 	std::vector<uint64_t> sec((size_t)n);	/* every row's section, as PQ_U_SEC */
+	chunk_rooms rooms;
 
 	p.n = n;
-	p.slots = p.room_bytes = p.run_records = 0;
+	p.n_z = p.slots = p.run_records = 0;
+	for (uint64_t r = 0; r < n; r++)
+		p.n_z += pq_page_of(rows + PQ_WORDS * r).compressed;
+	chunk_decode_cols d(p.cols, p.n_z);
 	for (uint64_t r = 0; r < n; r++) {
 		const uint64_t *w = rows + PQ_WORDS * r;
 		const pq_page s = pq_page_of(w);
 		uint64_t z = 0;
 
 		if (s.compressed) {
-			d[PQ_D_IN_OFF].push_back(s.off + s.def_len);
-			d[PQ_D_IN_N].push_back(s.csize - s.def_len);
-			d[PQ_D_OUT_OFF].push_back(p.room_bytes);
-			d[PQ_D_OUT_N].push_back(s.usize - s.def_len);
-			z = d[0].size();
-			sec[(size_t)r] = p.room_bytes;
-			p.room_bytes += pq_align16(s.usize - s.def_len);
+			sec[(size_t)r] = rooms.take(s.usize - s.def_len);
+			z = 1 + d.add(false, s.off + s.def_len, s.csize - s.def_len, sec[(size_t)r],
+				      s.usize - s.def_len);
 		} else {
 			sec[(size_t)r] = PQ_IN_PLACE | (s.off + s.def_len);
 		}
@@ -270,18 +254,11 @@ static inline void pq_plan_build(uint64_t n, const uint64_t *rows, pq_plan &p)
 		u[PQ_U_ICAP].push_back(pq_index_cap(s));
 		p.run_records += pq_index_cap(s);
 	}
-	p.n_z = d[0].size();
 	p.n_u = u[0].size();
 	p.tiles = (p.slots + PQ_TILE - 1) / PQ_TILE;
-	p.cols.clear();
-	for (size_t a = 0; a < PQ_DCOLS; a++)
-		p.cols.insert(p.cols.end(), d[a].begin(), d[a].end());
-	p.u_at = p.cols.size();
-	for (size_t a = 0; a < PQ_UCOLS; a++)
-		p.cols.insert(p.cols.end(), u[a].begin(), u[a].end());
-	p.v_at = p.cols.size();
-	for (size_t a = 0; a < PQ_VCOLS; a++)
-		p.cols.insert(p.cols.end(), v[a].begin(), v[a].end());
+	p.room_bytes = rooms.bytes;
+	p.u_at = chunk_append(p.cols, u, PQ_UCOLS);
+	p.v_at = chunk_append(p.cols, v, PQ_VCOLS);
 }
 
 } /* namespace lda */

@@ -37,7 +37,7 @@
 #include <string>
 #include <vector>
 
-#include "write_pieces_plan.h"
+#include "chunk_plan.h"
 
 namespace lda {
 
@@ -51,23 +51,19 @@ enum {
 	SHUF_GEN_BYTES = 16384,	/* LDA_SHUF_GEN_BYTES: about the bytes of a tile, any other es */
 	/* a row's words */
 	SHUF_W_STORED_OFF = 0, SHUF_W_STORED_N, SHUF_W_RAW_OFF, SHUF_W_RAW_N, SHUF_W_ES, SHUF_W_MASK,
-	/* the decode batches' columns, n_dec words each */
-	SHUF_D_IN_OFF = 0, SHUF_D_IN_N, SHUF_D_OUT_OFF, SHUF_D_OUT_N, SHUF_DCOLS,
 	/* the transpose kernels' columns, n_u words each */
 	SHUF_U_TILE_END = 0,	/* the tiles of this row and all before it */
 	SHUF_U_SRC,		/* where the kernel reads, SHUF_SRC_ALT: from the second base */
 	SHUF_U_DST,
 	SHUF_U_GEOM,		/* the raw size | es << 32 */
 	SHUF_UCOLS,
-	/* the writer's per-chunk columns, n words each */
-	SHUFW_E_FIRST = 0, SHUFW_E_COUNT, SHUFW_E_USIZE, SHUFW_E_ES, SHUFW_E_MASK, SHUFW_E_RAW_OFF,
+	/* the writer's per-chunk columns, n words each, behind CHUNKW_E_USIZE */
+	SHUFW_E_ES = CHUNKW_E_USIZE + 1, SHUFW_E_MASK, SHUFW_E_RAW_OFF,
 	SHUFW_ECOLS
 };
 #define SHUF_MAX_CHUNKS ((uint64_t)1 << 28)
 #define SHUF_SRC_ALT ((uint64_t)1 << 63)	/* LDA_SHUF_SRC_ALT */
 #define SHUF_VERD_OWN ((uint64_t)1 << 63)	/* LDA_SHUF_VERD_OWN: the low bits are the verdict */
-
-static inline uint64_t shuf_align16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
 
 /* is es one of the sizes the kernels transpose in registers? */
 static inline bool shuf_reg_es(uint64_t es) { return es == 1 || es == 2 || es == 4 || es == 8; }
@@ -125,74 +121,38 @@ static inline bool
 shuf_check(int format, uint64_t n, const uint64_t *rows, bool reader, uint64_t stored_avail,
 	   uint64_t raw_avail, int level, std::string &err)
 {
-	char msg[200];
-
 	if (format < 0 || format > 2) {
-		snprintf(msg, sizeof(msg), "unknown format %d", format);
-		err = msg;
+		err = "unknown format " + std::to_string(format);
 		return false;
 	}
-	if (n > SHUF_MAX_CHUNKS) {
-		snprintf(msg, sizeof(msg), "n_chunks %llu above 2^28", (unsigned long long)n);
-		err = msg;
-		return false;
-	}
-	for (uint64_t r = 0; r < n; r++) {
-		const char *why = shuf_row_why(rows + SHUF_WORDS * r, reader, stored_avail, raw_avail,
-					       level);
-		if (why) {
-			snprintf(msg, sizeof(msg), "row %llu: %s", (unsigned long long)r, why);
-			err = msg;
-			return false;
-		}
-	}
-	return true;
-}
-
-/* libdeflate_<format>_compress_bound(len): 5 bytes per 5000-byte block */
-static inline uint64_t shuf_stream_bound(int format, uint64_t len)
-{
-	uint64_t blocks = (len + 4999) / 5000;
-	if (blocks < 1)
-		blocks = 1;
-	return 5 * blocks + len + (format == 1 ? 6 : format == 2 ? 18 : 0);
+	return chunk_check("n_chunks", n, SHUF_MAX_CHUNKS, [&](uint64_t r) {
+		return shuf_row_why(rows + SHUF_WORDS * r, reader, stored_avail, raw_avail, level);
+	}, err);
 }
 
 /* the sum of the streams' bounds; 0 for rows the writer refuses */
 static inline uint64_t shuf_bound(int format, uint64_t n, const uint64_t *rows)
 {
-	uint64_t sum = 0;
-	if (format < 0 || format > 2 || n > SHUF_MAX_CHUNKS)
+	if (format < 0 || format > 2)
 		return 0;
-	for (uint64_t r = 0; r < n; r++) {
-		if (shuf_row_why(rows + SHUF_WORDS * r, false, 0, ~(uint64_t)0, -1))
-			return 0;
-		sum += shuf_stream_bound(format, rows[SHUF_WORDS * r + SHUF_W_RAW_N]);
-	}
-	return sum;
+	return chunk_bound(n, SHUF_MAX_CHUNKS, [&](uint64_t r) {
+		return shuf_row_why(rows + SHUF_WORDS * r, false, 0, ~(uint64_t)0, -1);
+	}, [&](uint64_t r) { return chunk_stream_bound(format, rows[SHUF_WORDS * r + SHUF_W_RAW_N]); });
 }
 
-/* the kernels' rows: one call per row in order, then nothing */
+/* the kernels' rows: one call per row in order, then chunk_append() */
 struct shuf_kernel_rows {
 	uint64_t n_u = 0, tiles = 0;
-	std::vector<uint64_t> src, dst, geom, tile_end;
+	std::vector<uint64_t> col[SHUF_UCOLS];
 
 	void add(uint64_t s, uint64_t d, uint64_t n, uint64_t es)
 	{
 		tiles += shuf_tiles(n, es);
-		tile_end.push_back(tiles);
-		src.push_back(s);
-		dst.push_back(d);
-		geom.push_back(n | es << 32);
+		col[SHUF_U_TILE_END].push_back(tiles);
+		col[SHUF_U_SRC].push_back(s);
+		col[SHUF_U_DST].push_back(d);
+		col[SHUF_U_GEOM].push_back(n | es << 32);
 		n_u++;
-	}
-	/* SHUF_UCOLS x n_u words behind what cols holds */
-	void append_to(std::vector<uint64_t> &cols) const
-	{
-		cols.insert(cols.end(), tile_end.begin(), tile_end.end());
-		cols.insert(cols.end(), src.begin(), src.end());
-		cols.insert(cols.end(), dst.begin(), dst.end());
-		cols.insert(cols.end(), geom.begin(), geom.end());
 	}
 };
 
@@ -202,7 +162,7 @@ struct shuf_read_plan {
 	uint64_t n_id;		/* deflated, identity: decoded into d_out */
 	uint64_t n_u, tiles;	/* the unshuffle kernel's rows and tiles */
 	uint64_t scratch;	/* bytes of the scratch rooms */
-	/* what goes up: [SHUF_DCOLS x (n_sd + n_id)] at 0, [SHUF_UCOLS x n_u] at
+	/* what goes up: [CHUNK_DCOLS x (n_sd + n_id)] at 0, [SHUF_UCOLS x n_u] at
 	 * u_at, [n verdict words] at verd_at */
 	uint64_t u_at, verd_at;
 	std::vector<uint64_t> cols;
@@ -212,7 +172,7 @@ struct shuf_read_plan {
 static inline void shuf_read_plan_build(uint64_t n, const uint64_t *rows, shuf_read_plan &p)
 {
 	p.n = n;
-	p.n_sd = p.n_id = p.scratch = 0;
+	p.n_sd = p.n_id = 0;
 	for (uint64_t r = 0; r < n; r++) {
 		const uint64_t *w = rows + SHUF_WORDS * r;
 		if (w[SHUF_W_MASK] & SHUF_NO_DEFLATE)
@@ -222,17 +182,10 @@ static inline void shuf_read_plan_build(uint64_t n, const uint64_t *rows, shuf_r
 		else
 			p.n_sd++;
 	}
-	const uint64_t n_dec = p.n_sd + p.n_id;
 	std::vector<uint64_t> verd((size_t)n);
+	chunk_decode_cols d(p.cols, p.n_sd, p.n_id);
+	chunk_rooms rooms;
 	shuf_kernel_rows u;
-	uint64_t sd = 0, id = p.n_sd;
-	p.cols.assign((size_t)(SHUF_DCOLS * n_dec), 0);
-	auto dec_row = [&](uint64_t at, const uint64_t *w, uint64_t out_off) {
-		p.cols[(size_t)(SHUF_D_IN_OFF * n_dec + at)] = w[SHUF_W_STORED_OFF];
-		p.cols[(size_t)(SHUF_D_IN_N * n_dec + at)] = w[SHUF_W_STORED_N];
-		p.cols[(size_t)(SHUF_D_OUT_OFF * n_dec + at)] = out_off;
-		p.cols[(size_t)(SHUF_D_OUT_N * n_dec + at)] = w[SHUF_W_RAW_N];
-	};
 	for (uint64_t r = 0; r < n; r++) {
 		const uint64_t *w = rows + SHUF_WORDS * r;
 		const uint64_t raw = w[SHUF_W_RAW_N], es = w[SHUF_W_ES];
@@ -244,61 +197,47 @@ static inline void shuf_read_plan_build(uint64_t n, const uint64_t *rows, shuf_r
 				u.add(w[SHUF_W_STORED_OFF] | SHUF_SRC_ALT, w[SHUF_W_RAW_OFF], raw,
 				      ident ? 1 : es);
 		} else if (ident) {
-			verd[(size_t)r] = id;
-			dec_row(id++, w, w[SHUF_W_RAW_OFF]);
+			verd[(size_t)r] = d.add(true, w[SHUF_W_STORED_OFF], w[SHUF_W_STORED_N],
+						w[SHUF_W_RAW_OFF], raw);
 		} else {
-			verd[(size_t)r] = sd;
-			dec_row(sd++, w, p.scratch);
-			u.add(p.scratch, w[SHUF_W_RAW_OFF], raw, es);
-			p.scratch += shuf_align16(raw);
+			const uint64_t room = rooms.take(raw);
+			verd[(size_t)r] = d.add(false, w[SHUF_W_STORED_OFF], w[SHUF_W_STORED_N], room, raw);
+			u.add(room, w[SHUF_W_RAW_OFF], raw, es);
 		}
 	}
 	p.n_u = u.n_u;
 	p.tiles = u.tiles;
-	p.u_at = p.cols.size();
-	u.append_to(p.cols);
-	p.verd_at = p.cols.size();
-	p.cols.insert(p.cols.end(), verd.begin(), verd.end());
+	p.scratch = rooms.bytes;
+	p.u_at = chunk_append(p.cols, u.col, SHUF_UCOLS);
+	p.verd_at = chunk_append(p.cols, &verd);
 }
 
-struct shuf_write_plan : zipw_pieces {
-	uint64_t n, raw_total;
+struct shuf_write_plan : chunk_write_plan {
 	uint64_t n_u, tiles;	/* the shuffle kernel's rows and tiles */
-	uint64_t rooms_bytes;	/* the rooms of the shuffled chunks */
-	/* what goes up in front of the pieces: [SHUFW_ECOLS x n][SHUF_UCOLS x n_u] */
-	std::vector<uint64_t> ecols;
+	/* ecols: [SHUFW_ECOLS x n][SHUF_UCOLS x n_u] */
 };
 
 /* the rows have passed shuf_check(); pr.store is false whatever the level */
 static inline void
 shuf_write_plan_build(const zipw_params &pr, uint64_t n, const uint64_t *rows, shuf_write_plan &p)
 {
-	std::vector<uint64_t> room((size_t)n), size((size_t)n);
+	chunk_write_rows e(p, n, SHUFW_ECOLS);
 	shuf_kernel_rows u;
 
-	p.n = n;
-	p.raw_total = p.rooms_bytes = 0;
-	p.ecols.assign((size_t)(SHUFW_ECOLS * n), 0);
 	for (uint64_t k = 0; k < n; k++) {
 		const uint64_t *w = rows + SHUF_WORDS * k;
 		const uint64_t raw = w[SHUF_W_RAW_N], es = w[SHUF_W_ES];
-		room[(size_t)k] = p.rooms_bytes;
-		size[(size_t)k] = raw;
+		const uint64_t room = e.add(raw, raw);
 		if (raw)
-			u.add(w[SHUF_W_RAW_OFF], p.rooms_bytes, raw,
-			      shuf_identity(raw, es, w[SHUF_W_MASK]) ? 1 : es);
-		p.rooms_bytes += shuf_align16(raw);
-		p.raw_total += raw;
-		p.ecols[(size_t)(SHUFW_E_USIZE * n + k)] = raw;
+			u.add(w[SHUF_W_RAW_OFF], room, raw, shuf_identity(raw, es, w[SHUF_W_MASK]) ? 1 : es);
 		p.ecols[(size_t)(SHUFW_E_ES * n + k)] = es;
 		p.ecols[(size_t)(SHUFW_E_MASK * n + k)] = w[SHUF_W_MASK];
 		p.ecols[(size_t)(SHUFW_E_RAW_OFF * n + k)] = w[SHUF_W_RAW_OFF];
 	}
 	p.n_u = u.n_u;
 	p.tiles = u.tiles;
-	zipw_cut_pieces(pr, n, room.data(), size.data(), p.ecols.data() + SHUFW_E_FIRST * n,
-			p.ecols.data() + SHUFW_E_COUNT * n, p);
-	u.append_to(p.ecols);
+	e.cut(pr);
+	chunk_append(p.ecols, u.col, SHUF_UCOLS);
 }
 
 } /* namespace lda */

@@ -44,7 +44,7 @@
 #include <string>
 #include <vector>
 
-#include "write_pieces_plan.h"
+#include "chunk_plan.h"
 
 namespace lda {
 
@@ -56,8 +56,6 @@ enum {
 	/* a row's words */
 	TIFF_W_STORED_OFF = 0, TIFF_W_STORED_N, TIFF_W_RAW_OFF, TIFF_W_PITCH, TIFF_W_CODED,
 	TIFF_W_KEPT, TIFF_W_FMT, TIFF_W_RESERVED,
-	/* the decode batches' columns, n_dec words each */
-	TIFF_D_IN_OFF = 0, TIFF_D_IN_N, TIFF_D_OUT_OFF, TIFF_D_OUT_N, TIFF_DCOLS,
 	/* the unpredict kernel's columns, n_k words each */
 	TIFF_K_QUAD_END = 0,	/* the quads of this scan and all before it */
 	TIFF_K_SRC,		/* where the first row is read, in the scratch */
@@ -75,17 +73,14 @@ enum {
 	TIFF_G_PLANE,		/* coded samples of a row - the planes' distance; the rows' is bps
 				 * times it - | the items << 32: kept_rows * ceil(kept samples / 4) */
 	TIFF_GCOLS,
-	/* the writer's per-segment columns, n words each: the first three are
-	 * what lda_shufw_chunk_kernel and lda_shufw_place_kernel read */
-	TIFFW_E_FIRST = 0, TIFFW_E_COUNT, TIFFW_E_USIZE, TIFFW_E_RAW_OFF, TIFFW_E_PITCH,
-	TIFFW_E_CODED, TIFFW_E_KEPT, TIFFW_E_FMT, TIFFW_E_ROOM, TIFFW_E_TILE_END,
+	/* the writer's per-segment columns, n words each, behind CHUNKW_E_USIZE */
+	TIFFW_E_RAW_OFF = CHUNKW_E_USIZE + 1, TIFFW_E_PITCH, TIFFW_E_CODED, TIFFW_E_KEPT, TIFFW_E_FMT,
+	TIFFW_E_ROOM, TIFFW_E_TILE_END,
 	TIFFW_ECOLS
 };
 #define TIFF_MAX_SEGMENTS ((uint64_t)1 << 28)
 #define TIFF_DST_WS ((uint64_t)1 << 63)	/* LDA_TIFF_DST_WS */
 #define TIFF_PIECE_MAX 0xFFFFFF00ull	/* as SHUF_PIECE_MAX */
-
-static inline uint64_t tiff_align16(uint64_t v) { return (v + 15) & ~(uint64_t)15; }
 
 /* a row taken apart; sizes as 64-bit numbers */
 struct tiff_seg {
@@ -164,45 +159,17 @@ static inline bool
 tiff_check(uint64_t n, const uint64_t *rows, bool reader, uint64_t stored_avail, uint64_t raw_avail,
 	   int level, std::string &err)
 {
-	char msg[200];
-
-	if (n > TIFF_MAX_SEGMENTS) {
-		snprintf(msg, sizeof(msg), "n_segments %llu above 2^28", (unsigned long long)n);
-		err = msg;
-		return false;
-	}
-	for (uint64_t r = 0; r < n; r++) {
-		const char *why = tiff_row_why(rows + TIFF_WORDS * r, reader, stored_avail, raw_avail, level);
-		if (why) {
-			snprintf(msg, sizeof(msg), "row %llu: %s", (unsigned long long)r, why);
-			err = msg;
-			return false;
-		}
-	}
-	return true;
+	return chunk_check("n_segments", n, TIFF_MAX_SEGMENTS, [&](uint64_t r) {
+		return tiff_row_why(rows + TIFF_WORDS * r, reader, stored_avail, raw_avail, level);
+	}, err);
 }
 
-/* libdeflate_zlib_compress_bound(len): 5 bytes per 5000-byte block, 6 around */
-static inline uint64_t tiff_stream_bound(uint64_t len)
-{
-	uint64_t blocks = (len + 4999) / 5000;
-	if (blocks < 1)
-		blocks = 1;
-	return 5 * blocks + len + 6;
-}
-
-/* the sum of the streams' bounds; 0 for rows the writer refuses */
+/* the sum of the zlib streams' bounds; 0 for rows the writer refuses */
 static inline uint64_t tiff_bound(uint64_t n, const uint64_t *rows)
 {
-	uint64_t sum = 0;
-	if (n > TIFF_MAX_SEGMENTS)
-		return 0;
-	for (uint64_t r = 0; r < n; r++) {
-		if (tiff_row_why(rows + TIFF_WORDS * r, false, 0, ~(uint64_t)0, -1))
-			return 0;
-		sum += tiff_stream_bound(tiff_seg_of(rows + TIFF_WORDS * r).coded);
-	}
-	return sum;
+	return chunk_bound(n, TIFF_MAX_SEGMENTS, [&](uint64_t r) {
+		return tiff_row_why(rows + TIFF_WORDS * r, false, 0, ~(uint64_t)0, -1);
+	}, [&](uint64_t r) { return chunk_stream_bound(1, tiff_seg_of(rows + TIFF_WORDS * r).coded); });
 }
 
 /* is the row decoded straight into d_out? */
@@ -283,7 +250,7 @@ struct tiff_read_plan {
 	uint64_t n_k, quads;	/* the unpredict kernel's rows and quads */
 	uint64_t n_g, gtiles;	/* the gather kernel's rows and tiles */
 	uint64_t scratch;	/* bytes of the scratch rooms */
-	/* what goes up: [TIFF_DCOLS x (n_ws + n_direct)] at 0, [TIFF_KCOLS x n_k]
+	/* what goes up: [CHUNK_DCOLS x (n_ws + n_direct)] at 0, [TIFF_KCOLS x n_k]
 	 * at k_at, [TIFF_GCOLS x n_g] at g_at, [n verdict words] at verd_at */
 	uint64_t k_at, g_at, verd_at;
 	std::vector<uint64_t> cols;
@@ -293,99 +260,81 @@ struct tiff_read_plan {
 static inline void tiff_read_plan_build(uint64_t n, const uint64_t *rows, tiff_read_plan &p)
 {
 	p.n = n;
-	p.n_ws = p.n_direct = p.scratch = 0;
+	p.n_ws = p.n_direct = 0;
 	for (uint64_t r = 0; r < n; r++) {
 		if (tiff_direct(rows + TIFF_WORDS * r))
 			p.n_direct++;
 		else
 			p.n_ws++;
 	}
-	const uint64_t n_dec = n;
 	std::vector<uint64_t> verd((size_t)n);
 	std::vector<uint64_t> g[TIFF_GCOLS];
+	chunk_decode_cols d(p.cols, p.n_ws, p.n_direct);
+	chunk_rooms rooms;
 	tiff_kernel_rows k;
-	uint64_t ws = 0, di = p.n_ws, gtiles = 0;
-	p.cols.assign((size_t)(TIFF_DCOLS * n_dec), 0);
+	uint64_t gtiles = 0;
 	for (uint64_t r = 0; r < n; r++) {
 		const uint64_t *w = rows + TIFF_WORDS * r;
 		const tiff_seg s = tiff_seg_of(w);
 		const bool direct = tiff_direct(w);
-		const uint64_t at = direct ? di++ : ws++;
+		const uint64_t room = direct ? 0 : rooms.take(s.coded);
 		const uint64_t pitch = s.kr > 1 ? w[TIFF_W_PITCH] : 0;
-		verd[(size_t)r] = at;
-		p.cols[(size_t)(TIFF_D_IN_OFF * n_dec + at)] = w[TIFF_W_STORED_OFF];
-		p.cols[(size_t)(TIFF_D_IN_N * n_dec + at)] = w[TIFF_W_STORED_N];
-		p.cols[(size_t)(TIFF_D_OUT_OFF * n_dec + at)] = direct ? w[TIFF_W_RAW_OFF] : p.scratch;
-		p.cols[(size_t)(TIFF_D_OUT_N * n_dec + at)] = s.coded;
+		verd[(size_t)r] = d.add(direct, w[TIFF_W_STORED_OFF], w[TIFF_W_STORED_N],
+					direct ? w[TIFF_W_RAW_OFF] : room, s.coded);
 		if (direct)
 			continue;
 		if (s.pred == 3) {
 			/* the whole coded row of every kept row, in place; then the gather */
-			k.add(p.scratch, p.scratch | TIFF_DST_WS, s.coded_rb, s.coded_rb, s.kr, s.coded_rb,
-			      1, s.spp);
+			k.add(room, room | TIFF_DST_WS, s.coded_rb, s.coded_rb, s.kr, s.coded_rb, 1, s.spp);
 			const uint64_t ns = s.kw * s.spp;
 			const uint64_t items = s.kr * ((ns + 3) / 4);	/* (below 2^32: the coded size is) */
 			gtiles += (items + 255) / 256;
 			g[TIFF_G_TILE_END].push_back(gtiles);
-			g[TIFF_G_SRC].push_back(p.scratch);
+			g[TIFF_G_SRC].push_back(room);
 			g[TIFF_G_DST].push_back(w[TIFF_W_RAW_OFF]);
 			g[TIFF_G_DPITCH].push_back(pitch);
 			g[TIFF_G_GEOM].push_back(ns | s.bps << 32);
 			g[TIFF_G_PLANE].push_back(s.cw * s.spp | items << 32);
 		} else {
-			k.add(p.scratch, w[TIFF_W_RAW_OFF], s.coded_rb, pitch, s.kr, s.kept_rb, s.bps,
+			k.add(room, w[TIFF_W_RAW_OFF], s.coded_rb, pitch, s.kr, s.kept_rb, s.bps,
 			      s.pred == 2 ? s.px : 0);
 		}
-		p.scratch += tiff_align16(s.coded);
 	}
+	p.scratch = rooms.bytes;
 	p.n_k = k.scans.size();
 	p.k_at = p.cols.size();
 	p.quads = k.append_to(p.cols);
 	p.n_g = g[0].size();
 	p.gtiles = gtiles;
-	p.g_at = p.cols.size();
-	for (size_t a = 0; a < TIFF_GCOLS; a++)
-		p.cols.insert(p.cols.end(), g[a].begin(), g[a].end());
-	p.verd_at = p.cols.size();
-	p.cols.insert(p.cols.end(), verd.begin(), verd.end());
+	p.g_at = chunk_append(p.cols, g, TIFF_GCOLS);
+	p.verd_at = chunk_append(p.cols, &verd);
 }
 
-struct tiff_write_plan : zipw_pieces {
-	uint64_t n, raw_total;	/* the kept rectangles' bytes */
+struct tiff_write_plan : chunk_write_plan {	/* raw_total: the kept rectangles' bytes */
 	uint64_t tiles;		/* the predict kernel's */
-	uint64_t rooms_bytes;
-	/* what goes up in front of the pieces: [TIFFW_ECOLS x n] */
-	std::vector<uint64_t> ecols;
+	/* ecols: [TIFFW_ECOLS x n] */
 };
 
 /* the rows have passed tiff_check(); pr.store is false whatever the level */
 static inline void
 tiff_write_plan_build(const zipw_params &pr, uint64_t n, const uint64_t *rows, tiff_write_plan &p)
 {
-	std::vector<uint64_t> room((size_t)n), size((size_t)n);
+	chunk_write_rows e(p, n, TIFFW_ECOLS);
 
-	p.n = n;
-	p.raw_total = p.rooms_bytes = p.tiles = 0;
-	p.ecols.assign((size_t)(TIFFW_ECOLS * n), 0);
+	p.tiles = 0;
 	for (uint64_t k = 0; k < n; k++) {
 		const uint64_t *w = rows + TIFF_WORDS * k;
 		const tiff_seg s = tiff_seg_of(w);
-		room[(size_t)k] = p.rooms_bytes;
-		size[(size_t)k] = s.coded;
 		p.tiles += (s.coded + TIFF_PTILE - 1) / TIFF_PTILE;
-		p.ecols[(size_t)(TIFFW_E_USIZE * n + k)] = s.coded;
 		p.ecols[(size_t)(TIFFW_E_RAW_OFF * n + k)] = w[TIFF_W_RAW_OFF];
 		p.ecols[(size_t)(TIFFW_E_PITCH * n + k)] = w[TIFF_W_PITCH];
 		p.ecols[(size_t)(TIFFW_E_CODED * n + k)] = w[TIFF_W_CODED];
 		p.ecols[(size_t)(TIFFW_E_KEPT * n + k)] = w[TIFF_W_KEPT];
 		p.ecols[(size_t)(TIFFW_E_FMT * n + k)] = w[TIFF_W_FMT];
-		p.ecols[(size_t)(TIFFW_E_ROOM * n + k)] = p.rooms_bytes;
+		p.ecols[(size_t)(TIFFW_E_ROOM * n + k)] = e.add(s.coded, s.kept_rb * s.kr);
 		p.ecols[(size_t)(TIFFW_E_TILE_END * n + k)] = p.tiles;
-		p.rooms_bytes += tiff_align16(s.coded);
-		p.raw_total += s.kept_rb * s.kr;
 	}
-	zipw_cut_pieces(pr, n, room.data(), size.data(), p.ecols.data() + TIFFW_E_FIRST * n,
-			p.ecols.data() + TIFFW_E_COUNT * n, p);
+	e.cut(pr);
 }
 
 } /* namespace lda */

@@ -204,7 +204,7 @@ static void read_plan(void)
 	CHECK(p.n == n && p.n_z == 4 && p.n_copy == 1 && p.n_l == 4);
 	CHECK(p.utiles == 2 + 5 + 1 + 1);
 	CHECK(p.coded_bytes == 3008 + 8208 + 160 + 16 && p.raw_bytes == 8208 + 160 + 16);
-	CHECK(p.u_at == EXR_DCOLS * 4 && p.p_at == p.u_at + EXR_UCOLS * 4 && p.l_at == p.p_at + EXR_PCOLS);
+	CHECK(p.u_at == CHUNK_DCOLS * 4 && p.p_at == p.u_at + EXR_UCOLS * 4 && p.l_at == p.p_at + EXR_PCOLS);
 	CHECK(p.verd_at == p.l_at + EXR_LCOLS * 4 && p.cols.size() == p.verd_at + n);
 	const uint64_t *d = p.cols.data(), *u = d + p.u_at, *c = d + p.p_at, *l = d + p.l_at,
 		       *v = d + p.verd_at;
@@ -213,8 +213,8 @@ static void read_plan(void)
 	uint64_t room = 0, tiles = 0, raw_room = 0;
 	for (size_t i = 0; i < 4; i++) {
 		const uint64_t *w = r.data() + EXR_WORDS * zrows[i];
-		CHECK(d[EXR_D_IN_OFF * 4 + i] == w[0] && d[EXR_D_IN_N * 4 + i] == w[1]);
-		CHECK(d[EXR_D_OUT_OFF * 4 + i] == room && d[EXR_D_OUT_N * 4 + i] == zn[i] && room % 16 == 0);
+		CHECK(d[CHUNK_D_IN_OFF * 4 + i] == w[0] && d[CHUNK_D_IN_N * 4 + i] == w[1]);
+		CHECK(d[CHUNK_D_OUT_OFF * 4 + i] == room && d[CHUNK_D_OUT_N * 4 + i] == zn[i] && room % 16 == 0);
 		tiles += (zn[i] + EXR_TILE - 1) / EXR_TILE;
 		CHECK(u[EXR_U_TILE_END * 4 + i] == tiles && u[EXR_U_SRC * 4 + i] == room &&
 		      u[EXR_U_N * 4 + i] == zn[i]);
@@ -222,9 +222,9 @@ static void read_plan(void)
 			CHECK(u[EXR_U_DST * 4 + i] == (1000 | EXR_DST_OUT));
 		} else {
 			CHECK(u[EXR_U_DST * 4 + i] == raw_room && raw_room % 16 == 0);
-			raw_room += exr_align16(zn[i]);
+			raw_room += chunk_align16(zn[i]);
 		}
-		room += exr_align16(zn[i]);
+		room += chunk_align16(zn[i]);
 		CHECK(v[zrows[i]] == i);
 	}
 	CHECK(v[1] == (EXR_VERD_OWN | 0) && v[2] == (EXR_VERD_OWN | 1) && v[3] == (EXR_VERD_OWN | 0));
@@ -292,12 +292,12 @@ static void write_plan(void)
 	uint64_t room = 0, ct = 0;
 	for (uint64_t k = 0; k < n; k++) {
 		ct += (sizes[k] + EXR_CTILE - 1) / EXR_CTILE;
-		CHECK(e[EXRW_E_USIZE * n + k] == sizes[k] && e[EXRW_E_ROOM * n + k] == room && room % 16 == 0);
+		CHECK(e[CHUNKW_E_USIZE * n + k] == sizes[k] && e[EXRW_E_ROOM * n + k] == room && room % 16 == 0);
 		CHECK(e[EXRW_E_CTILE_END * n + k] == ct);
 		for (uint64_t a = 0; a < 8; a++)
 			CHECK(e[(EXRW_E_WORDS + a) * n + k] == r[EXR_WORDS * k + 2 + a]);
 		/* the pieces tile the room */
-		const uint64_t first = e[EXRW_E_FIRST * n + k], cnt = e[EXRW_E_COUNT * n + k];
+		const uint64_t first = e[CHUNKW_E_FIRST * n + k], cnt = e[CHUNKW_E_COUNT * n + k];
 		uint64_t at = room;
 		CHECK(cnt >= 1);
 		for (uint64_t j = first; j < first + cnt; j++) {
@@ -305,9 +305,9 @@ static void write_plan(void)
 			at += p.pcols[ZIPW_P_PC_N * p.np + j];
 		}
 		CHECK(at == room + sizes[k]);
-		room += exr_align16(sizes[k]);
+		room += chunk_align16(sizes[k]);
 	}
-	CHECK(e[EXRW_E_COUNT * n + 1] > 1);	/* above 128 KiB: primed segments */
+	CHECK(e[CHUNKW_E_COUNT * n + 1] > 1);	/* above 128 KiB: primed segments */
 	CHECK(p.rooms_bytes == room && p.ctiles == ct && p.l_at == EXRW_ECOLS * n);
 	CHECK(p.ecols.size() == p.l_at + EXR_LCOLS * n);
 	const uint64_t *l = e + p.l_at;

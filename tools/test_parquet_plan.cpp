@@ -147,9 +147,9 @@ static void check_plan(const Rows &rows)
 		if (packed) {
 			const uint64_t *d = p.cols.data();
 			CHECK(z < p.n_z);
-			CHECK(d[PQ_D_IN_OFF * p.n_z + z] == w[0] + def_len && d[PQ_D_IN_N * p.n_z + z] == w[1] - def_len);
-			CHECK(d[PQ_D_OUT_OFF * p.n_z + z] == rooms && rooms % 16 == 0);
-			CHECK(d[PQ_D_OUT_N * p.n_z + z] == sec_n);
+			CHECK(d[CHUNK_D_IN_OFF * p.n_z + z] == w[0] + def_len && d[CHUNK_D_IN_N * p.n_z + z] == w[1] - def_len);
+			CHECK(d[CHUNK_D_OUT_OFF * p.n_z + z] == rooms && rooms % 16 == 0);
+			CHECK(d[CHUNK_D_OUT_N * p.n_z + z] == sec_n);
 			sec[r] = rooms;
 			rooms += (sec_n + 15) / 16 * 16;
 			z++;
@@ -203,7 +203,7 @@ static void check_plan(const Rows &rows)
 	}
 	CHECK(z == p.n_z && u == p.n_u && rooms == p.room_bytes && slots == p.slots && recs == p.run_records);
 	CHECK(p.tiles == (slots + PQ_TILE - 1) / PQ_TILE);
-	CHECK(p.u_at == PQ_DCOLS * p.n_z && p.v_at == p.u_at + PQ_UCOLS * p.n_u &&
+	CHECK(p.u_at == CHUNK_DCOLS * p.n_z && p.v_at == p.u_at + PQ_UCOLS * p.n_u &&
 	      p.cols.size() == p.v_at + PQ_VCOLS * n);
 }
 

@@ -135,7 +135,7 @@ static void refusals_and_bound(void)
 	CHECK(shuf_bound(0, 3, w.data()) == 45 + 12 + 5 && shuf_bound(1, 3, w.data()) == 45 + 12 + 5 + 18);
 	CHECK(shuf_bound(2, 3, w.data()) == 45 + 12 + 5 + 54 && shuf_bound(2, 0, NULL) == 0);
 	CHECK(shuf_bound(1, 3, ok.data()) == 0 && shuf_bound(3, 3, w.data()) == 0);
-	CHECK(shuf_stream_bound(0, 5000) == 5005 && shuf_stream_bound(0, 5001) == 5011);
+	CHECK(chunk_stream_bound(0, 5000) == 5005 && chunk_stream_bound(0, 5001) == 5011);
 	CHECK(shuf_bound(2, 1, big.data()) == 0xFFFFFF01ull + 5 * ((0xFFFFFF01ull + 4999) / 5000) + 18);
 }
 
@@ -158,7 +158,7 @@ static void check_read_plan(const Rows &r)
 	}
 	CHECK(p.n == n && p.n_sd == n_sd && p.n_id == n_id && p.n_u == n_u);
 	const uint64_t n_dec = n_sd + n_id;
-	CHECK(p.u_at == SHUF_DCOLS * n_dec && p.verd_at == p.u_at + SHUF_UCOLS * n_u);
+	CHECK(p.u_at == CHUNK_DCOLS * n_dec && p.verd_at == p.u_at + SHUF_UCOLS * n_u);
 	CHECK(p.cols.size() == p.verd_at + n);
 	if (p.cols.size() != p.verd_at + n)
 		return;
@@ -176,14 +176,14 @@ static void check_read_plan(const Rows &r)
 		} else {
 			const uint64_t at = ident ? id++ : sd++;
 			CHECK(verd[k] == at);
-			CHECK(dc[SHUF_D_IN_OFF * n_dec + at] == w[0] && dc[SHUF_D_IN_N * n_dec + at] == w[1]);
-			CHECK(dc[SHUF_D_OUT_N * n_dec + at] == w[3]);
+			CHECK(dc[CHUNK_D_IN_OFF * n_dec + at] == w[0] && dc[CHUNK_D_IN_N * n_dec + at] == w[1]);
+			CHECK(dc[CHUNK_D_OUT_N * n_dec + at] == w[3]);
 			if (ident) {
-				CHECK(dc[SHUF_D_OUT_OFF * n_dec + at] == w[2]);
+				CHECK(dc[CHUNK_D_OUT_OFF * n_dec + at] == w[2]);
 				continue;
 			}
 			/* a room of its own on a 16-byte boundary, behind the one before */
-			CHECK(dc[SHUF_D_OUT_OFF * n_dec + at] == scratch && scratch % 16 == 0);
+			CHECK(dc[CHUNK_D_OUT_OFF * n_dec + at] == scratch && scratch % 16 == 0);
 			CHECK(uc[SHUF_U_SRC * n_u + u] == scratch);
 			scratch += (w[3] + 15) / 16 * 16;
 		}
@@ -227,8 +227,8 @@ static void check_write_plan(const zipw_params &pr, const Rows &r)
 		const uint64_t *w = &r[k * SHUF_WORDS];
 		const bool ident = w[4] == 1 || w[3] / w[4] <= 1 || (w[5] & 2);
 		const uint64_t ues = ident ? 1 : w[4], S = model_S(pr, w[3]);
-		const uint64_t f = ec[SHUFW_E_FIRST * n + k], cnt = ec[SHUFW_E_COUNT * n + k];
-		CHECK(ec[SHUFW_E_USIZE * n + k] == w[3] && ec[SHUFW_E_ES * n + k] == w[4]);
+		const uint64_t f = ec[CHUNKW_E_FIRST * n + k], cnt = ec[CHUNKW_E_COUNT * n + k];
+		CHECK(ec[CHUNKW_E_USIZE * n + k] == w[3] && ec[SHUFW_E_ES * n + k] == w[4]);
 		CHECK(ec[SHUFW_E_MASK * n + k] == w[5] && ec[SHUFW_E_RAW_OFF * n + k] == w[2]);
 		CHECK(cnt == (S ? (w[3] + S - 1) / S : w[3] ? 1 : 0));
 		CHECK(room % 16 == 0);

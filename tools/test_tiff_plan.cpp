@@ -173,7 +173,7 @@ static void refusals_and_bound(void)
 	CHECK(tiff_check(3, w.data(), false, 0, 200, 6, err));
 	CHECK(refused(w, false, 0, 199, 6, "in_avail", 2));
 	/* the bound: the sum of libdeflate_zlib_compress_bound(coded size) */
-	CHECK(tiff_stream_bound(0) == 11 && tiff_stream_bound(5000) == 5011 && tiff_stream_bound(5001) == 5017);
+	CHECK(chunk_stream_bound(1, 0) == 11 && chunk_stream_bound(1, 5000) == 5011 && chunk_stream_bound(1, 5001) == 5017);
 	CHECK(tiff_bound(3, w.data()) == (120 + 11) + (32 + 11) + (20 + 11) && tiff_bound(0, NULL) == 0);
 	w[TIFF_WORDS + TIFF_W_RESERVED] = 5;
 	CHECK(tiff_bound(3, w.data()) == 0);
@@ -197,7 +197,7 @@ static void check_read_plan(const Rows &r)
 		n_g += pred == 3;
 	}
 	CHECK(p.n == n && p.n_ws == n_ws && p.n_direct == n_direct && p.n_k == n_ws && p.n_g == n_g);
-	CHECK(p.k_at == TIFF_DCOLS * n && p.g_at == p.k_at + TIFF_KCOLS * n_ws);
+	CHECK(p.k_at == CHUNK_DCOLS * n && p.g_at == p.k_at + TIFF_KCOLS * n_ws);
 	CHECK(p.verd_at == p.g_at + TIFF_GCOLS * n_g && p.cols.size() == p.verd_at + n);
 	if (p.cols.size() != p.verd_at + n)
 		return;
@@ -212,14 +212,14 @@ static void check_read_plan(const Rows &r)
 		const bool direct = tiff_direct(w);
 		const uint64_t at = direct ? di++ : ws++;
 		CHECK(verd[k] == at);
-		CHECK(dc[TIFF_D_IN_OFF * n + at] == w[0] && dc[TIFF_D_IN_N * n + at] == w[1]);
-		CHECK(dc[TIFF_D_OUT_N * n + at] == coded);
+		CHECK(dc[CHUNK_D_IN_OFF * n + at] == w[0] && dc[CHUNK_D_IN_N * n + at] == w[1]);
+		CHECK(dc[CHUNK_D_OUT_N * n + at] == coded);
 		if (direct) {
-			CHECK(dc[TIFF_D_OUT_OFF * n + at] == w[2]);
+			CHECK(dc[CHUNK_D_OUT_OFF * n + at] == w[2]);
 			continue;
 		}
 		/* a room of its own on a 16-byte boundary, behind the one before */
-		CHECK(dc[TIFF_D_OUT_OFF * n + at] == scratch && scratch % 16 == 0);
+		CHECK(dc[CHUNK_D_OUT_OFF * n + at] == scratch && scratch % 16 == 0);
 		/* its scan: somewhere in the kernel's rows, once */
 		const uint64_t rb = pred == 3 ? cw * px : kw * px, sb = pred == 3 ? 1 : bps;
 		const uint64_t st = pred == 3 ? spp : pred == 2 ? px : 0, G = model_group(rb, st);
@@ -291,8 +291,8 @@ static void check_write_plan(const zipw_params &pr, const Rows &r)
 		const uint64_t cw = w[4] & 0xFFFFFFFF, cr = w[4] >> 32, kw = w[5] & 0xFFFFFFFF, kr = w[5] >> 32;
 		const uint64_t px = (w[6] & 0xFF) * ((w[6] >> 8) & 0xFF), coded = cw * cr * px;
 		const uint64_t S = model_S(pr, coded);
-		const uint64_t f = ec[TIFFW_E_FIRST * n + k], cnt = ec[TIFFW_E_COUNT * n + k];
-		CHECK(ec[TIFFW_E_USIZE * n + k] == coded && ec[TIFFW_E_RAW_OFF * n + k] == w[2]);
+		const uint64_t f = ec[CHUNKW_E_FIRST * n + k], cnt = ec[CHUNKW_E_COUNT * n + k];
+		CHECK(ec[CHUNKW_E_USIZE * n + k] == coded && ec[TIFFW_E_RAW_OFF * n + k] == w[2]);
 		CHECK(ec[TIFFW_E_PITCH * n + k] == w[3] && ec[TIFFW_E_CODED * n + k] == w[4]);
 		CHECK(ec[TIFFW_E_KEPT * n + k] == w[5] && ec[TIFFW_E_FMT * n + k] == w[6]);
 		CHECK(ec[TIFFW_E_ROOM * n + k] == room && room % 16 == 0);
