@@ -2704,7 +2704,8 @@ libdeflate_amd_exr_encode_batch(struct libdeflate_compressor *compressor, size_t
  * 16 bytes per slot of a page with levels or indices -; one memory-bound launch
  * over the slots of all pages writes values and validity.
  *
- * Not covered: BYTE_ARRAY (strings) and BOOLEAN columns; nested and repeated
+ * Not covered: BYTE_ARRAY (strings: libdeflate_amd_parquet_decode_batch_ex
+ * below reads them) and BOOLEAN columns; nested and repeated
  * columns (max_rep above 0, max_def above 1); the DELTA_* encodings and
  * BYTE_STREAM_SPLIT; the Snappy, ZSTD, LZ4 and Brotli codecs; page CRCs;
  * encryption; the page index and bloom filters; writing; host-pointer forms;
@@ -2724,6 +2725,77 @@ libdeflate_amd_parquet_decode_batch(struct libdeflate_decompressor *decompressor
 				    const void *d_in, size_t in_nbytes, void *d_out, size_t out_avail,
 				    void *d_valid /* may be NULL */, size_t valid_avail,
 				    int32_t *d_results, void *stream);
+
+/*
+ * The same call with BYTE_ARRAY columns - Parquet's `string` and `binary` -
+ * read into Arrow's large layout: int64 offsets in d_out and one run of bytes
+ * in d_bytes.  A row without LIBDEFLATE_AMD_PARQUET_BYTE_ARRAY (word 3 bit 14)
+ * means exactly what it means above and is decoded by the same kernels in the
+ * same call; a row with it describes a BYTE_ARRAY page, and its width field
+ * must be 0.  (libdeflate_amd_parquet_decode_batch goes on refusing the bit.)
+ *
+ * A BYTE_ARRAY value is a 4-byte little-endian length and that many bytes.  A
+ * dictionary page holds `entries` of them, a PLAIN data page one per valid
+ * slot; a dictionary-coded data page holds indices as above.
+ *
+ * Output of a BYTE_ARRAY data page.  Word 5 is the byte offset in d_out, a
+ * multiple of 8, of count + 1 little-endian int64 entries: entry r is where
+ * slot r's bytes start in d_bytes, entry `count` where they end.  A null slot
+ * has length 0.  The entries are absolute positions in d_bytes: the bytes of
+ * all BYTE_ARRAY data pages of the call lie back to back in d_bytes in row
+ * order from 0, so that nothing has to come back to the host to place them,
+ * and the consecutive data pages of one column - while no other column's
+ * BYTE_ARRAY data page stands between them in the call (not checked) - make one
+ * Arrow array: lay page k + 1's entries at page k's entry `count`, which both
+ * write with the same value.  (Arrow allows offsets[0] != 0.)  Dictionary pages
+ * and fixed-width rows take no room.  Validity bytes are as above (word 6).
+ *
+ * Capacity.  d_bytes_total[0] (device memory) is always written: the room the
+ * call's BYTE_ARRAY pages take.  A page whose bytes do not end at or below
+ * bytes_avail writes none of them and ends as LIBDEFLATE_INSUFFICIENT_SPACE;
+ * its entries and validity bytes are still written, and no byte at or behind
+ * bytes_avail is touched.  d_bytes NULL with bytes_avail 0 is the sizing call.
+ * A failed page's entries and bytes are undefined; it takes no room where its
+ * levels, its indices, its values' walk or its dictionary failed, and else -
+ * an index at or above the entry count - the room of its other slots, the bad
+ * index counting as length 0.
+ *
+ * d_results[i] of a BYTE_ARRAY row: as above, with width 1 wherever a width is
+ * asked for, and where that is SUCCESS: LIBDEFLATE_BAD_DATA for a dictionary
+ * page whose section ends before `entries` length-prefixed values do (inside a
+ * prefix included), for a PLAIN data page whose values section ends before
+ * (the valid slots) values do, and for a data page whose dictionary failed so;
+ * else LIBDEFLATE_INSUFFICIENT_SPACE as said; else SUCCESS.
+ *
+ * LIBDEFLATE_AMD_BAD_ARG before any device work, beyond the list above: bit 14
+ * with a non-zero width field; word 5 of a BYTE_ARRAY data page not a multiple
+ * of 8; a dictionary reference across types (bit 14 on one side only); entries
+ * outside out_avail for (count + 1) * 8; d_bytes_total NULL while a row has bit
+ * 14; d_bytes NULL with bytes_avail != 0; non-zero flags.  d_bytes_total may
+ * be NULL otherwise.  The call only enqueues; object, stream, scratch and
+ * pinned-block rules are the old call's.
+ *
+ * Cost beyond the old call's: a wave per dictionary page and PLAIN data page
+ * lists the starts of its values (4 bytes of scratch per value) - the chain of
+ * length prefixes is broken up by pointer doubling in windows of 1 KiB, so a
+ * long string is a jump and 256 empty ones nine rounds -; two launches over
+ * the slots sum and scan the lengths and write the entries (16 bytes of scratch
+ * per slot); one launch over the output bytes, 4 KiB a workgroup, gathers them.
+ *
+ * Not covered: int32 offsets; BOOLEAN; DELTA_LENGTH_BYTE_ARRAY, DELTA_BYTE_ARRAY
+ * and the other DELTA encodings; UTF-8 validation; and what the old call does
+ * not cover.
+ */
+#define LIBDEFLATE_AMD_PARQUET_BYTE_ARRAY ((uint64_t)1 << 14)
+
+LIBDEFLATEAPI int
+libdeflate_amd_parquet_decode_batch_ex(struct libdeflate_decompressor *decompressor, int format,
+				       size_t n_pages, const uint64_t *rows /* host rows */,
+				       const void *d_in, size_t in_nbytes, void *d_out,
+				       size_t out_avail, void *d_valid /* may be NULL */,
+				       size_t valid_avail, void *d_bytes /* may be NULL */,
+				       size_t bytes_avail, uint64_t *d_bytes_total /* uint64_t[1] */,
+				       uint64_t flags /* 0 */, int32_t *d_results, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1075,6 +1075,31 @@ class Decompressor:
                                   results, stream, in_nbytes, out_avail, fmt=FORMATS[fmt],
                                   more=(valid.data_ptr() if valid is not None else None, v_avail))
 
+    def parquet_decode_batch_ex(self, fmt, rows, data, out, valid, strings, total, results,
+                                stream=None, in_nbytes=None, out_avail=None, valid_avail=None,
+                                bytes_avail=None, flags=0):
+        """libdeflate_amd_parquet_decode_batch_ex: parquet_decode_batch with
+        BYTE_ARRAY rows (parquet_rows(byte_array=1),
+        libdeflate_amd.parquet.pages(strings=True)).  Such a data page writes
+        count + 1 int64 offsets into `out` at its word 5 and its bytes into
+        `strings`, where the bytes of all such pages of the call lie back to
+        back; the offsets are positions in `strings`.  strings: uint8 CUDA
+        tensor, or None for the sizing call; total: uint64 or int64 CUDA
+        tensor of one element, which receives the room the strings need - a
+        page that does not fit ends as INSUFFICIENT_SPACE -, or None while no
+        row is BYTE_ARRAY.  The rest as parquet_decode_batch.  Only
+        enqueues."""
+        v_avail = (0 if valid is None else valid.numel()) if valid_avail is None \
+            else int(valid_avail)
+        b_avail = (0 if strings is None else strings.numel()) if bytes_avail is None \
+            else int(bytes_avail)
+        return self._chunk_decode(
+            "parquet_decode_batch_ex", binding.PARQUET_WORDS, rows, data, out, results, stream,
+            in_nbytes, out_avail, fmt=FORMATS[fmt],
+            more=(valid.data_ptr() if valid is not None else None, v_avail,
+                  strings.data_ptr() if strings is not None and strings.numel() else None, b_avail,
+                  total.data_ptr() if total is not None else None, int(flags)))
+
     def decompress_batch_dict(self, fmt, dictionary, data, in_offsets, in_nbytes, out,
                               out_offsets, out_avail, results, actual_in=None,
                               actual_out=None, stream=None):
@@ -1531,7 +1556,7 @@ def exr_rows(pix_offsets, pitches, sizes, wide, layout=0, slots=None, data_offse
 
 
 def parquet_rows(offsets, csizes, usizes, kinds, counts, widths, encodings=0, compressed=True,
-                 max_def=0, def_lens=0, out_offsets=0, valid_offsets=0, dict_rows=0):
+                 max_def=0, def_lens=0, out_offsets=0, valid_offsets=0, dict_rows=0, byte_array=0):
     """The host rows of the Parquet call, one per page, in the call's order.
     offsets, csizes, usizes: the page bodies in the compressed buffer and
     their two sizes; kinds: binding.PARQUET_DATA_V1, _DICT or _DATA_V2;
@@ -1540,18 +1565,20 @@ def parquet_rows(offsets, csizes, usizes, kinds, counts, widths, encodings=0, co
     section) a stream; max_def: 0 or 1; def_lens: V2's
     definition_levels_byte_length; out_offsets / valid_offsets: slot 0 in the
     output and in the validity bytes; dict_rows: the row of a dictionary-coded
-    page's dictionary.  All but offsets: one value or one per page.
-    -> numpy uint64 (pages, PARQUET_WORDS)."""
+    page's dictionary; byte_array: 1 for a BYTE_ARRAY page of
+    parquet_decode_batch_ex, whose width is 1 (the field 0) and whose
+    out_offset is that of its int64 offsets.  All but offsets: one value or
+    one per page.  -> numpy uint64 (pages, PARQUET_WORDS)."""
     n = len(offsets)
     per = functools.partial(_per_row, n=n)
-    cs, us, kd, ct, wd, en, cp, md, dl, oo, vo, dr = (per(v) for v in (
+    cs, us, kd, ct, wd, en, cp, md, dl, oo, vo, dr, ba = (per(v) for v in (
         csizes, usizes, kinds, counts, widths, encodings, compressed, max_def, def_lens,
-        out_offsets, valid_offsets, dict_rows))
+        out_offsets, valid_offsets, dict_rows, byte_array))
     rows = np.zeros((n, binding.PARQUET_WORDS), dtype=np.uint64)
     for k in range(n):
         rows[k, 0], rows[k, 1], rows[k, 2] = int(offsets[k]), int(cs[k]), int(us[k])
         rows[k, 3] = int(kd[k]) | int(en[k]) << 4 | int(bool(cp[k])) << 12 | int(md[k]) << 13 | \
-            (int(wd[k]) - 1) << 16
+            (int(wd[k]) - 1) << 16 | (binding.PARQUET_BYTE_ARRAY if ba[k] else 0)
         rows[k, 4] = int(ct[k]) | int(dl[k]) << 32
         rows[k, 5], rows[k, 6], rows[k, 7] = int(oo[k]), int(vo[k]), int(dr[k])
     return rows

@@ -78,6 +78,7 @@ EXR_LINES, EXR_PIXELS = 0, 1
 # Parquet pages: u64 per row, the page kinds of a row's word 3
 PARQUET_WORDS = 8
 PARQUET_DATA_V1, PARQUET_DICT, PARQUET_DATA_V2 = 0, 2, 3
+PARQUET_BYTE_ARRAY = 1 << 14      # word 3 of a row of the _ex call: a BYTE_ARRAY page
 
 # every symbol include/libdeflate_amd.h declares
 DROPIN_SYMBOLS = [
@@ -140,7 +141,7 @@ BATCH_SYMBOLS = [
     "libdeflate_amd_tiff_encode_batch",
     "libdeflate_amd_exr_decode_batch", "libdeflate_amd_exr_encode_bound",
     "libdeflate_amd_exr_encode_batch",
-    "libdeflate_amd_parquet_decode_batch",
+    "libdeflate_amd_parquet_decode_batch", "libdeflate_amd_parquet_decode_batch_ex",
 ]
 
 _lib = None
@@ -306,6 +307,9 @@ def load():
     # Parquet pages: host rows of PARQUET_WORDS u64, the file in a device
     # buffer -> column slots and validity bytes
     sig("libdeflate_amd_parquet_decode_batch", c_int, P, c_int, SZ, P, P, SZ, P, SZ, P, SZ, P, P)
+    # ... with BYTE_ARRAY rows: d_bytes, bytes_avail, d_bytes_total, flags
+    sig("libdeflate_amd_parquet_decode_batch_ex", c_int, P, c_int, SZ, P, P, SZ, P, SZ, P, SZ,
+        P, SZ, P, ctypes.c_uint64, P, P)
     # PNG files written: the bound (host arithmetic), and pixel arrays of a
     # device buffer -> files (the image rows on the host)
     sig("libdeflate_amd_png_encode_bound", SZ, P, SZ, P)

@@ -772,6 +772,44 @@ extern "C" __global__ void
 lda_pq_final_kernel(uint64_t n, const uint64_t *vcols, const int32_t *decode, const uint32_t *info,
 		    int32_t *results);
 
+/* parquet_strings_kernels.hip: the BYTE_ARRAY pages of
+ * libdeflate_amd_parquet_decode_batch_ex - the starts of the length-prefixed
+ * values of every walk section listed, a wave a section; the lengths of the
+ * string slots summed per tile of LDA_PQ_TILE, placed by the scan and written
+ * as int64 entries; the bytes gathered; the verdicts added.  wcols, scols and
+ * svcols are parquet_strings_plan.h's PQS_WCOLS, PQS_SCOLS and PQS_VCOLS;
+ * `walks` holds two words per walk section (failed, the
+ * values owed) and behind them the start lists; `sums` the tile sums, their
+ * places and the scan's block sums; `places` per string slot its length and
+ * then its place in d_bytes, the total behind the last, and then per slot where
+ * its bytes lie.
+ * Copies of the plan's constants (static_assert in host_parquet.hip) */
+enum {
+	LDA_PQS_W_SEC = 0, LDA_PQS_W_SEC_N, LDA_PQS_W_Z, LDA_PQS_W_U, LDA_PQS_W_COUNT, LDA_PQS_W_STARTS,
+	LDA_PQS_W_CAP, LDA_PQS_WCOLS,
+	LDA_PQS_S_SLOT_END = 0, LDA_PQS_S_U, LDA_PQS_S_WALK, LDA_PQS_S_STARTS, LDA_PQS_SCOLS,
+	LDA_PQS_V_S = 0, LDA_PQS_V_WALK, LDA_PQS_V_DWALK, LDA_PQS_VCOLS
+};
+extern "C" __global__ void
+lda_pqs_walk_kernel(uint64_t n_w, const uint64_t *wcols, const int32_t *decode, const uint32_t *info,
+		    const uint8_t *in, const uint8_t *rooms, uint32_t *walks);
+extern "C" __global__ void
+lda_pqs_sum_kernel(uint64_t n_u, uint64_t n_s, uint64_t n_tiles, const uint64_t *ucols,
+		   const uint64_t *scols, const uint8_t *in, const uint8_t *rooms, const uint4 *runs,
+		   uint32_t *info, const uint32_t *walks, uint64_t *sums, uint8_t *valid,
+		   uint64_t *places);
+extern "C" __global__ void
+lda_pqs_offsets_kernel(uint64_t n_u, uint64_t n_s, uint64_t n_tiles, const uint64_t *ucols,
+		       const uint64_t *scols, const uint64_t *sums, uint8_t *out, uint64_t *places);
+extern "C" __global__ void
+lda_pqs_copy_kernel(uint64_t n_s, const uint64_t *scols, const uint64_t *places, const uint8_t *in,
+		    const uint8_t *rooms, uint8_t *bytes, uint64_t bytes_avail);
+extern "C" __global__ void
+lda_pqs_final_kernel(uint64_t n, uint64_t n_u, uint64_t n_s, const uint64_t *svcols,
+		     const uint64_t *ucols, const uint64_t *scols, const uint32_t *winfo,
+		     const uint64_t *ent, const uint64_t *total, uint64_t bytes_avail, uint8_t *out,
+		     uint64_t *bytes_total, int32_t *results);
+
 /* selfcheck_kernels.hip: the hardware behaviours the kernels rely on, checked
  * per device (counters: [0] lanes, [1] order mismatches, [2] same-instruction
  * conflicts seen, [3] loads, [4] stale loads) */

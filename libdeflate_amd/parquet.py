@@ -1,4 +1,5 @@
-"""The host side of the Parquet call (libdeflate_amd_parquet_decode_batch):
+"""The host side of the Parquet calls (libdeflate_amd_parquet_decode_batch and
+its _ex form, which reads BYTE_ARRAY columns too):
 parse() reads the footer of a host copy of a Parquet file, pages() walks the
 page headers of the selected column chunks and makes the page rows the decode
 call takes plus a layout of the columns, and read_columns() runs the call and
@@ -10,7 +11,9 @@ hands back tensors.
 
 Flat columns of INT32, INT64, INT96, FLOAT, DOUBLE and FIXED_LEN_BYTE_ARRAY,
 PLAIN or dictionary-coded, in V1 or V2 pages, GZIP or uncompressed; anything
-else raises with the column's name and the reason.  Everything here is host
+else raises with the column's name and the reason.  BYTE_ARRAY columns -
+`string` and `binary` - come back as ((offsets int64 [rows + 1], bytes uint8),
+mask), Arrow's large layout.  Everything here is host
 arithmetic on the footer and the page headers; no column byte is touched.  Pure
 Python: a small Thrift compact-protocol reader, no Parquet library."""
 import struct
@@ -199,21 +202,26 @@ def parse(buf):
 class Column:
     """where a selected column lies: offset in d_out, valid_offset in d_valid
     (None for max_def 0), rows, width, type, dtype (numpy's name, or None for
-    INT96 and FIXED_LEN_BYTE_ARRAY: uint8 [rows, width])"""
+    INT96 and FIXED_LEN_BYTE_ARRAY: uint8 [rows, width]).  byte_array: at
+    offset lie rows + 1 int64 offsets into the call's d_bytes instead, and width
+    is None"""
 
     def __init__(self, name, offset, valid_offset, rows, leaf):
         self.name, self.offset, self.valid_offset, self.rows = name, offset, valid_offset, rows
         self.width, self.type, self.dtype = leaf.width, leaf.type, TYPE_DTYPE.get(leaf.type)
+        self.byte_array = leaf.type == BYTE_ARRAY
 
 
 class Pages:
     """rows: numpy uint64 (pages, PARQUET_WORDS); format: "gzip", "zlib" or
     "deflate"; columns: {name: Column}; out_nbytes, valid_nbytes: what d_out
-    and d_valid must hold"""
+    and d_valid must hold; bytes_estimate: an estimate from the page headers of
+    what d_bytes must hold, 0 without a BYTE_ARRAY column"""
 
-    def __init__(self, rows, fmt, columns, out_nbytes, valid_nbytes):
+    def __init__(self, rows, fmt, columns, out_nbytes, valid_nbytes, bytes_estimate=0):
         self.rows, self.format, self.columns = rows, fmt, columns
         self.out_nbytes, self.valid_nbytes = out_nbytes, valid_nbytes
+        self.bytes_estimate = bytes_estimate
 
 
 def _align(v):
@@ -228,13 +236,15 @@ def _format_of(head):
     return "deflate"
 
 
-def pages(buf, columns=None, row_groups=None, file=None):
+def pages(buf, columns=None, row_groups=None, file=None, strings=False):
     """The page rows of the selected column chunks.  columns: names (None: every
     leaf); row_groups: indices in the order their rows shall lie in every
     column (None: all, in the file's order); file: parse(buf), if at hand.
     Every selected column is one contiguous array of (its rows) x width at a
     64-byte aligned offset of d_out, its validity bytes likewise in d_valid.
-    -> Pages.  Raises ValueError for what is out of scope, with the column's
+    strings: take BYTE_ARRAY columns too, as rows of
+    libdeflate_amd_parquet_decode_batch_ex: such a column is (its rows + 1) x 8
+    bytes of int64 offsets.  -> Pages.  Raises ValueError for what is out of scope, with the column's
     name and the reason."""
     buf = memoryview(buf).cast("B")
     f = file or parse(buf)
@@ -242,7 +252,7 @@ def pages(buf, columns=None, row_groups=None, file=None):
     groups = list(range(len(f.row_groups))) if row_groups is None else list(row_groups)
     total = sum(f.row_groups[g][0] for g in groups)
     rows, layout, fmt = [], {}, None
-    out_at = valid_at = 0
+    out_at = valid_at = estimate = 0
 
     for name in names:
         leaf = f.leaves[f.leaf_index(name)]
@@ -251,15 +261,19 @@ def pages(buf, columns=None, row_groups=None, file=None):
             return ValueError("parquet: column %r: %s" % (name, why))
         if leaf.max_rep or leaf.max_def > 1:
             raise no("nested or repeated (max_def %d, max_rep %d)" % (leaf.max_def, leaf.max_rep))
-        if leaf.type in (BOOLEAN, BYTE_ARRAY) or leaf.type not in range(8):
+        is_str = bool(strings) and leaf.type == BYTE_ARRAY
+        if not is_str and (leaf.type in (BOOLEAN, BYTE_ARRAY) or leaf.type not in range(8)):
             raise no("physical type %s" % (TYPE_NAMES[leaf.type] if leaf.type in range(8)
                                            else leaf.type))
-        if not leaf.width or not 1 <= leaf.width <= 256:
+        if not is_str and (not leaf.width or not 1 <= leaf.width <= 256):
             raise no("a value width of %r bytes (1 .. 256)" % (leaf.width,))
         out_at, valid_at = _align(out_at), _align(valid_at)
         col = Column(name, out_at, valid_at if leaf.max_def else None, total, leaf)
         layout[name] = col
-        base = (binding.PARQUET_DATA_V1 | leaf.max_def << 13 | (leaf.width - 1) << 16)
+        # what a slot takes of d_out: a value, or an int64 offset
+        step = 8 if is_str else leaf.width
+        base = binding.PARQUET_DATA_V1 | leaf.max_def << 13 | \
+            (binding.PARQUET_BYTE_ARRAY if is_str else (leaf.width - 1) << 16)
         done = 0
         for g in groups:
             g_rows, chunks = f.row_groups[g]
@@ -269,7 +283,7 @@ def pages(buf, columns=None, row_groups=None, file=None):
                                        else ch.codec))
             if ch.start < 4 or ch.start + ch.nbytes > len(buf) - 8:
                 raise no("its pages leave the file")
-            at, end, slots, dict_row = ch.start, ch.start + ch.nbytes, 0, None
+            at, end, slots, dict_row, mean = ch.start, ch.start + ch.nbytes, 0, None, 0
             while at < end and slots < ch.num_values:
                 th = Thrift(buf, at)
                 ph = th.struct()
@@ -289,6 +303,8 @@ def pages(buf, columns=None, row_groups=None, file=None):
                     dict_row = len(rows)
                     word3 = (base & ~(1 << 13)) | binding.PARQUET_DICT
                     word4 = h.get(1, 0)
+                    # the mean entry, rounded up: what an index is estimated to take
+                    mean = -(-max(usize - 4 * word4, 0) // max(word4, 1))
                 elif kind in (DATA_PAGE, DATA_PAGE_V2):
                     h = ph.get(5 if kind == DATA_PAGE else 8)
                     if h is None:
@@ -322,7 +338,9 @@ def pages(buf, columns=None, row_groups=None, file=None):
                     fmt = _format_of(bytes(buf[body + skip:body + skip + 2]))
                 row = [body, csize, usize, word3 | int(packed) << 12, word4, 0, 0, 0]
                 if kind != DICTIONARY_PAGE:
-                    row[5] = col.offset + (done + slots) * leaf.width
+                    row[5] = col.offset + (done + slots) * step
+                    if is_str:
+                        estimate += n * mean if (word3 >> 4 & 255) != PLAIN else usize
                     row[6] = col.valid_offset + done + slots if leaf.max_def else 0
                     row[7] = dict_row if (word3 >> 4 & 255) != PLAIN else 0
                     slots += n
@@ -330,36 +348,60 @@ def pages(buf, columns=None, row_groups=None, file=None):
             if slots != g_rows:
                 raise no("%d values in a row group of %d rows" % (slots, g_rows))
             done += g_rows
-        out_at += total * leaf.width
+        out_at += (total + 1) * 8 if is_str else total * leaf.width
         valid_at += total if leaf.max_def else 0
     r = np.array(rows, dtype=np.uint64).reshape(-1, binding.PARQUET_WORDS)
-    return Pages(r, fmt or "gzip", layout, _align(out_at), _align(valid_at))
+    return Pages(r, fmt or "gzip", layout, _align(out_at), _align(valid_at), estimate)
 
 
-def read_columns(dec, buf, d_in, columns=None, row_groups=None, stream=None):
+def read_columns(dec, buf, d_in, columns=None, row_groups=None, stream=None, bytes_estimate=None):
     """The selected columns of the file `buf` (host bytes), whose copy in device
     memory is d_in (uint8 CUDA tensor), decoded by dec
     (libdeflate_amd.Decompressor).  -> {name: (values, mask)}: values a tensor
     of the column's type - INT96 and FIXED_LEN_BYTE_ARRAY as uint8 [rows,
-    width] - with zeros where null; mask a torch.bool tensor, True where
-    valid, or None for a required column.  Waits for the device and raises if a
-    page failed."""
+    width] - with zeros where null, or for a BYTE_ARRAY column the pair
+    (offsets int64 [rows + 1] from 0, bytes uint8); mask a torch.bool tensor,
+    True where valid, or None for a required column.  The strings' room is
+    estimated from the page headers (bytes_estimate: instead of that); only
+    where a page then ends as INSUFFICIENT_SPACE the call is made again with
+    the room it reported.  Waits for the device and raises if a page failed."""
     import torch
-    pg = pages(buf, columns, row_groups)
+    f = parse(buf)
+    names = [leaf.name for leaf in f.leaves] if columns is None else list(columns)
+    strings = any(f.leaves[f.leaf_index(n)].type == BYTE_ARRAY for n in names)
+    pg = pages(buf, names, row_groups, file=f, strings=strings)
     out = torch.empty(max(pg.out_nbytes, ALIGN), dtype=torch.uint8, device=d_in.device)
     valid = torch.empty(max(pg.valid_nbytes, ALIGN), dtype=torch.uint8, device=d_in.device)
     results = torch.empty(max(len(pg.rows), 1), dtype=torch.int32, device=d_in.device)
-    dec.parquet_decode_batch(pg.format, pg.rows, d_in, out, valid, results, stream=stream)
-    res = results[:len(pg.rows)].cpu().numpy()
+    data = None
+    if not strings:
+        dec.parquet_decode_batch(pg.format, pg.rows, d_in, out, valid, results, stream=stream)
+        res = results[:len(pg.rows)].cpu().numpy()
+    else:
+        room = pg.bytes_estimate if bytes_estimate is None else int(bytes_estimate)
+        total = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+        for _ in range(2):
+            data = torch.empty(room, dtype=torch.uint8, device=d_in.device)
+            dec.parquet_decode_batch_ex(pg.format, pg.rows, d_in, out, valid, data, total, results,
+                                        stream=stream)
+            res = results[:len(pg.rows)].cpu().numpy()
+            if not (res == 3).any() or int(total.item()) <= room:    # INSUFFICIENT_SPACE
+                break
+            room = int(total.item())
     if res.any():
         k = int(np.flatnonzero(res)[0])
         raise ValueError("parquet: page row %d failed with libdeflate_result %d" % (k, res[k]))
     cols = {}
     for name, c in pg.columns.items():
-        v = out[c.offset:c.offset + c.rows * c.width]
-        v = v.view(getattr(torch, c.dtype)) if c.dtype else v.view(c.rows, c.width)
         m = None
         if c.valid_offset is not None:
             m = valid[c.valid_offset:c.valid_offset + c.rows].view(torch.bool)
+        if c.byte_array:
+            o = out[c.offset:c.offset + (c.rows + 1) * 8].view(torch.int64)
+            first, last = int(o[0].item()), int(o[-1].item())
+            cols[name] = ((o - first, data[first:last]), m)
+            continue
+        v = out[c.offset:c.offset + c.rows * c.width]
+        v = v.view(getattr(torch, c.dtype)) if c.dtype else v.view(c.rows, c.width)
         cols[name] = (v, m)
     return cols
